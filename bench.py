@@ -13,7 +13,11 @@ file under the temporary directory -- no torch.distributed process group is crea
 `python bench.py --gpus N` without a launcher spawns the N ranks itself (torch.distributed.run, before anything in this
 process touches a GPU); under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the ranks.
 
-Besides the contract line, the N=1 run reports
+A plain run sets up, warms up (W steps), times exactly K steps and prints the contract line (--dump-outputs DIR: what the last timed
+step returned, as .npy files).  With --full, besides the contract line, the N=1 run reports
+  queued         the device-resident form: K updates enqueued back to back, nothing read between them;
+  roofline       per-kernel times (HIP events) against the FP64 peak, and the counters of the committed PMC profile;
+  cpu_baseline   the plain-C restatement of the reference algorithm, one thread and all cores;
   latency        per-update latency (median / p95 over >= 200 updates): device-resident, host-visible through
                  the handle's pinned arena written in place (orcvio_msckf_io_update), host-visible through the copying call,
                  and with the covariance resident in HBM;
@@ -567,10 +571,16 @@ def main():
     ap.add_argument('--clones', type=int, default=30)
     ap.add_argument('--features', type=int, default=400)
     ap.add_argument('--latency-updates', type=int, default=300, help='updates per latency mode (>= 200, SURVEY 8d)')
-    ap.add_argument('--timed-blocks', type=int, default=5, help='the K timed steps are run at least this many times (each block bracketed '
-                    'by barrier + synchronize on both sides); the MEDIAN of the last `timed-blocks` blocks is the one reported')
-    ap.add_argument('--max-blocks', type=int, default=25, help='blocks are timed until the last `timed-blocks` agree within 0.7 %% or this '
+    ap.add_argument('--timed-blocks', type=int, default=1, help='the K timed steps are run at least this many times (each block bracketed '
+                    'by barrier + synchronize on both sides); the MEDIAN of the last `timed-blocks` blocks is the one reported.  Default 1: '
+                    'exactly K timed steps (5 with --max-blocks 25: repeated until the blocks agree)')
+    ap.add_argument('--max-blocks', type=int, default=1, help='blocks are timed until the last `timed-blocks` agree within 0.7 %% or this '
                     'many have run (the clocks of a device that was idle ramp up for tens of ms)')
+    ap.add_argument('--full', action='store_true', help='every side measurement besides the metric: the queued form, latency modes, '
+                    'roofline, objects, configs, streams, CPU baselines, the sharded profile (bench_detail.json).  Without it: set up, '
+                    'warm up, time the K steps, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps: what the last timed step returned to its '
+                    'caller (dx, P+, gamma, accept, stats) as DIR/<name>.npy, float64')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -664,10 +674,12 @@ def main():
     def median_block(blocks):
         used = sorted(blocks[-nblk:])
         return float(used[len(used) // 2])
-    # (a) the QUEUED form, a side figure: K device-resident updates enqueued back to back, nothing read between them
-    for _ in range(args.warmup):
-        step()
-    queued_dt = median_block(run_blocks(step))
+    # (a) the QUEUED form, a side figure (--full): K device-resident updates enqueued back to back, nothing read between them
+    queued_dt = None
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        queued_dt = median_block(run_blocks(step))
     # (b) THE metric: host-visible updates, one at a time -- flat inputs in host memory (the handle's pinned
     # arena, written in place by the caller) -> dx, P+, gamma, accept in host memory; update k+1 starts when update k's results are
     # there, as in a filter.  With more than one rank: the sharded update and a stream synchronisation per step.
@@ -683,6 +695,10 @@ def main():
     gc.enable()
     dt = median_block(block_dt)
     ms = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, _io_views if world == 1 else upd.download())
+    if not args.full:
+        return finish_plain(args, capi, upd, use_dist, world, rank, N, F, dt, ms, block_dt, nblk)
     upd.upload(win)   # (the staged form again: what the per-kernel profile and the side measurements below run on)
 
     # per-update latency of the joint update on every rank count (sync after every update)
@@ -970,26 +986,8 @@ def main():
         # aggregate in the metric's own unit -- 400-feature update shards processed per second by all ranks =
         # world x joint updates/s -- so that value(N) / (N value(1)) is the usual weak-scaling efficiency T(1)/T(N);
         # the joint-update rate is reported beside it.
-        try:
-            import hashlib
-            lib_sha16 = hashlib.sha256(open(capi.LIB_PATH, 'rb').read()).hexdigest()[:16]
-        except Exception:
-            lib_sha16 = None
-        out = dict(lib_sha16=lib_sha16, metric='EKF updates/sec, 30 clones x 400 feats', value=world * args.steps / dt, unit='updates/s',
-                   n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms, higher_is_better=True,
-                   scaling='weak', vs_baseline=None, dtype='f64', data='synthetic',
-                   config=dict(workload='config2: synthetic 30-clone window, 400 point features x 30 observations '
-                                        'per GPU (22 800 stacked rows x 202 columns), LARVIO Jacobians',
-                               clones=N, features_per_gpu=F, observations_per_feature=N,
-                               unit='one update of 30 clones x 400 features; at N GPUs one step is a joint update of '
-                                    '400 N features = N units',
-                               joint_updates_per_s=args.steps / dt, features_per_joint_update=F * world,
-                               parallelism=f'features sharded over {world} GPU(s), all-gather of compressed blocks through '
-                                           'the handle\'s RCCL communicator (the only communicator of the process)',
-                               value_is='HOST-VISIBLE updates, one at a time (SURVEY 8d): tracks + poses + P in the pinned arena -> dx, P+, gamma, '
-                                        'accept in host memory (orcvio_msckf_io_update); the queued device-resident throughput is queued_updates_per_s'),
+        out = dict(headline(args, capi, world, N, F, dt, ms, block_dt, nblk),
                    queued_updates_per_s=world * args.steps / queued_dt, queued_ms_per_step=queued_dt / args.steps * 1e3,
-                   timed_blocks=len(block_dt), blocks_reported=nblk, block_ms_per_step=[round(v / args.steps * 1e3, 5) for v in block_dt],
                    sequential_updates_per_s=(1000.0 / latency['host_visible']['median_ms']) if 'host_visible' in latency else None,
                    sequential_is='1 / median host-visible latency over >= 200 updates of the same call `value` times in blocks of K',
                    comm=comm, roofline=roofline, cpu_baseline=cpu, latency=latency, objects_update=objects, configs=configs, stream_config1=stream1, stream_config5=stream5)
@@ -1012,6 +1010,66 @@ def main():
         except Exception:
             pass
         emit(out, block_dt)
+    if bad_comm:
+        raise SystemExit(3)
+
+
+def headline(args, capi, world, N, F, dt, ms, block_dt, nblk):
+    """The metric and how it was timed: every key of a plain run's record (a --full run adds its side measurements to it)."""
+    try:
+        import hashlib
+        lib_sha16 = hashlib.sha256(open(capi.LIB_PATH, 'rb').read()).hexdigest()[:16]
+    except Exception:
+        lib_sha16 = None
+    return dict(lib_sha16=lib_sha16, metric='EKF updates/sec, 30 clones x 400 feats', value=world * args.steps / dt, unit='updates/s',
+                n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms, higher_is_better=True,
+                scaling='weak', vs_baseline=None, dtype='f64', data='synthetic',
+                config=dict(workload='config2: synthetic 30-clone window, 400 point features x 30 observations '
+                                     'per GPU (22 800 stacked rows x 202 columns), LARVIO Jacobians',
+                            clones=N, features_per_gpu=F, observations_per_feature=N,
+                            unit='one update of 30 clones x 400 features; at N GPUs one step is a joint update of '
+                                 '400 N features = N units',
+                            joint_updates_per_s=args.steps / dt, features_per_joint_update=F * world,
+                            parallelism=f'features sharded over {world} GPU(s), all-gather of compressed blocks through '
+                                        'the handle\'s RCCL communicator (the only communicator of the process)',
+                            value_is='HOST-VISIBLE updates, one at a time (SURVEY 8d): tracks + poses + P in the pinned arena -> dx, P+, gamma, '
+                                     'accept in host memory (orcvio_msckf_io_update); the queued device-resident throughput is queued_updates_per_s'),
+                timed_blocks=len(block_dt), blocks_reported=nblk, block_ms_per_step=[round(v / args.steps * 1e3, 5) for v in block_dt])
+
+
+def dump_outputs(d, res):
+    """--dump-outputs: what the last timed step handed its caller -- dx [n], P+ [n, n], gamma [F], accept [F], stats [8] -- as
+    d/<name>.npy in float64 (at world 1 the views of the handle's pinned arena the io call wrote; at N > 1 the joint update's
+    results downloaded from the handle).  Copied before anything else runs on the handle."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, key in (('dx', 'dx'), ('P_new', 'P_out' if 'P_out' in res else 'P_new'), ('gamma', 'gamma'), ('accept', 'accept'), ('stats', 'stats')):
+        np.save(os.path.join(d, name + '.npy'), np.array(res[key], dtype=np.float64))
+
+
+def finish_plain(args, capi, upd, use_dist, world, rank, N, F, dt, ms, block_dt, nblk):
+    """The end of a run without --full: the metric's line, no side measurement and no detail file.  At N > 1 the communicator's
+    record stays in the line: a block missing from the joint update makes the figure invalid (exit code 3, as with --full)."""
+    comm = None
+    if use_dist:
+        comm = dict(upd.comm_details())
+        if not comm.get('ipc_across_devices_unverified'):
+            comm.pop('ipc_across_devices_unverified', None)
+        comm.pop('rank', None)
+        upd.comm_barrier()
+    upd.close()
+    bad_comm = bool(use_dist and comm.get('ranks_seen') != world)
+    if rank == 0:
+        out = dict(headline(args, capi, world, N, F, dt, ms, block_dt, nblk), comm=comm)
+        if bad_comm:
+            out['comm']['error'] = 'ranks_seen %s != world %d: the line is NOT a valid N-rank measurement' % (comm.get('ranks_seen'), world)
+        sys.stdout.flush()
+        try:   # RCCL writes its version banner through C stdio: flush that buffer first so that the JSON line comes last
+            import ctypes
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        print(compact_line(out, block_dt, None), flush=True)
     if bad_comm:
         raise SystemExit(3)
 

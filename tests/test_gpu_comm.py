@@ -101,7 +101,7 @@ def test_bench_distributed_path_world_1(built):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, ORCVIO_BENCH_FORCE_DIST='1', ORCVIO_COMM_TIMEOUT_S='60')
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '5', '--warmup', '1', '--no-cpu-baseline', '--no-configs',
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '5', '--warmup', '1', '--no-cpu-baseline', '--no-configs',
                         '--latency-updates', '200'], capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])

@@ -1,18 +1,19 @@
-"""integration/orcvio_msckf.patch: the call-site patch INTEGRATION.md describes, as a file that applies.  In the build
-container the reference tree is at /root/reference: `git apply --check` must accept the patch there (the anchors -- src/orcvio.cpp
-:2154-2193 removeLostObjects, :2497-2560 removeLostFeatures, :2803-2851 pruneImuStateBuffer, include/orcvio/orcvio.h:200-214,
-CMakeLists.txt -- still match the reference text).  The patch travels, the reference tree does not: skipped where it is absent.
-Wherever it is: everything the patch adds to the C++ sources sits inside #ifdef ORCVIO_USE_AMD_MSCKF, so the reference builds and
-behaves as before without the definition, and it names only entry points include/orcvio_msckf.h declares."""
+"""integration/orcvio_msckf.patch: the call-site patch INTEGRATION.md describes, as a file that applies.  Its anchors
+-- src/orcvio.cpp :2154-2193 removeLostObjects, :2497-2560 removeLostFeatures, :2803-2851 pruneImuStateBuffer,
+include/orcvio/orcvio.h:200-214, CMakeLists.txt -- must still match the reference text: tests/golden/integration_anchors.json holds
+the position of every hunk in the reference tree and the sha256 of the reference lines there (scripts/make_golden_patch_anchors.py
+records it from a reference tree, after `git apply --check` accepted the patch there), so the check needs no copy of the reference.
+Everything the patch adds to the C++ sources sits inside #ifdef ORCVIO_USE_AMD_MSCKF, so the reference builds and behaves as before
+without the definition, and it names only entry points include/orcvio_msckf.h declares."""
+import hashlib
+import json
 import os
 import re
 import subprocess
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATCH = os.path.join(ROOT, 'integration', 'orcvio_msckf.patch')
-REF = '/root/reference'
+ANCHORS = os.path.join(ROOT, 'tests', 'golden', 'integration_anchors.json')
 
 
 def _hunks():
@@ -69,7 +70,40 @@ def test_patch_calls_only_declared_entry_points():
     assert lib_names <= declared | {'orcvio_msckf'}, lib_names - declared
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'src')), reason='the reference tree is not on this machine (it never travels to the GPU box)')
-def test_patch_applies_to_the_reference_tree():
-    r = subprocess.run(['git', 'apply', '--check', '-p1', '--verbose', PATCH], cwd=REF, capture_output=True, text=True)
+def _preimages():
+    """{file: [(old_start, old_len, the lines the hunk expects there)]} -- what `git apply` looks for in the tree it patches."""
+    files, cur, left = {}, None, 0
+    for line in open(PATCH).read().splitlines():
+        if left > 0 and line[:1] in (' ', '-', ''):   # (a hunk's own lines: context and removed lines, counted by its header)
+            files[cur][-1][2].append(line[1:])
+            left -= 1
+        elif line.startswith('+++ '):
+            cur = line[4:].split('\t')[0]
+            cur = cur[2:] if cur.startswith('b/') else cur
+            files[cur] = []
+        elif line.startswith('@@') and cur is not None:
+            m = re.match(r'@@ -(\d+)(?:,(\d+))? \+', line)
+            left = int(m.group(2) or 1)
+            files[cur].append((int(m.group(1)), left, []))
+    return files
+
+
+def test_patch_applies_to_the_reference_tree(tmp_path):
+    """Every hunk's context is the reference text at the recorded position (sha256), and `git apply --check` accepts the patch on a
+    stand-in tree that holds exactly that text there (hunk headers, line counts, order)."""
+    anchors = json.load(open(ANCHORS))
+    pre = _preimages()
+    assert set(pre) == set(anchors)
+    for path, hunks in pre.items():
+        rec = anchors[path]['hunks']
+        assert [(h['old_start'], h['old_len']) for h in rec] == [(s, n) for s, n, _ in hunks], path
+        lines = ['/* stand-in line %d */' % (i + 1) for i in range(anchors[path]['lines'])]
+        for (start, n, body), h in zip(hunks, rec):
+            assert len(body) == n, (path, start)
+            assert hashlib.sha256('\n'.join(body).encode()).hexdigest() == h['sha256'], (path, start, 'context differs from the reference')
+            lines[start - 1:start - 1 + n] = body
+        os.makedirs(os.path.dirname(os.path.join(tmp_path, path)), exist_ok=True)
+        with open(os.path.join(tmp_path, path), 'w') as f:
+            f.write('\n'.join(lines))
+    r = subprocess.run(['git', 'apply', '--check', '-p1', '--verbose', PATCH], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
