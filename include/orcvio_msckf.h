@@ -838,6 +838,47 @@ int32_t orcvio_msckf_cov_commit_new_features(orcvio_msckf_handle* h, double* dx_
 /* Schmidt branch of pruneImuStateBuffer (src/orcvio.cpp:2881-2920): the listed clones (window ranks before the call, ascending)
  * leave the window but stay in the resident covariance as nuisance states -- their blocks move to the end, in the listed order. */
 int32_t orcvio_msckf_cov_clones_to_nuisance(orcvio_msckf_handle* h, int32_t leg_dim, const int32_t* clone_indices, int32_t count);
+/* In-state SLAM features of the hybrid filter on the resident covariance.  State layout [LEG | 6 n_clones | idp_dim per feature
+ * state, in feature_states order | 6 per nuisance state].  Both calls keep the resident square-root factor, so the next update
+ * starts from it instead of a Cholesky factorisation of P.
+ *   cov_remove_features   removeLostFeatures -> rmLostFeaturesCov, src/orcvio.cpp:2233, :3776-3828: the idp_dim rows and columns of
+ *                         each listed feature are deleted; slots are positions in feature_states BEFORE the call, strictly
+ *                         ascending; what stands behind the n_feature_states features must be whole 6-wide nuisance blocks (they
+ *                         stay).  Refused (ORCVIO_ERR_INVALID, nothing changed): leg + 6 n_clones + idp_dim n_feature_states > the
+ *                         resident dimension, a rest that is not a multiple of 6, slots out of range or not ascending.  The caller
+ *                         lowers ORCVIO_OPT_EXTRA_STATES by idp_dim count before its next upload.
+ *   cov_change_anchors    pruneImuStateBuffer, in-state features whose anchor clone leaves (:2664-2720): the new parameters in the
+ *                         new anchor's camera frame (3-d :2680-2687 invParam; 1-d :2700-2712 invDepth and obs_anchor) and the
+ *                         covariance update updateFeatureCov_3didp (:3457-3609) / _1didp (:3611-3774), for up to 16 features
+ *                         in ONE launch: P <- T P T^T with T = I except the changed features' rows (their J: the feature, the old
+ *                         and new anchor clones, the extrinsics -- no J reads another changed feature's row, so this equals the
+ *                         reference's one-feature-after-the-other loop up to rounding).  poses: [n_clones][ORCVIO_POSE_STRIDE]
+ *                         records as in the io arena (a clone's camera pose comes from its own record); R_b2c [9] / t_c_b [3]:
+ *                         the CURRENT extrinsics (state_server.imu_state), read for p_old under if_FEJ and for the extrinsic
+ *                         columns.  flags: leg_dim and if_fej are read.  literal_3d (idp_dim 3): 1 = the reference as written,
+ *                         whose "new" pose and column are looked up under old_state_id (:3487, :3544: the new clone gets no
+ *                         entries, H_x_new lands in the old clone's block); 0 = the consistent Jacobian with the new anchor's
+ *                         pose and columns.  The new anchor is the caller's choice (3-d: the newest clone; 1-d: getNewAnchorId,
+ *                         :3892-3950).  Out: new_param [count][3] (3-d: invParam; 1-d: obs_anchor (u, v, 1)), new_inv_depth
+ *                         [count] (may be NULL), to be written back to map_server with id_anchor = new_anchor.  The feature
+ *                         states are taken to be everything behind the clones except the last 6 k states when
+ *                         ORCVIO_OPT_SCHMIDT_STATES = k is set (the nuisance block): with nuisance states in the resident covariance,
+ *                         set that option first, or a slot that reaches into the nuisance block cannot be told from a feature's.
+ *                         Refused (ORCVIO_ERR_INVALID, P and its factor unchanged): a slot beyond the feature states or listed
+ *                         twice, a feature region that is not a multiple of idp_dim, old == new, an anchor >= n_clones, a
+ *                         non-finite pose / extrinsic / position, more than 16 changes. */
+typedef struct orcvio_msckf_anchor_change {
+    int32_t slot;          /* position of the feature in feature_states                                  */
+    int32_t old_anchor;    /* window rank of Feature::id_anchor (the clone about to leave)                */
+    int32_t new_anchor;    /* window rank of the new anchor                                              */
+    double p_w[3];         /* Feature::position                                                          */
+    double p_fej[3];       /* Feature::position_FEJ, read under if_fej                                   */
+} orcvio_msckf_anchor_change;
+int32_t orcvio_msckf_cov_remove_features(orcvio_msckf_handle* h, int32_t leg_dim, int32_t n_clones, int32_t idp_dim, int32_t n_feature_states,
+                                         const int32_t* slots, int32_t count);
+int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags, int32_t idp_dim, int32_t literal_3d,
+                                        int32_t n_clones, const double* poses, const double* R_b2c, const double* t_c_b,
+                                        const orcvio_msckf_anchor_change* changes, int32_t count, double* new_param, double* new_inv_depth);
 
 /* ---- Environment switches (read once per process; diagnostics and A/B measurements -- every one of them leaves the results unchanged) ----
  *   ORCVIO_COMM_TIMEOUT_S   bound of every wait another rank can strand, seconds (default 180)

@@ -43,7 +43,7 @@ EXPORTS = [
     'orcvio_msckf_comm_barrier', 'orcvio_msckf_comm_allreduce_max', 'orcvio_msckf_io_begin', 'orcvio_msckf_io_update',
     'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect',
     'orcvio_msckf_objects_refined', 'orcvio_msckf_counters', 'orcvio_msckf_comm_details', 'orcvio_msckf_profile_sharded',
-    'orcvio_msckf_io_step_frame',
+    'orcvio_msckf_io_step_frame', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
 ]
 
 
@@ -188,6 +188,9 @@ def _bind(lib):
     lib.orcvio_msckf_cov_commit.argtypes = [C.c_void_p]
     lib.orcvio_msckf_cov_prefactor.argtypes = [C.c_void_p]
     lib.orcvio_msckf_cov_clones_to_nuisance.argtypes = [C.c_void_p, C.c_int32, _ip, C.c_int32]
+    lib.orcvio_msckf_cov_remove_features.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip, C.c_int32]
+    lib.orcvio_msckf_cov_change_anchors.argtypes = [C.c_void_p, C.POINTER(MsckfFlags), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
+                                                    C.POINTER(AnchorChange), C.c_int32, _dp, _dp]
     lib.orcvio_msckf_upload_nuisance_poses.argtypes = [C.c_void_p, C.c_void_p]
     lib.orcvio_msckf_update_object_tracks.argtypes = [C.c_void_p, C.POINTER(MsckfFlags), C.POINTER(ObjectEvalFlags), C.c_int32,
                                                       C.POINTER(ObjectTrackC), C.c_int32, _dp, C.POINTER(MsckfResult)]
@@ -269,6 +272,12 @@ class FrameResult(C.Structure):
                 ('accept', C.POINTER(C.c_int32)), ('prune_dx', C.POINTER(C.c_double)), ('prune_gamma', C.POINTER(C.c_double)),
                 ('prune_accept', C.POINTER(C.c_int32)), ('n_after', C.c_int32), ('status_first', C.c_int32), ('status_prune', C.c_int32),
                 ('repaired', C.c_int32)]
+
+
+class AnchorChange(C.Structure):
+    """orcvio_msckf_anchor_change (include/orcvio_msckf.h)."""
+    _fields_ = [('slot', C.c_int32), ('old_anchor', C.c_int32), ('new_anchor', C.c_int32), ('p_w', C.c_double * 3),
+                ('p_fej', C.c_double * 3)]
 
 
 class MsckfNewFeatures(C.Structure):
@@ -1009,6 +1018,32 @@ class MsckfUpdater:
         ix = np.ascontiguousarray(indices, dtype=np.int32)
         self._chk(self.lib.orcvio_msckf_cov_clones_to_nuisance(self.h, leg_dim, _i(ix), len(ix)), 'orcvio_msckf_cov_clones_to_nuisance')
 
+    def cov_remove_features(self, leg_dim, n_clones, idp_dim, n_feature_states, slots):
+        """orcvio_msckf_cov_remove_features: rmLostFeaturesCov on the resident covariance (slots ascending, numbered before the call)."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        self._chk(self.lib.orcvio_msckf_cov_remove_features(self.h, leg_dim, n_clones, idp_dim, n_feature_states, _i(sl) if len(sl) else None,
+                                                            len(sl)), 'orcvio_msckf_cov_remove_features')
+
+    def cov_change_anchors(self, flags, idp_dim, poses, R_b2c, t_c_b, changes, literal_3d=0):
+        """orcvio_msckf_cov_change_anchors on the resident covariance.  poses [N][28] (synth.pack_poses); changes: objects with the
+        attributes slot, old, new (window ranks), p_w, p_fej.  Returns (param [k, 3], rho [k])."""
+        ps = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, POSE_STRIDE)
+        Rb = np.ascontiguousarray(R_b2c, dtype=np.float64).reshape(9)
+        tb = np.ascontiguousarray(t_c_b, dtype=np.float64).reshape(3)
+        k = len(changes)
+        arr = (AnchorChange * max(k, 1))()
+        for q, c in enumerate(changes):
+            arr[q].slot, arr[q].old_anchor, arr[q].new_anchor = int(c.slot), int(c.old), int(c.new)
+            arr[q].p_w[:] = [float(x) for x in c.p_w]
+            pf = c.p_w if getattr(c, 'p_fej', None) is None else c.p_fej
+            arr[q].p_fej[:] = [float(x) for x in pf]
+        fl = make_flags(flags)
+        param = np.zeros((max(k, 1), 3))
+        rho = np.zeros(max(k, 1))
+        self._chk(self.lib.orcvio_msckf_cov_change_anchors(self.h, C.byref(fl), int(idp_dim), int(literal_3d), ps.shape[0], _d(ps), _d(Rb), _d(tb),
+                                                           arr, k, _d(param), _d(rho)), 'orcvio_msckf_cov_change_anchors')
+        return param[:k], rho[:k]
+
     def set_object_dof_rank(self, on: bool):
         """ORCVIO_OPT_OBJECT_DOF: 1 = the object gate counts rows - rank(H_f) degrees of freedom (default rows - columns)."""
         self._chk(self.lib.orcvio_msckf_set_option(self.h, 11, int(bool(on))), 'orcvio_msckf_set_option')
@@ -1282,6 +1317,27 @@ def debug_read(upd: MsckfUpdater, which: str):
         if rc != 0:
             raise MsckfError(rc, f'debug_read {which}')
     return out
+
+
+def debug_factor_state(upd: MsckfUpdater):
+    """Test helper (diagnostics build): dict(fac_valid, fac_n, fac_k, res_n) of the resident covariance and its factor."""
+    lib = upd.lib
+    lib.orcvio_msckf_debug_read.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    st = np.zeros(4, dtype=np.int32)
+    rc = lib.orcvio_msckf_debug_read(upd.h, 11, st.ctypes.data_as(C.c_void_p), st.nbytes)
+    if rc != 0:
+        raise MsckfError(rc, 'debug_read factor state')
+    return dict(fac_valid=int(st[0]), fac_n=int(st[1]), fac_k=int(st[2]), res_n=int(st[3]))
+
+
+def debug_factor(upd: MsckfUpdater):
+    """Test helper (diagnostics build): the resident square-root factor S [fac_n, fac_k] (P = S S^T)."""
+    st = debug_factor_state(upd)
+    out = np.zeros((st['fac_k'], st['fac_n']))
+    rc = upd.lib.orcvio_msckf_debug_read(upd.h, 12, out.ctypes.data_as(C.c_void_p), out.nbytes)
+    if rc != 0:
+        raise MsckfError(rc, 'debug_read factor')
+    return out.T.copy()
 
 
 def debug_potrf(upd: MsckfUpdater, X, tol_rel=0.0, force_lds_path=False):

@@ -158,16 +158,10 @@ int32_t orcvio_msckf_cov_augment(orcvio_msckf_handle* h) {
     return ORCVIO_OK;
 }
 
-int32_t orcvio_msckf_cov_remove_clones(orcvio_msckf_handle* h, int32_t leg, const int32_t* idx, int32_t count) {
-    if (!h || (count > 0 && !idx) || count < 0 || (leg != 22 && leg != 46) || h->res_n < leg) { g_last_error = "cov_remove_clones: invalid"; return ORCVIO_ERR_INVALID; }
-    if (count == 0) return ORCVIO_OK;
-    HIPCHK(hipSetDevice(h->device));
-    const int n = h->res_n, N = (n - leg) / 6;
-    std::vector<char> drop(n, 0);
-    for (int k = 0; k < count; ++k) {
-        if (idx[k] < 0 || idx[k] >= N) { g_last_error = "cov_remove_clones: index out of the window"; return ORCVIO_ERR_INVALID; }
-        for (int c = 0; c < 6; ++c) drop[leg + 6 * idx[k] + c] = 1;
-    }
+// The states with drop[i] set leave the resident covariance (rows and columns deleted, the rest keeps its order); deleting
+// states deletes rows of the resident square-root factor, which is kept.
+static int cov_remove_rows(orcvio_msckf_handle* h, const std::vector<char>& drop) {
+    const int n = h->res_n;
     std::vector<int> map;
     for (int i = 0; i < n; ++i)
         if (!drop[i]) map.push_back(i);
@@ -191,6 +185,19 @@ int32_t orcvio_msckf_cov_remove_clones(orcvio_msckf_handle* h, int32_t leg, cons
     std::swap(h->d_Pres, h->d_Ptmp);
     h->res_n = m;
     return ORCVIO_OK;
+}
+
+int32_t orcvio_msckf_cov_remove_clones(orcvio_msckf_handle* h, int32_t leg, const int32_t* idx, int32_t count) {
+    if (!h || (count > 0 && !idx) || count < 0 || (leg != 22 && leg != 46) || h->res_n < leg) { g_last_error = "cov_remove_clones: invalid"; return ORCVIO_ERR_INVALID; }
+    if (count == 0) return ORCVIO_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const int n = h->res_n, N = (n - leg) / 6;
+    std::vector<char> drop(n, 0);
+    for (int k = 0; k < count; ++k) {
+        if (idx[k] < 0 || idx[k] >= N) { g_last_error = "cov_remove_clones: index out of the window"; return ORCVIO_ERR_INVALID; }
+        for (int c = 0; c < 6; ++c) drop[leg + 6 * idx[k] + c] = 1;
+    }
+    return cov_remove_rows(h, drop);
 }
 
 // Schmidt branch of pruneImuStateBuffer (src/orcvio.cpp:2881-2920): the listed clones leave the window but STAY in the covariance
@@ -227,6 +234,98 @@ int32_t orcvio_msckf_cov_clones_to_nuisance(orcvio_msckf_handle* h, int32_t leg,
         std::swap(h->d_Sres, h->d_Stmp);
     } else h->fac_valid = false;
     std::swap(h->d_Pres, h->d_Ptmp);
+    return ORCVIO_OK;
+}
+
+// rmLostFeaturesCov (src/orcvio.cpp:3776-3828) on the resident covariance: the d rows and columns of the listed in-state features
+// (slots in feature_states before the call, ascending) are deleted; the nuisance block behind the features stays.  A gather with
+// a map (k_cov_remove), the factor's rows with it (k_fac_remove): the factor is kept.
+int32_t orcvio_msckf_cov_remove_features(orcvio_msckf_handle* h, int32_t leg, int32_t n_clones, int32_t idp_dim, int32_t n_feature_states,
+                                         const int32_t* slots, int32_t count) {
+    if (!h || (count > 0 && !slots) || count < 0 || (leg != 22 && leg != 46) || (idp_dim != 1 && idp_dim != 3) || n_clones < 0 ||
+        n_feature_states < 0 || count > n_feature_states) { g_last_error = "cov_remove_features: invalid"; return ORCVIO_ERR_INVALID; }
+    const int n = h->res_n, base = leg + 6 * n_clones, end = base + idp_dim * n_feature_states;
+    if (n == 0 || end > n || (n - end) % 6 != 0) { g_last_error = "cov_remove_features: leg + 6N + d nf does not fit the resident covariance, or what is behind it is not whole nuisance blocks"; return ORCVIO_ERR_INVALID; }
+    for (int q = 0; q < count; ++q)
+        if (slots[q] < 0 || slots[q] >= n_feature_states || (q > 0 && slots[q] <= slots[q - 1])) { g_last_error = "cov_remove_features: slots must be ascending and in range"; return ORCVIO_ERR_INVALID; }
+    if (count == 0) return ORCVIO_OK;
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<char> drop(n, 0);
+    for (int q = 0; q < count; ++q)
+        for (int c = 0; c < idp_dim; ++c) drop[base + idp_dim * slots[q] + c] = 1;
+    return cov_remove_rows(h, drop);
+}
+
+// The in-state branch of pruneImuStateBuffer (src/orcvio.cpp:2664-2720) for up to 16 features at once: new parameters in the new
+// anchor's camera frame and P <- T P T^T (updateFeatureCov_1didp :3611-3774 / _3didp :3457-3609), in one launch
+// (k_cov_change_anchors); the resident factor goes along as S <- T S.
+static bool all_finite(const double* x, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(x[i])) return false;
+    return true;
+}
+int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags, int32_t idp_dim, int32_t literal_3d,
+                                        int32_t n_clones, const double* poses, const double* R_b2c, const double* t_c_b,
+                                        const orcvio_msckf_anchor_change* changes, int32_t count, double* new_param, double* new_inv_depth) {
+    if (!h || !flags || (idp_dim != 1 && idp_dim != 3) || count < 0 || count > ANCHOR_MAX_K || (count > 0 && (!changes || !poses || !R_b2c || !t_c_b)) ||
+        (flags->leg_dim != 22 && flags->leg_dim != 46) || n_clones < 2) { g_last_error = "cov_change_anchors: invalid"; return ORCVIO_ERR_INVALID; }
+    const int n = h->res_n, leg = flags->leg_dim, base = leg + 6 * n_clones, d = idp_dim;
+    if (n == 0 || base > n) { g_last_error = "cov_change_anchors: the window does not fit the resident covariance"; return ORCVIO_ERR_INVALID; }
+    // the feature states end where the nuisance block of ORCVIO_OPT_SCHMIDT_STATES begins: a slot may not reach into it
+    const int feat_end = n - 6 * h->n_nui;
+    if (feat_end < base || (feat_end - base) % d != 0) { g_last_error = "cov_change_anchors: the states behind the clones are not d-wide feature states followed by the ORCVIO_OPT_SCHMIDT_STATES nuisance block"; return ORCVIO_ERR_INVALID; }
+    if (count == 0) return ORCVIO_OK;
+    std::vector<int> ci(3 * count);
+    std::vector<double> cd(6 * count);
+    for (int q = 0; q < count; ++q) {
+        const orcvio_msckf_anchor_change& c = changes[q];
+        if (c.slot < 0 || base + d * (c.slot + 1) > feat_end) { g_last_error = "cov_change_anchors: slot out of range"; return ORCVIO_ERR_INVALID; }
+        for (int p = 0; p < q; ++p)
+            if (changes[p].slot == c.slot) { g_last_error = "cov_change_anchors: a slot listed twice"; return ORCVIO_ERR_INVALID; }
+        if (c.old_anchor < 0 || c.old_anchor >= n_clones || c.new_anchor < 0 || c.new_anchor >= n_clones) { g_last_error = "cov_change_anchors: anchor outside the window"; return ORCVIO_ERR_INVALID; }
+        if (c.old_anchor == c.new_anchor) { g_last_error = "cov_change_anchors: old anchor == new anchor"; return ORCVIO_ERR_INVALID; }
+        if (!all_finite(c.p_w, 3) || (flags->if_fej && !all_finite(c.p_fej, 3))) { g_last_error = "cov_change_anchors: non-finite feature position"; return ORCVIO_ERR_INVALID; }
+        ci[3 * q] = c.slot; ci[3 * q + 1] = c.old_anchor; ci[3 * q + 2] = c.new_anchor;
+        for (int a = 0; a < 3; ++a) { cd[6 * q + a] = c.p_w[a]; cd[6 * q + 3 + a] = flags->if_fej ? c.p_fej[a] : c.p_w[a]; }
+    }
+    double ext[12];
+    for (int a = 0; a < 9; ++a) ext[a] = R_b2c[a];
+    for (int a = 0; a < 3; ++a) ext[9 + a] = t_c_b[a];
+    if (!all_finite(ext, 12)) { g_last_error = "cov_change_anchors: non-finite extrinsics"; return ORCVIO_ERR_INVALID; }
+    for (int i = 0; i < n_clones; ++i)
+        if (!all_finite(poses + (size_t)i * ORCVIO_POSE_STRIDE, 27)) { g_last_error = "cov_change_anchors: non-finite pose record"; return ORCVIO_ERR_INVALID; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    // staging in the propagation scratch (46 n_max + 2 46^2 doubles >= 28 N + 12 + 10 k): poses | ext | p_w, p_fej | params out
+    double* dposes = h->d_covT;
+    double* dext = dposes + (size_t)ORCVIO_POSE_STRIDE * n_clones;
+    double* dcd = dext + 12;
+    double* dpar = dcd + 6 * count;
+    {
+        const AuxCopy cp[] = {{dposes, poses, sizeof(double) * (size_t)ORCVIO_POSE_STRIDE * n_clones}, {dext, ext, sizeof(ext)},
+                              {dcd, cd.data(), sizeof(double) * cd.size()}, {h->d_covmap, ci.data(), sizeof(int) * ci.size()}};
+        const int rc = aux_copies(h, s, cp, 4);
+        if (rc != ORCVIO_OK) return rc;
+    }
+    const bool fac = h->fac_valid && h->fac_n == n;
+    // Y = J P [k d][n] goes to d_Ptmp (n_max^2 >= k d n: k d <= n - base)
+#define LAUNCH_CA(D) hipLaunchKernelGGL(k_cov_change_anchors<D>, dim3(1), dim3(AnchorThreads<D>::value), 0, s, h->d_Pres, n, fac ? h->d_Sres : (double*)nullptr, \
+                                        h->fac_ld, h->fac_k, (const double*)dposes, (const double*)dext, (const int*)h->d_covmap, (const double*)dcd, \
+                                        count, base, leg, flags->if_fej ? 1 : 0, literal_3d ? 1 : 0, dpar, h->d_Ptmp)
+    if (d == 3) LAUNCH_CA(3);
+    else LAUNCH_CA(1);
+#undef LAUNCH_CA
+    HIPCHK(hipGetLastError());
+    if (!fac) h->fac_valid = false;   // (T S touches rows >= 15 only: the factor's zero trailing columns, fac_tail, stay zero)
+    std::vector<double> par(4 * count);
+    const FetchCopy fc[] = {{par.data(), dpar, sizeof(double) * par.size()}};
+    const int rc = fetch_copies(h, s, fc, 1);
+    if (rc != ORCVIO_OK) return rc;
+    for (int q = 0; q < count; ++q) {
+        if (new_param)
+            for (int a = 0; a < 3; ++a) new_param[3 * q + a] = par[4 * q + a];
+        if (new_inv_depth) new_inv_depth[q] = par[4 * q + 3];
+    }
     return ORCVIO_OK;
 }
 

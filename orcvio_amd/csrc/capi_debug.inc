@@ -5,7 +5,8 @@
 //      (orcvio_amd/lib/liborcvio_msckf_dbg.so, -DORCVIO_DEBUG_HOOKS), which the tests that need them load explicitly ----------
 #ifdef ORCVIO_DEBUG_HOOKS
 // ---- debug access to intermediate device buffers (tests only; not part of the public header) ---
-// which: 0 Hs [m_tot x NAP], 1 Ab, 2 A (summed block), 3 RP, 4 M, 5 RM, 6 Z, 8 U, 7 dims -> int32[8]
+// which: 0 Hs [m_tot x NAP], 1 Ab, 2 A (summed block), 3 RP, 4 M, 5 RM, 6 Z, 8 U, 7 dims -> int32[8],
+//        11 {fac_valid, fac_n, fac_k, res_n} -> int32[4], 12 the resident factor [fac_k][fac_n]
 int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst, int64_t max_bytes) {
     if (!h || !dst) return ORCVIO_ERR_INVALID;
     HIPCHK(hipSetDevice(h->device));
@@ -34,6 +35,19 @@ int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst
         case 10: {   // how often an update was re-run on the forked path because the fused front end lost a hand-off
             if ((size_t)max_bytes < sizeof(int32_t)) return ORCVIO_ERR_INVALID;
             *reinterpret_cast<int32_t*>(dst) = h->front_fallbacks;
+            return ORCVIO_OK;
+        }
+        case 11: {   // the resident covariance and its square-root factor: {fac_valid, fac_n, fac_k, res_n}
+            int32_t st[4] = {h->fac_valid ? 1 : 0, h->fac_n, h->fac_k, h->res_n};
+            if ((size_t)max_bytes < sizeof(st)) return ORCVIO_ERR_INVALID;
+            std::memcpy(dst, st, sizeof(st));
+            return ORCVIO_OK;
+        }
+        case 12: {   // the resident factor itself: [fac_k][fac_n] (S(j, i) at [i][j]), the padding to fac_ld dropped
+            if (!h->fac_valid) { g_last_error = "debug_read: no resident factor"; return ORCVIO_ERR_INVALID; }
+            if ((size_t)max_bytes < (size_t)h->fac_k * h->fac_n * sizeof(double)) { g_last_error = "debug_read: buffer too small"; return ORCVIO_ERR_INVALID; }
+            HIPCHK(hipMemcpy2D(dst, sizeof(double) * h->fac_n, h->d_Sres, sizeof(double) * h->fac_ld, sizeof(double) * h->fac_n, h->fac_k,
+                               hipMemcpyDeviceToHost));
             return ORCVIO_OK;
         }
         case 7: {

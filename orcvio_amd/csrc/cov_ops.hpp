@@ -2,10 +2,14 @@
 // besides the update where the reference touches state_cov, so that P never has to cross PCIe between updates.
 //   k_cov_propagate_*  OrcVIO::processModel      (src/orcvio.cpp:800-816)
 //   k_cov_augment      OrcVIO::stateAugmentation (:962-1010, feature / nuisance states behind the clones included)
-//   k_cov_remove       OrcVIO::pruneImuStateBuffer (:2935-2951, non-Schmidt branch)
+//   k_cov_remove       OrcVIO::pruneImuStateBuffer (:2935-2951, non-Schmidt branch); with a map that drops feature rows,
+//                      rmLostFeaturesCov (:3776-3828)
+//   k_cov_change_anchors  the in-state features' anchor change of pruneImuStateBuffer (:2664-2720, updateFeatureCov_*)
 // All three are HBM-bound element kernels over an n x n matrix (n <= 406): coalesced row-major reads and writes.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "feature_anchor.hpp"
 
 namespace orcvio_amd {
 
@@ -177,6 +181,104 @@ __global__ __launch_bounds__(256) void k_aug_assemble(const double* __restrict__
         v = p;
     }
     out[idx] = v;
+}
+
+
+
+// ---- in-state SLAM features on the resident covariance (src/orcvio.cpp:2664-2720, updateFeatureCov_1didp :3611-3774,
+//      _3didp :3457-3609) ----------------------------------------------------------------------------------------------------
+// Anchor change of k <= 16 features in ONE workgroup: P <- T P T^T, T = I except the changed features' d rows, which are their J
+// (feature_anchor.hpp: d x 21 non-zeros -- the feature, the old and new anchor clones, the extrinsics).  No J row reads another
+// changed feature's rows, so this equals the reference's one-feature-after-the-other loop in real arithmetic.
+//   1. J and the new parameters per feature (one lane per feature) -> LDS
+//   2. Y = J P (k d rows) -> scratch Y [k d][n] (HBM/L2: 3-d at k = 16, n = 406 would be 156 KB, beyond a workgroup's LDS);
+//      the factor, if given: S <- T S, row by row in place (a feature's new rows read only its own rows, clones and extrinsics)
+//   3. the feature rows and columns of P from Y, the (k d)^2 block from Y J^T, symmetrised (Pff of the 3-d form is, :3602)
+// P is changed in place: only the k d rows and columns are written.  chg_i [k][3] = slot, old, new anchor; chg_d [k][6] = p_w,
+// p_fej; ext = R_b2c 9 | t_c_b 3; params out [k][4] = param 3 | rho.
+// (512 lanes for 1-d; the 3-d form's per-feature math needs ~300 VGPRs in lane q: 256 lanes, one wave per SIMD, no spill)
+enum { ANCHOR_MAX_K = 16 };
+template <int d> struct AnchorThreads { enum { value = d == 3 ? 256 : 512 }; };
+__device__ __forceinline__ int anchor_col(int t, int fcol, int oc, int nc) {
+    return t < ANCHOR_J_OLD ? fcol + t : (t < ANCHOR_J_NEW ? oc + t - ANCHOR_J_OLD : (t < ANCHOR_J_EXT ? nc + t - ANCHOR_J_NEW : 15 + t - ANCHOR_J_EXT));
+}
+template <int d>
+__global__ __launch_bounds__(AnchorThreads<d>::value) void k_cov_change_anchors(double* __restrict__ P, int n, double* __restrict__ F, int ld, int fk,
+                                                                   const double* __restrict__ poses, const double* __restrict__ ext,
+                                                                   const int* __restrict__ chg_i, const double* __restrict__ chg_d, int k,
+                                                                   int base, int leg, int if_fej, int literal_3d,
+                                                                   double* __restrict__ params, double* __restrict__ Y) {
+    __shared__ double sJ[ANCHOR_MAX_K * 3 * ANCHOR_J_STRIDE];
+    __shared__ int sC[ANCHOR_MAX_K * ANCHOR_J_STRIDE];   // state column of entry t of feature q's J rows
+    __shared__ int sF[ANCHOR_MAX_K];                     // first column of feature q
+    constexpr int ANCHOR_THREADS = AnchorThreads<d>::value;
+    const int tid = threadIdx.x;
+    if (tid < k) {
+        const int q = tid;
+        const int slot = chg_i[3 * q], o = chg_i[3 * q + 1], nw = chg_i[3 * q + 2];
+        double par[3], rho;   // (J straight into LDS: 63 doubles fewer in registers)
+        anchor_change(poses + (size_t)o * POSE_STRIDE, poses + (size_t)nw * POSE_STRIDE, ext, ext + 9, chg_d + 6 * q, chg_d + 6 * q + 3,
+                      d, if_fej, literal_3d, par, &rho, sJ + q * 3 * ANCHOR_J_STRIDE);
+        const int fcol = base + d * slot;
+        const int oc = leg + 6 * o, nc = leg + 6 * ((d == 3 && literal_3d) ? o : nw);
+        for (int t = 0; t < ANCHOR_J_STRIDE; ++t) sC[q * ANCHOR_J_STRIDE + t] = anchor_col(t, fcol, oc, nc);
+        sF[q] = fcol;
+        params[4 * q + 0] = par[0]; params[4 * q + 1] = par[1]; params[4 * q + 2] = par[2]; params[4 * q + 3] = rho;
+    }
+    __syncthreads();
+    // (entries 0 .. d-1 of the feature block, then the 18 pose / extrinsic entries)
+#define ANCHOR_DOT(acc, r, q, ld_, off)                                                                            \
+    {                                                                                                            \
+        const double* Jr = sJ + (q) * 3 * ANCHOR_J_STRIDE + (r) * ANCHOR_J_STRIDE;                               \
+        const int* Cq = sC + (q) * ANCHOR_J_STRIDE;                                                              \
+        acc = 0.0;                                                                                               \
+        for (int t = 0; t < d; ++t) acc += Jr[t] * src[(size_t)Cq[t] * (ld_) + (off)];                            \
+        for (int t = ANCHOR_J_OLD; t < ANCHOR_J_STRIDE; ++t) acc += Jr[t] * src[(size_t)Cq[t] * (ld_) + (off)];   \
+    }
+    {   // 2. Y = J P  (j fastest: coalesced reads of P's rows)
+        const double* src = P;
+        for (int idx = tid; idx < k * n; idx += ANCHOR_THREADS) {
+            const int q = idx / n, j = idx - q * n;
+            for (int r = 0; r < d; ++r) {
+                double acc;
+                ANCHOR_DOT(acc, r, q, n, j)
+                Y[(size_t)(q * d + r) * n + j] = acc;
+            }
+        }
+    }
+    if (F) {   // S <- T S: S(state c, column i) = F[i ld + c]; feature q fastest (threads of a wave share column i)
+        for (int idx = tid; idx < k * fk; idx += ANCHOR_THREADS) {
+            const int i = idx / k, q = idx - i * k;
+            double* col = F + (size_t)i * ld;
+            const double* src = col;
+            double acc[3] = {0.0, 0.0, 0.0};
+            for (int r = 0; r < d; ++r) ANCHOR_DOT(acc[r], r, q, 1, 0)
+            for (int r = 0; r < d; ++r) col[sF[q] + r] = acc[r];
+        }
+    }
+    __syncthreads();
+    {   // 3. rows / columns of P from Y; the (k d)^2 block from Y J^T, symmetrised
+        const int m = k * d;
+        for (int idx = tid; idx < m * n; idx += ANCHOR_THREADS) {
+            const int rr = idx / n, j = idx - rr * n;
+            const int fr = sF[rr / d] + rr % d;
+            int s = -1;
+            for (int q = 0; q < k; ++q)
+                if (j >= sF[q] && j < sF[q] + d) s = q * d + (j - sF[q]);
+            double v;
+            if (s < 0) {
+                v = Y[(size_t)rr * n + j];
+                P[(size_t)j * n + fr] = v;
+            } else {
+                double z1, z2;
+                { const double* src = Y + (size_t)rr * n; ANCHOR_DOT(z1, s % d, s / d, 1, 0) }
+                { const double* src = Y + (size_t)s * n; ANCHOR_DOT(z2, rr % d, rr / d, 1, 0) }
+                v = 0.5 * (z1 + z2);
+            }
+            P[(size_t)fr * n + j] = v;
+        }
+    }
+#undef ANCHOR_DOT
 }
 
 }  // namespace orcvio_amd

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <iterator>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -81,8 +82,78 @@ struct Feature {
     double invDepth = 0;
     double obs_anchor[3] = {0, 0, 1};   // corrected observation in the anchor frame (1-d inverse depth, feature.hpp)
     bool failed_by_neg_dpth = false, failed_by_big_proj = false;
+    bool in_state = false;   // an EKF-SLAM feature of the hybrid filter (its states are in state_cov, slot = rank in feature_states)
 };
 typedef std::map<FeatureIDType, Feature> MapServer;
+
+// getNewAnchorId (src/orcvio.cpp:3892-3950): the new anchor of a 1-d inverse-depth feature whose anchor clone leaves -- among the
+// first size - 2 clones of the window, the one that observed the feature, is not in rmIDs and reprojects its position closest to
+// its observation there (first of equals); the newest clone if there is none, or if the window has at most two clones.
+inline StateIDType getNewAnchorId(const StateServer& ss, const Feature& feature, const std::vector<StateIDType>& rmIDs) {
+    const auto& aug = ss.imu_states_augment;
+    const int size = (int)aug.size();
+    if (size <= 2) return std::prev(aug.end())->first;
+    bool bValid = false;
+    double minDis = 99999;
+    StateIDType Id_min = 0;
+    auto it = aug.begin();
+    for (int i = 0; i < size - 2; ++i, ++it) {
+        auto ob = feature.observations.find(it->first);
+        if (ob == feature.observations.end()) continue;
+        if (std::find(rmIDs.begin(), rmIDs.end(), it->first) != rmIDs.end()) continue;
+        const double* Rc = it->second.orientation_cam;   // R_c2w
+        const double* tc = it->second.position_cam;
+        double d[3] = {feature.position[0] - tc[0], feature.position[1] - tc[1], feature.position[2] - tc[2]}, p[3];
+        for (int a = 0; a < 3; ++a) p[a] = Rc[0 * 3 + a] * d[0] + Rc[1 * 3 + a] * d[1] + Rc[2 * 3 + a] * d[2];
+        const double ex = p[0] / p[2] - ob->second.x, ey = p[1] / p[2] - ob->second.y;
+        const double dis = std::sqrt(ex * ex + ey * ey);
+        if (minDis > dis) { minDis = dis; Id_min = it->first; bValid = true; }
+    }
+    return bValid ? Id_min : std::prev(aug.end())->first;
+}
+
+// What pruneImuStateBuffer (src/orcvio.cpp:2664-2720) does to the in-state features when the clones rm_imu_state_ids leave: every
+// feature with in_state set whose anchor is among the clones it was observed by that leave gets a new anchor (3-d: the newest clone;
+// 1-d: getNewAnchorId).  Under use_schmidt a MATURE anchor (imu_state.id - id_anchor > 2) becomes a nuisance state instead: such
+// features are listed in not_handled and get no change here.  Changes come in map_server order (the reference's).
+struct AnchorChangePlan {
+    std::vector<FeatureIDType> ids;                    // the features that change anchor ...
+    std::vector<StateIDType> new_anchor_ids;           // ... their new anchors ...
+    std::vector<orcvio_msckf_anchor_change> changes;   // ... and the records of orcvio_msckf_cov_change_anchors
+    std::vector<FeatureIDType> not_handled;            // mature anchors under use_schmidt (the nuisance branch, :2668-2675)
+};
+// Returns ORCVIO_OK, or ORCVIO_ERR_INVALID (plan left partial) if an in-state feature is missing from feature_states or an anchor is not
+// a clone of the window (e.g. imu_state.id before its augmentation).
+inline int planAnchorChanges(const StateServer& ss, const MapServer& map_server, const std::vector<StateIDType>& rm_imu_state_ids,
+                             int idp_dim, bool use_schmidt, AnchorChangePlan& plan) {
+    plan = AnchorChangePlan{};
+    std::map<StateIDType, int> rank;
+    int N = 0;
+    for (const auto& kv : ss.imu_states_augment) rank[kv.first] = N++;
+    for (const auto& item : map_server) {
+        const Feature& f = item.second;
+        if (!f.in_state) continue;
+        std::vector<StateIDType> involved;
+        for (StateIDType sid : rm_imu_state_ids)
+            if (f.observations.count(sid)) involved.push_back(sid);
+        if (std::find(involved.begin(), involved.end(), f.id_anchor) == involved.end()) continue;
+        if (use_schmidt && ss.imu_state.id - f.id_anchor > 2) { plan.not_handled.push_back(f.id); continue; }
+        const StateIDType new_id = idp_dim == 3 ? ss.imu_state.id : getNewAnchorId(ss, f, involved);
+        auto slot_it = std::find(ss.feature_states.begin(), ss.feature_states.end(), f.id);
+        auto ro = rank.find(f.id_anchor), rn = rank.find(new_id);
+        if (slot_it == ss.feature_states.end() || ro == rank.end() || rn == rank.end()) return ORCVIO_ERR_INVALID;
+        orcvio_msckf_anchor_change c{};
+        c.slot = (int32_t)std::distance(ss.feature_states.begin(), slot_it);
+        c.old_anchor = ro->second;
+        c.new_anchor = rn->second;
+        std::memcpy(c.p_w, f.position, sizeof(c.p_w));
+        std::memcpy(c.p_fej, f.position_FEJ, sizeof(c.p_fej));
+        plan.ids.push_back(f.id);
+        plan.new_anchor_ids.push_back(new_id);
+        plan.changes.push_back(c);
+    }
+    return ORCVIO_OK;
+}
 
 struct UpdateOutcome {
     int status = ORCVIO_OK;
@@ -215,6 +286,66 @@ class MsckfBackend {
             ++i;
         }
         return orcvio_msckf_cov_remove_clones(h_, flags.leg_dim, idx.data(), (int32_t)idx.size());
+    }
+    // removeLostFeatures -> rmLostFeaturesCov (src/orcvio.cpp:2233, :3776-3828) on the resident covariance: the listed in-state features
+    // leave state_cov (its factor is kept), feature_states and map_server
+    int removeLostFeaturesFromCovariance(StateServer& ss, MapServer& map_server, const std::vector<FeatureIDType>& lost_ids, int idp_dim) {
+        std::vector<int32_t> slots;
+        for (FeatureIDType fid : lost_ids) {
+            auto it = std::find(ss.feature_states.begin(), ss.feature_states.end(), fid);
+            if (it != ss.feature_states.end()) slots.push_back((int32_t)std::distance(ss.feature_states.begin(), it));
+        }
+        std::sort(slots.begin(), slots.end());
+        const int rc = orcvio_msckf_cov_remove_features(h_, flags.leg_dim, (int32_t)ss.imu_states_augment.size(), idp_dim,
+                                                        (int32_t)ss.feature_states.size(), slots.data(), (int32_t)slots.size());
+        if (rc != ORCVIO_OK) return rc;
+        for (FeatureIDType fid : lost_ids) {
+            auto it = std::find(ss.feature_states.begin(), ss.feature_states.end(), fid);
+            if (it == ss.feature_states.end()) continue;
+            ss.feature_states.erase(it);
+            map_server.erase(fid);
+        }
+        return ORCVIO_OK;
+    }
+    // pruneImuStateBuffer's in-state branch (:2664-2720) on the resident covariance, BEFORE the clones leave: planAnchorChanges,
+    // orcvio_msckf_cov_change_anchors (<= 16 per call), then id_anchor and the new parameters back into map_server.  literal_3d: see
+    // include/orcvio_msckf.h.  Returns the plan (its not_handled features are the caller's: the Schmidt branch).
+    int changeAnchorsOnCovariance(const StateServer& ss, MapServer& map_server, const std::vector<StateIDType>& rm_imu_state_ids, int idp_dim,
+                                  bool use_schmidt, int literal_3d, AnchorChangePlan* plan_out = nullptr) {
+        AnchorChangePlan plan;
+        { const int rp = planAnchorChanges(ss, map_server, rm_imu_state_ids, idp_dim, use_schmidt, plan); if (rp != ORCVIO_OK) return rp; }
+        std::vector<double> R_b2w, t_b_w, t_fej, R_b2c, t_c_b;
+        std::map<StateIDType, int> index_of;
+        flattenWindow(ss, R_b2w, t_b_w, t_fej, R_b2c, t_c_b, index_of);
+        const int N = (int)index_of.size();
+        std::vector<double> poses((size_t)N * ORCVIO_POSE_STRIDE, 0.0);
+        for (int i = 0; i < N; ++i) {
+            double* r = &poses[(size_t)i * ORCVIO_POSE_STRIDE];
+            std::memcpy(r, &R_b2w[9 * i], 9 * sizeof(double)); std::memcpy(r + 9, &t_b_w[3 * i], 3 * sizeof(double));
+            std::memcpy(r + 12, &t_fej[3 * i], 3 * sizeof(double)); std::memcpy(r + 15, &R_b2c[9 * i], 9 * sizeof(double));
+            std::memcpy(r + 24, &t_c_b[3 * i], 3 * sizeof(double));
+        }
+        const int K = (int)plan.changes.size();
+        std::vector<double> param(3 * (size_t)K), rho(K);
+        for (int q0 = 0; q0 < K; q0 += 16) {
+            const int cnt = std::min(16, K - q0);
+            const int rc = orcvio_msckf_cov_change_anchors(h_, &flags, idp_dim, literal_3d, N, poses.data(), ss.imu_state.R_imu_cam0,
+                                                           ss.imu_state.t_cam0_imu, plan.changes.data() + q0, cnt, param.data() + 3 * q0,
+                                                           rho.data() + q0);
+            if (rc != ORCVIO_OK) return rc;
+        }
+        for (int q = 0; q < K; ++q) {
+            Feature& f = map_server.at(plan.ids[q]);
+            if (idp_dim == 3) {
+                std::memcpy(f.invParam, &param[3 * q], 3 * sizeof(double));
+            } else {
+                f.invDepth = rho[q];
+                f.obs_anchor[0] = param[3 * q]; f.obs_anchor[1] = param[3 * q + 1];
+            }
+            f.id_anchor = plan.new_anchor_ids[q];
+        }
+        if (plan_out) *plan_out = std::move(plan);
+        return ORCVIO_OK;
     }
 
     // ---- multi-GPU: one process per GPU, one MsckfBackend per process (include/orcvio_msckf.h "Multi-GPU") ---------------------
