@@ -628,8 +628,9 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
  *   prune_tracks     the second update of the frame: observations of the clones that leave only (CSR, window indices, p_w given);
  *                    NULL: none.  Its window is the first update's, its prior what the first update commits.
  *   prune_apply_dx   != 0: the window poses of the second update are the arena's poses incremented by the first update's dx ON THE
- *                    DEVICE (incrementState_IMUCam, src/orcvio.cpp:4468-4567: clone orientation / position and the extrinsics;
- *                    skipped when discard_large_update discards dx) -- what the reference's state is when pruneImuStateBuffer runs;
+ *                    DEVICE (incrementState_IMUCam, src/orcvio.cpp:4468-4567: clone orientation / position; every clone keeps its
+ *                    own R_b2c / t_c_b, frozen at its augmentation; skipped when discard_large_update discards dx) -- what the
+ *                    reference's state is when pruneImuStateBuffer runs;
  *                    0: the same poses as the first update (the caller's state increment does not reach into this call)
  *   remove_clones    window indices (ascending) of the clones marginalised at the end; n_remove <= 8
  * Not in this call: features ENTERING the state (orcvio_msckf_upload_new_features / _cov_commit_new_features change the state's dimension

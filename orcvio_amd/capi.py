@@ -1269,8 +1269,9 @@ def augment_state(idp_dim, H_1, H_2, r_1, sigma2, dx, P_upd):
 
 
 def increment_window(win, dx):
-    """incrementState_IMUCam (orcvio_msckf_increment_state, host arithmetic) applied to the clone poses and the extrinsics of a
-    synth.Window: the window a caller flattens for the NEXT update of the frame.  Returns (window, applied)."""
+    """incrementState_IMUCam (orcvio_msckf_increment_state, host arithmetic) applied to the clone poses of a synth.Window: the
+    window a caller flattens for the NEXT update of the frame.  Every clone keeps its own R_b2c / t_c_b (frozen at its
+    augmentation; only the IMU's extrinsic moves, and it is not part of the window).  Returns (window, applied)."""
     import dataclasses
     N = win.N
     s = MsckfState()
@@ -1286,10 +1287,8 @@ def increment_window(win, dx):
     rc = load().orcvio_msckf_increment_state(C.byref(fl), _d(dxc), C.byref(s))
     if rc < 0:
         raise MsckfError(1, 'orcvio_msckf_increment_state')
-    Rc = np.array(s.R_b2c[:]).reshape(3, 3)
-    tc = np.array(s.t_c_b[:])
-    return dataclasses.replace(win, R_b2w=R, t_b_w=t, R_b2c=np.ascontiguousarray(np.repeat(Rc[None], N, 0)),
-                               t_c_b=np.ascontiguousarray(np.repeat(tc[None], N, 0))), rc == 1
+    return dataclasses.replace(win, R_b2w=R, t_b_w=t, R_b2c=np.ascontiguousarray(win.R_b2c, dtype=np.float64).copy(),
+                               t_c_b=np.ascontiguousarray(win.t_c_b, dtype=np.float64).copy()), rc == 1
 
 
 def chi2_quantile(dof, prob=0.95):

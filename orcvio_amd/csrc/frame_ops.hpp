@@ -4,8 +4,8 @@
 // separate launches and copies each of these costs a launch slot (~4.5 us back to back on one stream), which is what bounds a frame
 // of 20 clones x 20-200 short tracks -- not the arithmetic.  HBM-bound element kernels, coalesced, one thread per output element.
 //   k_pose_step     the window poses of the frame's second update: the first update's, incremented by its dx
-//                   (incrementState_IMUCam, src/orcvio.cpp:4468-4567, clone + extrinsic part) or copied; keeps the first
-//                   update's status words for the second update's commit
+//                   (incrementState_IMUCam, src/orcvio.cpp:4468-4567, clone part; each clone keeps its own extrinsic) or copied;
+//                   keeps the first update's status words for the second update's commit
 //   k_frame_head    processModel's covariance propagation (:800-816) + stateAugmentation (:962-1010) in one pass, and the pull of
 //                   the frame's inputs out of the pinned arena (tracks, derived index arrays, in-state feature records)
 //   k_cov_remove_fac  marginalisation (:2935-2951) of the covariance AND of its resident square-root factor in one launch
@@ -46,9 +46,10 @@ __device__ __forceinline__ void dev_mat3_mul(const double* A, const double* B, d
 }
 
 // One thread per clone: pose record [R_b2w 9 | t_b_w 3 | t_fej 3 | R_b2c 9 | t_c_b 3 | pad] of the second update's window.
-// apply == 0: a copy.  apply != 0: incrementState_IMUCam's clone and extrinsic part with dx of the update that has just run
-// (left: use_larvio || use_left_perturbation, :4498, :4543; the extrinsic rotation by smallAngleQuaternion, :4512-4516), unless
-// discard_large_update discards dx (:4479-4494).  t_fej is the first estimate and stays.
+// apply == 0: a copy.  apply != 0: incrementState_IMUCam's clone part with dx of the update that has just run (left:
+// use_larvio || use_left_perturbation, :4498, :4543), unless discard_large_update discards dx (:4479-4494).  t_fej is the first
+// estimate and stays; so do R_b2c / t_c_b: a clone's extrinsic is the one it froze at its augmentation (:950-951) and the clone
+// loop (:4535-4565) never writes it -- dx[15:21] moves the IMU's extrinsic alone, which is not in the record.
 // Thread 0 also copies the status words info[0..15] of the update that has just run into `keep` (the second update's commit
 // refuses itself when the first was refused: EpilogueArgs.info_also).
 struct PoseStepArgs { const double* src; double* dst; int N, stride; const double* dx; int leg, apply, left, discard_large; const int* info; int* keep; };
@@ -71,20 +72,6 @@ __device__ __forceinline__ void pose_step_body(const double* __restrict__ src, d
         dev_so3_exp(w, Rt);
         if (left) dev_mat3_mul(Rt, r, r); else dev_mat3_mul(r, Rt, r);
         r[9] += da[3]; r[10] += da[4]; r[11] += da[5];
-        // extrinsic: R_b2c <- R_b2c * R(smallAngleQuaternion(dtheta))^T (math_utils.hpp:104-121), t_c_b += dx[18:21]
-        double q0 = 0.5 * dx[15], q1 = 0.5 * dx[16], q2 = 0.5 * dx[17], q3;
-        const double n2 = q0 * q0 + q1 * q1 + q2 * q2;
-        if (n2 <= 1.0) q3 = sqrt(1.0 - n2);
-        else {
-            const double s = 1.0 / sqrt(1.0 + n2);
-            q0 *= s; q1 *= s; q2 *= s; q3 = s;
-        }
-        const double x = q0, y = q1, z = q2, ww = q3;
-        const double RqT[9] = {1 - 2 * (y * y + z * z), 2 * (x * y + z * ww), 2 * (x * z - y * ww),
-                               2 * (x * y - z * ww), 1 - 2 * (x * x + z * z), 2 * (y * z + x * ww),
-                               2 * (x * z + y * ww), 2 * (y * z - x * ww), 1 - 2 * (x * x + y * y)};
-        dev_mat3_mul(r + 15, RqT, r + 15);
-        r[24] += dx[18]; r[25] += dx[19]; r[26] += dx[20];
     }
     for (int i = 0; i < 28; ++i) dst[(size_t)c * stride + i] = r[i];
 }

@@ -240,13 +240,17 @@ def make_new_slam_features(win: "Window", n_feat: int, seed: int = 0, outlier_fr
 
 def make_window(N: int = 30, F: int = 400, seed: int = 0, track_len=None,
                 flags: Flags | None = None, estimate_extrin: bool = False,
-                sigma_px: float | None = None, outlier_frac: float = 0.0, depth=(4.0, 12.0)) -> Window:
+                sigma_px: float | None = None, outlier_frac: float = 0.0, depth=(4.0, 12.0),
+                clone_extrinsic_spread: float = 0.0) -> Window:
     """SURVEY.md Appendix A synthetic generator.
 
     track_len: None -> every feature seen in all N clones; int M -> contiguous
     run of M clones at a random start; (lo, hi) -> ragged M_j in [lo, hi].
     outlier_frac: fraction of tracks with 12x observation noise, which the
     chi-square gate rejects (exercises the accept mask).
+    clone_extrinsic_spread: 0 -> every clone carries the EuRoC extrinsic; s > 0 -> clone i carries
+    R_b2c0 * exp(s * n_i), t_c_b0 + s * m_i (rad, m; n_i, m_i standard normal from a generator of their own): the
+    extrinsic each clone froze at its augmentation when the filter estimates it (reference src/orcvio.cpp:950-951).
     """
     flags = flags or Flags()
     rng = np.random.default_rng(seed)
@@ -261,6 +265,11 @@ def make_window(N: int = 30, F: int = 400, seed: int = 0, track_len=None,
     t_fej = t_b_w + 1e-3 * rng.standard_normal((N, 3))
     R_b2c = np.broadcast_to(R_b2c0, (N, 3, 3)).copy()
     t_c_b = np.broadcast_to(t_c_b0, (N, 3)).copy()
+    if clone_extrinsic_spread > 0:
+        erng = np.random.default_rng(50_000 + seed)   # (the draws of `rng` stay those of the default call)
+        for i in range(N):
+            R_b2c[i] = R_b2c0 @ so3_exp(clone_extrinsic_spread * erng.standard_normal(3))
+            t_c_b[i] = t_c_b0 + clone_extrinsic_spread * erng.standard_normal(3)
 
     # camera poses
     R_c2w = np.einsum('nij,nkj->nik', R_b2w, R_b2c)            # R_b2w * R_b2c^T
@@ -422,18 +431,22 @@ def subset_tracks(win: "Window", clone_ids, min_obs: int = 0) -> "Window":
                                obs_zvel=win.obs_zvel[keep].copy())
 
 
-def make_stream(flags: "Flags", sigma_px=None, cycle: int = 8, seed: int = 0, n_slam: int = 12, idp: int = 1, leg: int = LEG_DIM):
+def make_stream(flags: "Flags", sigma_px=None, cycle: int = 8, seed: int = 0, n_slam: int = 12, idp: int = 1, leg: int = LEG_DIM,
+                estimate_extrin: bool = False, clone_extrinsic_spread: float = 0.0):
     """A cycle of pre-generated filter frames at the reference's shipped operating point (sw_size 20, max_track_len 6,
     max_features_in_one_grid 1 -> hybrid filter with `n_slam` in-state features of `idp` parameter(s); config/euroc.yaml:49-109,
     config/kitti_raw.yaml:77-148): 19 / 20 clones alternating, 20-200 lost features per frame with 3-6 observations each; the
     20-clone frames carry the prune update on the two oldest clones (features seen in both) and their marginalisation.  Returns
-    (frames, P0): frames[k] = dict(w, slam, prune | None, Phi, Q, remove), P0 the 18-clone covariance the loop starts from."""
+    (frames, P0): frames[k] = dict(w, slam, prune | None, Phi, Q, remove), P0 the 18-clone covariance the loop starts from.
+    estimate_extrin: P0 keeps its extrinsic rows (estimate_extrin: 1); clone_extrinsic_spread: make_window's per-clone extrinsics.
+    The defaults give the same bytes as before either existed (bench.py's stream legs)."""
     rng = np.random.default_rng(seed)
     frames = []
     for k in range(cycle):
         N = 20 if k % 2 else 19
         F = int(rng.integers(20, 201))
-        w0 = make_window(N=N, F=F, seed=1000 + k, track_len=(3, 6), flags=flags, outlier_frac=0.05, sigma_px=sigma_px)
+        w0 = make_window(N=N, F=F, seed=1000 + k, track_len=(3, 6), flags=flags, outlier_frac=0.05, sigma_px=sigma_px,
+                         estimate_extrin=estimate_extrin, clone_extrinsic_spread=clone_extrinsic_spread)
         w = with_extra_states(w0, idp * n_slam, seed=k)
         slam = make_slam_features(w, n_slam, seed=k, outlier_frac=0.1, sigma_px=sigma_px)
         prune = None
@@ -445,7 +458,7 @@ def make_stream(flags: "Flags", sigma_px=None, cycle: int = 8, seed: int = 0, n_
         G = rng.standard_normal((leg, 12))
         frames.append(dict(w=w, slam=slam, prune=prune, Phi=np.ascontiguousarray(Phi), Q=np.ascontiguousarray(1e-7 * G @ G.T),
                            remove=[0, 1] if N == 20 else []))
-    P0 = with_extra_states(make_window(N=18, F=1, seed=5, flags=flags), idp * n_slam, seed=1).P
+    P0 = with_extra_states(make_window(N=18, F=1, seed=5, flags=flags, estimate_extrin=estimate_extrin), idp * n_slam, seed=1).P
     return frames, np.ascontiguousarray(P0)
 
 

@@ -1,8 +1,9 @@
 """Randomised soak of orcvio_msckf_io_step_frame (one filter frame in one call): random runs of frames on the resident covariance,
 each with random flags / leg_dim / window size, a random number of lost tracks (0 .. 250, sometimes all outliers), a prune update of
 0 .. 40 rows on random leaving clones (so that both the direct form of a thin stack and the square-root path take it), propagation
-and augmentation sometimes left out, 0 .. 2 clones marginalised -- against the SAME loop on the host: numpy mirrors for the covariance
-bookkeeping (oracle/mirror_cov.py), the C oracle for both updates (on the window incremented by the first update's dx when
+and augmentation sometimes left out, 0 .. 2 clones marginalised, in every third run live extrinsic rows in P and clones with extrinsics of
+their own -- against the SAME loop on the host: numpy mirrors for the covariance bookkeeping (oracle/mirror_cov.py), the C oracle for
+both updates (on the window incremented by the first update's dx with the oracle's literal increment, oracle/mirror_frame.py, when
 prune_apply_dx is drawn).  Every dx, the accept masks and the covariance at the end of every frame, at 1e-6.
 usage: python scripts/gpu_soak_step.py [seconds] [first_seed]"""
 import sys, os, json, time, dataclasses
@@ -12,6 +13,7 @@ import numpy as np
 from orcvio_amd import capi, synth
 from oracle import oracle
 from oracle import mirror_cov as mc
+from oracle import mirror_frame
 from helpers import rel
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
@@ -42,9 +44,11 @@ while time.time() < t_end:
                         discard_large_update=int(rng.integers(0, 2)))
     N = int(rng.integers(3, 22))
     frames = int(rng.integers(3, 8))
-    par = dict(seed=seed, leg=leg, variant=variant, N0=N, frames=frames)
+    extrin = seed % 3 == 0   # (not drawn from rng: the other draws of a seed stay what they were)
+    spread = 5e-3 if extrin else 0.0
+    par = dict(seed=seed, leg=leg, variant=variant, N0=N, frames=frames, extrin=extrin)
     try:
-        P = synth.make_window(N=N, F=1, seed=seed, flags=flags).P.copy()
+        P = synth.make_window(N=N, F=1, seed=seed, flags=flags, estimate_extrin=extrin).P.copy()
         upd.cov_set(P)
         good = True
         for fr in range(frames):
@@ -62,7 +66,8 @@ while time.time() < t_end:
             N = (P.shape[0] - leg) // 6
             F = int(rng.choice([0, rng.integers(1, 30), rng.integers(30, 250)], p=[0.1, 0.45, 0.45]))
             out_frac = float(rng.choice([0.0, 0.2, 1.0], p=[0.5, 0.4, 0.1]))
-            w = synth.make_window(N=N, F=max(F, 1), seed=1000 * seed + fr, flags=flags, track_len=(min(3, N), min(N, 8)), outlier_frac=out_frac, sigma_px=0.008)
+            w = synth.make_window(N=N, F=max(F, 1), seed=1000 * seed + fr, flags=flags, track_len=(min(3, N), min(N, 8)), outlier_frac=out_frac, sigma_px=0.008,
+                                  clone_extrinsic_spread=spread)
             if F == 0:
                 w = dataclasses.replace(w, p_w=w.p_w[:0].copy(), obs_ptr=np.zeros(1, np.int32), obs_clone=w.obs_clone[:0].copy(),
                                         obs_z=w.obs_z[:0].copy(), obs_zvel=w.obs_zvel[:0].copy())
@@ -74,14 +79,13 @@ while time.time() < t_end:
             prune, ref2, apply_dx = None, None, bool(rng.integers(0, 2))
             if N >= 4 and rng.integers(0, 3) > 0:
                 leave = sorted(rng.choice(N - 1, int(rng.integers(2, 4)), replace=False).tolist())
-                wp = synth.make_window(N=N, F=int(rng.integers(1, 40)), seed=2000 * seed + fr, flags=flags, track_len=(min(3, N), min(N, 8)), sigma_px=0.008)
+                wp = synth.make_window(N=N, F=int(rng.integers(1, 40)), seed=2000 * seed + fr, flags=flags, track_len=(min(3, N), min(N, 8)), sigma_px=0.008,
+                                       clone_extrinsic_spread=spread)
                 wp = dataclasses.replace(wp, R_b2w=w.R_b2w, t_b_w=w.t_b_w, t_fej=w.t_fej, R_b2c=w.R_b2c, t_c_b=w.t_c_b)
                 sub = synth.subset_tracks(wp, leave, min_obs=2)
                 if int(sub.obs_ptr[-1]) > 0:
                     prune = sub
-                    host_win = sub
-                    if apply_dx and ref is not None:
-                        host_win, applied = capi.increment_window(sub, dx1)
+                    host_win, _ = mirror_frame.prune_window(sub, dx1 if ref is not None else None, flags, apply_dx)
                     host_win = dataclasses.replace(host_win, P=P1)
                     ref2 = oracle.msckf_update(host_win, want_blocks=False, want_K=False)
                     rows = int(sum(max(2 * int(m) - 3, 0) for m in np.diff(sub.obs_ptr)))

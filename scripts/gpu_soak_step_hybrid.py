@@ -7,6 +7,7 @@ import sys, os, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from orcvio_amd import capi, synth
+from oracle import mirror_frame
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -30,9 +31,7 @@ def by_calls(u, fr, apply_dx):
     u.io_update(want_P=False, commit=True)
     out = [io['dx'].copy(), io['gamma'].copy(), io['accept'].copy(), None]
     if fr['prune'] is not None:
-        p = fr['prune']
-        if apply_dx:
-            p = capi.increment_window(p, out[0])
+        p, _ = mirror_frame.prune_window(fr['prune'], out[0], fr['prune'].flags, apply_dx)   # (the oracle's literal increment)
         io = u.io_begin(p.flags, p.N, p.F, int(p.obs_ptr[-1]), with_P=False)
         u.io_fill(io, p, with_P=False)
         u.io_update(want_P=False, commit=True)

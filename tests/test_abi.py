@@ -1,6 +1,7 @@
 """CPU tests of the C-ABI library: it loads, exports every declared symbol, its host-side
 pieces (chi-square quantile, state increment) are right, and it refuses to compute without a GPU."""
 import ctypes as C
+import dataclasses
 import os
 import re
 
@@ -8,7 +9,7 @@ import numpy as np
 import pytest
 
 from orcvio_amd import capi, synth
-from oracle import mirror
+from oracle import mirror, mirror_frame
 from helpers import GOLDEN, rel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -161,3 +162,26 @@ def test_the_committed_pmc_profile_is_of_these_sources():
     newest = sorted(glob.glob(os.path.join(root, 'profiles', 'r*_pmc_traffic.json')), key=key)[-1]
     rec = json.load(open(newest)).get('build')
     assert isinstance(rec, dict) and rec.get('source_sha16') == s1, (newest, rec, s1)
+
+
+@pytest.mark.parametrize('flags', [dict(use_larvio=1), dict(use_larvio=0, use_left_perturbation=0), dict(use_larvio=0, use_left_perturbation=1)],
+                         ids=['larvio', 'right', 'left'])
+def test_increment_window_keeps_each_clones_extrinsic(built, flags):
+    """capi.increment_window (the host's orcvio_msckf_increment_state on a window) against the oracle's literal increment, on clones
+    with extrinsics of their own: the clone poses to rounding, every clone's R_b2c / t_c_b and t_fej untouched."""
+    fl = synth.Flags(**flags)
+    w = synth.make_window(N=7, F=2, seed=6, track_len=3, flags=fl, estimate_extrin=True, clone_extrinsic_spread=5e-3)
+    dx = np.random.default_rng(9).standard_normal(22 + 6 * w.N) * 0.02
+    got, applied = capi.increment_window(w, dx)
+    ref, applied_ref, _ = mirror_frame.increment_window(w, dx, fl)
+    assert applied and applied_ref
+    assert rel(got.R_b2w, ref.R_b2w) <= 1e-14 and rel(got.t_b_w, ref.t_b_w) <= 1e-14
+    assert not np.array_equal(got.R_b2w, w.R_b2w)
+    for k in ('R_b2c', 't_c_b', 't_fej'):
+        assert np.array_equal(getattr(got, k), getattr(w, k)) and np.array_equal(getattr(got, k), getattr(ref, k)), k
+    big = dx.copy()
+    big[3] = 1.5
+    got, applied = capi.increment_window(dataclasses.replace(w, flags=synth.Flags(**dict(flags, discard_large_update=1))), big)
+    assert not applied
+    for k in ('R_b2w', 't_b_w', 't_fej', 'R_b2c', 't_c_b'):
+        assert np.array_equal(getattr(got, k), getattr(w, k)), k

@@ -82,6 +82,33 @@ def test_joint_update_with_slam_rows(upd, idp, case, on_device):
     assert np.array_equal(got['P_new'], got['P_new'].T)
 
 
+@pytest.mark.parametrize('on_device', [False, True], ids=['rows', 'features'])
+@pytest.mark.parametrize('idp', [3, 1])
+def test_in_state_rows_with_per_clone_extrinsics(upd, idp, on_device):
+    """Clones with extrinsics of their own and live extrinsic rows in P: the rows of an in-state feature read the observing clone's
+    R_b2c / t_c_b (measurementJacobian_ekf_*, reference src/orcvio.cpp:1256, :1277).  Guard: clone 0's extrinsic everywhere gives
+    another update."""
+    import dataclasses
+    w0 = synth.make_window(N=14, F=60, seed=44, track_len=(3, 9), flags=synth.Flags(use_larvio=1, estimate_td=1), estimate_extrin=True,
+                           clone_extrinsic_spread=5e-3)
+    slam = synth.make_slam_features(w0, 12, seed=idp, outlier_frac=0.25)
+    w = synth.with_extra_states(w0, idp * len(slam), seed=7)
+    ref = mh.hybrid_update(w, slam, idp)
+    assert ref['ekf_accept'].sum() > 0
+    one = dataclasses.replace(w, R_b2c=np.repeat(w.R_b2c[:1], w.N, 0), t_c_b=np.repeat(w.t_c_b[:1], w.N, 0))
+    # (the MSCKF rows alone would move too: the guard holds for the in-state rows on their own)
+    guard = rel(mh.hybrid_update(dataclasses.replace(one, obs_ptr=np.zeros(1, np.int32), p_w=w.p_w[:0]), slam, idp)['dx'],
+                mh.hybrid_update(dataclasses.replace(w, obs_ptr=np.zeros(1, np.int32), p_w=w.p_w[:0]), slam, idp)['dx'])
+    assert guard >= 100 * TOL, guard
+    got = run(upd, w, slam, idp, on_device)
+    assert np.array_equal(got['ekf_accept'], ref['ekf_accept'])
+    assert rel(got['ekf_gamma'], ref['ekf_gamma']) < 1e-9
+    assert np.array_equal(got['accept'], ref['accept'])
+    assert rel(got['dx'], ref['dx']) < TOL
+    assert rel(got['P_new'], ref['P_new']) < TOL
+    assert rel(got['G'], ref['G']) < TOL
+
+
 def test_anchor_equal_to_the_observing_state(upd):
     """state == anchor (src/orcvio.cpp:1302-1310): the 3-d row pair observes the first two parameters directly; on the
     device and through the restatement."""

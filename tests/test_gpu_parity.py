@@ -95,6 +95,33 @@ def test_flag_variants_ragged(upd, larvio, left, fej, td, seed):
     _compare(got, ref, w)
 
 
+SPREAD_SHAPES = {'config1': dict(N=20, F=120, track_len=(3, 6), outlier_frac=0.25), 'full30': dict(N=30, F=60, track_len=None, outlier_frac=0.25),
+                 'thin': dict(N=9, F=4, track_len=2), 'block40': dict(N=40, F=60, track_len=(3, 12), outlier_frac=0.25)}
+
+
+@pytest.mark.parametrize('larvio,left,fej,td', [(1, 0, 0, 0), (1, 0, 1, 1), (0, 0, 0, 0), (0, 1, 0, 0), (0, 1, 1, 1), (0, 0, 1, 0)])
+@pytest.mark.parametrize('shape', list(SPREAD_SHAPES))
+def test_flag_variants_with_per_clone_extrinsics(upd, shape, larvio, left, fej, td):
+    """Clones with extrinsics of their own (frozen at their augmentation, reference src/orcvio.cpp:950-951, read per clone by
+    measurementJacobian_msckf, :1080-1082) and live extrinsic rows in P: the config-1 shape, full 30-clone tracks, a thin stack of
+    one row per track and the 40-clone window of the 2 x 2 block factorisation -- against the C oracle and the numpy mirror.
+    Guard: the same window with clone 0's extrinsic everywhere gives another update."""
+    from oracle import mirror
+    f = synth.Flags(use_larvio=larvio, use_left_perturbation=left, if_fej=fej, estimate_td=td)
+    w = synth.make_window(seed=500 + 7 * larvio + 3 * left + fej, flags=f, estimate_extrin=True, clone_extrinsic_spread=5e-3,
+                          **SPREAD_SHAPES[shape])
+    ref = oracle.msckf_update(w)
+    assert ref['accept'].sum() > 0
+    one = dataclasses.replace(w, R_b2c=np.repeat(w.R_b2c[:1], w.N, 0), t_c_b=np.repeat(w.t_c_b[:1], w.N, 0))
+    guard = rel(oracle.msckf_update(one)['dx'], ref['dx'])
+    assert guard >= 100 * TOL, guard
+    got = upd.update_features(w, want_G=True)
+    _compare(got, ref, w)
+    ref_np = mirror.msckf_update(w)
+    assert np.array_equal(got['accept'], ref_np['accept'])
+    assert rel(got['dx'], ref_np['dx']) < TOL and rel(got['P_new'], ref_np['P_new']) < TOL
+
+
 def test_config1_euroc_shape(upd):
     w = synth.config_window(1)
     _compare(upd.update_features(w, want_G=True), oracle.msckf_update(w), w)

@@ -95,14 +95,15 @@ def test_cpp_stream_harness_both_modes_agree(built, tmp_path):
 
 def test_step_frame_with_the_state_increment_on_the_device(built):
     """prune_apply_dx: the second update's window = the first update's poses incremented by its dx (incrementState_IMUCam,
-    reference src/orcvio.cpp:4468-4567) on the device -- against the separate calls with the host's increment between them."""
-    import dataclasses
+    reference src/orcvio.cpp:4468-4567) on the device -- against the separate calls with the oracle's literal increment
+    (oracle/mirror_frame.py increment_window, not the library's) between them."""
+    from oracle import mirror_frame
     for fl in (synth.Flags(use_larvio=1), synth.Flags(use_larvio=0, use_left_perturbation=0), synth.Flags(use_larvio=0, use_left_perturbation=1)):
         frames, P0 = synth.make_stream(fl)
         a, b = _handle(), _handle()
 
         def incremented(p, dx):
-            return capi.increment_window(p, dx)[0]
+            return mirror_frame.increment_window(p, dx, p.flags)[0]
         try:
             a.cov_set(P0); b.cov_set(P0)
             for it in range(8):

@@ -48,6 +48,19 @@ def test_config_windows(upd, cfg):
     _compare(upd.triangulate(w), mt.triangulate_tracks(w))
 
 
+def test_per_clone_extrinsics(upd):
+    """Clones with extrinsics of their own: every observation's camera pose from its own clone's R_b2c / t_c_b.  Guard: clone 0's
+    extrinsic everywhere moves the solutions."""
+    w = synth.make_window(N=12, F=80, seed=37, track_len=(2, 12), outlier_frac=0.1, estimate_extrin=True, clone_extrinsic_spread=5e-3)
+    ref = mt.triangulate_tracks(w)
+    ok = ref['valid'] == 1
+    assert ok.sum() > 40
+    one = mt.triangulate_tracks(dataclasses.replace(w, R_b2c=np.repeat(w.R_b2c[:1], w.N, 0), t_c_b=np.repeat(w.t_c_b[:1], w.N, 0)))
+    both = ok & (one['valid'] == 1)
+    assert rel(one['p_w'][both], ref['p_w'][both]) >= 100 * TOL
+    _compare(upd.triangulate(w), ref)
+
+
 def test_thresholds_and_iteration_limits(upd):
     w = synth.make_window(N=10, F=60, seed=31, track_len=(2, 9), outlier_frac=0.3)
     for c in (mt.OptimizationConfig(translation_threshold=0.05, cost_threshold=1e-5),

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from orcvio_amd import synth
-from oracle import mirror, oracle
+from oracle import mirror, mirror_frame, oracle
 from helpers import rel, golden_files, window_from_golden, subset_window, GOLDEN
 
 
@@ -156,6 +156,73 @@ def test_increment_state_discard(built):
     dx[6] = 0.1
     s2, applied = mirror.increment_state(st, dx, f)
     assert applied and np.isclose(s2['p'][0], 0.1)
+
+
+@pytest.mark.parametrize('flags', [dict(use_larvio=1), dict(use_larvio=0, use_left_perturbation=0, noise_feature=1.0, discard_large_update=1),
+                                   dict(use_larvio=0, use_left_perturbation=1)], ids=['larvio', 'right', 'left'])
+def test_increment_window_keeps_each_clones_extrinsic(built, flags):
+    """mirror_frame.increment_window: incrementState_IMUCam (reference src/orcvio.cpp:4468-4567) on a window whose clones carry extrinsics
+    of their own -- the clone poses move as increment_state moves them, every clone's R_b2c / t_c_b and t_fej stay as they were,
+    only the IMU's extrinsic takes dx[15:21]."""
+    fl = synth.Flags(**flags)
+    w = synth.make_window(N=8, F=40, seed=3, track_len=(3, 8), flags=fl, estimate_extrin=True, clone_extrinsic_spread=5e-3,
+                          sigma_px=0.008)
+    assert len({w.R_b2c[i].tobytes() for i in range(w.N)}) == w.N and len({w.t_c_b[i].tobytes() for i in range(w.N)}) == w.N
+    ref = mirror.msckf_update(w)
+    c = oracle.msckf_update(w)
+    assert ref['updated'] and np.array_equal(c['accept'], ref['accept'])
+    assert rel(c['dx'], ref['dx']) <= 1e-10 and rel(c['P_new'], ref['P_new']) <= 1e-10
+    dx = ref['dx']
+    assert np.abs(dx[15:21]).max() > 0   # the extrinsic rows are live
+    out, applied, (R_imu, t_imu) = mirror_frame.increment_window(w, dx, fl)
+    assert applied
+    assert np.array_equal(out.R_b2c, w.R_b2c) and np.array_equal(out.t_c_b, w.t_c_b) and np.array_equal(out.t_fej, w.t_fej)
+    st = dict(R_b2w_imu=np.eye(3), v=np.zeros(3), p=np.zeros(3), bg=np.zeros(3), ba=np.zeros(3), R_b2c=w.R_b2c[-1], t_c_b=w.t_c_b[-1],
+              td=np.zeros(()), R_b2w=w.R_b2w, t_b_w=w.t_b_w)
+    s, applied = mirror.increment_state(st, dx, fl)
+    assert applied
+    assert np.array_equal(out.R_b2w, s['R_b2w']) and np.array_equal(out.t_b_w, s['t_b_w'])
+    assert np.array_equal(R_imu, s['R_b2c']) and np.array_equal(t_imu, s['t_c_b'])
+    assert not np.array_equal(R_imu, w.R_b2c[-1]) and not np.array_equal(t_imu, w.t_c_b[-1])
+    assert not np.array_equal(out.R_b2w, w.R_b2w)
+    # discard_large_update: the window comes back unchanged
+    big = dx.copy()
+    big[6] = 2.0
+    fd = synth.Flags(**dict(flags, discard_large_update=1))
+    out, applied, _ = mirror_frame.increment_window(w, big, fd)
+    assert not applied
+    for k in ('R_b2w', 't_b_w', 't_fej', 'R_b2c', 't_c_b'):
+        assert np.array_equal(getattr(out, k), getattr(w, k)), k
+
+
+def test_synthetic_inputs_default_to_one_extrinsic():
+    """make_window / make_stream without the new parameters equal the explicit-zero call array for array (bench.py's stream legs
+    read make_stream); with a spread only the extrinsics and what is drawn through them (p_w, the observations) change."""
+    def arrays(win):
+        return [win.R_b2w, win.t_b_w, win.t_fej, win.R_b2c, win.t_c_b, win.p_w, win.obs_ptr, win.obs_clone, win.obs_z, win.obs_zvel, win.P]
+    a = synth.make_window(N=9, F=30, seed=4, track_len=(3, 6))
+    b = synth.make_window(N=9, F=30, seed=4, track_len=(3, 6), clone_extrinsic_spread=0.0)
+    assert all(np.array_equal(x, y) for x, y in zip(arrays(a), arrays(b)))
+    c = synth.make_window(N=9, F=30, seed=4, track_len=(3, 6), clone_extrinsic_spread=5e-3)
+    for k in ('R_b2w', 't_b_w', 't_fej', 'obs_ptr', 'obs_clone', 'obs_zvel', 'P'):   # (p_w: drawn in the middle clone's camera)
+        assert np.array_equal(getattr(a, k), getattr(c, k)), k
+    assert not np.array_equal(a.obs_z, c.obs_z) and not np.array_equal(a.p_w, c.p_w)
+    dR = np.array([np.linalg.norm(c.R_b2c[i] - a.R_b2c[i]) for i in range(9)])
+    dt = np.linalg.norm(c.t_c_b - a.t_c_b, axis=1)
+    assert np.all((dR > 1e-4) & (dR < 0.1)) and np.all((dt > 1e-4) & (dt < 0.05))
+    for fl, sp in ((synth.Flags(use_larvio=1), None),
+                   (synth.Flags(use_larvio=0, use_left_perturbation=0, noise_feature=1.0, discard_large_update=1), 0.008)):
+        fa, Pa = synth.make_stream(fl, sigma_px=sp)
+        fb, Pb = synth.make_stream(fl, sigma_px=sp, estimate_extrin=False, clone_extrinsic_spread=0.0)
+        assert np.array_equal(Pa, Pb)
+        for x, y in zip(fa, fb):
+            assert all(np.array_equal(p, q) for p, q in zip(arrays(x['w']), arrays(y['w'])))
+            assert (x['prune'] is None) == (y['prune'] is None)
+            if x['prune'] is not None:
+                assert all(np.array_equal(p, q) for p, q in zip(arrays(x['prune']), arrays(y['prune'])))
+            assert np.array_equal(x['Phi'], y['Phi']) and np.array_equal(x['Q'], y['Q']) and x['remove'] == y['remove']
+            assert all(np.array_equal(getattr(s, k), getattr(t, k)) for s, t in zip(x['slam'], y['slam'])
+                       for k in ('inv_param', 'obs_anchor', 'p_w', 'z', 'z_vel', 'p_fej'))
 
 
 @pytest.mark.parametrize('flags', [dict(use_larvio=1), dict(use_larvio=0, use_left_perturbation=0, estimate_td=1, if_fej=1),
