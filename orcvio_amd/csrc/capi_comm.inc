@@ -393,7 +393,8 @@ int32_t orcvio_msckf_update_object_tracks_sharded(orcvio_msckf_handle* h, const 
         { const int rw = comm_stream_wait(h, h->comm_stream, "update_object_tracks_sharded"); if (rw != ORCVIO_OK) return rw; }
         for (int r = 0; r < world; ++r) dof_total += (int)h->h_dofs[r];
     }
-    rc = objects_finish_impl(h, base, world, slot, base + ne, dof_total, s);
+    UpdateCall c;
+    rc = objects_finish_impl(h, base, world, slot, base + ne, dof_total, s, c);
     if (rc != ORCVIO_OK) return rc;
     rc = download_enqueue(h, s, res->P_out != nullptr);
     if (rc != ORCVIO_OK) return rc;

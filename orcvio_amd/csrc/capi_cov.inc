@@ -14,8 +14,9 @@ int32_t orcvio_msckf_profile_update(orcvio_msckf_handle* h, void* stream, int32_
     // stages see the stream as the update itself does (a host round trip per stage would add its dispatch latency to every figure).
     hipEvent_t ev[10];
     for (int k = 0; k <= nk; ++k) HIPCHK(hipEventCreate(&ev[k]));
-    const bool front = front_fused_active(h);   // k_front = tracks + compression + chol(P) in one launch: reported as entry 0
-    const bool defer = front_defers_assembly(h);
+    UpdateCall c;   // (a plain update)
+    const bool front = front_fused_active(h, false);   // k_front = tracks + compression + chol(P) in one launch: reported as entry 0
+    const bool defer = front_defers_assembly(h, false);
     for (int k = 0; k < nk; ++k) ms[k] = 0.0;
     std::vector<float> samples[9];   // per kernel: the MEDIAN over the repetitions is reported (one preempted launch is not the kernel's time)
     for (int r = 0; r < reps; ++r) {
@@ -25,10 +26,10 @@ int32_t orcvio_msckf_profile_update(orcvio_msckf_handle* h, void* stream, int32_
             if (!(front && k >= 1 && k <= 3)) {
                 int rc = ORCVIO_OK;
                 h->A_deferred = defer;
-                if (k == 0) rc = front ? launch_front(h, s, h->d_A, defer) : launch_feature(h, s);
+                if (k == 0) rc = front ? launch_front(h, s, c, h->d_A, defer) : launch_feature(h, s);
                 else if (k == 1) rc = launch_gram(h, s);
                 else if (k == 2) rc = launch_assemble(h, s, h->d_A);
-                else rc = launch_solve_stage(h, s, k - 3);
+                else rc = launch_solve_stage(h, s, k - 3, c);
                 if (rc != ORCVIO_OK) return rc;
                 ran[k] = true;
             }
@@ -54,11 +55,11 @@ int32_t orcvio_msckf_profile_update(orcvio_msckf_handle* h, void* stream, int32_
             int rc = ORCVIO_OK;
             HIPCHK(hipEventRecord(ev[0], s));
             for (int q = 0; q < K && rc == ORCVIO_OK; ++q) {
-                rc = launch_solve_stage(h, s, ST_FORM_M);
-                if (rc == ORCVIO_OK) rc = launch_solve_stage(h, s, ST_POTRF_M);
+                rc = launch_solve_stage(h, s, ST_FORM_M, c);
+                if (rc == ORCVIO_OK) rc = launch_solve_stage(h, s, ST_POTRF_M, c);
             }
             HIPCHK(hipEventRecord(ev[1], s));
-            for (int q = 0; q < K && rc == ORCVIO_OK; ++q) rc = launch_solve_stage(h, s, ST_FORM_M);
+            for (int q = 0; q < K && rc == ORCVIO_OK; ++q) rc = launch_solve_stage(h, s, ST_FORM_M, c);
             HIPCHK(hipEventRecord(ev[2], s));
             HIPCHK(hipEventSynchronize(ev[2]));
             if (rc != ORCVIO_OK) return rc;
@@ -77,11 +78,11 @@ int32_t orcvio_msckf_profile_update(orcvio_msckf_handle* h, void* stream, int32_
     int no = 0;
     for (int k = 0; k < nk; ++k) {
         if (k == 3 + ST_TRSM && fused_solve_active(h)) continue;   // nothing launched: part of k_potrf_solve(M)
-        if (k == 3 + ST_FINISH && finish_fused_active(h)) continue;   // nothing launched: part of k_potrf_solve_la(M) (LaFin)
+        if (k == 3 + ST_FINISH && finish_fused_active(h, c)) continue;   // nothing launched: part of k_potrf_solve_la(M) (LaFin)
         if (front && k >= 1 && k <= 3) continue;                   // part of k_front
         ms[no] = ms[k];
         names[no] = (k == 3 + ST_POTRF_M && fused_solve_active(h))
-                        ? (la_solve_active(h, (h->kf - h->tail + 15) / 16) ? "k_potrf_solve_la(M)" : "k_potrf_solve(M)")
+                        ? (la_solve_active(h, (h->kf - h->tail + 15) / 16, false) ? "k_potrf_solve_la(M)" : "k_potrf_solve(M)")
                         : ((front && k == 0) ? "k_front" : kn[k]);
         ++no;
     }
@@ -151,9 +152,7 @@ int32_t orcvio_msckf_cov_augment(orcvio_msckf_handle* h) {
         hipLaunchKernelGGL(k_fac_augment, dim3((h->fac_k * m + 255) / 256), dim3(256), 0, h->stream, h->d_Sres, h->fac_ld, h->fac_k, n,
                            n - h->n_extra, h->d_Stmp, ldo);
         HIPCHK(hipGetLastError());
-        std::swap(h->d_Sres, h->d_Stmp);
-        h->fac_n = m; h->fac_ld = ldo;
-        h->fac_tail = 0;   // (the new clone's rows are copies of IMU rows: not zero in the trailing columns)
+        fac_adopt(h, m, h->fac_k, ldo, 0);   // (tail 0: the new clone's rows are copies of IMU rows, not zero in the trailing columns)
     } else h->fac_valid = false;
     return ORCVIO_OK;
 }
@@ -179,8 +178,7 @@ static int cov_remove_rows(orcvio_msckf_handle* h, const std::vector<char>& drop
         hipLaunchKernelGGL(k_fac_remove, dim3((h->fac_k * m + 255) / 256), dim3(256), 0, s, h->d_Sres, h->fac_ld, h->fac_k, h->d_covmap, m,
                            h->d_Stmp, ldo);
         HIPCHK(hipGetLastError());
-        std::swap(h->d_Sres, h->d_Stmp);
-        h->fac_n = m; h->fac_ld = ldo;
+        fac_adopt(h, m, h->fac_k, ldo, h->fac_tail);
     } else h->fac_valid = false;
     std::swap(h->d_Pres, h->d_Ptmp);
     h->res_n = m;
@@ -231,7 +229,7 @@ int32_t orcvio_msckf_cov_clones_to_nuisance(orcvio_msckf_handle* h, int32_t leg,
         hipLaunchKernelGGL(k_fac_remove, dim3((h->fac_k * n + 255) / 256), dim3(256), 0, s, h->d_Sres, h->fac_ld, h->fac_k, h->d_covmap, n,
                            h->d_Stmp, h->fac_ld);
         HIPCHK(hipGetLastError());
-        std::swap(h->d_Sres, h->d_Stmp);
+        fac_adopt(h, n, h->fac_k, h->fac_ld, h->fac_tail);
     } else h->fac_valid = false;
     std::swap(h->d_Pres, h->d_Ptmp);
     return ORCVIO_OK;
@@ -342,8 +340,7 @@ int32_t orcvio_msckf_cov_commit(orcvio_msckf_handle* h) {
                            h->last_update_objects ? h->d_obj_accept : (const int*)nullptr, pf.base, pf.sLi, pf.sLj, h->d_Stmp, h->ldz,
                            (const int*)(h->d_info + 2));
         HIPCHK(hipGetLastError());
-        std::swap(h->d_Sres, h->d_Stmp);
-        h->fac_n = n; h->fac_k = kf; h->fac_ld = h->ldz; h->fac_valid = true; h->fac_tail = h->tail;
+        fac_adopt(h, n, kf, h->ldz, h->tail);
     }
     HIPCHK(hipMemcpyAsync(h->d_Pres, h->d_Pout, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, s));
     if (s != h->stream) HIPCHK(hipStreamSynchronize(s));   // the other cov_* calls run on the handle's own stream
@@ -417,19 +414,11 @@ int32_t orcvio_msckf_cov_prefactor(orcvio_msckf_handle* h) {
     // factor comes out with its rows in reverse order: it is written to scratch and flipped into place, and its last 15 columns
     // are zero in the active rows (fac_tail)
     const double eps = 2.220446049250313e-16;
-    const int need = potrf_slots_needed(nb);
     const bool rev = h->rev_prior_opt && h->fused_solve && n - 15 >= 16;
     double* dst = rev ? h->d_KG : h->d_Stmp;   // (d_KG: scratch of the optional outputs, free between updates)
-#define LAUNCH_PF(NS) hipLaunchKernelGGL(k_potrf_reg<NS>, dim3(1), dim3(512), 0, s, (const double*)h->d_Pres, n, n, 8.0 * eps, dst, ld, h->d_DinvP, \
-                                         h->d_info, (unsigned long long*)nullptr, (size_t)0, (size_t)0, (size_t)0, 0, 0, 1, rev ? 1 : 0)
-    if (need <= 4) LAUNCH_PF(4);
-    else if (need <= 8) LAUNCH_PF(8);
-    else if (need <= 12) LAUNCH_PF(12);
-    else LAUNCH_PF(16);
-#undef LAUNCH_PF
+    { const int rp = launch_potrf_reg_slots(s, h->d_Pres, n, n, 8.0 * eps, dst, ld, h->d_DinvP, h->d_info, 1, rev ? 1 : 0); if (rp != ORCVIO_OK) return rp; }
     if (rev) hipLaunchKernelGGL(k_fac_flip, dim3((n * ld + 255) / 256), dim3(256), 0, s, (const double*)dst, ld, n, h->d_Stmp, ld);
     HIPCHK(hipGetLastError());
-    std::swap(h->d_Sres, h->d_Stmp);
-    h->fac_n = n; h->fac_k = n; h->fac_ld = ld; h->fac_valid = true; h->fac_tail = rev ? 15 : 0;
+    fac_adopt(h, n, n, ld, rev ? 15 : 0);
     return ORCVIO_OK;
 }

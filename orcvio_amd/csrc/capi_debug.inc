@@ -186,7 +186,8 @@ int32_t orcvio_msckf_debug_potrf_stamps(orcvio_msckf_handle* h, unsigned long lo
     const bool cold = dbg_getenv("ORCVIO_POTRF_COLD") != nullptr && h->ran;
     for (int rep = 0; rep < 4; ++rep) {
         if (cold) {
-            const int rcf = launch_solve_stage(h, h->stream, ST_FORM_M);
+            UpdateCall c;
+            const int rcf = launch_solve_stage(h, h->stream, ST_FORM_M, c);
             if (rcf != ORCVIO_OK) return rcf;
             hipLaunchKernelGGL(k_potrf_reg<16>, dim3(1), dim3(512), 0, h->stream, h->d_M, NP, h->kf, 0.0, h->d_RM, NP, h->d_DinvM,
                                h->d_info + 6, d, (size_t)0, (size_t)0, (size_t)0, 0, ablate, 0);
@@ -239,23 +240,13 @@ int32_t orcvio_msckf_debug_potrf_solve(orcvio_msckf_handle* h, const double* X, 
     unsigned long long* d_st = nullptr;
     if (stamps) { HIPCHK(hipMalloc(&d_st, sizeof(unsigned long long) * 512)); HIPCHK(hipMemset(d_st, 0, sizeof(unsigned long long) * 512)); }
     hipStream_t s = h->stream;
-    const int nb = (n + 15) / 16, need = potrf_slots_needed(nb);
-    const int ncb = (nrhs + 15) / 16;
     auto once = [&](unsigned long long* st) -> int {
         HIPCHK(hipMemsetAsync(h->d_flag, 0, sizeof(int), s));
         HIPCHK(hipMemsetAsync(h->d_la_rdy, 0, 64, s));
         if (la) return launch_potrf_solve_la(h, s, la, h->d_M, NP, n, h->d_RM, NP, h->d_DinvM, h->d_info + 2, h->d_flag, h->d_la_rdy, h->d_info + 8,
                                              h->d_U, (long)nrhs, 1L, nrhs, nullptr, 0L, h->d_Z, ldz, 0, 0.0, st);
-        const dim3 grid(1 + (ncb + SOLVE_WPB - 1) / SOLVE_WPB), block(512);
-#define DBG_PS(NS) hipLaunchKernelGGL(k_potrf_solve<NS>, grid, block, 0, s, (const double*)h->d_M, NP, n, 0.0, h->d_RM, NP, h->d_DinvM, h->d_info + 2, \
-                                      h->d_flag, h->d_info + 8, (const double*)h->d_U, (long)nrhs, 1L, nrhs, (const double*)nullptr, 0L, h->d_Z, ldz, 0, 0.0)
-        if (need <= 4) DBG_PS(4);
-        else if (need <= 8) DBG_PS(8);
-        else if (need <= 12) DBG_PS(12);
-        else DBG_PS(16);
-#undef DBG_PS
-        HIPCHK(hipGetLastError());
-        return ORCVIO_OK;
+        return launch_potrf_solve_slots(s, h->d_M, NP, n, h->d_RM, NP, h->d_DinvM, h->d_info + 2, h->d_flag, h->d_info + 8, h->d_U, (long)nrhs, 1L, nrhs, nullptr, 0L,
+                                        h->d_Z, ldz, 0, 0.0);
     };
     int rc = once(d_st);
     if (rc == ORCVIO_OK && reps > 0 && us_out) {

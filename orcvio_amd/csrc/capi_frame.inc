@@ -9,17 +9,20 @@
 // stream of its own right behind the launch of the feature update and runs BESIDE the features' solve; the object solve joins
 // both.  Same kernels, same arguments, same results as orcvio_msckf_io_update(commit) + orcvio_msckf_update_object_tracks.
 
-// the two calls in sequence on what stands in the arena (the reference form; also the fall-back of the overlapped form)
+// the two calls in sequence on what stands in the arena (the reference form; also the fall-back of the overlapped form);
+// retry_forked: the repeat of a frame that lost an in-launch hand-off -- BOTH halves take the one-workgroup factorisation + solve
 static int frame_sequential(orcvio_msckf_handle* h, orcvio_msckf_result* res_f, const FeatureView& v, const orcvio_msckf_flags* oflags,
                             const orcvio_object_eval_flags* efl, int N, const orcvio_object_track* tracks, int n_tracks, int commit_objects,
-                            orcvio_msckf_result* res_o) {
-    int rc = io_run(h, false, true, res_f->stats);
+                            orcvio_msckf_result* res_o, bool retry_forked = false) {
+    UpdateCall cf, co;
+    cf.retry_forked = co.retry_forked = retry_forked;
+    int rc = io_run(h, false, true, res_f->stats, cf);
     if (rc != ORCVIO_OK) { res_f->stats[3] = 0; return rc; }   // (refused: nothing was applied)
     const char* so = h->h_stage + h->in_cap;
     if (res_f->dx) std::memcpy(res_f->dx, so + v.oo_dx, sizeof(double) * v.n);
     if (res_f->gamma) std::memcpy(res_f->gamma, so + v.oo_gamma, sizeof(double) * v.F);
     if (res_f->accept) std::memcpy(res_f->accept, so + v.oo_accept, sizeof(int32_t) * v.F);
-    rc = orcvio_msckf_update_object_tracks(h, oflags, efl, N, tracks, n_tracks, nullptr, res_o);
+    rc = update_object_tracks_impl(h, oflags, efl, N, tracks, n_tracks, nullptr, res_o, co);
     if (rc == ORCVIO_OK && commit_objects) rc = orcvio_msckf_cov_commit(h);
     return rc;
 }
@@ -30,27 +33,12 @@ static int frame_sequential(orcvio_msckf_handle* h, orcvio_msckf_result* res_f, 
 // once (it is valid either way: a refused commit leaves the prior and a copy of its factor).  Saves the frame the host round trip of a
 // separate cov_commit (k_fac_commit + a device-to-device copy of P+, ~10 us after the results were read).
 static int publish_commit_enqueue(orcvio_msckf_handle* h, hipStream_t s) {
-    const int n = h->n;
-    EpilogueArgs ea{};
-    ea.small_src = reinterpret_cast<const u32x4*>(h->d_outs);
-    ea.small_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap + h->out_shift);
-    ea.small16 = h->outs_small / 16;
-    ea.P16 = 0; ea.nb_P = 0;
-    ea.commit = 2;
-    ea.Pout = h->d_Pout; ea.Pres = h->d_Pres; ea.nn = (size_t)n * n;
-    const PriorFactor pf = prior_factor(h);
-    ea.Z = h->d_Z; ea.ldz = h->ldz; ea.kf = h->kf; ea.n = n; ea.sigma = h->flags.noise_feature;
-    ea.prior = pf.base; ea.sLi = pf.sLi; ea.sLj = pf.sLj; ea.Sout = h->d_Stmp; ea.ldo = h->ldz;
-    ea.dx = h->d_dx; ea.info = h->d_info; ea.accept = h->d_obj_accept;
-    ea.counter = h->d_pubcnt; ea.seq = h->d_seq; ea.flag = h->h_flag_dev;
-    ea.info_also = h->d_step_words;   // (the feature half's status words, kept by its epilogue: a refused feature half -- chol(M1) not PD -- refuses this commit too; ADVICE r5)
-    hipLaunchKernelGGL(k_epilogue, dim3(1 + 40), dim3(256), 0, s, ea);
-    HIPCHK(hipGetLastError());
+    // info_also: the feature half's status words, kept by its epilogue -- a refused feature half (chol(M1) not PD) refuses this commit too; ADVICE r5
+    const int rc = launch_epilogue(s, epilogue_args(h, solve_out(h), h->out_shift, false, 2, h->d_obj_accept, h->d_step_words));
+    if (rc != ORCVIO_OK) return rc;
     h->pub_pending = true;
     h->pub_enqueued++;
-    std::swap(h->d_Sres, h->d_Stmp);
-    h->fac_n = n; h->fac_k = h->kf; h->fac_ld = h->ldz; h->fac_valid = true; h->fac_tail = h->tail;
-    h->res_n = n;
+    fac_adopt_update(h);
     return ORCVIO_OK;
 }
 
@@ -113,9 +101,9 @@ static int frame_chain_solve(orcvio_msckf_handle* h, const ChainGeom& g, unsigne
         const size_t o_dx = 256, o_gamma = o_dx + al256(sizeof(double) * n), o_accept = o_gamma + al256(sizeof(double)), o_Pout = o_accept + al256(sizeof(int));
         fin.P_out = reinterpret_cast<double*>(h->d_outs2 + o_Pout); fin.dx = reinterpret_cast<double*>(h->d_outs2 + o_dx);
         fin.P = h->d_Pres; fin.keep_tail = 0;
-        fin.gate.rr = h->d_A + (size_t)NA * NAP + NA; fin.gate.thr = dof > 0 ? orcvio_msckf_chi2_quantile(dof, chi2_prob) : -1.0;   // (the OBJECT update's flags: h->flags are still the feature half's here)
-        fin.gate.gamma = h->d_obj_gamma; fin.gate.accept = h->d_obj_accept;
-        fin.gate.gamma_out = reinterpret_cast<double*>(h->d_outs2 + o_gamma); fin.gate.accept_out = reinterpret_cast<int*>(h->d_outs2 + o_accept);
+        // (the threshold from the OBJECT update's flags: h->flags are still the feature half's here, as are h->NA / h->NAP = g's)
+        fin.gate = object_gate(h, dof > 0 ? orcvio_msckf_chi2_quantile(dof, chi2_prob) : -1.0, reinterpret_cast<double*>(h->d_outs2 + o_gamma),
+                               reinterpret_cast<int*>(h->d_outs2 + o_accept), nullptr);
         h->chain_fin_oo = o_Pout;
         fin.wait_word = h->d_chain_words + 1; fin.wait_expect = w2;   // (a rejected update copies P+: what the feature half commits)
         nfin = (ncb * (ncb + 1) / 2 + 1) / 2;
@@ -130,7 +118,7 @@ static int frame_chain_solve(orcvio_msckf_handle* h, const ChainGeom& g, unsigne
 // part 2: the gate + P++ + dx, the results and the commit
 static int frame_chain_finish(orcvio_msckf_handle* h, const ChainGeom& g, int dof, size_t obj_shift, unsigned w2) {
     hipStream_t sb = h->obj_stream;
-    const int n = g.n, NA = g.NA, NAP = g.NAP, ldz = g.ldz, kf = g.kf;
+    const int n = g.n, ldz = g.ldz, kf = g.kf;
     const double sigma2 = g.sigma * g.sigma;
     int* info2 = reinterpret_cast<int*>(h->d_outs2);
     double* dx2 = reinterpret_cast<double*>(h->d_outs2 + h->oo_dx);
@@ -141,35 +129,19 @@ static int frame_chain_finish(orcvio_msckf_handle* h, const ChainGeom& g, int do
     h->obj_thr = dof > 0 ? orcvio_msckf_chi2_quantile(dof, h->flags.chi2_prob) : -1.0;
     if (h->chain_fin_dof != dof || h->chain_fin_thr != h->obj_thr || h->chain_fin_oo != h->oo_Pout) {   // (else: decided and written by the finish workgroups of the factorisation launch, LaFin)
         const int nb = (n + 1 + 15) / 16, tiles = nb * (nb + 1) / 2;
-        ObjGate gate;
-        gate.fail = info2 + 2;
-        gate.rr = h->d_A + (size_t)NA * NAP + NA; gate.thr = h->obj_thr;
-        gate.gamma = h->d_obj_gamma; gate.accept = h->d_obj_accept;
-        gate.gamma_out = reinterpret_cast<double*>(h->d_outs2 + h->oo_gamma); gate.accept_out = reinterpret_cast<int*>(h->d_outs2 + h->oo_accept);
+        const ObjGate gate = object_gate(h, h->obj_thr, reinterpret_cast<double*>(h->d_outs2 + h->oo_gamma), reinterpret_cast<int*>(h->d_outs2 + h->oo_accept), info2 + 2);
         hipLaunchKernelGGL(k_finish_sqrt, dim3(tiles), dim3(256), 0, sb, (const double*)h->d_Z2, ldz, n, kf, sigma2, Pout2, dx2, gate, (const double*)h->d_Pres, 0);
     }
     HIPCHK(hipGetLastError());
     // results + commit in one launch (as publish_commit_enqueue), from the second outputs arena; the flag rises behind the commit too
-    EpilogueArgs ea{};
-    ea.small_src = reinterpret_cast<const u32x4*>(h->d_outs2);
-    ea.small_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap + obj_shift);
-    ea.small16 = h->outs_small / 16;
-    ea.P16 = 0; ea.nb_P = 0;
-    ea.commit = 2;
-    ea.Pout = Pout2; ea.Pres = h->d_Pres; ea.nn = (size_t)n * n;
-    ea.Z = h->d_Z2; ea.ldz = ldz; ea.kf = kf; ea.n = n; ea.sigma = g.sigma;
-    ea.prior = h->d_Sres; ea.sLi = 1L; ea.sLj = (long)h->fac_ld;   // (a rejected object update keeps the factor the feature half committed)
-    ea.Sout = h->d_Stmp; ea.ldo = ldz;
-    ea.dx = dx2; ea.info = info2; ea.accept = h->d_obj_accept;
-    ea.counter = h->d_pubcnt; ea.seq = h->d_seq; ea.flag = h->h_flag_dev;
-    ea.pub_all = 1;
-    ea.info_also = h->d_info;   // (a refused feature half -- its M1 is not to be trusted -- refuses this commit too)
-    hipLaunchKernelGGL(k_epilogue, dim3(1 + 40), dim3(256), 0, sb, ea);
-    HIPCHK(hipGetLastError());
+    // (a rejected object update keeps the factor the feature half committed; info_also = the feature half's status words: a refused
+    //  feature half -- its M1 is not to be trusted -- refuses this commit too)
+    const SolveOut so2{h->d_outs2, Pout2, dx2, info2, h->d_Z2, ldz, kf, g.sigma, PriorFactor{h->d_Sres, 1L, (long)h->fac_ld}};
+    const int re = launch_epilogue(sb, epilogue_args(h, so2, obj_shift, false, 2, h->d_obj_accept, h->d_info, nullptr, 1));
+    if (re != ORCVIO_OK) return re;
     h->pub_pending = true;
     h->pub_enqueued++;
-    std::swap(h->d_Sres, h->d_Stmp);
-    h->fac_n = n; h->fac_k = kf; h->fac_ld = ldz; h->fac_valid = true; h->fac_tail = g.tail;
+    fac_adopt(h, n, kf, ldz, g.tail);
     h->res_n = n;
     h->ran = true; h->last_update_objects = true; h->last_run_kind = 2; h->last_sharded = false;
     h->last_stream = sb;
@@ -247,7 +219,7 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     // flight: legal only while the feature half never touches those blocks, i.e. while it defers the assembly of A (k_front leaves the
     // Grams, k_gemm_asmA assembles strips in LDS).  Whenever it assembles A in memory -- no tracks, more than ~510 tracks, NA > 192
     // (leg_dim 46 with N >= 27), more than four row chunks, ORCVIO_OPT_FUSED_FRONT = 0 -- the two halves run in sequence (ADVICE r3).
-    if (!overlap || !fac_ok || h->n_nui > 0 || !h->factor_opt || h->obj_dof_rank || res_o->P_out || res_o->G || !front_defers_assembly(h))
+    if (!overlap || !fac_ok || h->n_nui > 0 || !h->factor_opt || h->obj_dof_rank || res_o->P_out || res_o->G || !front_defers_assembly(h, false))
         return frame_sequential(h, res_f, v, oflags, efl, N, tracks, n_tracks, commit_objects, res_o);
     if (!h->obj_stream) {
         HIPCHK(hipStreamCreateWithFlags(&h->obj_stream, hipStreamNonBlocking));
@@ -291,7 +263,7 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     // the chained object solve (above): opt-in, for frames whose objects all take the one-launch compression and commit in the call
     bool chain = h->frame_chain && early && !frame_graph && commit_objects != 0 && !h->ekf_mode && h->n_extra == 0 && oflags->leg_dim == fflags.leg_dim &&
                  oflags->noise_feature == fflags.noise_feature &&   // (M12 = M1 + L_a^T A' L_a holds for ONE sigma)
-                 fused_solve_active(h) && la_solve_active(h, (h->kf - h->tail + 15) / 16) && front_fused_active(h);
+                 fused_solve_active(h) && la_solve_active(h, (h->kf - h->tail + 15) / 16, false) && front_fused_active(h, false);
     const bool signal_done = !chain;   // (the chained solve runs on the compression's own stream: no completion word to poll)
     unsigned w1 = 0u, w2 = 0u;
     int chain_rc = ORCVIO_OK;
@@ -300,7 +272,6 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
         const int rb = chain_buffers(h);
         if (rb != ORCVIO_OK) return rb;
         w1 = ++h->chain_seq; w2 = w1;
-        h->mark_M_word = h->d_chain_words; h->mark_M_val = w1;   // (launch_solve_stage(ST_FORM_M) of the feature half stores it)
     }
     const ChainGeom cgeom{prior_factor(h), h->n, h->NA, h->NAP, h->NP, h->ldz, h->kf, h->tail, h->flags.noise_feature};   // (the FEATURE update's solve, before the book-keeping below)
     std::function<int()> mid = [&]() -> int {
@@ -313,23 +284,22 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
         if (chain && early_rc == ORCVIO_OK) { chain_rc = frame_chain_solve(h, cgeom, w1, w2, early_dof, oflags->chi2_prob); chain_part1 = true; }
         return ORCVIO_OK;   // (a refusal of the object half must not stop the feature half: it is reported below)
     };
-    h->fin_frame = chain;   // (the feature half's P+ / dx by finish workgroups of its solve launch: finish_fused_active)
     { const int rw = step_words(h); if (rw != ORCVIO_OK) return rw; }
-    h->epi_info_keep = h->d_step_words;   // (its epilogue keeps a copy of its status words for the object half's commit)
-    if (frame_graph) rc = run_with_graph(h, h->g_io, io_signature(h, s, false, true), s, [&](bool) { return io_enqueue(h, s, false, true); });
-    else { rc = io_enqueue(h, s, false, true, early ? &mid : nullptr); h->cnt_plain_runs++; }
-    h->fin_frame = false;
-    h->epi_info_keep = nullptr;
-    h->A_deferred = front_defers_assembly(h);
+    UpdateCall cf;   // the feature half
+    cf.fin_frame = chain;   // (its P+ / dx by finish workgroups of its solve launch: finish_fused_active)
+    cf.info_keep = h->d_step_words;   // (its epilogue keeps a copy of its status words for the object half's commit)
+    if (chain) { cf.mark_M_word = h->d_chain_words; cf.mark_M_val = w1; }   // (launch_solve_stage(ST_FORM_M) stores it)
+    if (frame_graph) rc = run_with_graph(h, h->g_io, io_signature(h, s, false, true, cf), s, [&](bool) { return io_enqueue(h, s, false, true, cf); });
+    else { cf.mid = early ? &mid : nullptr; rc = io_enqueue(h, s, false, true, cf); h->cnt_plain_runs++; }
+    h->A_deferred = front_defers_assembly(h, false);
     tmark(1);
     if (chain && rc == ORCVIO_OK) {   // the word behind the feature half's epilogue (its commit): a launch of its own, behind the kernel boundary
-        if (h->mark_M_word) {   // (the feature half did not pass ST_FORM_M -- not the shape this is for: release what waits for the word, drop the chain)
-            h->mark_M_word = nullptr; chain = false;
+        if (cf.mark_M_word) {   // (the feature half did not pass ST_FORM_M -- not the shape this is for: release what waits for the word, drop the chain)
+            chain = false;
             hipLaunchKernelGGL(k_obj_done, dim3(1), dim3(64), 0, s, h->d_chain_words, w1);
         }
         else hipLaunchKernelGGL(k_obj_done, dim3(1), dim3(64), 0, s, h->d_chain_words + 1, w2);
     }
-    h->mark_M_word = nullptr;
     if (rc != ORCVIO_OK) {
         // The feature half could not be enqueued to its end, but `mid` may have put the objects' compression and the chained solve on the
         // objects' stream already: its launches poll words that will never rise.  Release them, drain both streams, clear the second
@@ -355,14 +325,8 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     //  free again whenever the caller can write it.)
     // the host-side book-keeping of that commit, AHEAD of its results (undone below if the device refuses the update): the object
     // solve enqueued next takes the factor the epilogue is going to write
-    struct Undo { double *Sres, *Stmp; int fac_n, fac_k, fac_ld, fac_tail, res_n; bool fac_valid; } undo{h->d_Sres, h->d_Stmp, h->fac_n, h->fac_k, h->fac_ld, h->fac_tail, h->res_n, h->fac_valid};
-    std::swap(h->d_Sres, h->d_Stmp);
-    h->fac_n = h->n; h->fac_k = h->kf; h->fac_ld = h->ldz; h->fac_valid = true; h->fac_tail = h->tail;
-    h->res_n = h->n;
-    auto roll_back = [&]() {
-        h->d_Sres = undo.Sres; h->d_Stmp = undo.Stmp;
-        h->fac_n = undo.fac_n; h->fac_k = undo.fac_k; h->fac_ld = undo.fac_ld; h->fac_tail = undo.fac_tail; h->res_n = undo.res_n; h->fac_valid = undo.fac_valid;
-    };
+    const CovState undo = cov_state(h);
+    fac_adopt_update(h);
     // the feature results land at the start of the pinned output block; the object results go where P+ would have gone
     const size_t obj_shift = (h->oo_Pout + 63) & ~(size_t)63;
     // ---- objects: staging on the host while the tracks of the feature update run, compression on its own stream
@@ -388,12 +352,13 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
         // which costs ~10 us of dispatch on this stream even when the event fired long ago (ORCVIO_FRAME_EVENT_JOIN=1: the event, as the
         // general path takes it)
         static const bool event_join = [] { const char* e = dbg_getenv("ORCVIO_FRAME_EVENT_JOIN"); return e && atoi(e) != 0; }();
-        if (h->obj_last_fused && !event_join && signal_done) { h->join_wait = h->d_obj_done; h->join_expect = h->obj_done_total; }
+        UpdateCall co;   // the object half's solve
+        if (h->obj_last_fused && !event_join && signal_done) { co.join_wait = h->d_obj_done; co.join_expect = h->obj_done_total; }
         else {
             if (!early || !signal_done) HIPCHK(hipEventRecord(h->ev_obj, h->obj_stream));   // (!signal_done: the chain was dropped after the compression went out without its event)
             HIPCHK(hipStreamWaitEvent(s, h->ev_obj, 0));
         }
-        rco = objects_finish_impl(h, h->d_A, 1, 0, nullptr, dof, s);
+        rco = objects_finish_impl(h, h->d_A, 1, 0, nullptr, dof, s, co);
     }
     if (rco == ORCVIO_OK && !chain) {
         h->out_shift = obj_shift;
@@ -417,22 +382,18 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
         (void)hipStreamSynchronize(h->obj_stream);
         (void)hipStreamSynchronize(s);
         h->dl_pending = false; h->pub_pending = false; h->out_shift = 0; h->objects_mode = false; h->ran = false;
-        roll_back();
+        cov_restore(h, undo);
         if (!redo) { res_f->stats[3] = 0; return rc; }   // (refused: nothing was applied)
-        HIPCHK(hipMemset(h->d_info + 8, 0, sizeof(int)));
-        HIPCHK(hipMemset(h->d_sync, 0, 256));
-        HIPCHK(hipMemset(h->d_la_rdy, 0, 256));   // (the words of the look-ahead factorisations: a lost hand-off leaves them as they were)
-        h->front_fallbacks++;
+        { const int rh = handoff_reset(h); if (rh != ORCVIO_OK) return rh; }
         const bool keep_fused = h->front_fused;
-        h->front_fused = false;   // (plain launches, no in-launch device-wide wait, for the repeat)
-        h->front_retry_forked = true;   // (... and the one-workgroup factorisation + solve: the far workgroups of the look-ahead form are
-                                        //  one more thing that has to be co-resident; both halves of the repeat)
+        h->front_fused = false;   // (plain launches, no in-launch device-wide wait, for the repeat ... and, retry_forked, the one-workgroup
+                                  //  factorisation + solve: the far workgroups of the look-ahead form are one more thing that has to be
+                                  //  co-resident; both halves of the repeat)
         rc = upload_begin(h, &fflags, N, F, nobs, false, true, who);
         if (rc == ORCVIO_OK) rc = ingest_raw(h, h->stream);
         if (rc == ORCVIO_OK) { h->io_open = true; rc = upload_finalize(h, who); }
-        if (rc == ORCVIO_OK) { h->pw_missing = false; rc = frame_sequential(h, res_f, v, oflags, efl, N, tracks, n_tracks, commit_objects, res_o); }
+        if (rc == ORCVIO_OK) { h->pw_missing = false; rc = frame_sequential(h, res_f, v, oflags, efl, N, tracks, n_tracks, commit_objects, res_o, true); }
         h->front_fused = keep_fused;
-        h->front_retry_forked = false;
         return rc;
     }
     if (res_f->dx) std::memcpy(res_f->dx, so + v.oo_dx, sizeof(double) * v.n);

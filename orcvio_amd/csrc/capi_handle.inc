@@ -227,26 +227,6 @@ static bool obj_publish_kernel() {
     static const bool v = [] { const char* e = dbg_getenv("ORCVIO_OBJ_PUBLISH"); return e ? atoi(e) != 0 : false; }();
     return v;
 }
-// the results of the update on `s` -> the pinned output block, then the flag (k_epilogue without a commit): what replaces
-// the device-to-host copy + stream synchronisation of the one-shot calls
-static int publish_enqueue(orcvio_msckf_handle* h, hipStream_t s, bool want_P) {
-    EpilogueArgs ea{};
-    ea.small_src = reinterpret_cast<const u32x4*>(h->d_outs);
-    ea.small_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap + h->out_shift);
-    ea.small16 = h->outs_small / 16;
-    ea.P_src = reinterpret_cast<const u32x4*>(h->d_outs + h->oo_Pout);
-    ea.P_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap + h->out_shift + h->oo_Pout);
-    ea.P16 = want_P ? (sizeof(double) * (size_t)h->n * h->n + 15) / 16 : 0;
-    ea.nb_P = want_P ? 40 : 0;
-    ea.commit = 0;
-    ea.counter = h->d_pubcnt; ea.seq = h->d_seq; ea.flag = h->h_flag_dev;
-    hipLaunchKernelGGL(k_epilogue, dim3(1 + ea.nb_P), dim3(256), 0, s, ea);
-    HIPCHK(hipGetLastError());
-    h->pub_pending = true;
-    h->pub_enqueued++;
-    return ORCVIO_OK;
-}
-
 // ---- create / destroy ---------------------------------------------------------------------
 static void free_all(orcvio_msckf_handle* h) {
     (void)hipDeviceSynchronize();   // (asynchronous copies out of the pinned buffers, a commit's tail: nothing of this handle is in flight any more)
@@ -523,7 +503,7 @@ static int comm_stream_wait(orcvio_msckf_handle* h, hipStream_t s, const char* w
 static int ipc_check_lost(orcvio_msckf_handle* h, const char* who);
 static int feature_outcome(orcvio_msckf_handle* h, const char* so, int32_t* stats);
 static int run_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, int n_blocks, size_t stride, const double* meta0, hipStream_t s);
-static int objects_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, int n_blocks, size_t stride, const double* meta0, int dof_total, hipStream_t s);
+static int objects_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, int n_blocks, size_t stride, const double* meta0, int dof_total, hipStream_t s, UpdateCall& c);
 // Gram of the rows stacked under the MSCKF rows (EKF-SLAM rows that passed their gate, caller-projected dense rows)
 static inline const double* extra_gram(const orcvio_msckf_handle* h) { return (h->ekf_F > 0 || h->dense_rows > 0) ? h->d_Gekf : nullptr; }
 
@@ -550,4 +530,71 @@ static PriorFactor prior_factor(const orcvio_msckf_handle* h) {
     long sLi, sLj;
     factor_strides(h, sLi, sLj);
     return PriorFactor{h->d_RP, sLi, sLj};
+}
+
+// ---- what the last launch of an update publishes and commits -------------------------------------------------------------------
+// The buffers one solve leaves its results in: the handle's own (solve_out), or the frame call's second context (capi_frame.inc).
+struct SolveOut {
+    const char* outs;         // outputs arena: [info | dx | gamma | accept | P+]
+    const double* Pout;       // P+ inside it
+    const double* dx;
+    const int* info;          // its status words
+    const double* Z; int ldz, kf;
+    double sigma;
+    PriorFactor prior;        // the factor a rejected or refused update keeps
+};
+static inline SolveOut solve_out(const orcvio_msckf_handle* h) {
+    return SolveOut{h->d_outs, h->d_Pout, h->d_dx, h->d_info, h->d_Z, h->ldz, h->kf, h->flags.noise_feature, prior_factor(h)};
+}
+// k_epilogue's arguments: the small block (and P+ if want_P) to the pinned output block at dst_shift, the commit (0: none, 1: P+ over the
+// resident covariance, 2: ... and S+ = sigma Z^T into the spare factor buffer), then the flag.  accept: the gate's word of an object update.
+static EpilogueArgs epilogue_args(const orcvio_msckf_handle* h, const SolveOut& so, size_t dst_shift, bool want_P, int commit, const int* accept,
+                                  const int* info_also, int* info_keep = nullptr, int pub_all = 0) {
+    const int n = h->n;
+    EpilogueArgs ea{};
+    ea.small_src = reinterpret_cast<const u32x4*>(so.outs);
+    ea.small_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap + dst_shift);
+    ea.small16 = h->outs_small / 16;
+    if (want_P) {
+        ea.P_src = reinterpret_cast<const u32x4*>(so.outs + h->oo_Pout);
+        ea.P_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap + dst_shift + h->oo_Pout);
+        ea.P16 = (sizeof(double) * (size_t)n * n + 15) / 16;
+        ea.nb_P = 40;
+    }
+    ea.commit = commit;
+    ea.Pout = so.Pout; ea.Pres = h->d_Pres; ea.nn = (size_t)n * n;
+    ea.Z = so.Z; ea.ldz = so.ldz; ea.kf = so.kf; ea.n = n; ea.sigma = so.sigma;
+    ea.prior = so.prior.base; ea.sLi = so.prior.sLi; ea.sLj = so.prior.sLj; ea.Sout = h->d_Stmp; ea.ldo = so.ldz;
+    ea.dx = so.dx; ea.info = so.info; ea.accept = accept;
+    ea.counter = h->d_pubcnt; ea.seq = h->d_seq; ea.flag = h->h_flag_dev;
+    ea.info_also = info_also; ea.info_keep = info_keep; ea.pub_all = pub_all;
+    return ea;
+}
+static int launch_epilogue(hipStream_t s, const EpilogueArgs& ea) {
+    hipLaunchKernelGGL(k_epilogue, dim3(1 + ea.nb_P + (ea.commit ? 40 : 0)), dim3(256), 0, s, ea);
+    HIPCHK(hipGetLastError());
+    return ORCVIO_OK;
+}
+// k_finish_pub's: the finish of a feature update, its commit (P+ into the SPARE covariance buffer) and the publication in one launch
+static FinishPubArgs finish_pub_args(const orcvio_msckf_handle* h, const SolveOut& so, int commit, const int* info_also) {
+    FinishPubArgs fp{};
+    fp.Z = so.Z; fp.ldz = so.ldz; fp.n = h->n; fp.kdim = so.kf; fp.s2 = so.sigma * so.sigma; fp.P = h->d_P; fp.dx = h->d_dx;
+    fp.commit = commit;
+    fp.P_dst = commit ? h->d_Ptmp : h->d_Pout;
+    fp.sigma = so.sigma; fp.prior = so.prior.base; fp.sLi = so.prior.sLi; fp.sLj = so.prior.sLj; fp.Sout = h->d_Stmp; fp.ldo = so.ldz;
+    fp.info = so.info; fp.info_also = info_also;
+    fp.small_src = reinterpret_cast<const u32x4*>(so.outs);
+    fp.small_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap);
+    fp.small16 = h->outs_small / 16;
+    fp.counter = h->d_pubcnt; fp.seq = h->d_seq; fp.flag = h->h_flag_dev;
+    return fp;
+}
+// the results of the update on `s` -> the pinned output block, then the flag (k_epilogue without a commit): what replaces
+// the device-to-host copy + stream synchronisation of the one-shot calls
+static int publish_enqueue(orcvio_msckf_handle* h, hipStream_t s, bool want_P) {
+    const int rc = launch_epilogue(s, epilogue_args(h, solve_out(h), h->out_shift, want_P, 0, nullptr, nullptr));
+    if (rc != ORCVIO_OK) return rc;
+    h->pub_pending = true;
+    h->pub_enqueued++;
+    return ORCVIO_OK;
 }

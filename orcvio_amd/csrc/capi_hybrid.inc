@@ -596,17 +596,21 @@ int32_t orcvio_msckf_download_ekf(orcvio_msckf_handle* h, double* gamma, int32_t
     return ORCVIO_OK;
 }
 
-int32_t orcvio_msckf_run_update(orcvio_msckf_handle* h, void* stream) {
+static int run_update_impl(orcvio_msckf_handle* h, void* stream, UpdateCall& c) {
     if (!h || !h->uploaded) { g_last_error = "run_update: nothing uploaded"; return ORCVIO_ERR_INVALID; }
     if (h->pw_missing) { g_last_error = "run_update: tracks were uploaded without positions and have not been triangulated"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = pick_stream(h, stream);
     h->last_stream = s;
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }   // (a copy of the previous results nobody fetched)
-    int rc = run_with_graph(h, h->g_update, launch_signature(h, s, nullptr, 0), s, [&](bool) { return enqueue_update(h, s); });
-    h->A_deferred = front_defers_assembly(h);   // (a replayed graph does not pass through enqueue_update)
+    int rc = run_with_graph(h, h->g_update, launch_signature(h, s, nullptr, 0, c), s, [&](bool) { return enqueue_update(h, s, c); });
+    h->A_deferred = front_defers_assembly(h, c.retry_forked);   // (a replayed graph does not pass through enqueue_update)
     if (rc == ORCVIO_OK) { h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false; }
     return rc;
+}
+int32_t orcvio_msckf_run_update(orcvio_msckf_handle* h, void* stream) {
+    UpdateCall c;
+    return run_update_impl(h, stream, c);
 }
 
 int32_t orcvio_msckf_sync(orcvio_msckf_handle* h, void* stream) {

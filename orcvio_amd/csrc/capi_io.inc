@@ -46,7 +46,18 @@ static int download_enqueue(orcvio_msckf_handle* h, hipStream_t sd, bool with_P)
     return ORCVIO_OK;
 }
 
-int32_t orcvio_msckf_download(orcvio_msckf_handle* h, orcvio_msckf_result* res) {
+// An update whose in-launch hand-off was lost, run again on the forked path (plain launches, no in-launch device-wide wait, the
+// one-workgroup factorisation + solve) on what is uploaded already, with the copy of its results behind it
+static int rerun_forked(orcvio_msckf_handle* h, hipStream_t s, bool want_P) {
+    UpdateCall c;
+    c.retry_forked = true;
+    int rr = run_update_impl(h, s, c);
+    if (rr == ORCVIO_OK) rr = download_enqueue(h, s ? s : h->stream, want_P);
+    return rr;
+}
+
+// retried: this is the look at the results of the repeat
+static int download_impl(orcvio_msckf_handle* h, orcvio_msckf_result* res, bool retried) {
     if (!h || !res || !h->ran) { g_last_error = "download: no finished update"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     const int n = h->n, NA = h->NA, NAP = h->NAP, NP = h->NP, F = h->F;
@@ -76,18 +87,12 @@ int32_t orcvio_msckf_download(orcvio_msckf_handle* h, orcvio_msckf_result* res) 
     std::memcpy(info, so, sizeof(int) * 16);
     if (info[8] != 0) {   // a wait inside a launch gave up: a workgroup of k_front at its device-wide counter (somebody else's kernel
                           // held CUs it needed), or a solver wavefront of k_potrf_solve
-        HIPCHK(hipMemset(h->d_info + 8, 0, sizeof(int)));
-        HIPCHK(hipMemset(h->d_sync, 0, 256));
-        HIPCHK(hipMemset(h->d_la_rdy, 0, 256));   // (the words of the look-ahead factorisations: a lost hand-off leaves them as they were)
-        if (h->last_run_kind == 0 && !h->front_retry_forked) {
-            // single-GPU update: run it again, on the forked path (plain launches, no in-launch device-wide wait), inside this call
-            h->front_retry_forked = true;
-            h->front_fallbacks++;
-            int rr = orcvio_msckf_run_update(h, h->last_stream);
-            if (rr == ORCVIO_OK) rr = download_enqueue(h, h->last_stream ? h->last_stream : h->stream, want_P);
-            h->front_retry_forked = false;
+        const bool again = h->last_run_kind == 0 && !retried;   // single-GPU update: run it again inside this call
+        { const int rh = handoff_reset(h, again); if (rh != ORCVIO_OK) return rh; }
+        if (again) {
+            const int rr = rerun_forked(h, h->last_stream, want_P);
             if (rr != ORCVIO_OK) return rr;
-            return orcvio_msckf_download(h, res);   // (a second time-out in the forked form is reported as an error below)
+            return download_impl(h, res, true);   // (a second time-out in the forked form is reported as an error below)
         }
         // the solve ran through on stale bytes: nothing of this update may be committed (ADVICE r2)
         h->ran = false;
@@ -138,13 +143,14 @@ int32_t orcvio_msckf_download(orcvio_msckf_handle* h, orcvio_msckf_result* res) 
     }
     return ORCVIO_OK;
 }
+int32_t orcvio_msckf_download(orcvio_msckf_handle* h, orcvio_msckf_result* res) { return download_impl(h, res, false); }
 
 // ---- the zero-copy update (orcvio_msckf_io_begin / _io_update; the copying one-shot calls run on it too) ----------------------
 // ONE graph launch per update: k_ingest (pinned arena -> HBM) -> the update's kernels -> k_epilogue (results -> host-coherent
 // memory, [the commit of P+ and its square-root factor], then the flag).  No copy-engine transfer, no stream
 // synchronisation: the calling thread spins on the flag.
-static unsigned long long io_signature(const orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool commit, bool finpub = false) {
-    unsigned long long sig = launch_signature(h, s, h->h_stage_dev, (long)(0x100 | (want_P ? 1 : 0) | (commit ? 2 : 0) | (finpub ? 4 : 0)));
+static unsigned long long io_signature(const orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool commit, const UpdateCall& c, bool finpub = false) {
+    unsigned long long sig = launch_signature(h, s, h->h_stage_dev, (long)(0x100 | (want_P ? 1 : 0) | (commit ? 2 : 0) | (finpub ? 4 : 0)), c);
     auto mix = [&](unsigned long long v) { sig = (sig ^ v) * 1099511628211ull; };
     mix((unsigned long long)upload_bytes(h)); mix((unsigned long long)h->io_poses); mix((unsigned long long)(size_t)h->d_Stmp); mix((unsigned long long)(size_t)h->d_Pres);
     mix(h->factor_opt); mix((unsigned long long)h->outs_small); mix((unsigned long long)(size_t)h->d_Ptmp); mix(h->finpub_opt);
@@ -160,56 +166,23 @@ static int step_words(orcvio_msckf_handle* h) {
 }
 
 // k_finish_sqrt + k_epilogue as ONE launch (k_finish_pub): feature updates on the in-place paths whose finish is a launch of its own
-static inline bool finpub_active(const orcvio_msckf_handle* h) {
-    return h->finpub_opt && !h->objects_mode && h->n_nui == 0 && !finish_fused_active(h);
+static inline bool finpub_active(const orcvio_msckf_handle* h, const UpdateCall& c) {
+    return h->finpub_opt && !h->objects_mode && h->n_nui == 0 && !finish_fused_active(h, c);
 }
-static int io_enqueue(orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool commit, const std::function<int()>* mid = nullptr, const int* info_also = nullptr,
-                      bool allow_finpub = false) {
-    const int n = h->n;
-    const bool fac = commit && h->factor_opt && h->n_nui == 0;
-    const PriorFactor pf = prior_factor(h);
-    const bool fp_on = allow_finpub && finpub_active(h) && !want_P;   // (P+ to the host: k_finish_sqrt + k_epilogue's copy workgroups are faster, profiles/r6a)
-    FinishPubArgs fp{};
-    if (fp_on) {
-        fp.commit = commit ? (fac ? 2 : 1) : 0;
-        fp.P_dst = commit ? h->d_Ptmp : h->d_Pout;
-        fp.sigma = h->flags.noise_feature; fp.prior = pf.base; fp.sLi = pf.sLi; fp.sLj = pf.sLj; fp.Sout = h->d_Stmp; fp.ldo = h->ldz;
-        fp.info = h->d_info; fp.info_also = info_also;
-        fp.small_src = reinterpret_cast<const u32x4*>(h->d_outs);
-        fp.small_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap);
-        fp.small16 = h->outs_small / 16;
-        fp.counter = h->d_pubcnt; fp.seq = h->d_seq; fp.flag = h->h_flag_dev;
-        h->fin_pub = &fp;
-    }
-    h->last_finpub_commit = fp_on && commit;
+static int io_enqueue(orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool commit, UpdateCall& c, bool allow_finpub = false) {
+    const int mode = commit ? (h->factor_opt && h->n_nui == 0 ? 2 : 1) : 0;
+    const SolveOut so = solve_out(h);
+    c.fin_pub = allow_finpub && finpub_active(h, c) && !want_P;   // (P+ to the host: k_finish_sqrt + k_epilogue's copy workgroups are faster, profiles/r6a)
+    if (c.fin_pub) c.pub = finish_pub_args(h, so, mode, c.info_also);
+    h->last_finpub_commit = c.fin_pub && commit;
     // inputs: the derived index arrays at the head of the arena (the caller-written part behind them went ahead: ingest_raw)
     int rc = ORCVIO_OK;
-    if (h->step_ingested) h->step_ingested = false;   // (orcvio_msckf_io_step_frame: k_frame_head has pulled the whole arena)
-    else rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, early_ingest() ? h->io_poses : upload_bytes(h));
-    if (rc == ORCVIO_OK) rc = enqueue_update(h, s, mid);
-    h->fin_pub = nullptr;
-    if (rc != ORCVIO_OK || fp_on) return rc;
+    if (!c.already_ingested) rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, early_ingest() ? h->io_poses : upload_bytes(h));
+    if (rc == ORCVIO_OK) rc = enqueue_update(h, s, c);
+    if (rc != ORCVIO_OK || c.fin_pub) return rc;
     // ONE launch behind the update: the results to host-coherent memory, the commit (refused on the device if the update is),
     // and the flag the caller waits on (k_epilogue)
-    EpilogueArgs ea{};
-    ea.small_src = reinterpret_cast<const u32x4*>(h->d_outs);
-    ea.small_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap);
-    ea.small16 = h->outs_small / 16;
-    ea.P_src = reinterpret_cast<const u32x4*>(h->d_outs + h->oo_Pout);
-    ea.P_dst = reinterpret_cast<u32x4*>(h->h_stage_dev + h->in_cap + h->oo_Pout);
-    ea.P16 = want_P ? (sizeof(double) * (size_t)n * n + 15) / 16 : 0;
-    ea.nb_P = want_P ? 40 : 0;
-    ea.commit = commit ? (fac ? 2 : 1) : 0;
-    ea.Pout = h->d_Pout; ea.Pres = h->d_Pres; ea.nn = (size_t)n * n;
-    ea.Z = h->d_Z; ea.ldz = h->ldz; ea.kf = h->kf; ea.n = n; ea.sigma = h->flags.noise_feature;
-    ea.prior = pf.base; ea.sLi = pf.sLi; ea.sLj = pf.sLj; ea.Sout = h->d_Stmp; ea.ldo = h->ldz;
-    ea.dx = h->d_dx; ea.info = h->d_info;
-    ea.counter = h->d_pubcnt; ea.seq = h->d_seq; ea.flag = h->h_flag_dev;
-    ea.info_also = info_also;   // (orcvio_msckf_io_step_frame: a refused first update refuses the second update's commit as well)
-    ea.info_keep = h->epi_info_keep;
-    hipLaunchKernelGGL(k_epilogue, dim3(1 + ea.nb_P + (commit ? 40 : 0)), dim3(256), 0, s, ea);
-    HIPCHK(hipGetLastError());
-    return ORCVIO_OK;
+    return launch_epilogue(s, epilogue_args(h, so, 0, want_P, mode, nullptr, c.info_also, c.info_keep));
 }
 
 // Wait for the next publication: spin on the host-coherent flag (bounded), then fall back to a stream synchronisation.
@@ -286,15 +259,16 @@ static int feature_outcome_view(orcvio_msckf_handle* h, const FeatureView& v, co
 }
 
 // the update on what stands in the arena (after upload_finalize), first half: ONE launch (captured graph or plain), nothing waited for
-static int io_launch(orcvio_msckf_handle* h, bool want_P, bool commit) {
+static int io_launch(orcvio_msckf_handle* h, bool want_P, bool commit, UpdateCall& c) {
     if (h->pw_missing) { g_last_error = "update: tracks were uploaded without positions and have not been triangulated"; return ORCVIO_ERR_INVALID; }
     hipStream_t s = h->stream;
     h->last_stream = s;
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }
-    int rc = run_with_graph(h, h->g_io, io_signature(h, s, want_P, commit, finpub_active(h) && !want_P), s, [&](bool) { return io_enqueue(h, s, want_P, commit, nullptr, nullptr, true); });
-    h->A_deferred = front_defers_assembly(h);   // (a replayed graph does not pass through enqueue_update)
-    h->last_finpub_commit = commit && finpub_active(h) && !want_P;   // (... nor through io_enqueue)
-    h->last_update_thin = finpub_active(h) && !want_P && thin_possible(h);
+    const bool finpub = finpub_active(h, c) && !want_P;
+    int rc = run_with_graph(h, h->g_io, io_signature(h, s, want_P, commit, c, finpub), s, [&](bool) { return io_enqueue(h, s, want_P, commit, c, true); });
+    h->A_deferred = front_defers_assembly(h, c.retry_forked);   // (a replayed graph does not pass through enqueue_update)
+    h->last_finpub_commit = commit && finpub;   // (... nor through io_enqueue)
+    h->last_update_thin = finpub && thin_possible(h, c);
     if (h->last_update_thin) h->A_deferred = false;
     if (rc != ORCVIO_OK) return rc;
     h->pub_enqueued++;   // (one k_epilogue per launch, captured or not)
@@ -303,10 +277,10 @@ static int io_launch(orcvio_msckf_handle* h, bool want_P, bool commit) {
 }
 // ... second half: the results are in the pinned output block when this returns
 static int io_finish(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats);
-static int io_run(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats) {
+static int io_run(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats, UpdateCall& c) {
     static const bool timing = dbg_getenv("ORCVIO_TIMING") != nullptr;
     const auto tl0 = std::chrono::steady_clock::now();
-    int rc = io_launch(h, want_P, commit);
+    int rc = io_launch(h, want_P, commit, c);
     if (rc != ORCVIO_OK) return rc;
     const auto tl1 = std::chrono::steady_clock::now();
     rc = io_finish(h, want_P, commit, stats);
@@ -317,6 +291,12 @@ static int io_run(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* sta
                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl1).count());
     }
     return rc;
+}
+// the committing update on what stands in the arena, run the safe way: the repeat of an update of a frame that lost an in-launch hand-off
+static int io_run_forked(orcvio_msckf_handle* h, int32_t* stats) {
+    UpdateCall c;
+    c.retry_forked = true;
+    return io_run(h, false, true, stats, c);
 }
 static int io_finish(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats) {
     hipStream_t s = h->stream;
@@ -330,14 +310,8 @@ static int io_finish(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* 
         // wait), inside this call; the inputs are in HBM already.  The commit workgroups of the first attempt refuse themselves
         // on info[8] -- and may still be at it (the flag rises before they are done): the stream is drained before the word is cleared.
         HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemset(h->d_info + 8, 0, sizeof(int)));
-        HIPCHK(hipMemset(h->d_sync, 0, 256));
-        HIPCHK(hipMemset(h->d_la_rdy, 0, 256));   // (the words of the look-ahead factorisations: a lost hand-off leaves them as they were)
-        h->front_retry_forked = true;
-        h->front_fallbacks++;
-        int rr = orcvio_msckf_run_update(h, s);
-        if (rr == ORCVIO_OK) rr = download_enqueue(h, s, want_P);
-        h->front_retry_forked = false;
+        int rr = handoff_reset(h);
+        if (rr == ORCVIO_OK) rr = rerun_forked(h, s, want_P);
         if (rr != ORCVIO_OK) { h->ran = false; return rr; }
         HIPCHK(hipStreamSynchronize(s));
         h->dl_pending = false;
@@ -353,15 +327,8 @@ static int io_finish(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* 
     }
     rc = feature_outcome(h, so, stats);
     if (rc != ORCVIO_OK) return rc;
-    if (commit) {   // the kernels have written S+ into the spare factor buffer and P+ over the resident covariance (k_epilogue) or into the spare one (k_finish_pub)
-        if (h->last_finpub_commit) { std::swap(h->d_Pres, h->d_Ptmp); h->last_finpub_commit = false; }
-        if (h->last_update_thin) h->fac_valid = false;   // (the direct form of a thin stack leaves no square-root factor)
-        else if (h->factor_opt && h->n_nui == 0) {
-            std::swap(h->d_Sres, h->d_Stmp);
-            h->fac_n = h->n; h->fac_k = h->kf; h->fac_ld = h->ldz; h->fac_valid = true; h->fac_tail = h->tail;
-        } else if (h->n_nui > 0) h->fac_valid = false;   // Schmidt: the nuisance block of P+ is the prior's, so P+ != s2 Z^T Z
-        h->res_n = h->n;
-    }
+    // the kernels have written S+ into the spare factor buffer and P+ over the resident covariance (k_epilogue) or into the spare one (k_finish_pub)
+    if (commit) commit_bookkeeping(h);
     return ORCVIO_OK;
 }
 
@@ -412,7 +379,8 @@ int32_t orcvio_msckf_io_update(orcvio_msckf_handle* h, int32_t want_P, int32_t c
     }
     h->pw_missing = false;
     h->io_open = true;   // ... and may run the next update of the same shape without a new io_begin
-    return io_run(h, want_P != 0, commit != 0, stats);
+    UpdateCall c;
+    return io_run(h, want_P != 0, commit != 0, stats, c);
 }
 
 // orcvio_msckf_io_update in two halves: submit returns when the update has been LAUNCHED (the calling thread is free for ~0.1 ms:
@@ -426,7 +394,8 @@ int32_t orcvio_msckf_io_submit(orcvio_msckf_handle* h, int32_t want_P, int32_t c
     if (rc != ORCVIO_OK) { (void)arena_mark_read(h, h->stream); return rc; }   // (the early pull may still be reading the arena)
     h->pw_missing = false;
     h->io_open = true;
-    rc = io_launch(h, want_P != 0, commit != 0);
+    UpdateCall c;
+    rc = io_launch(h, want_P != 0, commit != 0, c);
     if (rc != ORCVIO_OK) return rc;
     h->io_submitted = true; h->io_sub_P = want_P != 0; h->io_sub_commit = commit != 0;
     return ORCVIO_OK;
@@ -448,9 +417,9 @@ int32_t orcvio_msckf_update_features(orcvio_msckf_handle* h, const orcvio_msckf_
     if (rc != ORCVIO_OK) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     const bool want_P = result->P_out != nullptr;
-    h->thin_blocked = result->H_thin || result->r_thin || result->K || result->G;   // (derived from the general path's factors)
-    rc = io_run(h, want_P, false, result->stats);
-    h->thin_blocked = false;
+    UpdateCall c;
+    c.thin_blocked = result->H_thin || result->r_thin || result->K || result->G;   // (derived from the general path's factors)
+    rc = io_run(h, want_P, false, result->stats, c);
     const auto t3 = std::chrono::steady_clock::now();
     if (rc != ORCVIO_OK) return rc;
     const int n = h->n, F = h->F;

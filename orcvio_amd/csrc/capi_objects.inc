@@ -912,7 +912,7 @@ int32_t orcvio_msckf_objects_local_tracks(orcvio_msckf_handle* h, const orcvio_m
 // Second part: rank-ordered sum of the gathered blocks, replicated solve, joint chi-square gate with the TOTAL degrees
 // of freedom of all ranks' objects, gated write-back.
 static int objects_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, int n_blocks, size_t stride, const double* meta0, int dof_total,
-                               hipStream_t s) {
+                               hipStream_t s, UpdateCall& c) {
     h->last_stream = s;
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }
     h->obj_dof = dof_total;
@@ -932,10 +932,10 @@ static int objects_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, i
     // table value below 500 dof, on the fly above (:1962-1968); dof 0 (no usable object anywhere) can never pass.  The gate is
     // decided inside k_finish_sqrt (ObjGate) -- or by the finish workgroups of the solve's launch (LaFin), which is why it is known here.
     h->obj_thr = dof_total > 0 ? orcvio_msckf_chi2_quantile(dof_total, h->flags.chi2_prob) : -1.0;
-    for (int st = ST_FORM_U; st <= ST_TRSM && rc == ORCVIO_OK; ++st) rc = launch_solve_stage(h, s, st);
+    for (int st = ST_FORM_U; st <= ST_TRSM && rc == ORCVIO_OK; ++st) rc = launch_solve_stage(h, s, st, c);
     if (rc != ORCVIO_OK) return rc;
     prof_mark(h, s, "k_gemm(U)+k_gemm(M)+k_potrf_solve(M)");
-    rc = launch_solve_stage(h, s, ST_FINISH);
+    rc = launch_solve_stage(h, s, ST_FINISH, c);
     prof_mark(h, s, "k_finish_sqrt (gate inside)");
     if (rc == ORCVIO_OK) { h->ran = true; h->last_update_objects = true; h->last_run_kind = 2; h->last_sharded = meta0 != nullptr; }
     return rc;
@@ -943,10 +943,14 @@ static int objects_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, i
 
 // Second part: rank-ordered sum of the gathered blocks, replicated solve, joint chi-square gate with the TOTAL degrees
 // of freedom of all ranks' objects, gated write-back.
-int32_t orcvio_msckf_objects_finish(orcvio_msckf_handle* h, const double* d_blocks, int32_t n_blocks, int32_t dof_total, void* stream) {
+static int objects_finish_checked(orcvio_msckf_handle* h, const double* d_blocks, int32_t n_blocks, int32_t dof_total, void* stream, UpdateCall& c) {
     if (!h || !h->uploaded || !h->objects_mode || !d_blocks || n_blocks < 1) { g_last_error = "objects_finish: no local object block"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
-    return objects_finish_impl(h, d_blocks, n_blocks, 0, nullptr, dof_total, pick_stream(h, stream));
+    return objects_finish_impl(h, d_blocks, n_blocks, 0, nullptr, dof_total, pick_stream(h, stream), c);
+}
+int32_t orcvio_msckf_objects_finish(orcvio_msckf_handle* h, const double* d_blocks, int32_t n_blocks, int32_t dof_total, void* stream) {
+    UpdateCall c;
+    return objects_finish_checked(h, d_blocks, n_blocks, dof_total, stream, c);
 }
 
 // Results of an object update (after orcvio_msckf_objects_finish): accept[0], gamma[0], dx, P_out, stats, optional G.
@@ -1084,9 +1088,10 @@ int32_t orcvio_msckf_update_objects(orcvio_msckf_handle* h, const orcvio_msckf_f
     return rc;
 }
 
-int32_t orcvio_msckf_update_object_tracks(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags, const orcvio_object_eval_flags* fl,
-                                          int32_t n_clones, const orcvio_object_track* tracks, int32_t n_tracks, const double* P,
-                                          orcvio_msckf_result* res) {
+// c: the record of the solve (the repeat of a frame call that lost a hand-off asks for the one-workgroup factorisation + solve)
+static int update_object_tracks_impl(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags, const orcvio_object_eval_flags* fl,
+                                     int32_t n_clones, const orcvio_object_track* tracks, int32_t n_tracks, const double* P,
+                                     orcvio_msckf_result* res, UpdateCall& c) {
     if (!res) { g_last_error = "update_object_tracks: null argument"; return ORCVIO_ERR_INVALID; }
     int32_t dof = 0;
     static const bool timing = dbg_getenv("ORCVIO_TIMING") != nullptr;   // diagnostics: host wall time of the three parts
@@ -1095,7 +1100,7 @@ int32_t orcvio_msckf_update_object_tracks(orcvio_msckf_handle* h, const orcvio_m
     if (rc == ORCVIO_OK) rc = objects_rank_dof(h, h->stream, &dof);
     if (rc != ORCVIO_OK) return rc;
     const auto t1 = std::chrono::steady_clock::now();
-    rc = orcvio_msckf_objects_finish(h, h->d_A, 1, dof, nullptr);
+    rc = objects_finish_checked(h, h->d_A, 1, dof, nullptr, c);
     if (rc == ORCVIO_OK) rc = obj_publish_kernel() ? publish_enqueue(h, h->stream, res->P_out != nullptr)   // results -> pinned block, then the flag
                                                    : download_enqueue(h, h->stream, res->P_out != nullptr);
     if (rc != ORCVIO_OK) return rc;
@@ -1109,7 +1114,12 @@ int32_t orcvio_msckf_update_object_tracks(orcvio_msckf_handle* h, const orcvio_m
     h->objects_mode = false;
     return rc;
 }
-
+int32_t orcvio_msckf_update_object_tracks(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags, const orcvio_object_eval_flags* fl,
+                                          int32_t n_clones, const orcvio_object_track* tracks, int32_t n_tracks, const double* P,
+                                          orcvio_msckf_result* res) {
+    UpdateCall c;
+    return update_object_tracks_impl(h, flags, fl, n_clones, tracks, n_tracks, P, res, c);
+}
 
 // ---- the object update from ObjectLM messages (SURVEY.md 8f rank 4) ----------------------------------------------------
 // Sophus v1.0.0 SE3d::exp, tangent (upsilon, omega): R = exp(omega), t = V upsilon

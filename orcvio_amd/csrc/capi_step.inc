@@ -45,27 +45,6 @@ static int step_validate_tracks(const orcvio_msckf_handle* h, const orcvio_msckf
     return ORCVIO_OK;
 }
 
-// resident covariance / factor bookkeeping of the handle: saved and restored around steps that are enqueued ahead of their outcome
-struct CovState { double *Pres, *Ptmp, *Sres, *Stmp; int res_n, fac_n, fac_k, fac_ld, fac_tail; bool fac_valid; };
-static inline CovState cov_state(const orcvio_msckf_handle* h) {
-    return CovState{h->d_Pres, h->d_Ptmp, h->d_Sres, h->d_Stmp, h->res_n, h->fac_n, h->fac_k, h->fac_ld, h->fac_tail, h->fac_valid};
-}
-static inline void cov_restore(orcvio_msckf_handle* h, const CovState& c) {
-    h->d_Pres = c.Pres; h->d_Ptmp = c.Ptmp; h->d_Sres = c.Sres; h->d_Stmp = c.Stmp;
-    h->res_n = c.res_n; h->fac_n = c.fac_n; h->fac_k = c.fac_k; h->fac_ld = c.fac_ld; h->fac_tail = c.fac_tail; h->fac_valid = c.fac_valid;
-}
-// the host-side bookkeeping of a commit that rides in the update's last launch (valid whether or not the device refuses the update:
-// a refused commit leaves the prior and a copy of its factor, io_ops.hpp k_epilogue)
-static inline void step_commit_bookkeeping(orcvio_msckf_handle* h) {
-    if (h->last_finpub_commit) { std::swap(h->d_Pres, h->d_Ptmp); h->last_finpub_commit = false; }   // (k_finish_pub wrote P+ into the spare buffer)
-    if (h->last_update_thin) h->fac_valid = false;   // (the direct form of a thin stack leaves no square-root factor)
-    else if (h->factor_opt && h->n_nui == 0) {
-        std::swap(h->d_Sres, h->d_Stmp);
-        h->fac_n = h->n; h->fac_k = h->kf; h->fac_ld = h->ldz; h->fac_valid = true; h->fac_tail = h->tail;
-    } else if (h->n_nui > 0) h->fac_valid = false;
-    h->res_n = h->n;
-}
-
 // marginalisation of the listed clones (ascending, checked by the caller), enqueued: the covariance and its resident factor in ONE
 // launch, the removed clones by value (k_cov_remove_fac) -- orcvio_msckf_cov_remove_clones' arithmetic (a gather), no index map to copy
 static int step_remove(orcvio_msckf_handle* h, int leg, const int32_t* idx, int count) {
@@ -80,7 +59,7 @@ static int step_remove(orcvio_msckf_handle* h, int leg, const int32_t* idx, int 
     hipLaunchKernelGGL(k_cov_remove_fac, dim3(nb_P + nb_F), dim3(256), 0, h->stream, (const double*)h->d_Pres, n, m, r, h->d_Ptmp, nb_P,
                        (const double*)h->d_Sres, h->fac_ld, fac ? h->fac_k : 0, h->d_Stmp, ldo);
     HIPCHK(hipGetLastError());
-    if (fac) { std::swap(h->d_Sres, h->d_Stmp); h->fac_n = m; h->fac_ld = ldo; }
+    if (fac) fac_adopt(h, m, h->fac_k, ldo, h->fac_tail);
     else h->fac_valid = false;
     std::swap(h->d_Pres, h->d_Ptmp);
     h->res_n = m;
@@ -142,12 +121,7 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
     if (rc == ORCVIO_OK) rc = upload_finalize(h, who);
     if (rc != ORCVIO_OK) return rc;
     h->pw_missing = false;
-    if (safe) {
-        h->front_retry_forked = true;
-        rc = io_run(h, false, true, stats);
-        h->front_retry_forked = false;
-        return rc;
-    }
+    if (safe) return io_run_forked(h, stats);
     h->last_stream = s;
     if (h->step_fused) {   // ONE launch in front of the update: the pose step and the pull of the tracks + derived index arrays
         FrameHeadArgs fa{};
@@ -157,15 +131,17 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
         fa.src[1] = h->h_stage_dev + h->io_optr; fa.dst[1] = h->d_in + h->io_optr; fa.bytes[1] = (unsigned)(upload_bytes(h) - h->io_optr);
         rc = launch_frame_head(h, s, fa);
         if (rc != ORCVIO_OK) return rc;
-        h->step_ingested = true;
     }
-    rc = io_enqueue(h, s, false, true, nullptr, h->d_step_words, true);
-    h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h);
+    UpdateCall c;
+    c.already_ingested = h->step_fused;   // (k_frame_head has pulled the whole arena)
+    c.info_also = h->d_step_words;        // (a refused first update refuses this update's commit as well)
+    rc = io_enqueue(h, s, false, true, c, true);
+    h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h, false);
     if (rc != ORCVIO_OK) return rc;
     h->cnt_plain_runs++;
     h->pub_enqueued++;
     h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false;
-    step_commit_bookkeeping(h);
+    commit_bookkeeping(h);
     return ORCVIO_OK;
 }
 
@@ -234,8 +210,7 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
                 HIPCHK(hipGetLastError());
                 return ORCVIO_OK;
             });
-            std::swap(h->d_Sres, h->d_Stmp);
-            h->fac_n = m; h->fac_ld = ldo; h->fac_tail = 0;
+            fac_adopt(h, m, fk, ldo, 0);
         } else h->fac_valid = false;
     }
     if (!fused && st->Phi) {
@@ -274,8 +249,7 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
                 HIPCHK(hipGetLastError());
                 return ORCVIO_OK;
             });
-            std::swap(h->d_Sres, h->d_Stmp);
-            h->fac_n = m; h->fac_ld = ldo; h->fac_tail = 0;
+            fac_adopt(h, m, fk, ldo, 0);
         } else h->fac_valid = false;
     }
     // ---- the first update's tracks: validated, the derived index arrays written (upload_finalize needs the prior's bookkeeping above)
@@ -302,7 +276,6 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
         }
         rc = launch_frame_head(h, s, fa);
         if (rc != ORCVIO_OK) return rc;
-        h->step_ingested = true;
     }
     for (auto& f : head) { rc = f(); if (rc != ORCVIO_OK) return rc; }
     res->n_after = h->res_n;
@@ -323,10 +296,11 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
     unsigned long long pubA = 0;
     h->ekf_side_used = false;
     if (first) {
-        h->ekf_side_now = fused;   // (the in-state rows beside k_front: enqueue_update)
-        rc = io_enqueue(h, s, false, true, nullptr, nullptr, true);
-        h->ekf_side_now = false;
-        h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h);
+        UpdateCall c;
+        c.ekf_side = fused;           // (the in-state rows beside k_front: enqueue_update)
+        c.already_ingested = fused;   // (k_frame_head has pulled the whole arena)
+        rc = io_enqueue(h, s, false, true, c, true);
+        h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h, false);
         if (rc != ORCVIO_OK) {
             if (h->ekf_side_used) {   // (a launch failed with the side stream's wait already out: let it through and drain it)
                 hipLaunchKernelGGL(k_obj_done, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned*>(h->d_step_words) + 32, h->ekf_side_seq);
@@ -338,9 +312,8 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
         h->pub_enqueued++;
         pubA = h->pub_enqueued;
         h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false;
-        step_commit_bookkeeping(h);
+        commit_bookkeeping(h);
     } else {
-        h->step_ingested = false;
         std::memset(h->h_stage + h->in_cap, 0, h->outs_small);   // (dx = 0, no status words)
         infoA = nullptr;
     }
@@ -403,12 +376,9 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
             HIPCHK(hipStreamSynchronize(h->side));
             h->ekf_side_skip_until = h->cnt_step_frames + 4096;
         }
-        HIPCHK(hipMemset(h->d_info + 8, 0, sizeof(int)));
-        HIPCHK(hipMemset(h->d_sync, 0, 256));
-        HIPCHK(hipMemset(h->d_la_rdy, 0, 256));
+        { const int rh = handoff_reset(h); if (rh != ORCVIO_OK) return rh; }
         cov_restore(h, cov_before_remove);
         h->fac_valid = false;   // (the factor a lost update left in the spare buffer is garbage or the prior's: the repeat factors P itself)
-        h->front_fallbacks++;
         if (lostA) {
             if (h->arena_swapped) step_arena_swap(h);
             rc = upload_begin(h, &fl, N, FA, nobsA, false, true, who);
@@ -416,9 +386,7 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
             if (rc == ORCVIO_OK) { h->io_open = true; rc = upload_finalize(h, who); }
             if (rc == ORCVIO_OK) {
                 h->pw_missing = false;
-                h->front_retry_forked = true;
-                rc = io_run(h, false, true, res->stats);
-                h->front_retry_forked = false;
+                rc = io_run_forked(h, res->stats);
             }
             res->repaired++; h->cnt_step_repairs++;
             res->status_first = rc;

@@ -316,10 +316,10 @@ static int launch_feature(orcvio_msckf_handle* h, hipStream_t s) {
 // The Cholesky of the prior and the feature tracks in one launch (k_front) when everything is co-resident: register
 // path (n <= 224), 1 + ceil(F/2) workgroups on the device's CUs, two feature teams + the factorisation's LDS within one
 // CU's 160 KB.  Otherwise the caller forks the factorisation to the side stream and launches k_feature.
-static bool front_fused_active(const orcvio_msckf_handle* h) {
+static bool front_fused_active(const orcvio_msckf_handle* h, bool retry_forked) {
     if (!h->front_fused || h->front_blocked_by_comm || !h->reg_path || h->F < 1) return false;
     if (1 + (h->F + 1) / 2 > h->n_cus) return false;   // one workgroup per CU (by LDS size), all resident at once
-    if (h->front_retry_forked) return false;   // a hand-off of the fused launch timed out: this update is re-run on the forked path
+    if (retry_forked) return false;   // a hand-off of the fused launch timed out: this update is re-run on the forked path
     const size_t team = feat_lds_bytes(h->Mmax, h->NAP, h->N);
     const size_t lds = 2 * team > sizeof(double) * POTRF_LDS_DOUBLES ? 2 * team : sizeof(double) * POTRF_LDS_DOUBLES;
     return lds <= (size_t)160 * 1024 && (h->NAP + 63) / 64 <= 4;
@@ -341,16 +341,16 @@ static int front_row_chunks(const orcvio_msckf_handle* h) {
 }
 // U = [A; b^T] L_a can assemble A on the fly (k_gemm_asmA) when there are at most four partial Grams: k_front then stops
 // after the Grams (one device-wide barrier instead of two, no assembly pass)
-static bool front_defers_assembly(const orcvio_msckf_handle* h) { return front_fused_active(h) && front_row_chunks(h) <= 4 && h->NA <= 192; }
+static bool front_defers_assembly(const orcvio_msckf_handle* h, bool retry_forked) { return front_fused_active(h, retry_forked) && front_row_chunks(h) <= 4 && h->NA <= 192; }
 
 // ... and the product U = [A; b^T] L_a itself can run inside k_front, behind the Grams (FrontUArgs): when the prior is factored in the
 // look-ahead form (its step counter tells the feature workgroups which block rows of the factor are out) or its factor is resident
-static bool front_forms_U(const orcvio_msckf_handle* h) {
-    return h->front_u && front_defers_assembly(h) && (h->use_factor || front_far_workgroups(h) > 0) && !h->join_wait;
+static bool front_forms_U(const orcvio_msckf_handle* h, const UpdateCall& c) {
+    return h->front_u && front_defers_assembly(h, c.retry_forked) && (h->use_factor || front_far_workgroups(h) > 0) && !c.join_wait;
 }
 // compress_dst != nullptr: the compression (Grams + assembly of A into compress_dst) runs inside the same launch;
 // grams_only: ... without the assembly (the caller's next kernel is k_gemm_asmA)
-static int launch_front(orcvio_msckf_handle* h, hipStream_t s, double* compress_dst, bool grams_only = false) {
+static int launch_front(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c, double* compress_dst, bool grams_only = false) {
     const FeatArgs a = feature_args(h);
     const double eps = 2.220446049250313e-16;
     const int nfar = front_far_workgroups(h);
@@ -361,8 +361,8 @@ static int launch_front(orcvio_msckf_handle* h, hipStream_t s, double* compress_
     if (nfar > 0 && lds < sizeof(double) * la_lds_doubles<3>()) lds = sizeof(double) * la_lds_doubles<3>();
     const int team_doubles = (int)(team / sizeof(double));
     FrontGramArgs g{};
-    g.enabled = compress_dst != nullptr ? (grams_only ? (front_forms_U(h) ? 3 : 2) : 1) : 0;
-    h->front_did_U = g.enabled == 3;
+    g.enabled = compress_dst != nullptr ? (grams_only ? (front_forms_U(h, c) ? 3 : 2) : 1) : 0;
+    c.front_did_U = g.enabled == 3;
     FrontUArgs u{};
     if (g.enabled == 3) {   // (launch_solve_stage(ST_FORM_U)'s product, deferred form)
         const PriorFactor pf = prior_factor(h);
@@ -380,8 +380,7 @@ static int launch_front(orcvio_msckf_handle* h, hipStream_t s, double* compress_
     g.rows_per_chunk = round_up((t3rows + g.chunks - 1) / g.chunks, 4);
     g.Gpart = h->d_Gpart; g.S = h->d_S; g.clone_rows = h->d_clone_ptr; g.counter = h->d_sync; g.lost = h->d_info + 8;
     g.A_dst = compress_dst; g.cb0 = h->flags.leg_dim - 15; g.plus = extra_gram(h); g.spin_limit = h->front_spin_limit;
-    g.started = h->front_mark; g.started_val = h->front_mark_val;
-    h->front_mark = nullptr;
+    g.started = c.front_mark; g.started_val = c.front_mark_val;
     if (g.enabled && g.chunks > h->gram_chunks_cap) { g_last_error = "launch_front: too many row chunks"; return ORCVIO_ERR_CAPACITY; }
     // (few tracks: workgroups without tracks join at the device-wide counter and share the Gram items -- 65 of them for a 20-clone window,
     //  seven rounds over the ten workgroups of a 20-track frame: the Grams ended 6 us behind the prior's factorisation)
@@ -437,25 +436,21 @@ static int launch_gram(orcvio_msckf_handle* h, hipStream_t s) {
     return ORCVIO_OK;
 }
 
-static int launch_assemble(orcvio_msckf_handle* h, hipStream_t s, double* dst) {
+static int launch_assemble_from(orcvio_msckf_handle* h, hipStream_t s, double* dst, int chunks, int dbg) {
     const int total = h->NAP * h->NAP;
     hipLaunchKernelGGL(k_assemble_A, dim3((total + 255) / 256), dim3(256), 0, s, h->d_S, h->F > 0 ? h->N : 0,
-                       h->flags.leg_dim - 15, h->NA, h->NAP, h->d_Gpart, h->chunks, (size_t)total, dst,
-                       asm_dbg(), extra_gram(h));
+                       h->flags.leg_dim - 15, h->NA, h->NAP, h->d_Gpart, chunks, (size_t)total, dst, dbg, extra_gram(h));
     HIPCHK(hipGetLastError());
     return ORCVIO_OK;
 }
+static int launch_assemble(orcvio_msckf_handle* h, hipStream_t s, double* dst) { return launch_assemble_from(h, s, dst, h->chunks, asm_dbg()); }
 
 // d_A on demand (optional outputs, tests) after an update whose k_front left the Grams only
 static int assemble_deferred(orcvio_msckf_handle* h, hipStream_t s) {
     if (!h->A_deferred) return ORCVIO_OK;
-    const int total = h->NAP * h->NAP;
-    hipLaunchKernelGGL(k_assemble_A, dim3((total + 255) / 256), dim3(256), 0, s, h->d_S, h->F > 0 ? h->N : 0,
-                       h->flags.leg_dim - 15, h->NA, h->NAP, h->d_Gpart, h->front_chunks, (size_t)total, h->d_A, 0,
-                       extra_gram(h));
-    HIPCHK(hipGetLastError());
-    h->A_deferred = false;
-    return ORCVIO_OK;
+    const int rc = launch_assemble_from(h, s, h->d_A, h->front_chunks, 0);
+    if (rc == ORCVIO_OK) h->A_deferred = false;
+    return rc;
 }
 
 // stride: doubles between consecutive blocks (0: packed); meta0: the status words behind the first block of a sharded update
@@ -495,15 +490,31 @@ static inline bool blk2_active(const orcvio_msckf_handle* h, int nn) {
 }
 static inline int blk2_split(int nn) { return 16 * (((nn + 15) / 16 + 1) / 2); }   // rows of the leading block (a multiple of 16)
 
+// the register-resident factorisations are compiled for 4, 8, 12 and 16 register slots per worker: index of the smallest that holds a
+// matrix of nb block steps, into the kernel tables below
+static inline int potrf_slot_index(int nb) {
+    const int need = potrf_slots_needed(nb);
+    return need <= 4 ? 0 : need <= 8 ? 1 : need <= 12 ? 2 : 3;
+}
+// k_potrf_reg of X (nn x nn, ld ldx) into Rf (ld ldr) with no stamps and no ablation
+static int launch_potrf_reg_slots(hipStream_t s, const double* X, int ldx, int nn, double tol_rel, double* Rf, int ldr, double* Dinv, int* info, int zero_lower, int rev) {
+    static constexpr decltype(&k_potrf_reg<4>) kern[4] = {k_potrf_reg<4>, k_potrf_reg<8>, k_potrf_reg<12>, k_potrf_reg<16>};
+    hipLaunchKernelGGL(kern[potrf_slot_index((nn + 15) / 16)], dim3(1), dim3(512), 0, s, X, ldx, nn, tol_rel, Rf, ldr, Dinv, info,
+                       (unsigned long long*)nullptr, (size_t)0, (size_t)0, (size_t)0, 0, 0, zero_lower, rev);
+    HIPCHK(hipGetLastError());
+    return ORCVIO_OK;
+}
 static int launch_potrf_reg_at(hipStream_t s, const double* X, int ldx, int nn, double tol_rel, double* Rf, int ldr, double* Dinv, int* info) {
-    const int need = potrf_slots_needed((nn + 15) / 16);
-#define LAUNCH_PRA(NS) hipLaunchKernelGGL(k_potrf_reg<NS>, dim3(1), dim3(512), 0, s, X, ldx, nn, tol_rel, Rf, ldr, Dinv, info, \
-                                          (unsigned long long*)nullptr, (size_t)0, (size_t)0, (size_t)0, 0, 0, 1, 0)
-    if (need <= 4) LAUNCH_PRA(4);
-    else if (need <= 8) LAUNCH_PRA(8);
-    else if (need <= 12) LAUNCH_PRA(12);
-    else LAUNCH_PRA(16);
-#undef LAUNCH_PRA
+    return launch_potrf_reg_slots(s, X, ldx, nn, tol_rel, Rf, ldr, Dinv, info, 1, 0);
+}
+// k_potrf_solve: chol(X) and Z = L^-1 [B1 | bx] in one launch (one factorisation workgroup, solver workgroups trailing it)
+static int launch_potrf_solve_slots(hipStream_t s, const double* X, int ldx, int nn, double* Rf, int ldr, double* Dinv, int* info, int* flag, int* lost,
+                                    const double* B1, long sB1i, long sB1c, int nc1, const double* bx, long sbx, double* Z, int ldz, int tail, double tail_scale) {
+    const int ncb = (nc1 + (bx ? 1 : 0) + 15) / 16;
+    const dim3 grid(1 + (ncb + SOLVE_WPB - 1) / SOLVE_WPB), block(512);
+    static constexpr decltype(&k_potrf_solve<4>) kern[4] = {k_potrf_solve<4>, k_potrf_solve<8>, k_potrf_solve<12>, k_potrf_solve<16>};
+    hipLaunchKernelGGL(kern[potrf_slot_index((nn + 15) / 16)], grid, block, 0, s, X, ldx, nn, 0.0, Rf, ldr, Dinv, info, flag, lost, B1, sB1i, sB1c, nc1,
+                       bx, sbx, Z, ldz, tail, tail_scale);
     HIPCHK(hipGetLastError());
     return ORCVIO_OK;
 }
@@ -516,23 +527,19 @@ static int launch_trsm_lds_at(hipStream_t s, const double* Rf, int ldr, const do
 }
 static int launch_potrf_solve_at(hipStream_t s, const double* X, int ldx, int nn, double* Rf, int ldr, double* Dinv, int* info, int* flag, int* lost,
                                  const double* B1, long sB1i, long sB1c, int nc1, double* Z, int ldz) {
-    const int need = potrf_slots_needed((nn + 15) / 16);
-    const int ncb = (nc1 + 15) / 16;
-    const dim3 grid(1 + (ncb + SOLVE_WPB - 1) / SOLVE_WPB), block(512);
     HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), s));   // (no k_gemm of the usual sequence stands ahead of this launch)
-#define LAUNCH_PSA(NS) hipLaunchKernelGGL(k_potrf_solve<NS>, grid, block, 0, s, X, ldx, nn, 0.0, Rf, ldr, Dinv, info, flag, lost, B1, sB1i, sB1c, nc1, \
-                                          (const double*)nullptr, 0L, Z, ldz, 0, 0.0)
-    if (need <= 4) LAUNCH_PSA(4);
-    else if (need <= 8) LAUNCH_PSA(8);
-    else if (need <= 12) LAUNCH_PSA(12);
-    else LAUNCH_PSA(16);
-#undef LAUNCH_PSA
+    return launch_potrf_solve_slots(s, X, ldx, nn, Rf, ldr, Dinv, info, flag, lost, B1, sB1i, sB1c, nc1, nullptr, 0L, Z, ldz, 0, 0.0);
+}
+static int launch_gemm(hipStream_t s, const double* A, long sAi, long sAk, const double* B, long sBk, long sBj, int M, int N,
+                       int K, double alpha, double diag_add, int upper_only, double* C, long sCi, long sCj, int* clear = nullptr,
+                       const unsigned* wait = nullptr, unsigned expect = 0u, int* lost = nullptr, int* clear16 = nullptr,
+                       const double* Cin = nullptr, int* clear1 = nullptr) {
+    const int tiles = ((M + 15) / 16) * ((N + 15) / 16);
+    hipLaunchKernelGGL(k_gemm, dim3(tiles), dim3(256), 0, s, A, sAi, sAk, B, sBk, sBj, M, N, K, alpha, diag_add,
+                       upper_only, C, sCi, sCj, Cin, clear, wait, expect, lost, 1 << 19, clear16, clear1);
     HIPCHK(hipGetLastError());
     return ORCVIO_OK;
 }
-static int launch_gemm(hipStream_t s, const double* A, long sAi, long sAk, const double* B, long sBk, long sBj, int M, int N,
-                       int K, double alpha, double diag_add, int upper_only, double* C, long sCi, long sCj, int* clear,
-                       const unsigned* wait, unsigned expect, int* lost, int* clear16, const double* Cin, int* clear1 = nullptr);
 
 // semi-definite X (the prior: pivots <= tol are dropped), n x n with ld ldx, NOT modified; out: the lower factor (ld NP), Dinv per block
 static int launch_potrf_blk2(orcvio_msckf_handle* h, hipStream_t s, const double* X, int ldx, int nn, double tol_rel, double* out, double* Dinv, int* info) {
@@ -559,17 +566,9 @@ static int launch_potrf(orcvio_msckf_handle* h, hipStream_t s, const double* X, 
                         double* Dinv, int* info, int rev = 0) {
     const int NP = h->NP;
     if (h->reg_path) {
-        const int nb = (nn + 15) / 16, noff = nb * (nb - 1) / 2;
-        const int need = potrf_slots_needed(nb);   // wave 0 keeps the diagonal tiles in LDS, the workers the rest in registers
-        (void)noff;
+        // (wave 0 keeps the diagonal tiles in LDS, the workers the rest in registers)
         // zero_lower = 0: `out` is d_RP / d_RM, whose strictly-lower tiles factor_layout_clean() keeps zero
-#define LAUNCH_PR(NS) hipLaunchKernelGGL(k_potrf_reg<NS>, dim3(1), dim3(512), 0, s, X, ldx, nn, tol_rel, out, NP, Dinv, info, \
-                                         (unsigned long long*)nullptr, (size_t)0, (size_t)0, (size_t)0, 0, 0, 0, rev)
-        if (need <= 4) LAUNCH_PR(4);
-        else if (need <= 8) LAUNCH_PR(8);
-        else if (need <= 12) LAUNCH_PR(12);
-        else LAUNCH_PR(16);
-#undef LAUNCH_PR
+        return launch_potrf_reg_slots(s, X, ldx, nn, tol_rel, out, NP, Dinv, info, 0, rev);
     } else if (blk2_active(h, nn)) {
         return launch_potrf_blk2(h, s, X, ldx, nn, tol_rel, out, Dinv, info);
     } else {
@@ -582,17 +581,6 @@ static int launch_potrf(orcvio_msckf_handle* h, hipStream_t s, const double* X, 
 
 static inline void factor_strides(const orcvio_msckf_handle* h, long& sLi, long& sLj) {
     if (h->reg_path) { sLi = 1; sLj = h->NP; } else { sLi = h->NP; sLj = 1; }
-}
-
-static int launch_gemm(hipStream_t s, const double* A, long sAi, long sAk, const double* B, long sBk, long sBj, int M, int N,
-                       int K, double alpha, double diag_add, int upper_only, double* C, long sCi, long sCj, int* clear = nullptr,
-                       const unsigned* wait = nullptr, unsigned expect = 0u, int* lost = nullptr, int* clear16 = nullptr,
-                       const double* Cin = nullptr, int* clear1) {
-    const int tiles = ((M + 15) / 16) * ((N + 15) / 16);
-    hipLaunchKernelGGL(k_gemm, dim3(tiles), dim3(256), 0, s, A, sAi, sAk, B, sBk, sBj, M, N, K, alpha, diag_add,
-                       upper_only, C, sCi, sCj, Cin, clear, wait, expect, lost, 1 << 19, clear16, clear1);
-    HIPCHK(hipGetLastError());
-    return ORCVIO_OK;
 }
 
 static int launch_trsm(orcvio_msckf_handle* h, hipStream_t s, const double* L, const double* Dinv, int nn, const double* B1,
@@ -615,8 +603,8 @@ static inline bool fused_solve_active(const orcvio_msckf_handle* h) { return h->
 
 // k_potrf_solve_la instead of k_potrf_solve: from six block steps (below that the whole trailing matrix is a handful of tiles), never
 // in the re-run of an update whose in-launch hand-off timed out (the far workgroups are one more thing that has to be co-resident)
-static inline bool la_solve_active(const orcvio_msckf_handle* h, int nb) {
-    return (h->la_solve == 2 || h->la_solve == 3) && nb >= 6 && nb <= LA_NBMAX && !h->front_retry_forked;
+static inline bool la_solve_active(const orcvio_msckf_handle* h, int nb, bool retry_forked) {
+    return (h->la_solve == 2 || h->la_solve == 3) && nb >= 6 && nb <= LA_NBMAX && !retry_forked;
 }
 static int launch_potrf_solve_la(orcvio_msckf_handle* h, hipStream_t s, int la, const double* X, int ldx, int nn, double* Rf, int ldr, double* Dinv,
                                  int* info, int* flag, int* rdy, int* lost, const double* B1, long sB1i, long sB1c, int nc1, const double* bx,
@@ -647,8 +635,18 @@ static int launch_potrf_solve_la(orcvio_msckf_handle* h, hipStream_t s, int la, 
 
 // P+ and dx (and an object update's chi-square gate: h->obj_thr is set before the solve's stages are launched) inside the factorisation +
 // solve launch (LaFin) instead of a k_finish_sqrt behind it: updates whose solve runs in the look-ahead form
-static inline bool finish_fused_active(const orcvio_msckf_handle* h) {
-    return (h->fuse_finish >= 2 || (h->fuse_finish == 1 && h->fin_frame)) && fused_solve_active(h) && la_solve_active(h, (h->kf - h->tail + 15) / 16);
+static inline bool finish_fused_active(const orcvio_msckf_handle* h, const UpdateCall& c) {
+    return (h->fuse_finish >= 2 || (h->fuse_finish == 1 && c.fin_frame)) && fused_solve_active(h) && la_solve_active(h, (h->kf - h->tail + 15) / 16, c.retry_forked);
+}
+
+// the joint chi-square gate of an object update (h->obj_thr is set before the solve's stages are launched): k_finish_sqrt decides it, or the
+// finish workgroups of the solve's launch (LaFin::gate, which does not read `fail`); *_out: where the decision is published from
+static inline ObjGate object_gate(const orcvio_msckf_handle* h, double thr, double* gamma_out, int* accept_out, const int* fail) {
+    ObjGate gate;
+    gate.fail = fail;
+    gate.rr = h->d_A + (size_t)h->NA * h->NAP + h->NA; gate.thr = thr;
+    gate.gamma = h->d_obj_gamma; gate.accept = h->d_obj_accept; gate.gamma_out = gamma_out; gate.accept_out = accept_out;
+    return gate;
 }
 
 // stages of the square-root Kalman solve (see msckf_kernels.hpp)
@@ -691,7 +689,18 @@ static int launch_potrf_solve_blk2(orcvio_msckf_handle* h, hipStream_t s, const 
 // frame must not wait tens of milliseconds to find out; the call then repairs the frame and keeps the rows on one stream for a while
 static inline int side_spin_limit(const orcvio_msckf_handle* h) { return h->front_spin_limit < (1 << 14) ? h->front_spin_limit : (1 << 14); }
 
-static int launch_solve_stage(orcvio_msckf_handle* h, hipStream_t s, int stage) {
+// A wait inside a launch gave up (info[8]): the words of the in-launch hand-offs are put back -- the lost flag, k_front's device-wide
+// counter, the words of the look-ahead factorisations (a lost hand-off leaves them as they were) -- once the caller has drained what
+// may still read them; `counted`: the update is going to be run again (orcvio_msckf_counters [0])
+static int handoff_reset(orcvio_msckf_handle* h, bool counted = true) {
+    HIPCHK(hipMemset(h->d_info + 8, 0, sizeof(int)));
+    HIPCHK(hipMemset(h->d_sync, 0, 256));
+    HIPCHK(hipMemset(h->d_la_rdy, 0, 256));
+    if (counted) h->front_fallbacks++;
+    return ORCVIO_OK;
+}
+
+static int launch_solve_stage(orcvio_msckf_handle* h, hipStream_t s, int stage, UpdateCall& c) {
     // n = states (rows of the prior's factor), kf = columns of that factor = dimension of M (kf == n unless the resident
     // factor of an earlier update of the frame is used)
     const int NA = h->NA, NAP = h->NAP, n = h->n, kf = h->kf, NP = h->NP, ldz = h->ldz;
@@ -706,77 +715,62 @@ static int launch_solve_stage(orcvio_msckf_handle* h, hipStream_t s, int stage) 
             if (h->use_factor) return ORCVIO_OK;   // the factor is resident
             return launch_potrf(h, s, h->d_P, n, n, 8.0 * eps, h->d_RP, h->d_DinvP, h->d_info, rev_prior_active(h) ? 1 : 0);
         case ST_FORM_U:    // U[(NA+1) x kf] = [A; b^T] * L_a
-            if (h->A_deferred && h->front_did_U) return ORCVIO_OK;   // (k_front formed U behind its Grams: FrontUArgs)
+            if (h->A_deferred && c.front_did_U) return ORCVIO_OK;   // (k_front formed U behind its Grams: FrontUArgs)
             if (h->A_deferred) {   // A = scatter(S) - sum Gpart assembled inside the product (k_front left the Grams only)
                 AsmArgs aa{h->d_S, h->N, h->flags.leg_dim - 15, NA, NAP, h->d_Gpart, h->front_chunks, (size_t)NAP * NAP, asm_dbg(),
                            extra_gram(h)};
                 const int tiles = ((NA + 1 + 15) / 16) * ((kfa + 15) / 16);
-                if (h->asm_wait) {   // (the Gram of the in-state rows comes from the side stream: enqueue_update)
-                    hipLaunchKernelGGL(k_gemm_asmA_w, dim3(tiles), dim3(256), 0, s, aa, La, sLi, sLj, NA + 1, kfa, NA, h->d_U, (long)NP, 1L, h->asm_wait,
-                                       h->asm_wait_val, side_spin_limit(h), h->d_info + 8);
-                    h->asm_wait = nullptr;
+                if (c.asm_wait) {   // (the Gram of the in-state rows comes from the side stream: enqueue_update)
+                    hipLaunchKernelGGL(k_gemm_asmA_w, dim3(tiles), dim3(256), 0, s, aa, La, sLi, sLj, NA + 1, kfa, NA, h->d_U, (long)NP, 1L, c.asm_wait,
+                                       c.asm_wait_val, side_spin_limit(h), h->d_info + 8);
                 } else
                 hipLaunchKernelGGL(k_gemm_asmA, dim3(tiles), dim3(256), 0, s, aa, La, sLi, sLj, NA + 1, kfa, NA, h->d_U, (long)NP, 1L, (int*)nullptr);
                 HIPCHK(hipGetLastError());
                 return ORCVIO_OK;
             }
-            if (h->join_wait) {   // (the frame call: A' comes from another stream; the product polls its completion counter, no stream-level join)
-                const unsigned* w = h->join_wait;
-                h->join_wait = nullptr;
-                return launch_gemm(s, h->d_A, NAP, 1, La, sLi, sLj, NA + 1, kfa, NA, 1.0, 0.0, 0, h->d_U, NP, 1, nullptr, w, h->join_expect, h->d_info + 8);
-            }
+            if (c.join_wait)   // (the frame call: A' comes from another stream; the product polls its completion counter, no stream-level join)
+                return launch_gemm(s, h->d_A, NAP, 1, La, sLi, sLj, NA + 1, kfa, NA, 1.0, 0.0, 0, h->d_U, NP, 1, nullptr, c.join_wait, c.join_expect, h->d_info + 8);
             return launch_gemm(s, h->d_A, NAP, 1, La, sLi, sLj, NA + 1, kfa, NA, 1.0, 0.0, 0, h->d_U, NP, 1);
         case ST_FORM_M:    // M = s2 I + L_a^T U[0:NA]   (upper tiles)
             // (the register-resident Cholesky reads the upper tiles only; the LDS-panel fallback factors the lower triangle in place)
         {
             const int rm = launch_gemm(s, La, sLj, sLi, h->d_U, NP, 1, kfa, kfa, NA, 1.0, sigma2, h->reg_path ? 1 : 0, h->d_M, NP, 1, h->d_flag,
                                        nullptr, 0u, nullptr, h->d_la_rdy, nullptr, h->d_la_rdy + 48);
-            if (rm == ORCVIO_OK && h->mark_M_word && !(fused_solve_active(h) && la_solve_active(h, (kfa + 15) / 16))) {
+            if (rm == ORCVIO_OK && c.mark_M_word && !(fused_solve_active(h) && la_solve_active(h, (kfa + 15) / 16, c.retry_forked))) {
                 // (the frame call's chained object solve waits for M on another stream: the word rises behind the product's kernel
                 //  boundary -- stored by the first instruction of the look-ahead solve launch that follows (LaEnd.mark), or by a launch
                 //  of its own where that form is not the one that runs)
-                hipLaunchKernelGGL(k_obj_done, dim3(1), dim3(64), 0, s, h->mark_M_word, h->mark_M_val);
-                h->mark_M_word = nullptr;
+                hipLaunchKernelGGL(k_obj_done, dim3(1), dim3(64), 0, s, c.mark_M_word, c.mark_M_val);
+                c.mark_M_word = nullptr;
                 HIPCHK(hipGetLastError());
             }
             return rm;
         }
         case ST_POTRF_M:
             if (fused_solve_active(h)) {   // chol(M) + Z = L_M^-1 [Lf^T | g] in one launch (solver workgroups trail the factorisation)
-                const int nbm = (kfa + 15) / 16, need = potrf_slots_needed(nbm);
+                const int nbm = (kfa + 15) / 16;
                 const int ncb = (n + 1 + 15) / 16;
-                const dim3 grid(1 + (ncb + SOLVE_WPB - 1) / SOLVE_WPB), block(512);
                 const double* g = h->d_U + (size_t)NA * NP;
-                if (la_solve_active(h, nbm)) {   // the trailing update spread over far workgroups (potrf_lookahead.hpp)
+                if (la_solve_active(h, nbm, c.retry_forked)) {   // the trailing update spread over far workgroups (potrf_lookahead.hpp)
                     LaFin fin;
                     int nfin = 0;
-                    if (finish_fused_active(h)) {   // ... and P+ / dx by finish workgroups of the same launch
+                    if (finish_fused_active(h, c)) {   // ... and P+ / dx by finish workgroups of the same launch
                         fin.done = reinterpret_cast<unsigned*>(h->d_la_rdy + 48);   // (a line of its own; cleared by ST_FORM_M's product like the block rows' words)
                         fin.step = h->d_flag; fin.last_step = nbm - 1;
                         { static const int acq = dbg_getenv("ORCVIO_FIN_ACQ") ? atoi(dbg_getenv("ORCVIO_FIN_ACQ")) : 0; fin.acq = acq; }
                         fin.nstate = n; fin.kdim = kf; fin.s2 = sigma2; fin.P_out = h->d_Pout; fin.dx = h->d_dx; fin.P = h->d_P; fin.keep_tail = 6 * h->n_nui;
                         nfin = (ncb * (ncb + 1) / 2 + 1) / 2;
-                        if (h->objects_mode) {
-                            fin.gate.rr = h->d_A + (size_t)NA * h->NAP + NA; fin.gate.thr = h->obj_thr;
-                            fin.gate.gamma = h->d_obj_gamma; fin.gate.accept = h->d_obj_accept; fin.gate.gamma_out = h->d_gamma; fin.gate.accept_out = h->d_accept;
-                        }
+                        if (h->objects_mode) fin.gate = object_gate(h, h->obj_thr, h->d_gamma, h->d_accept, nullptr);
                     }
                     LaEnd end;
-                    if (h->mark_M_word) { end.mark = h->mark_M_word; end.mark_val = h->mark_M_val; h->mark_M_word = nullptr; }
+                    if (c.mark_M_word) { end.mark = c.mark_M_word; end.mark_val = c.mark_M_val; c.mark_M_word = nullptr; }
                     const int rl = launch_potrf_solve_la(h, s, h->la_solve, h->d_M, NP, kfa, h->d_RM, NP, h->d_DinvM, h->d_info + 2, h->d_flag, h->d_la_rdy,
                                                          h->d_info + 8, pf.base, sLj, sLi, n, g, 1L, h->d_Z, ldz, h->tail, 1.0 / h->flags.noise_feature, nullptr,
                                                          end, fin, nfin);
                     return rl;
                 }
-#define LAUNCH_PS(NS) hipLaunchKernelGGL(k_potrf_solve<NS>, grid, block, 0, s, h->d_M, NP, kfa, 0.0, h->d_RM, NP, h->d_DinvM, h->d_info + 2, \
-                                         h->d_flag, h->d_info + 8, pf.base, sLj, sLi, n, g, 1L, h->d_Z, ldz, h->tail, 1.0 / h->flags.noise_feature)
-                if (need <= 4) LAUNCH_PS(4);
-                else if (need <= 8) LAUNCH_PS(8);
-                else if (need <= 12) LAUNCH_PS(12);
-                else LAUNCH_PS(16);
-#undef LAUNCH_PS
-                HIPCHK(hipGetLastError());
-                return ORCVIO_OK;
+                return launch_potrf_solve_slots(s, h->d_M, NP, kfa, h->d_RM, NP, h->d_DinvM, h->d_info + 2, h->d_flag, h->d_info + 8, pf.base, sLj, sLi, n, g, 1L,
+                                                h->d_Z, ldz, h->tail, 1.0 / h->flags.noise_feature);
             }
             if (blk2_active(h, kf)) return launch_potrf_solve_blk2(h, s, pf, n, kf, NA);   // (the triangular solve with it: ST_TRSM has nothing left to do)
             return launch_potrf(h, s, h->d_M, NP, kf, 0.0, h->d_RM, h->d_DinvM, h->d_info + 2);
@@ -785,21 +779,16 @@ static int launch_solve_stage(orcvio_msckf_handle* h, hipStream_t s, int stage) 
             if (blk2_active(h, kf)) return ORCVIO_OK;      // done with the 2 x 2 block factorisation
             return launch_trsm(h, s, h->d_RM, h->d_DinvM, kf, pf.base, sLj, sLi, n, h->d_U + (size_t)NA * NP, 1, h->d_Z, ldz);
         case ST_FINISH: {
-            if (finish_fused_active(h)) return ORCVIO_OK;   // done inside k_potrf_solve_la (LaFin)
+            if (finish_fused_active(h, c)) return ORCVIO_OK;   // done inside k_potrf_solve_la (LaFin)
             const int nb = (n + 1 + 15) / 16, tiles = nb * (nb + 1) / 2;
-            if (h->fin_pub) {   // (io_enqueue: the finish, the commit and the publication in ONE launch, frame_ops.hpp k_finish_pub)
-                FinishPubArgs fp = *h->fin_pub;
-                fp.Z = h->d_Z; fp.ldz = ldz; fp.n = n; fp.kdim = kf; fp.s2 = sigma2; fp.P = h->d_P; fp.dx = h->d_dx;
-                hipLaunchKernelGGL(k_finish_pub, dim3(tiles), dim3(256), 0, s, fp);
+            if (c.fin_pub) {   // (io_enqueue: the finish, the commit and the publication in ONE launch, frame_ops.hpp k_finish_pub)
+                hipLaunchKernelGGL(k_finish_pub, dim3(tiles), dim3(256), 0, s, c.pub);
                 HIPCHK(hipGetLastError());
                 return ORCVIO_OK;
             }
             ObjGate gate;
             gate.fail = h->d_info + 2;   // chol(M) of this update met a non-positive pivot: P+ = P, dx = 0
-            if (h->objects_mode) {
-                gate.rr = h->d_A + (size_t)NA * h->NAP + NA; gate.thr = h->obj_thr;
-                gate.gamma = h->d_obj_gamma; gate.accept = h->d_obj_accept; gate.gamma_out = h->d_gamma; gate.accept_out = h->d_accept;
-            }
+            if (h->objects_mode) gate = object_gate(h, h->obj_thr, h->d_gamma, h->d_accept, gate.fail);
             hipLaunchKernelGGL(k_finish_sqrt, dim3(tiles), dim3(256), 0, s, h->d_Z, ldz, n, kf, sigma2, h->d_Pout, h->d_dx, gate, h->d_P, 6 * h->n_nui);
             HIPCHK(hipGetLastError());
             return ORCVIO_OK;
@@ -814,16 +803,17 @@ static int launch_prior_fork(orcvio_msckf_handle* h, hipStream_t s) {
     if (h->use_factor) return ORCVIO_OK;   // the prior's factor is resident: nothing to fork, nothing to join
     HIPCHK(hipEventRecord(h->ev_fork, s));
     HIPCHK(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    int rc = launch_solve_stage(h, h->side, ST_POTRF_P);   // writes d_info[0..1] itself
+    UpdateCall none;   // (the prior's factorisation takes nothing of the call's record)
+    int rc = launch_solve_stage(h, h->side, ST_POTRF_P, none);   // writes d_info[0..1] itself
     if (rc != ORCVIO_OK) return rc;
     HIPCHK(hipEventRecord(h->ev_side, h->side));
     return ORCVIO_OK;
 }
 
-static int launch_solve_tail(orcvio_msckf_handle* h, hipStream_t s) {
+static int launch_solve_tail(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c) {
     if (h->prior_forked) HIPCHK(hipStreamWaitEvent(s, h->ev_side, 0));   // join the Cholesky of the prior
     int rc = ORCVIO_OK;
-    for (int st = ST_FORM_U; st < ST_COUNT && rc == ORCVIO_OK; ++st) rc = launch_solve_stage(h, s, st);
+    for (int st = ST_FORM_U; st < ST_COUNT && rc == ORCVIO_OK; ++st) rc = launch_solve_stage(h, s, st, c);
     return rc;
 }
 
@@ -834,18 +824,18 @@ static hipStream_t pick_stream(orcvio_msckf_handle* h, void* stream) { return st
 // tighter dispatch.  Capturing costs several hundred microseconds, so a slot captures only when the same launch
 // signature (sizes, flags, options, pointers, stream) shows up twice in a row -- a caller that replays one shape (the
 // benchmark, a fixed-size window) gets the graph, a caller whose track count changes every frame gets plain launches.
-static unsigned long long launch_signature(const orcvio_msckf_handle* h, hipStream_t s, const void* p0, long extra) {
+static unsigned long long launch_signature(const orcvio_msckf_handle* h, hipStream_t s, const void* p0, long extra, const UpdateCall& c) {
     unsigned long long sig = 1469598103934665603ull;
     auto mix = [&](unsigned long long v) { sig = (sig ^ v) * 1099511628211ull; };
     mix(h->N); mix(h->F); mix(h->nobs); mix(h->m_tot); mix(h->thin_opt); mix(h->Mmax); mix(h->chunks); mix(h->s_chunks); mix(h->rows_per_chunk);
     mix(h->flags.leg_dim); mix(h->flags.use_larvio); mix(h->flags.use_left_perturbation); mix(h->flags.if_fej);
-    mix(h->flags.estimate_td); mix(h->materialize); mix(h->skip_active); mix(h->fused_solve); mix(h->la_solve); mix(h->la_spin); mix(h->front_u); mix(h->fuse_finish); mix(h->fin_frame); mix(h->front_fused); mix(h->front_blocked_by_comm); mix(h->feat_ablate); mix(h->ekf_F); mix(h->ekf_mode); mix(h->n_extra); mix(h->n_nui); mix(h->dense_rows);
+    mix(h->flags.estimate_td); mix(h->materialize); mix(h->skip_active); mix(h->fused_solve); mix(h->la_solve); mix(h->la_spin); mix(h->front_u); mix(h->fuse_finish); mix(c.fin_frame); mix(h->front_fused); mix(h->front_blocked_by_comm); mix(h->feat_ablate); mix(h->ekf_F); mix(h->ekf_mode); mix(h->n_extra); mix(h->n_nui); mix(h->dense_rows);
     unsigned long long bits;
     double sg = h->flags.noise_feature;
     std::memcpy(&bits, &sg, 8); mix(bits);
     double cp = h->flags.chi2_prob;
     std::memcpy(&bits, &cp, 8); mix(bits);
-    mix(h->front_retry_forked); mix(h->front_spin_limit); mix(h->use_factor); mix(h->kf); mix(h->fac_ld); mix(h->graph_epoch); mix(h->ekf_idp); mix(h->ekf_eval); mix(h->ekf_cap); mix(h->dense_cap);
+    mix(c.retry_forked); mix(h->front_spin_limit); mix(h->use_factor); mix(h->kf); mix(h->fac_ld); mix(h->graph_epoch); mix(h->ekf_idp); mix(h->ekf_eval); mix(h->ekf_cap); mix(h->dense_cap);
     mix((unsigned long long)(size_t)h->d_ekf_i); mix((unsigned long long)(size_t)h->d_ekf_d); mix((unsigned long long)(size_t)h->d_ekf_E);
     mix((unsigned long long)(size_t)h->d_slam); mix((unsigned long long)(size_t)h->d_dense); mix((unsigned long long)(size_t)h->d_Gekf);
     mix((unsigned long long)(size_t)h->d_Hs); mix((unsigned long long)(size_t)h->d_P);
@@ -915,10 +905,11 @@ static int run_with_graph(orcvio_msckf_handle* h, orcvio_msckf_handle::GraphSlot
 static int run_local_impl(orcvio_msckf_handle* h, hipStream_t s, double* dst) {
     h->last_stream = s;
     { const int re = launch_ekf(h, s); if (re != ORCVIO_OK) return re; }
-    if (front_fused_active(h)) { h->prior_forked = false; return launch_front(h, s, dst); }   // one launch: tracks, compression, and the prior's factor
+    UpdateCall c;
+    if (front_fused_active(h, c.retry_forked)) { h->prior_forked = false; return launch_front(h, s, c, dst); }   // one launch: tracks, compression, and the prior's factor
     int rc = launch_prior_fork(h, s);
     if (rc != ORCVIO_OK) return rc;
-    return run_with_graph(h, h->g_local, launch_signature(h, s, dst, 0), s, [&](bool) {
+    return run_with_graph(h, h->g_local, launch_signature(h, s, dst, 0, c), s, [&](bool) {
         int r = launch_feature(h, s);
         if (r == ORCVIO_OK) r = launch_gram(h, s);
         if (r == ORCVIO_OK) r = launch_assemble(h, s, dst);
@@ -951,12 +942,13 @@ static int run_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, int n
     // the Cholesky of the prior was forked by run_local: join it here (outside the captured part)
     if (h->prior_forked) HIPCHK(hipStreamWaitEvent(s, h->ev_side, 0));
     h->A_deferred = false;   // d_A is the sum of the gathered blocks
-    unsigned long long sig = launch_signature(h, s, d_blocks, n_blocks);
+    UpdateCall c;
+    unsigned long long sig = launch_signature(h, s, d_blocks, n_blocks, c);
     sig = (sig ^ (unsigned long long)stride) * 1099511628211ull;
     sig = (sig ^ (unsigned long long)(size_t)meta0) * 1099511628211ull;
     int rc = run_with_graph(h, h->g_finish, sig, s, [&](bool) {
         int r = launch_reduce(h, s, d_blocks, n_blocks, h->d_A, stride, meta0);   // rank-ordered sum of the gathered blocks
-        for (int st = ST_FORM_U; st < ST_COUNT && r == ORCVIO_OK; ++st) r = launch_solve_stage(h, s, st);
+        for (int st = ST_FORM_U; st < ST_COUNT && r == ORCVIO_OK; ++st) r = launch_solve_stage(h, s, st, c);
         return r;
     });
     if (rc == ORCVIO_OK) { h->ran = true; h->last_update_objects = false; h->last_run_kind = 1; h->last_sharded = false; }
@@ -1023,12 +1015,12 @@ static int launch_ekf(orcvio_msckf_handle* h, hipStream_t s) {
 // the reference's direct form, S = H P H^T + s2 I of dimension m, instead of the square-root form of dimension n (frame_ops.hpp).
 // Only where the finish is k_finish_pub's (the in-place paths: io_update / io_submit / io_step_frame without P+ to the host) -- the
 // commit and the publication ride in k_thin_apply the same way.
-static inline bool thin_possible(const orcvio_msckf_handle* h) {
-    return h->thin_opt && !h->thin_blocked && h->F > 0 && h->m_tot > 0 && h->m_tot <= THIN_MAX_ROWS && h->ekf_F == 0 && h->dense_rows == 0 && h->n_nui == 0 &&
+static inline bool thin_possible(const orcvio_msckf_handle* h, const UpdateCall& c) {
+    return h->thin_opt && !c.thin_blocked &&h->F > 0 && h->m_tot > 0 && h->m_tot <= THIN_MAX_ROWS && h->ekf_F == 0 && h->dense_rows == 0 && h->n_nui == 0 &&
            !h->objects_mode && !h->materialize && h->feat_ablate == 0 && (h->NAP + 63) / 64 <= 7 &&
            sizeof(double) * thin_gain_lds_doubles(h->m_tot, h->NA, h->n) <= (size_t)150 * 1024;   // (k_thin_gain is ONE workgroup: everything in its LDS)
 }
-static int enqueue_thin(orcvio_msckf_handle* h, hipStream_t s) {
+static int enqueue_thin(orcvio_msckf_handle* h, hipStream_t s, const FinishPubArgs& fp) {
     const int n = h->n, NA = h->NA, m = h->m_tot;
     // the tracks, with the projected rows of the accepted ones materialised (zero rows for the others) into the thin stack
     double* keep_Hs = h->d_Hs;
@@ -1043,7 +1035,6 @@ static int enqueue_thin(orcvio_msckf_handle* h, hipStream_t s) {
         if (!attr_set) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_thin_gain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(152 * 1024))); attr_set = true; }
     }
     hipLaunchKernelGGL(k_thin_gain, dim3(1), dim3(1024), lds, s, g);
-    const FinishPubArgs& fp = *h->fin_pub;
     ThinApplyArgs a{h->d_Vthin, h->d_uthin, m, n, h->d_P, fp.P_dst, h->d_dx, fp.commit, fp.info, fp.info_also,
                     fp.small_src, fp.small_dst, fp.small16, fp.counter, fp.seq, fp.flag};
     hipLaunchKernelGGL(k_thin_apply, dim3((n * n + n + 255) / 256), dim3(256), 0, s, a);
@@ -1053,26 +1044,27 @@ static int enqueue_thin(orcvio_msckf_handle* h, hipStream_t s) {
     return ORCVIO_OK;
 }
 
-static int enqueue_update(orcvio_msckf_handle* h, hipStream_t s, const std::function<int()>* mid = nullptr) {
+static int enqueue_update(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c) {
+    const std::function<int()>* mid = c.mid;
     h->last_update_thin = false;
-    h->asm_wait = nullptr; h->front_mark = nullptr;
-    if (h->fin_pub && !mid && thin_possible(h)) return enqueue_thin(h, s);
+    c.asm_wait = nullptr; c.front_mark = nullptr;
+    if (c.fin_pub && !mid && thin_possible(h, c)) return enqueue_thin(h, s, c.pub);
     // The frame call's first update: the in-state features' rows and their Gram need the frame head's covariance and nothing of k_front,
     // and only the assembly behind k_front needs them -- they run on the side stream while k_front does, joined by two polled words
     // instead of stream-level events (a one-word launch is 2-5 us of stream time, a cross-queue event dependency 8).  Their launches go
     // out BEHIND k_front's: a wait enqueued ahead of what it waits for would stall a hardware queue the two streams happen to share (the
     // runtime maps any number of streams onto a few), and the host's time for four launches would stand in front of k_front.
-    const bool ekf_side = h->ekf_side_now && h->ekf_side_opt && h->cnt_step_frames >= h->ekf_side_skip_until && !mid && h->ekf_F > 0 && h->dense_rows == 0 && h->ekf_one_launch && h->d_step_words &&
-                          front_fused_active(h) && front_defers_assembly(h) && !front_forms_U(h) && h->F > 0;
+    const bool ekf_side = c.ekf_side && h->ekf_side_opt && h->cnt_step_frames >= h->ekf_side_skip_until && !mid && h->ekf_F > 0 && h->dense_rows == 0 && h->ekf_one_launch && h->d_step_words &&
+                          front_defers_assembly(h, c.retry_forked) && !front_forms_U(h, c) && h->F > 0;
     unsigned* side_words = ekf_side ? reinterpret_cast<unsigned*>(h->d_step_words) + 32 : nullptr;
-    if (ekf_side) { h->front_mark = side_words; h->front_mark_val = ++h->ekf_side_seq; }
+    if (ekf_side) { c.front_mark = side_words; c.front_mark_val = ++h->ekf_side_seq; }
     else { const int re = launch_ekf(h, s); if (re != ORCVIO_OK) return re; }
     // (the other way round -- prior on the origin stream, feature branch forked -- measured 15 us slower)
-    h->A_deferred = front_defers_assembly(h);
-    if (front_fused_active(h)) {   // one stream, no fork: the prior is factored by workgroup 0 of the feature launch
+    h->A_deferred = front_defers_assembly(h, c.retry_forked);
+    if (front_fused_active(h, c.retry_forked)) {   // one stream, no fork: the prior is factored by workgroup 0 of the feature launch
         // ... and the compression behind the tracks, under the factorisation
         h->prior_forked = false;
-        int rc = launch_front(h, s, h->d_A, h->A_deferred);
+        int rc = launch_front(h, s, c, h->d_A, h->A_deferred);
         if (rc == ORCVIO_OK && ekf_side) {
             const unsigned seq = h->ekf_side_seq;
             h->ekf_side_used = true;
@@ -1080,10 +1072,10 @@ static int enqueue_update(orcvio_msckf_handle* h, hipStream_t s, const std::func
             rc = launch_ekf(h, h->side);
             hipLaunchKernelGGL(k_obj_done, dim3(1), dim3(64), 0, h->side, side_words + 1, seq);
             HIPCHK(hipGetLastError());
-            h->asm_wait = side_words + 1; h->asm_wait_val = seq;
+            c.asm_wait = side_words + 1; c.asm_wait_val = seq;
         }
         if (rc == ORCVIO_OK && mid) rc = (*mid)();
-        for (int st = ST_FORM_U; st < ST_COUNT && rc == ORCVIO_OK; ++st) rc = launch_solve_stage(h, s, st);
+        for (int st = ST_FORM_U; st < ST_COUNT && rc == ORCVIO_OK; ++st) rc = launch_solve_stage(h, s, st, c);
         return rc;
     }
     if (mid) { const int rm = (*mid)(); if (rm != ORCVIO_OK) return rm; }
@@ -1091,6 +1083,6 @@ static int enqueue_update(orcvio_msckf_handle* h, hipStream_t s, const std::func
     if (rc == ORCVIO_OK) rc = launch_feature(h, s);
     if (rc == ORCVIO_OK) rc = launch_gram(h, s);
     if (rc == ORCVIO_OK) rc = launch_assemble(h, s, h->d_A);
-    if (rc == ORCVIO_OK) rc = launch_solve_tail(h, s);
+    if (rc == ORCVIO_OK) rc = launch_solve_tail(h, s, c);
     return rc;
 }

@@ -145,8 +145,6 @@ struct orcvio_msckf_handle {
     int obj_fused_opt = 1;              // ORCVIO_OBJ_FUSED=0: object tracks always through the three-launch pipeline (rows materialised)
     unsigned* d_obj_done = nullptr;     // completion counter of k_gemm_objA (cumulative; never reset)
     unsigned obj_done_total = 0u;       // what that counter reads once every compression enqueued so far has finished
-    const unsigned* join_wait = nullptr;   // the next ST_FORM_U product polls this counter (frame call) ...
-    unsigned join_expect = 0u;          // ... until it reaches this value
     int early_rows_tot = 0, early_no_max = 0, early_dof = 0, early_Fmax = 1; size_t early_nd = 0, early_ni = 0;   // ... and what its scan of the tracks found
     bool obj_early_done = false;        // orcvio_msckf_io_update_frame has enqueued this update's compression already (objects_local_tracks skips it)
     bool obj_last_fused = false;        // the last object update from tracks took the one-launch compression
@@ -178,7 +176,6 @@ struct orcvio_msckf_handle {
     int aux_next = 0;
     bool obj_status_cleared = false;    // k_object_rows_batch of the current object update has zeroed the shard status words (info[9..12])
     int last_run_kind = 0;              // 0: run_update (single GPU), 1: run_local / run_finish (staged or sharded), 2: objects
-    bool front_retry_forked = false;    // (download: the fused front end lost a hand-off; re-running on the forked path)
     int front_spin_limit = 1 << 19;    // polls before a workgroup of k_front gives up at the device-wide counter (tens of ms)
     int front_fallbacks = 0;            // how often that happened (orcvio_msckf_counters [0])
     long long cnt_graph_captures = 0, cnt_graph_replays = 0, cnt_plain_runs = 0;   // launch sequences captured / replayed from a graph / enqueued as plain launches
@@ -226,7 +223,6 @@ struct orcvio_msckf_handle {
     bool front_u = false;               // ORCVIO_FRONT_U=1: U = [A; b^T] L_a by the feature workgroups of k_front, behind the Grams (FrontUArgs) instead of the
                                         // k_gemm_asmA launch -- bit-identical, tested, and SLOWER (k_front 39.5 -> 54.9 us for a launch of 8.3 + gap: a
                                         // second device-wide barrier, and 144 strips of A read past the caches): a measured negative, kept opt-in
-    bool front_did_U = false;           // ... the launch_front of this update did
     double chain_fin_thr = 0.0;         // ... and the threshold it used
     std::shared_ptr<void> prestage;     // ObjPrestage (capi_objects.inc): what orcvio_msckf_io_stage_object_tracks left for the next frame call
     unsigned long long cnt_prestaged = 0;   // frame calls that found their object tracks staged ahead
@@ -236,7 +232,6 @@ struct orcvio_msckf_handle {
                                         // launch behind it: 1 = in the chained frame call (both halves: 8-9 us off the frame), 2 = every update whose solve
                                         // takes the look-ahead form (measured 2 us SLOWER per queued update: the in-launch hand-off costs what the launch
                                         // boundary does, and the longer launch delays the next replay), 0 = never (ORCVIO_FUSE_FINISH)
-    bool fin_frame = false;             // the chained frame call is enqueueing its feature half
     int la_spin = 1 << 22;              // polls (~1 us each) before a wait inside k_potrf_solve_la gives up: the update is then run again through k_potrf_solve
     // second solve context of the frame call's chained object solve (capi_frame.inc, ORCVIO_FRAME_CHAIN): allocated on first use
     double *d_U2 = nullptr, *d_M2 = nullptr, *d_RM2 = nullptr, *d_DinvM2 = nullptr, *d_Z2 = nullptr;
@@ -245,8 +240,6 @@ struct orcvio_msckf_handle {
     unsigned chain_seq = 0u;
     long long cnt_chained = 0;          // frames whose object solve ran chained (orcvio_msckf_counters [6])
     bool frame_chain = true;            // ORCVIO_FRAME_CHAIN (read at create, default 1): orcvio_msckf_io_update_frame runs the object solve chained (capi_frame.inc)
-    unsigned* mark_M_word = nullptr;    // launch_solve_stage(ST_FORM_M) stores mark_M_val there from a launch of its own behind the product (once)
-    unsigned mark_M_val = 0u;
     bool blk2_opt = true;               // ORCVIO_BLK2 (read at create): windows of 15 .. 26 block steps factor by 2 x 2 blocks out of the register kernels
     bool la_attr = false;               // the dynamic-LDS opt-in of k_potrf_solve_la is set for this handle's device
     // multi-GPU: RCCL communicator of this handle (orcvio_msckf_comm_init), the all-gather buffer [world][NAP_max^2] and
@@ -308,33 +301,81 @@ struct orcvio_msckf_handle {
     // orcvio_msckf_io_step_frame (capi_step.inc): the second update of a frame goes through an arena pair of its own, swapped in and out
     char *d_in2 = nullptr, *h_stage2 = nullptr, *h_stage2_dev = nullptr;
     bool arena_swapped = false;
-    int* epi_info_keep = nullptr;       // io_enqueue hands it to k_epilogue (EpilogueArgs.info_keep); set by orcvio_msckf_io_update_frame around its feature half
     int* d_step_words = nullptr;        // [0..15] status words of the frame's first update, kept for the second update's commit (info_also)
     std::vector<int> step_row_ptr;      // the second update's row offsets
     long long cnt_step_frames = 0, cnt_step_repairs = 0;   // frames through orcvio_msckf_io_step_frame; updates of such frames run again after a lost hand-off
-    bool step_ingested = false;         // k_frame_head has pulled the arena of the update being enqueued (io_enqueue skips its ingest launch)
     bool ekf_one_launch = true;         // the in-state features' evaluation, fill and gate in ONE launch (k_ekf_evalgate) instead of three (ORCVIO_EKF_ONE_LAUNCH=0, diagnostics)
     bool finpub_opt = true;             // a feature update's k_finish_sqrt + k_epilogue as ONE launch (k_finish_pub) on the in-place paths (ORCVIO_FINISH_PUB=0, diagnostics)
-    FinishPubArgs* fin_pub = nullptr;   // set by io_enqueue around enqueue_update: launch_solve_stage(ST_FINISH) launches k_finish_pub with it
     bool last_finpub_commit = false;    // the update enqueued last committed by writing P+ into the spare covariance buffer: the host swaps d_Pres / d_Ptmp
     bool thin_opt = true;               // updates of at most THIN_MAX_ROWS projected rows on the in-place paths take the reference's direct form (k_thin_gain / k_thin_apply;
                                         // ORCVIO_THIN_UPDATE=0, diagnostics): pruneImuStateBuffer's update is a handful of rows
     double *d_Hthin = nullptr, *d_Vthin = nullptr, *d_uthin = nullptr;   // its projected rows [THIN_MAX_ROWS][NAP_max], V [n_max][THIN_MAX_ROWS], u
-    bool thin_blocked = false;          // orcvio_msckf_update_features with K / G / H_thin requested: those are derived from the general path's factors
     bool last_update_thin = false;      // the update enqueued last took it: its commit leaves NO square-root factor
     bool step_fused = true;             // ORCVIO_STEP_FUSED=0 (diagnostics build): the frame's small steps as the separate launches and copies of the round-5 calls
     // the frame call's in-state rows beside k_front (enqueue_update): k_wait_word -> k_ekf_evalgate -> k_gram -> k_obj_done on `side`, joined
     // by two polled words (d_step_words[32]: k_front has started = the frame head is complete; [33]: the rows' Gram is complete, k_gemm_asmA_w)
     bool ekf_side_opt = true;           // ORCVIO_STEP_EKF_SIDE=0 (diagnostics build): the rows on the update's own stream, in front of k_front
-    bool ekf_side_now = false;          // set by orcvio_msckf_io_step_frame around its first update
     bool ekf_side_used = false;         // the frame being enqueued has work on `side` (a repair drains it)
     long long ekf_side_skip_until = 0;  // a frame whose side-stream join gave up was repaired: the next 4 096 frames keep the rows on the update's own stream
                                         // (a profiler that serialises dispatches, another tenant: the join must not cost its bound on every frame)
     unsigned ekf_side_seq = 0;
-    unsigned* front_mark = nullptr; unsigned front_mark_val = 0;       // launch_front: FrontGramArgs.started
-    const unsigned* asm_wait = nullptr; unsigned asm_wait_val = 0;     // launch_solve_stage(ST_FORM_U): k_gemm_asmA_w
     double chi2_prob_cached = -1.0;
 };
+
+// What ONE enqueue of an update is asked for, passed by reference down io_enqueue -> enqueue_update -> launch_front / launch_solve_stage.
+// Nothing of it is state of the filter: it dies with the scope of the caller that owns it.  A default-constructed record is a plain update.
+struct UpdateCall {
+    // ---- set by the caller
+    bool fin_pub = false;               // launch_solve_stage(ST_FINISH) launches k_finish_pub with pub (io_enqueue fills it); enqueue_thin takes its commit / publication part
+    FinishPubArgs pub{};
+    int* info_keep = nullptr;           // k_epilogue keeps a copy of this update's status words there (EpilogueArgs.info_keep: the frame call's feature half)
+    const int* info_also = nullptr;     // a second status block whose refusal refuses this update's commit too (the step call's second update)
+    bool fin_frame = false;             // the chained frame call is enqueueing its feature half (finish_fused_active)
+    bool ekf_side = false;              // the step call's first update: the in-state rows beside k_front, on the side stream
+    bool already_ingested = false;      // k_frame_head has pulled the arena of this update (io_enqueue skips its ingest launch)
+    unsigned* mark_M_word = nullptr;    // ST_FORM_M / ST_POTRF_M store mark_M_val there once M is formed, and put the pointer back to null: the caller
+    unsigned mark_M_val = 0u;           //  sees from its record whether the mark went out
+    const unsigned* join_wait = nullptr;   // the ST_FORM_U product polls this counter (the frame call's object half) ...
+    unsigned join_expect = 0u;          // ... until it reaches this value
+    bool thin_blocked = false;          // K / G / H_thin requested: those are derived from the general path's factors (thin_possible)
+    bool retry_forked = false;          // the repeat of an update that lost an in-launch hand-off: forked front end, one-workgroup factorisation + solve
+    const std::function<int()>* mid = nullptr;   // called once the tracks' launch is out (enqueue_update)
+    // ---- left by one stage for a later stage of the same enqueue
+    unsigned* front_mark = nullptr; unsigned front_mark_val = 0;       // enqueue_update -> launch_front: FrontGramArgs.started
+    const unsigned* asm_wait = nullptr; unsigned asm_wait_val = 0;     // enqueue_update -> launch_solve_stage(ST_FORM_U): k_gemm_asmA_w
+    bool front_did_U = false;           // launch_front formed U behind its Grams (ORCVIO_FRONT_U): ST_FORM_U has nothing to launch
+};
+
+// ---- resident covariance / factor bookkeeping of the handle ---------------------------------------------------------------------
+// saved and restored around steps that are enqueued ahead of their outcome
+struct CovState { double *Pres, *Ptmp, *Sres, *Stmp; int res_n, fac_n, fac_k, fac_ld, fac_tail; bool fac_valid; };
+static inline CovState cov_state(const orcvio_msckf_handle* h) {
+    return CovState{h->d_Pres, h->d_Ptmp, h->d_Sres, h->d_Stmp, h->res_n, h->fac_n, h->fac_k, h->fac_ld, h->fac_tail, h->fac_valid};
+}
+static inline void cov_restore(orcvio_msckf_handle* h, const CovState& c) {
+    h->d_Pres = c.Pres; h->d_Ptmp = c.Ptmp; h->d_Sres = c.Sres; h->d_Stmp = c.Stmp;
+    h->res_n = c.res_n; h->fac_n = c.fac_n; h->fac_k = c.fac_k; h->fac_ld = c.fac_ld; h->fac_tail = c.fac_tail; h->fac_valid = c.fac_valid;
+}
+// the factor the last launch wrote into the spare buffer becomes the resident one: S is n x k with leading dimension ld, its last `tail`
+// columns zero in the active rows (the ONE place the two factor buffers change roles)
+static inline void fac_adopt(orcvio_msckf_handle* h, int n, int k, int ld, int tail) {
+    std::swap(h->d_Sres, h->d_Stmp);
+    h->fac_n = n; h->fac_k = k; h->fac_ld = ld; h->fac_tail = tail; h->fac_valid = true;
+}
+// ... the factor S+ = sigma Z^T of the update that has just been enqueued, and its covariance
+static inline void fac_adopt_update(orcvio_msckf_handle* h) {
+    fac_adopt(h, h->n, h->kf, h->ldz, h->tail);
+    h->res_n = h->n;
+}
+// the host-side bookkeeping of a commit that rides in the update's last launch (valid whether or not the device refuses the update:
+// a refused commit leaves the prior and a copy of its factor, io_ops.hpp k_epilogue)
+static inline void commit_bookkeeping(orcvio_msckf_handle* h) {
+    if (h->last_finpub_commit) { std::swap(h->d_Pres, h->d_Ptmp); h->last_finpub_commit = false; }   // (k_finish_pub wrote P+ into the spare buffer)
+    if (h->last_update_thin) h->fac_valid = false;   // (the direct form of a thin stack leaves no square-root factor)
+    else if (h->factor_opt && h->n_nui == 0) fac_adopt(h, h->n, h->kf, h->ldz, h->tail);
+    else if (h->n_nui > 0) h->fac_valid = false;   // Schmidt: the nuisance block of P+ is the prior's, so P+ != s2 Z^T Z
+    h->res_n = h->n;
+}
 
 template <typename T>
 static int grow(T** p, size_t* cap, size_t need) {
