@@ -634,7 +634,8 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
  *                    0: the same poses as the first update (the caller's state increment does not reach into this call)
  *   remove_clones    window indices (ascending) of the clones marginalised at the end; n_remove <= 8
  * Not in this call: features ENTERING the state (orcvio_msckf_upload_new_features / _cov_commit_new_features change the state's dimension
- * between the updates: such frames take the separate calls), Schmidt nuisance poses, a communicator on the handle.
+ * between the updates: such frames take the separate calls), Schmidt nuisance poses, a communicator on the handle.  In-state features
+ * that LEAVE the state or change anchor: orcvio_msckf_io_step_frame_ex below.
  * Results: pointers into the handle's pinned output blocks, valid until the next call on the handle that takes tracks.
  * Status: a validation failure returns its code with NOTHING done.  A refusal on the device (ORCVIO_ERR_NOT_SPD: M not positive definite or
  * non-finite input) of the first update refuses the second as well; the covariance bookkeeping of the frame (propagation, augmentation,
@@ -880,6 +881,59 @@ int32_t orcvio_msckf_cov_remove_features(orcvio_msckf_handle* h, int32_t leg_dim
 int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags, int32_t idp_dim, int32_t literal_3d,
                                         int32_t n_clones, const double* poses, const double* R_b2c, const double* t_c_b,
                                         const orcvio_msckf_anchor_change* changes, int32_t count, double* new_param, double* new_inv_depth);
+
+/* ---- One filter frame in one call WITH the life cycle of the in-state features (hybrid filter) ------------------------------------
+ * orcvio_msckf_io_step_frame plus the frame's feature events, in the reference's order (processFeatures, src/orcvio.cpp:567-594):
+ *   1 propagation   2 augmentation   3 REMOVAL of the lost in-state features (removeLostFeatures -> rmLostFeaturesCov, :2233,
+ *   :3776-3828)   4 the first update, on the tracks and the in-state features that stay   5 the in-state features' INCREMENT
+ *   (measurementUpdate_hybrid :1842-1889) and the window's pose step   6 the ANCHOR CHANGES of the features whose anchor clone
+ *   leaves (pruneImuStateBuffer :2664-2720, updateFeatureCov_*)   7 the prune update   8 marginalisation
+ * -- still one call and one wait: the removal is an index map inside the frame's first launch, the feature step rides in the launch
+ * in front of the second update, the anchor change is enqueued between the two updates and stores its results into the pinned
+ * output block ahead of the flag the call waits on.
+ * Call order as orcvio_msckf_io_step_frame; io_begin takes the window and ORCVIO_OPT_EXTRA_STATES as they are AFTER the removals:
+ * the resident dimension + 6 augment - idp_dim n_lost must equal io_begin's n, and ORCVIO_OPT_EXTRA_STATES idp_dim x the features that stay.
+ *   lost_slots       positions in feature_states before the call, strictly ascending; n_lost <= n_feature_states
+ *   changes          as orcvio_msckf_cov_change_anchors', at most 16; slots are positions AFTER the removals; the new anchor is the
+ *                    caller's choice (planAnchorChanges / getNewAnchorId, orcvio_msckf_host.hpp) and may not be in remove_clones
+ *   R_b2c, t_c_b     the IMU's CURRENT extrinsics (state_server.imu_state) before this frame's first update
+ *   prune_apply_dx != 0 (and the frame has a first update): the changed features' world positions are what the reference's state
+ *                    holds when pruneImuStateBuffer runs, derived ON THE DEVICE: the feature's parameters from its slam_features
+ *                    record (every change's slot must have one, anchored at old_anchor) take dx at the feature's own columns, p_w
+ *                    follows from the OLD anchor's camera pose as the pose step leaves it; changes[].p_w is ignored, p_fej used as
+ *                    given; the extrinsics take dx[15:21] (incrementState_IMUCam :4512-4517).  Under discard_large_update a
+ *                    discarded dx leaves poses and extrinsics alone but the parameters are STILL incremented (the reference's feature
+ *                    loop runs after incrementState_IMUCam's early return); a refused first update increments nothing (the record's
+ *                    p_w, the given extrinsics).
+ *   prune_apply_dx == 0 (or no first update: dx is zero): changes[].p_w and the given extrinsics as they are -- bit for bit the
+ *                    separate calls cov_propagate, cov_augment, cov_remove_features, update, cov_change_anchors, update, cov_remove_clones.
+ * Results: new_param [n_changes][3], new_inv_depth [n_changes] (as orcvio_msckf_cov_change_anchors') in the pinned output block.
+ * Status: every validation failure (those of orcvio_msckf_cov_remove_features / _cov_change_anchors too) returns its code with NOTHING
+ * done.  Removals and anchor changes are bookkeeping: like propagation and marginalisation they stand when an update is refused on
+ * the device.  A changed feature whose derived position is not finite (an incremented inverse depth of zero) leaves P and its factor
+ * without ANY of the frame's anchor changes and refuses the prune update: status_changes = status_prune = ORCVIO_ERR_NOT_SPD.  A lost
+ * in-launch hand-off is repaired inside the call; the anchor changes are applied once.
+ * Not in this call: features ENTERING the state, Schmidt nuisance states (ORCVIO_OPT_SCHMIDT_STATES) together with events, a
+ * communicator on the handle, more than 512 in-state features (ORCVIO_ERR_CAPACITY). */
+typedef struct orcvio_msckf_frame_events {
+    int32_t idp_dim;               /* 1 or 3                                                                    */
+    int32_t literal_3d;            /* as orcvio_msckf_cov_change_anchors                                        */
+    int32_t n_feature_states;      /* in-state features BEFORE this frame's removals                            */
+    const int32_t* lost_slots;     /* [n_lost]                                                                  */
+    int32_t n_lost;
+    const orcvio_msckf_anchor_change* changes;   /* [n_changes]                                                 */
+    int32_t n_changes;
+    const double* R_b2c;           /* [9]                                                                       */
+    const double* t_c_b;           /* [3]                                                                       */
+} orcvio_msckf_frame_events;
+typedef struct orcvio_msckf_frame_result_ex {
+    orcvio_msckf_frame_result frame;   /* as orcvio_msckf_io_step_frame's                                       */
+    const double* new_param;       /* [n_changes][3]  NULL without changes                                      */
+    const double* new_inv_depth;   /* [n_changes]                                                               */
+    int32_t status_changes;        /* ORCVIO_OK, or ORCVIO_ERR_NOT_SPD: a changed feature's position not finite */
+} orcvio_msckf_frame_result_ex;
+int32_t orcvio_msckf_io_step_frame_ex(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* step, const orcvio_msckf_frame_events* events,
+                                      orcvio_msckf_frame_result_ex* result);
 
 /* ---- Environment switches (read once per process; diagnostics and A/B measurements -- every one of them leaves the results unchanged) ----
  *   ORCVIO_COMM_TIMEOUT_S   bound of every wait another rank can strand, seconds (default 180)

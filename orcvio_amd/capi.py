@@ -43,7 +43,7 @@ EXPORTS = [
     'orcvio_msckf_comm_barrier', 'orcvio_msckf_comm_allreduce_max', 'orcvio_msckf_io_begin', 'orcvio_msckf_io_update',
     'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect',
     'orcvio_msckf_objects_refined', 'orcvio_msckf_counters', 'orcvio_msckf_comm_details', 'orcvio_msckf_profile_sharded',
-    'orcvio_msckf_io_step_frame', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
+    'orcvio_msckf_io_step_frame', 'orcvio_msckf_io_step_frame_ex', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
 ]
 
 
@@ -211,6 +211,7 @@ def _bind(lib):
     lib.orcvio_msckf_io_submit.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.orcvio_msckf_io_collect.argtypes = [C.c_void_p, _ip]
     lib.orcvio_msckf_io_step_frame.argtypes = [C.c_void_p, C.POINTER(FrameStep), C.POINTER(FrameResult)]
+    lib.orcvio_msckf_io_step_frame_ex.argtypes = [C.c_void_p, C.POINTER(FrameStep), C.POINTER(FrameEvents), C.POINTER(FrameResultEx)]
     lib.orcvio_msckf_update_features_sharded.argtypes = lib.orcvio_msckf_update_features.argtypes
     lib.orcvio_msckf_update_object_tracks_sharded.argtypes = lib.orcvio_msckf_update_object_tracks.argtypes
     return lib
@@ -278,6 +279,19 @@ class AnchorChange(C.Structure):
     """orcvio_msckf_anchor_change (include/orcvio_msckf.h)."""
     _fields_ = [('slot', C.c_int32), ('old_anchor', C.c_int32), ('new_anchor', C.c_int32), ('p_w', C.c_double * 3),
                 ('p_fej', C.c_double * 3)]
+
+
+class FrameEvents(C.Structure):
+    """orcvio_msckf_frame_events (include/orcvio_msckf.h)."""
+    _fields_ = [('idp_dim', C.c_int32), ('literal_3d', C.c_int32), ('n_feature_states', C.c_int32), ('lost_slots', C.POINTER(C.c_int32)),
+                ('n_lost', C.c_int32), ('changes', C.POINTER(AnchorChange)), ('n_changes', C.c_int32), ('R_b2c', C.POINTER(C.c_double)),
+                ('t_c_b', C.POINTER(C.c_double))]
+
+
+class FrameResultEx(C.Structure):
+    """orcvio_msckf_frame_result_ex (include/orcvio_msckf.h)."""
+    _fields_ = [('frame', FrameResult), ('new_param', C.POINTER(C.c_double)), ('new_inv_depth', C.POINTER(C.c_double)),
+                ('status_changes', C.c_int32)]
 
 
 class MsckfNewFeatures(C.Structure):
@@ -952,8 +966,28 @@ class MsckfUpdater:
         self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), _d(P)), 'orcvio_msckf_cov_get')
         return P
 
+    def io_step_frame_ex(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
+                         n_feature_states=0, lost=(), changes=(), R_b2c=None, t_c_b=None, literal_3d=0, raise_on_refusal=True):
+        """orcvio_msckf_io_step_frame_ex: io_step_frame plus the frame's feature events.  `win` and set_extra_states are those AFTER the
+        removals; lost: slots in feature_states before the call (ascending), n_feature_states their count before the removals;
+        changes: objects with slot (after the removals), old, new, p_w, p_fej; R_b2c / t_c_b: the IMU's current extrinsics.
+        Returns io_step_frame's dict plus new_param [k, 3], new_inv_depth [k], status_changes."""
+        ls = np.ascontiguousarray(list(lost), dtype=np.int32)
+        k = len(changes)
+        arr = (AnchorChange * max(k, 1))()
+        for q, c in enumerate(changes):
+            arr[q].slot, arr[q].old_anchor, arr[q].new_anchor = int(c.slot), int(c.old), int(c.new)
+            arr[q].p_w[:] = [float(x) for x in c.p_w]
+            pf = c.p_w if getattr(c, 'p_fej', None) is None else c.p_fej
+            arr[q].p_fej[:] = [float(x) for x in pf]
+        Rb = None if R_b2c is None else np.ascontiguousarray(R_b2c, dtype=np.float64).reshape(9)
+        tb = None if t_c_b is None else np.ascontiguousarray(t_c_b, dtype=np.float64).reshape(3)
+        ev = FrameEvents(int(idp_dim), int(literal_3d), int(n_feature_states), _i(ls) if len(ls) else None, len(ls), arr if k else None, k,
+                         _d(Rb), _d(tb))
+        return self.io_step_frame(win, Phi, Q, augment, slam, idp_dim, prune, prune_apply_dx, remove, raise_on_refusal, _events=(ev, k, (ls, arr, Rb, tb)))
+
     def io_step_frame(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
-                      raise_on_refusal=True):
+                      raise_on_refusal=True, _events=None):
         """orcvio_msckf_io_step_frame: ONE filter frame on the resident covariance -- propagation, augmentation, the update on `win`'s
         tracks (+ the in-state features `slam`), the prune update on `prune`'s tracks (a synth.Window sharing win's poses), the
         marginalisation of `remove`.  Returns dict(dx, gamma, accept, stats, prune_dx, prune_gamma, prune_accept, prune_stats, n_after,
@@ -987,13 +1021,26 @@ class MsckfUpdater:
         if len(rm):
             st.remove_clones = _i(rm)
         st.n_remove = len(rm)
-        res = FrameResult()
-        rc = self.lib.orcvio_msckf_io_step_frame(self.h, C.byref(st), C.byref(res))
+        extra = {}
+        if _events is None:
+            res = FrameResult()
+            rc = self.lib.orcvio_msckf_io_step_frame(self.h, C.byref(st), C.byref(res))
+            where = 'orcvio_msckf_io_step_frame'
+        else:
+            rex = FrameResultEx()
+            rc = self.lib.orcvio_msckf_io_step_frame_ex(self.h, C.byref(st), C.byref(_events[0]), C.byref(rex))
+            where = 'orcvio_msckf_io_step_frame_ex'
+            res = rex.frame
         if rc != 0 and (raise_on_refusal or rc != 6):
-            raise MsckfError(rc, 'orcvio_msckf_io_step_frame')
+            raise MsckfError(rc, where)
         n = int(io['n'])
         arr = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(max(k, 1),))[:k].astype(dt, copy=True) if p else None
-        return dict(rc=rc, dx=arr(res.dx, n, np.float64), gamma=arr(res.gamma, win.F, np.float64), accept=arr(res.accept, win.F, np.int32),
+        if _events is not None:
+            k = _events[1]
+            par = arr(rex.new_param, 3 * k, np.float64)
+            extra = dict(new_param=None if par is None else par.reshape(k, 3), new_inv_depth=arr(rex.new_inv_depth, k, np.float64),
+                         status_changes=int(rex.status_changes))
+        return dict(**extra, rc=rc, dx=arr(res.dx, n, np.float64), gamma=arr(res.gamma, win.F, np.float64), accept=arr(res.accept, win.F, np.int32),
                     stats=np.array(res.stats[:], dtype=np.int32), prune_dx=arr(res.prune_dx, n, np.float64),
                     prune_gamma=arr(res.prune_gamma, F2, np.float64), prune_accept=arr(res.prune_accept, F2, np.int32),
                     prune_stats=np.array(res.prune_stats[:], dtype=np.int32), n_after=int(res.n_after), status_first=int(res.status_first),

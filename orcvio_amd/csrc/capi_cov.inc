@@ -273,7 +273,7 @@ int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msc
     const int feat_end = n - 6 * h->n_nui;
     if (feat_end < base || (feat_end - base) % d != 0) { g_last_error = "cov_change_anchors: the states behind the clones are not d-wide feature states followed by the ORCVIO_OPT_SCHMIDT_STATES nuisance block"; return ORCVIO_ERR_INVALID; }
     if (count == 0) return ORCVIO_OK;
-    std::vector<int> ci(3 * count);
+    std::vector<int> ci(ANCHOR_CHG_STRIDE * count, 0);
     std::vector<double> cd(6 * count);
     for (int q = 0; q < count; ++q) {
         const orcvio_msckf_anchor_change& c = changes[q];
@@ -283,7 +283,7 @@ int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msc
         if (c.old_anchor < 0 || c.old_anchor >= n_clones || c.new_anchor < 0 || c.new_anchor >= n_clones) { g_last_error = "cov_change_anchors: anchor outside the window"; return ORCVIO_ERR_INVALID; }
         if (c.old_anchor == c.new_anchor) { g_last_error = "cov_change_anchors: old anchor == new anchor"; return ORCVIO_ERR_INVALID; }
         if (!all_finite(c.p_w, 3) || (flags->if_fej && !all_finite(c.p_fej, 3))) { g_last_error = "cov_change_anchors: non-finite feature position"; return ORCVIO_ERR_INVALID; }
-        ci[3 * q] = c.slot; ci[3 * q + 1] = c.old_anchor; ci[3 * q + 2] = c.new_anchor;
+        ci[ANCHOR_CHG_STRIDE * q] = c.slot; ci[ANCHOR_CHG_STRIDE * q + 1] = c.old_anchor; ci[ANCHOR_CHG_STRIDE * q + 2] = c.new_anchor;
         for (int a = 0; a < 3; ++a) { cd[6 * q + a] = c.p_w[a]; cd[6 * q + 3 + a] = flags->if_fej ? c.p_fej[a] : c.p_w[a]; }
     }
     double ext[12];
@@ -309,7 +309,7 @@ int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msc
     // Y = J P [k d][n] goes to d_Ptmp (n_max^2 >= k d n: k d <= n - base)
 #define LAUNCH_CA(D) hipLaunchKernelGGL(k_cov_change_anchors<D>, dim3(1), dim3(AnchorThreads<D>::value), 0, s, h->d_Pres, n, fac ? h->d_Sres : (double*)nullptr, \
                                         h->fac_ld, h->fac_k, (const double*)dposes, (const double*)dext, (const int*)h->d_covmap, (const double*)dcd, \
-                                        count, base, leg, flags->if_fej ? 1 : 0, literal_3d ? 1 : 0, dpar, h->d_Ptmp)
+                                        count, base, leg, flags->if_fej ? 1 : 0, literal_3d ? 1 : 0, dpar, h->d_Ptmp, AnchorFrameArgs{})
     if (d == 3) LAUNCH_CA(3);
     else LAUNCH_CA(1);
 #undef LAUNCH_CA

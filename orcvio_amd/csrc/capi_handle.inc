@@ -244,6 +244,8 @@ static void free_all(orcvio_msckf_handle* h) {
     if (h->h_stage2) (void)hipHostFree(h->h_stage2);
     if (h->d_in2) (void)hipFree(h->d_in2);
     if (h->d_step_words) (void)hipFree(h->d_step_words);
+    if (h->h_evt) (void)hipHostFree(h->h_evt);
+    if (h->d_evt) (void)hipFree(h->d_evt);
     for (double* q : {h->d_Hthin, h->d_Vthin, h->d_uthin}) if (q) (void)hipFree(q);
     if (h->d_obj_in) (void)hipFree(h->d_obj_in);
     for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);

@@ -4,6 +4,11 @@
 // update (:2497-2560), pruneImuStateBuffer's update (:2803-2851) and marginalisation (:2874-2956) -- enqueued at once on the handle's
 // stream on the resident covariance; the calling thread waits once, for the flag word behind the last update.
 //
+// orcvio_msckf_io_step_frame_ex is the same call with the frame's feature events (ONE implementation, step_frame_impl): the lost
+// in-state features leave inside the first launch (an index map on k_frame_head's output), the changed features' positions and the
+// IMU's extrinsics are made by the launch in front of the second update, k_cov_change_anchors is enqueued between the two updates and
+// stores its results into pinned memory ahead of the flag the call waits on.
+//
 // The second update's tracks go through a SECOND pinned / device arena pair (the first update's inputs and results must stay where
 // they are: its kernels have their pointers, the caller reads its results when the call returns); the arenas are swapped in and out of
 // the handle's fields around the second update, so that every layout / launch helper works on it unchanged.
@@ -82,12 +87,59 @@ static int launch_frame_head(orcvio_msckf_handle* h, hipStream_t s, FrameHeadArg
     return ORCVIO_OK;
 }
 
+// ---- the frame's feature events (orcvio_msckf_io_step_frame_ex) --------------------------------------------------------------------
+// Staging of their own: pinned [chg_i 16 x 4 | chg_d FS_DOUBLES | par_host 64 doubles | status] and device [p_w, p_fej, extrinsics
+// FS_DOUBLES | params 64 doubles | status word | poses maxN records (a frame without a second update)].  The pinned block is written
+// by the host once per call, behind a wait that covers every reader of the call before (the anchor change runs in front of the flag
+// the call waits on, or raises it itself).
+enum { EVT_H_CHGD = 256, EVT_H_PAR = 1152, EVT_H_STATUS = 1664, EVT_H_BYTES = 2048, EVT_D_PAR = 1024, EVT_D_STATUS = 1536, EVT_D_POSES = 2048 };
+static int step_events(orcvio_msckf_handle* h) {
+    if (h->d_evt) return ORCVIO_OK;
+    HIPCHK(hipMalloc(&h->d_evt, EVT_D_POSES + sizeof(double) * POSE_STRIDE * (size_t)h->maxN));
+    HIPCHK(hipMemset(h->d_evt, 0, EVT_D_POSES));
+    HIPCHK(hipHostMalloc(&h->h_evt, EVT_H_BYTES, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->h_evt_dev), h->h_evt, 0));
+    std::memset(h->h_evt, 0, EVT_H_BYTES);
+    return ORCVIO_OK;
+}
+struct StepEvents {   // validated; k == 0 and lost.count == 0: a frame without events
+    int idp = 1, literal_3d = 0, k = 0;
+    LostMap lost{};
+    std::vector<int> lost_slots;
+    FeatureStepArgs fs{};
+};
+static inline int* evt_status_host(const orcvio_msckf_handle* h) { return reinterpret_cast<int*>(h->h_evt + EVT_H_STATUS); }
+// k_cov_change_anchors on the resident covariance as the stream leaves it at this point, its inputs the feature step's outputs
+static int launch_change_anchors(orcvio_msckf_handle* h, hipStream_t s, const StepEvents& e, const double* poses, const int* first_info, bool wire, bool publish) {
+    const int n = h->res_n, leg = h->flags.leg_dim, base = leg + 6 * h->N;
+    const bool fac = h->fac_valid && h->fac_n == n;
+    const double* dev = reinterpret_cast<const double*>(h->d_evt);
+    AnchorFrameArgs fr{};
+    fr.refuse = reinterpret_cast<const int*>(h->d_evt + EVT_D_STATUS);
+    fr.first_info = first_info;
+    fr.refuse_also = wire ? h->d_step_words + 3 : nullptr;
+    fr.par_host = reinterpret_cast<double*>(h->h_evt_dev + EVT_H_PAR);
+    fr.status_host = reinterpret_cast<int*>(h->h_evt_dev + EVT_H_STATUS);
+    if (publish) { fr.seq = h->d_seq; fr.flag = h->h_flag_dev; }
+    // (Y = J P goes to the spare covariance buffer: the buffer the commit in front has just left, overwritten as a whole by whatever writes it next)
+#define LAUNCH_CA(D) hipLaunchKernelGGL(k_cov_change_anchors<D>, dim3(1), dim3(AnchorThreads<D>::value), 0, s, h->d_Pres, n, fac ? h->d_Sres : (double*)nullptr, \
+                                        h->fac_ld, h->fac_k, poses, dev + FS_EXT, reinterpret_cast<const int*>(h->h_evt_dev), dev, e.k, base, leg, \
+                                        h->flags.if_fej ? 1 : 0, e.literal_3d ? 1 : 0, reinterpret_cast<double*>(h->d_evt + EVT_D_PAR), h->d_Ptmp, fr)
+    if (e.idp == 3) LAUNCH_CA(3);
+    else LAUNCH_CA(1);
+#undef LAUNCH_CA
+    HIPCHK(hipGetLastError());
+    if (!fac) h->fac_valid = false;
+    return ORCVIO_OK;
+}
+
 struct StepSecond {   // what the second update of the frame needs besides the handle
     const orcvio_msckf_tracks* tr;
     const double* posesA;   // device: the first update's window poses
     const double* dxA;      // device: its dx
     const int* infoA;       // device: its status words
     int apply_dx;
+    const StepEvents* ev;   // anchor changes between the pose step and the update (nullptr: none)
 };
 
 // the second update's inputs into the (swapped-in) second arena and its launches; `wait` = run it the safe way (separate launches, the
@@ -111,8 +163,10 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
     // window poses: the first update's, on the device (incremented by its dx or copied); the first update's status words are kept
     PoseStepArgs ps{b.posesA, h->d_poses, N, POSE_STRIDE, b.dxA, fl.leg_dim, b.apply_dx, (fl.use_larvio || fl.use_left_perturbation) ? 1 : 0,
                     fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words};
+    const bool events = b.ev && b.ev->k > 0;
     if (!h->step_fused || safe) {
-        hipLaunchKernelGGL(k_pose_step, dim3(1), dim3(64), 0, s, ps);
+        if (events) hipLaunchKernelGGL(k_event_step, dim3(1), dim3(128), 0, s, ps, b.ev->fs);
+        else hipLaunchKernelGGL(k_pose_step, dim3(1), dim3(64), 0, s, ps);
         HIPCHK(hipGetLastError());
         // everything the caller's tracks hold, behind the poses
         rc = launch_ingest(h, s, h->h_stage_dev + h->io_optr, h->d_in + h->io_optr, upload_bytes(h) - h->io_optr);
@@ -121,15 +175,28 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
     if (rc == ORCVIO_OK) rc = upload_finalize(h, who);
     if (rc != ORCVIO_OK) return rc;
     h->pw_missing = false;
-    if (safe) return io_run_forked(h, stats);
+    if (safe) {
+        if (events) {   // the repair path waits anyway: the changed features' status is read before the update goes out
+            rc = launch_change_anchors(h, s, *b.ev, h->d_poses, nullptr, false, false);
+            if (rc != ORCVIO_OK) return rc;
+            HIPCHK(hipStreamSynchronize(s));
+            if (*evt_status_host(h) != 0) { g_last_error = std::string(who) + ": a changed feature's position is not finite: no anchor change, no prune update"; return ORCVIO_ERR_NOT_SPD; }
+        }
+        return io_run_forked(h, stats);
+    }
     h->last_stream = s;
     if (h->step_fused) {   // ONE launch in front of the update: the pose step and the pull of the tracks + derived index arrays
         FrameHeadArgs fa{};
         fa.nb_cov = 0; fa.pose_block = 0; fa.ps = ps;
+        if (events) fa.fs = b.ev->fs;
         fa.nseg = 2;
         fa.src[0] = h->h_stage_dev; fa.dst[0] = h->d_in; fa.bytes[0] = (unsigned)h->io_poses;
         fa.src[1] = h->h_stage_dev + h->io_optr; fa.dst[1] = h->d_in + h->io_optr; fa.bytes[1] = (unsigned)(upload_bytes(h) - h->io_optr);
         rc = launch_frame_head(h, s, fa);
+        if (rc != ORCVIO_OK) return rc;
+    }
+    if (events) {   // enqueued, not waited for: between the first update's commit and this update
+        rc = launch_change_anchors(h, s, *b.ev, h->d_poses, h->d_step_words, true, false);
         if (rc != ORCVIO_OK) return rc;
     }
     UpdateCall c;
@@ -145,8 +212,89 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
     return ORCVIO_OK;
 }
 
-int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* st, orcvio_msckf_frame_result* res) {
-    const char* who = "orcvio_msckf_io_step_frame";
+// A frame without a second update that carries anchor changes: the pose step into the events' own pose records, the feature step and
+// the anchor change as two launches.  publish: nothing of the frame follows that the call could wait for -- the anchor change
+// raises the flag.  safe: the repair path (no kept status words: the first update has been run again and checked by the host).
+static int step_events_alone(orcvio_msckf_handle* h, hipStream_t s, const orcvio_msckf_flags& fl, int N, const StepSecond& b, bool safe, bool publish) {
+    double* poses = reinterpret_cast<double*>(h->d_evt + EVT_D_POSES);
+    PoseStepArgs ps{b.posesA, poses, N, POSE_STRIDE, b.dxA, fl.leg_dim, b.apply_dx, (fl.use_larvio || fl.use_left_perturbation) ? 1 : 0,
+                    fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words};
+    hipLaunchKernelGGL(k_event_step, dim3(1), dim3(128), 0, s, ps, b.ev->fs);
+    HIPCHK(hipGetLastError());
+    return launch_change_anchors(h, s, *b.ev, poses, safe ? (const int*)nullptr : h->d_step_words, false, publish);
+}
+
+// The events of a frame checked against the frame's step and what stands in the arena -- BEFORE anything of the frame is enqueued --
+// and marshalled: the lost slots as the head's index map, the changes into the pinned staging.  first: the frame has a first update.
+static int step_validate_events(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* st, const orcvio_msckf_frame_events* ev, bool first,
+                                StepEvents& e, const char* who) {
+    auto bad = [&](const char* what) { g_last_error = std::string(who) + ": " + what; return ORCVIO_ERR_INVALID; };
+    if (!ev || (ev->n_lost == 0 && ev->n_changes == 0)) {
+        if (h->res_n + (st->augment ? 6 : 0) != h->n) return bad("the resident covariance (+ this frame's augmentation) does not match the window of io_begin");
+        return ORCVIO_OK;
+    }
+    const int d = ev->idp_dim, nfs = ev->n_feature_states, leg = h->flags.leg_dim, N = h->N;
+    if (h->n_nui > 0) return bad("feature events with Schmidt nuisance states (ORCVIO_OPT_SCHMIDT_STATES) take the separate calls");
+    if ((d != 1 && d != 3) || nfs < 0 || ev->n_lost < 0 || ev->n_lost > nfs || (ev->n_lost > 0 && !ev->lost_slots)) return bad("events: idp_dim is 1 or 3, 0 <= n_lost <= n_feature_states");
+    if (nfs > 64 * FH_LOST_WORDS) { g_last_error = std::string(who) + ": more in-state features than the frame call's removal map holds"; return ORCVIO_ERR_CAPACITY; }
+    if (ev->n_changes < 0 || ev->n_changes > ANCHOR_MAX_K) return bad("at most 16 anchor changes");
+    for (int q = 0; q < ev->n_lost; ++q)
+        if (ev->lost_slots[q] < 0 || ev->lost_slots[q] >= nfs || (q > 0 && ev->lost_slots[q] <= ev->lost_slots[q - 1])) return bad("lost_slots must be ascending and in range");
+    const int nkeep = nfs - ev->n_lost;
+    if (h->res_n + (st->augment ? 6 : 0) - d * ev->n_lost != h->n) return bad("the resident covariance (+ this frame's augmentation - the lost features) does not match the window of io_begin");
+    if (h->n_extra != d * nkeep) return bad("ORCVIO_OPT_EXTRA_STATES is not idp_dim x the in-state features that stay");
+    e.idp = d; e.literal_3d = ev->literal_3d; e.k = ev->n_changes;
+    e.lost.count = ev->n_lost; e.lost.idp = d; e.lost.nkeep = nkeep;
+    e.lost.fbase = h->n - h->n_extra;   // (the augmented state in front of the removal: the features begin where they do behind it)
+    e.lost_slots.assign(ev->lost_slots, ev->lost_slots + ev->n_lost);
+    for (int q = 0; q < ev->n_lost; ++q) e.lost.bits[ev->lost_slots[q] >> 6] |= 1ull << (ev->lost_slots[q] & 63);
+    if (e.k == 0) return ORCVIO_OK;
+    if (!ev->changes || !ev->R_b2c || !ev->t_c_b) return bad("changes need changes[], R_b2c and t_c_b");
+    if (N < 2) return bad("an anchor change needs two clones");
+    const bool derive = first && st->prune_apply_dx != 0;
+    const orcvio_msckf_slam_features* sf = st->slam_features;
+    { const int re = step_events(h); if (re != ORCVIO_OK) return re; }
+    int ci[4 * ANCHOR_MAX_K] = {0};
+    double cd[FS_DOUBLES] = {0};
+    for (int q = 0; q < e.k; ++q) {
+        const orcvio_msckf_anchor_change& c = ev->changes[q];
+        if (c.slot < 0 || c.slot >= nkeep) return bad("change: slot out of range (slots are positions AFTER the removals)");
+        for (int p2 = 0; p2 < q; ++p2)
+            if (ev->changes[p2].slot == c.slot) return bad("change: a slot listed twice");
+        if (c.old_anchor < 0 || c.old_anchor >= N || c.new_anchor < 0 || c.new_anchor >= N) return bad("change: anchor outside the window");
+        if (c.old_anchor == c.new_anchor) return bad("change: old anchor == new anchor");
+        for (int r = 0; r < st->n_remove; ++r)
+            if (st->remove_clones[r] == c.new_anchor) return bad("change: the new anchor is in remove_clones");
+        int rec = -1;
+        if (sf && sf->idp_dim == d)
+            for (int f = 0; f < sf->n_features && rec < 0; ++f)
+                if (sf->slot[f] == c.slot) rec = f;
+        if (rec >= 0 && sf->anchor[rec] != c.old_anchor) return bad("change: the feature's slam_features record is anchored elsewhere than old_anchor");
+        if (derive && rec < 0) return bad("change: with prune_apply_dx the changed feature needs its slam_features record (every in-state feature is tracked)");
+        if ((!derive && !all_finite(c.p_w, 3)) || (h->flags.if_fej && !all_finite(c.p_fej, 3))) return bad("change: non-finite feature position");
+        ci[4 * q] = c.slot; ci[4 * q + 1] = c.old_anchor; ci[4 * q + 2] = c.new_anchor; ci[4 * q + 3] = rec < 0 ? 0 : rec;
+        for (int a = 0; a < 3; ++a) { cd[6 * q + a] = c.p_w[a]; cd[6 * q + 3 + a] = h->flags.if_fej ? c.p_fej[a] : c.p_w[a]; }
+    }
+    for (int a = 0; a < 9; ++a) cd[FS_EXT + a] = ev->R_b2c[a];
+    for (int a = 0; a < 3; ++a) cd[FS_EXT + 9 + a] = ev->t_c_b[a];
+    if (!all_finite(cd + FS_EXT, 12)) return bad("non-finite extrinsics");
+    const double* poses = reinterpret_cast<const double*>(h->h_stage + h->io_poses);
+    for (int i = 0; i < N; ++i)
+        if (!all_finite(poses + (size_t)i * POSE_STRIDE, 27)) return bad("non-finite pose record");
+    std::memcpy(h->h_evt, ci, sizeof(ci));
+    std::memcpy(h->h_evt + EVT_H_CHGD, cd, sizeof(cd));
+    *evt_status_host(h) = 0;
+    e.fs.k = e.k; e.fs.idp = d; e.fs.base = leg + 6 * N;
+    e.fs.chg_i = reinterpret_cast<const int*>(h->h_evt_dev);
+    e.fs.chg_d = reinterpret_cast<const double*>(h->h_evt_dev + EVT_H_CHGD);
+    e.fs.out = reinterpret_cast<double*>(h->d_evt);
+    e.fs.status = reinterpret_cast<int*>(h->d_evt + EVT_D_STATUS);
+    return ORCVIO_OK;   // (fs.slam / fs.cap: once the records' device buffers stand, slam_prepare)
+}
+
+// One implementation behind both calls: ev == nullptr (or empty) is orcvio_msckf_io_step_frame.
+static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* st, const orcvio_msckf_frame_events* ev, orcvio_msckf_frame_result* res,
+                           orcvio_msckf_frame_result_ex* rex, const char* who) {
     if (!h || !st || !res) { g_last_error = std::string(who) + ": null argument"; return ORCVIO_ERR_INVALID; }
     if (h->io_submitted) { g_last_error = std::string(who) + ": an update submitted with orcvio_msckf_io_submit has not been collected"; return ORCVIO_ERR_INVALID; }
     if (!h->io_open || h->io_with_P) { g_last_error = std::string(who) + ": call orcvio_msckf_io_begin with with_P = 2 (or 0) first: the frame runs on the resident covariance"; return ORCVIO_ERR_INVALID; }
@@ -155,8 +303,6 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
     const int leg = fl.leg_dim, N = h->N, n = h->n;
     if (st->leg_dim != leg) { g_last_error = std::string(who) + ": leg_dim differs from the flags of io_begin"; return ORCVIO_ERR_INVALID; }
     if ((st->Phi == nullptr) != (st->Q == nullptr)) { g_last_error = std::string(who) + ": Phi and Q come together"; return ORCVIO_ERR_INVALID; }
-    if (h->res_n + (st->augment ? 6 : 0) != n) { g_last_error = std::string(who) + ": the resident covariance (+ this frame's augmentation) does not match the window of io_begin"; return ORCVIO_ERR_INVALID; }
-    if (st->augment && h->n_extra > h->res_n - 15) { g_last_error = std::string(who) + ": more extra states than the resident covariance has"; return ORCVIO_ERR_INVALID; }
     if (st->n_remove < 0 || st->n_remove > 8 || (st->n_remove > 0 && !st->remove_clones)) { g_last_error = std::string(who) + ": remove_clones: at most eight"; return ORCVIO_ERR_INVALID; }
     for (int k = 0; k < st->n_remove; ++k)
         if (st->remove_clones[k] < 0 || st->remove_clones[k] >= N || (k > 0 && st->remove_clones[k] <= st->remove_clones[k - 1])) {
@@ -164,6 +310,10 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
         }
     if (st->prune_tracks) { const int rv = step_validate_tracks(h, st->prune_tracks, N, fl.estimate_td != 0, who); if (rv != ORCVIO_OK) return rv; }
     HIPCHK(hipSetDevice(h->device));
+    StepEvents evs;
+    { const int rv = step_validate_events(h, st, ev, h->F > 0 || (st->slam_features && st->slam_features->n_features > 0), evs, who); if (rv != ORCVIO_OK) return rv; }
+    const int d_lost = evs.idp * evs.lost.count;   // states that leave in front of the first update
+    if (st->augment && h->n_extra + d_lost > h->res_n - 15) { g_last_error = std::string(who) + ": more extra states than the resident covariance has"; return ORCVIO_ERR_INVALID; }
     static const bool timing = dbg_getenv("ORCVIO_TIMING") != nullptr;   // diagnostics: host wall time of the parts of this call
     const auto tt0 = std::chrono::steady_clock::now();
     static double tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -188,9 +338,10 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
     const bool fused = h->step_fused && off_aux + 2 * al256(sizeof(double) * leg * leg) + slam_bytes <= h->in_cap;
     FrameHeadArgs fa{};
     fa.pose_block = -1;
-    if (fused && (st->Phi || st->augment)) {
-        const int nn = h->res_n, m = nn + (st->augment ? 6 : 0);
-        fa.P = h->d_Pres; fa.n = nn; fa.out = h->d_Ptmp; fa.m = m; fa.leg = leg; fa.pose = st->augment ? nn - h->n_extra : -1;
+    if (fused && (st->Phi || st->augment || d_lost > 0)) {
+        const int nn = h->res_n, m = nn + (st->augment ? 6 : 0) - d_lost;   // (m: the state the first update sees)
+        fa.P = h->d_Pres; fa.n = nn; fa.out = h->d_Ptmp; fa.m = m; fa.leg = leg; fa.pose = st->augment ? nn - (h->n_extra + d_lost) : -1;
+        fa.lost = evs.lost;
         fa.nb_cov = (m * m + 255) / 256;   // (the three regions enumerate every output element once)
         if (st->Phi) {
             char* hp = h->h_stage + off_aux;
@@ -202,15 +353,18 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
         std::swap(h->d_Pres, h->d_Ptmp);
         h->res_n = m;
         if (st->Phi) h->fac_valid = false;
-        else if (h->fac_valid && h->fac_n == nn) {   // augmentation alone: the factor's rows are copied as orcvio_msckf_cov_augment copies them
+        else if (h->fac_valid && h->fac_n == nn) {   // no propagation: the factor's rows are copied as orcvio_msckf_cov_augment copies them ...
             const int pose = fa.pose, ldo = round_up(m + 1, 16), fk = h->fac_k, fld = h->fac_ld;
             double* fs = h->d_Sres; double* fd = h->d_Stmp;
+            const LostMap lm = evs.lost;
             head.push_back([=]() -> int {
-                hipLaunchKernelGGL(k_fac_augment, dim3((fk * m + 255) / 256), dim3(256), 0, s, (const double*)fs, fld, fk, nn, pose, fd, ldo);
+                if (lm.count > 0)   // ... and as orcvio_msckf_cov_remove_features deletes them, in the same gather
+                    hipLaunchKernelGGL(k_fac_head, dim3((fk * m + 255) / 256), dim3(256), 0, s, (const double*)fs, fld, fk, pose, lm, m, fd, ldo);
+                else hipLaunchKernelGGL(k_fac_augment, dim3((fk * m + 255) / 256), dim3(256), 0, s, (const double*)fs, fld, fk, nn, pose, fd, ldo);
                 HIPCHK(hipGetLastError());
                 return ORCVIO_OK;
             });
-            fac_adopt(h, m, fk, ldo, 0);
+            fac_adopt(h, m, fk, ldo, st->augment ? 0 : h->fac_tail);
         } else h->fac_valid = false;
     }
     if (!fused && st->Phi) {
@@ -232,7 +386,7 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
         h->fac_valid = false;
     }
     if (!fused && st->augment) {
-        const int nn = h->res_n, m = nn + 6, pose = nn - h->n_extra;
+        const int nn = h->res_n, m = nn + 6, pose = nn - (h->n_extra + d_lost);   // (in front of the feature states as they are BEFORE the removal)
         double* src = h->d_Pres; double* dst = h->d_Ptmp;
         head.push_back([=]() -> int {
             hipLaunchKernelGGL(k_cov_augment, dim3((m * m + 255) / 256), dim3(256), 0, s, (const double*)src, nn, pose, dst);
@@ -251,6 +405,37 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
             });
             fac_adopt(h, m, fk, ldo, 0);
         } else h->fac_valid = false;
+    }
+    if (!fused && d_lost > 0) {   // the separate call's kernels (k_cov_remove / k_fac_remove) with its map
+        const int nn = h->res_n, m = nn - d_lost;
+        double* src = h->d_Pres; double* dst = h->d_Ptmp;
+        auto map = std::make_shared<std::vector<int>>();
+        for (int i = 0; i < m; ++i) {   // new index -> old index (ascending slots)
+            int o = i;
+            if (o >= evs.lost.fbase) {
+                int slot = (o - evs.lost.fbase) / evs.idp;
+                const int r = (o - evs.lost.fbase) % evs.idp;
+                for (int ls : evs.lost_slots) if (ls <= slot) ++slot;
+                o = evs.lost.fbase + evs.idp * slot + r;
+            }
+            map->push_back(o);
+        }
+        const bool fac = h->fac_valid && h->fac_n == nn;
+        const int ldo = round_up(m + 1, 16), fk = h->fac_k, fld = h->fac_ld;
+        double* fs = h->d_Sres; double* fd = h->d_Stmp;
+        head.push_back([=]() -> int {
+            const AuxCopy cp[] = {{h->d_covmap, map->data(), sizeof(int) * (size_t)m}};
+            const int rc = aux_copies(h, s, cp, 1);
+            if (rc != ORCVIO_OK) return rc;
+            hipLaunchKernelGGL(k_cov_remove, dim3((m * m + 255) / 256), dim3(256), 0, s, (const double*)src, nn, (const int*)h->d_covmap, m, dst);
+            if (fac) hipLaunchKernelGGL(k_fac_remove, dim3((fk * m + 255) / 256), dim3(256), 0, s, (const double*)fs, fld, fk, (const int*)h->d_covmap, m, fd, ldo);
+            HIPCHK(hipGetLastError());
+            return ORCVIO_OK;
+        });
+        if (fac) fac_adopt(h, m, fk, ldo, h->fac_tail);
+        else h->fac_valid = false;
+        std::swap(h->d_Pres, h->d_Ptmp);
+        h->res_n = m;
     }
     // ---- the first update's tracks: validated, the derived index arrays written (upload_finalize needs the prior's bookkeeping above)
     int rc = ORCVIO_OK;
@@ -323,8 +508,14 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
     FeatureView vB{};
     const char* soB = nullptr;
     unsigned long long pubB = 0;
-    StepSecond sb{st->prune_tracks, posesA, dxA, infoA, first ? st->prune_apply_dx : 0};
+    if (evs.k > 0) { evs.fs.slam = h->d_slam; evs.fs.cap = h->ekf_cap; }   // (the records' buffers stand: slam_prepare above)
+    StepSecond sb{st->prune_tracks, posesA, dxA, infoA, first ? st->prune_apply_dx : 0, evs.k > 0 ? &evs : nullptr};
     int rcB = ORCVIO_OK;
+    unsigned long long pubE = 0;
+    if (!second && evs.k > 0) {   // no update behind the changes: the anchor change is what the call waits for
+        rcB = step_events_alone(h, s, fl, N, sb, false, true);
+        if (rcB == ORCVIO_OK) pubE = ++h->pub_enqueued;
+    }
     if (second) {
         step_arena_swap(h);
         rcB = step_second_update(h, fl, N, sb, false, nullptr, who);
@@ -342,7 +533,7 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
     if (rcB == ORCVIO_OK && st->n_remove > 0) rcR = step_remove(h, leg, st->remove_clones, st->n_remove);
     tmark(3);
     // ---- ONE wait: the flag word behind the last update
-    rc = (pubB || pubA) ? io_wait(h, s, pubB ? pubB : pubA) : ORCVIO_OK;
+    rc = (pubB || pubE || pubA) ? io_wait(h, s, pubB ? pubB : (pubE ? pubE : pubA)) : ORCVIO_OK;
     tmark(4);
     if (timing && (++tcalls % 128) == 0) {
         fprintf(stderr, "io_step_frame (mean of 128, us after entry): checks + finalize %.1f | head launched %.1f | first update enqueued %.1f | second + removal enqueued %.1f | results %.1f\n",
@@ -356,6 +547,16 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
         return code;
     };
     if (rc != ORCVIO_OK) { h->ran = false; return leave(rc); }
+    if (rex && evs.k > 0) {
+        rex->new_param = reinterpret_cast<const double*>(h->h_evt + EVT_H_PAR);
+        rex->new_inv_depth = rex->new_param + 3 * ANCHOR_MAX_K;
+    }
+    auto changes_status = [&]() {   // the word the anchor change left: a changed feature's position was not finite
+        const int sc = evs.k > 0 && *evt_status_host(h) != 0 ? ORCVIO_ERR_NOT_SPD : ORCVIO_OK;
+        if (rex) rex->status_changes = sc;
+        if (sc != ORCVIO_OK) g_last_error = std::string(who) + ": a changed feature's position is not finite (an incremented inverse depth of zero): no anchor change, no prune update";
+        return sc;
+    };
     res->dx = reinterpret_cast<const double*>(soA + vA.oo_dx);
     res->gamma = reinterpret_cast<const double*>(soA + vA.oo_gamma);
     res->accept = reinterpret_cast<const int32_t*>(soA + vA.oo_accept);
@@ -394,6 +595,16 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
             if (second) step_arena_swap(h);
         } else {
             res->status_first = first ? feature_outcome_view(h, vA, soA, res->stats) : ORCVIO_OK;
+            // the anchor changes went through behind the first update's commit and stand: the repeat of the second update does not
+            // apply them again.  Its pose step reads the first update's dx, which the lost update has overwritten on the device: put back
+            sb.ev = nullptr;
+            if (first) HIPCHK(hipMemcpyAsync(const_cast<double*>(dxA), soA + vA.oo_dx, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        }
+        // (lostA: the anchor change refused itself on the first update's kept status word; it runs behind the repeat, once)
+        if (sb.ev && (!second || res->status_first != ORCVIO_OK)) {   // no second update to carry them: the changes are bookkeeping and stand
+            rc = step_events_alone(h, s, fl, N, sb, true, false);
+            if (rc != ORCVIO_OK) return leave(rc);
+            HIPCHK(hipStreamSynchronize(s));
         }
         if (second) {
             HIPCHK(hipStreamSynchronize(s));
@@ -412,14 +623,17 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
         }
         if (st->n_remove > 0) { rcR = step_remove(h, leg, st->remove_clones, st->n_remove); if (rcR != ORCVIO_OK) return leave(rcR); }
         h->cnt_step_frames++;
-        return leave(res->status_first != ORCVIO_OK ? res->status_first : res->status_prune);
+        const int sc = changes_status();
+        return leave(res->status_first != ORCVIO_OK ? res->status_first : (res->status_prune != ORCVIO_OK ? res->status_prune : sc));
     }
     // ---- outcomes (the refusals of the device: M not positive definite, a non-finite result)
     res->status_first = first ? feature_outcome_view(h, vA, soA, res->stats) : ORCVIO_OK;
     if (res->status_first != ORCVIO_OK) res->stats[3] = 0;
+    const int sc_changes = changes_status();
     if (second) {
         if (rcB != ORCVIO_OK) res->status_prune = rcB;
         else if (res->status_first != ORCVIO_OK) { res->status_prune = res->status_first; res->prune_stats[3] = 0; }   // (refused with the first: info_also)
+        else if (sc_changes != ORCVIO_OK) { res->status_prune = sc_changes; res->prune_stats[3] = 0; }   // (refused with the changes: the kept status word)
         else {
             res->status_prune = feature_outcome_view(h, vB, soB, res->prune_stats);
             if (res->status_prune != ORCVIO_OK) res->prune_stats[3] = 0;
@@ -428,5 +642,17 @@ int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_fr
     h->ran = false;   // (both commits are part of the call: nothing is left for orcvio_msckf_cov_commit)
     h->cnt_step_frames++;
     if (rcR != ORCVIO_OK) return leave(rcR);
-    return leave(res->status_first != ORCVIO_OK ? res->status_first : res->status_prune);
+    if (!second && rcB != ORCVIO_OK) return leave(rcB);
+    return leave(res->status_first != ORCVIO_OK ? res->status_first : (res->status_prune != ORCVIO_OK ? res->status_prune : sc_changes));
+}
+
+int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* st, orcvio_msckf_frame_result* res) {
+    return step_frame_impl(h, st, nullptr, res, nullptr, "orcvio_msckf_io_step_frame");
+}
+int32_t orcvio_msckf_io_step_frame_ex(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* st, const orcvio_msckf_frame_events* ev,
+                                      orcvio_msckf_frame_result_ex* res) {
+    const char* who = "orcvio_msckf_io_step_frame_ex";
+    if (!res) { g_last_error = std::string(who) + ": null argument"; return ORCVIO_ERR_INVALID; }
+    res->new_param = nullptr; res->new_inv_depth = nullptr; res->status_changes = ORCVIO_OK;
+    return step_frame_impl(h, st, ev, &res->frame, res, who);
 }

@@ -21,8 +21,9 @@ static int upload_begin(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags,
     const int n = flags->leg_dim + 6 * N + h->n_extra;   // (n_extra: states behind the clones that no row of this update touches)
     if (n > h->n_max) { g_last_error = "window + extra states exceed the handle's capacity"; return ORCVIO_ERR_CAPACITY; }
     if (6 * h->n_nui > h->n_extra || N + h->n_nui > h->maxN) { g_last_error = std::string(who) + ": nuisance states do not fit the extra states / the pose capacity"; return ORCVIO_ERR_CAPACITY; }
-    // (pending_aug: orcvio_msckf_io_begin with_P = 2 -- the window of a frame whose augmentation orcvio_msckf_io_step_frame is about to enqueue)
-    if (!with_P && h->res_n != n && !(pending_aug && h->res_n + 6 == n)) { g_last_error = std::string(who) + ": P == NULL but the resident covariance does not match the window"; return ORCVIO_ERR_INVALID; }
+    // (pending_aug: orcvio_msckf_io_begin with_P = 2 -- the window of a frame whose augmentation orcvio_msckf_io_step_frame is about to enqueue;
+    //  smaller than that by the in-state features orcvio_msckf_io_step_frame_ex removes first: the frame call checks the exact dimension)
+    if (!with_P && h->res_n != n && !(pending_aug && n <= h->res_n + 6)) { g_last_error = std::string(who) + ": P == NULL but the resident covariance does not match the window"; return ORCVIO_ERR_INVALID; }
     h->uploaded = false; h->ran = false; h->io_open = false;
     h->last_update_thin = false;   // (set again by the update itself if it takes the direct form of a thin stack)
     h->flags = *flags;

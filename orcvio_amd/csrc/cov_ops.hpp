@@ -194,11 +194,30 @@ __global__ __launch_bounds__(256) void k_aug_assemble(const double* __restrict__
 //   2. Y = J P (k d rows) -> scratch Y [k d][n] (HBM/L2: 3-d at k = 16, n = 406 would be 156 KB, beyond a workgroup's LDS);
 //      the factor, if given: S <- T S, row by row in place (a feature's new rows read only its own rows, clones and extrinsics)
 //   3. the feature rows and columns of P from Y, the (k d)^2 block from Y J^T, symmetrised (Pff of the 3-d form is, :3602)
-// P is changed in place: only the k d rows and columns are written.  chg_i [k][3] = slot, old, new anchor; chg_d [k][6] = p_w,
+// P is changed in place: only the k d rows and columns are written.  chg_i [k][4] = slot, old, new anchor, unused; chg_d [k][6] = p_w,
 // p_fej; ext = R_b2c 9 | t_c_b 3; params out [k][4] = param 3 | rho.
 // (512 lanes for 1-d; the 3-d form's per-feature math needs ~300 VGPRs in lane q: 256 lanes, one wave per SIMD, no spill)
 enum { ANCHOR_MAX_K = 16 };
+// The launch inside the frame call (orcvio_msckf_io_step_frame_ex), enqueued between the frame's two updates; all null: the separate call.
+//   refuse       device word of the feature step: a changed feature's position is not finite -> P and S stay as they are,
+//                *refuse_also (the kept status word the prune update's commit reads) and *status_host are raised
+//   first_info   kept status words of the frame's first update: [8] != 0 = it lost an in-launch hand-off and committed nothing -- this
+//                launch does nothing either (P would be changed in place under the repeat): the call runs it again behind the repeat
+//   par_host     [ANCHOR_MAX_K][3] param | [ANCHOR_MAX_K] rho in the pinned output block, stored ahead of the flag the call waits on
+//                (system-scope fence by the storing lanes, as k_finish_pub's)
+//   seq, flag    not null: no update follows in the frame -- this launch raises the flag itself
+struct AnchorFrameArgs {
+    const int* refuse; const int* first_info; int* refuse_also;
+    double* par_host; int* status_host;
+    unsigned long long* seq; unsigned long long* flag;
+};
 template <int d> struct AnchorThreads { enum { value = d == 3 ? 256 : 512 }; };
+enum { ANCHOR_CHG_STRIDE = 4 };   // chg_i [k][4]: slot, old anchor, new anchor, (frame call: the feature's slam_features record)
+__device__ __forceinline__ void anchor_publish(unsigned long long* seq, unsigned long long* flag) {
+    __threadfence_system();
+    const unsigned long long v = atomicAdd(seq, 1ull) + 1ull;
+    __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 __device__ __forceinline__ int anchor_col(int t, int fcol, int oc, int nc) {
     return t < ANCHOR_J_OLD ? fcol + t : (t < ANCHOR_J_NEW ? oc + t - ANCHOR_J_OLD : (t < ANCHOR_J_EXT ? nc + t - ANCHOR_J_NEW : 15 + t - ANCHOR_J_EXT));
 }
@@ -207,15 +226,27 @@ __global__ __launch_bounds__(AnchorThreads<d>::value) void k_cov_change_anchors(
                                                                    const double* __restrict__ poses, const double* __restrict__ ext,
                                                                    const int* __restrict__ chg_i, const double* __restrict__ chg_d, int k,
                                                                    int base, int leg, int if_fej, int literal_3d,
-                                                                   double* __restrict__ params, double* __restrict__ Y) {
+                                                                   double* __restrict__ params, double* __restrict__ Y, AnchorFrameArgs fr) {
     __shared__ double sJ[ANCHOR_MAX_K * 3 * ANCHOR_J_STRIDE];
     __shared__ int sC[ANCHOR_MAX_K * ANCHOR_J_STRIDE];   // state column of entry t of feature q's J rows
     __shared__ int sF[ANCHOR_MAX_K];                     // first column of feature q
     constexpr int ANCHOR_THREADS = AnchorThreads<d>::value;
     const int tid = threadIdx.x;
+    {   // (the same words for every lane: a uniform branch)
+        const bool lost = fr.first_info && fr.first_info[8] != 0;
+        const bool bad = fr.refuse && *fr.refuse != 0;
+        if (lost || bad) {
+            if (tid == 0) {
+                if (bad && !lost && fr.refuse_also) *fr.refuse_also = 1;
+                if (fr.status_host) *fr.status_host = bad && !lost ? 1 : 0;
+                if (fr.flag) anchor_publish(fr.seq, fr.flag);
+            }
+            return;
+        }
+    }
     if (tid < k) {
         const int q = tid;
-        const int slot = chg_i[3 * q], o = chg_i[3 * q + 1], nw = chg_i[3 * q + 2];
+        const int slot = chg_i[ANCHOR_CHG_STRIDE * q], o = chg_i[ANCHOR_CHG_STRIDE * q + 1], nw = chg_i[ANCHOR_CHG_STRIDE * q + 2];
         double par[3], rho;   // (J straight into LDS: 63 doubles fewer in registers)
         anchor_change(poses + (size_t)o * POSE_STRIDE, poses + (size_t)nw * POSE_STRIDE, ext, ext + 9, chg_d + 6 * q, chg_d + 6 * q + 3,
                       d, if_fej, literal_3d, par, &rho, sJ + q * 3 * ANCHOR_J_STRIDE);
@@ -224,6 +255,12 @@ __global__ __launch_bounds__(AnchorThreads<d>::value) void k_cov_change_anchors(
         for (int t = 0; t < ANCHOR_J_STRIDE; ++t) sC[q * ANCHOR_J_STRIDE + t] = anchor_col(t, fcol, oc, nc);
         sF[q] = fcol;
         params[4 * q + 0] = par[0]; params[4 * q + 1] = par[1]; params[4 * q + 2] = par[2]; params[4 * q + 3] = rho;
+        if (fr.par_host) {
+            fr.par_host[3 * q + 0] = par[0]; fr.par_host[3 * q + 1] = par[1]; fr.par_host[3 * q + 2] = par[2];
+            fr.par_host[3 * ANCHOR_MAX_K + q] = rho;
+            if (q == 0) *fr.status_host = 0;
+            __threadfence_system();
+        }
     }
     __syncthreads();
     // (entries 0 .. d-1 of the feature block, then the 18 pose / extrinsic entries)
@@ -261,24 +298,29 @@ __global__ __launch_bounds__(AnchorThreads<d>::value) void k_cov_change_anchors(
         const int m = k * d;
         for (int idx = tid; idx < m * n; idx += ANCHOR_THREADS) {
             const int rr = idx / n, j = idx - rr * n;
-            const int fr = sF[rr / d] + rr % d;
+            const int frow = sF[rr / d] + rr % d;
             int s = -1;
             for (int q = 0; q < k; ++q)
                 if (j >= sF[q] && j < sF[q] + d) s = q * d + (j - sF[q]);
             double v;
             if (s < 0) {
                 v = Y[(size_t)rr * n + j];
-                P[(size_t)j * n + fr] = v;
+                P[(size_t)j * n + frow] = v;
             } else {
                 double z1, z2;
                 { const double* src = Y + (size_t)rr * n; ANCHOR_DOT(z1, s % d, s / d, 1, 0) }
                 { const double* src = Y + (size_t)s * n; ANCHOR_DOT(z2, rr % d, rr / d, 1, 0) }
                 v = 0.5 * (z1 + z2);
             }
-            P[(size_t)fr * n + j] = v;
+            P[(size_t)frow * n + j] = v;
         }
     }
 #undef ANCHOR_DOT
+    if (fr.flag) {   // (the frame's last launch the call waits for: every lane's stores are out before the flag rises)
+        __threadfence();
+        __syncthreads();
+        if (tid == 0) anchor_publish(fr.seq, fr.flag);
+    }
 }
 
 }  // namespace orcvio_amd

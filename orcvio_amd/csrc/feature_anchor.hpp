@@ -15,6 +15,8 @@
 // so the Jacobian is evaluated with the old pose in place of the new one and H_x_new lands in the old clone's block, over
 // H_x_old; the new clone's block stays zero.  literal_3d = 0: the consistent Jacobian with the new anchor's pose and columns.
 #pragma once
+#include <cmath>
+
 #include "msckf_math.hpp"
 
 namespace orcvio_amd {
@@ -71,6 +73,41 @@ ORC_HD void am_cam_pose(const double* pose, double* Rwc, double* tcw) {
     double r[3];
     am_mv(pose + POSE_R_B2W, pose + POSE_T_C_B, r);
     for (int a = 0; a < 3; ++a) tcw[a] = pose[POSE_T_B_W + a] + r[a];
+}
+
+// measurementUpdate_hybrid's increment of ONE in-state feature (:1842-1889): the parameters take their own entries of dx (3-d:
+// invParam += dxf[0..2]; 1-d: invDepth += dxf[0], obs_anchor stays), the world position follows from the anchor's camera pose as
+// the clones' increment has left it: p_w = R_c2w p_c + t_c_w, p_c = (a, b, 1) / rho.  pose_anchor: the anchor clone's record (its
+// own frozen extrinsic).  A rho of zero gives a non-finite p_w: the caller checks it.
+ORC_HD void feature_increment(const double* pose_anchor, const double* param, double rho, const double* dxf, int idp_dim, double p_w[3]) {
+    double a = param[0], b = param[1], r = rho;
+    if (idp_dim == 3) { a += dxf[0]; b += dxf[1]; r = param[2] + dxf[2]; }
+    else r += dxf[0];
+    const double pc[3] = {a / r, b / r, 1.0 / r};
+    double Rwc[9], tcw[3], q[3];
+    am_cam_pose(pose_anchor, Rwc, tcw);
+    am_tmv(Rwc, pc, q);
+    for (int c = 0; c < 3; ++c) p_w[c] = q[c] + tcw[c];
+}
+// incrementState_IMUCam's extrinsic part (:4512-4517, smallAngleQuaternion math_utils.hpp:104-121, Eigen's toRotationMatrix without
+// normalisation): ext = R_b2c 9 | t_c_b 3 of the IMU, de = dx[15:21].  The arithmetic of orcvio_msckf_increment_state (capi_state.inc).
+ORC_HD void extrinsic_increment(const double* de, double ext[12]) {
+    double q[4] = {0.5 * de[0], 0.5 * de[1], 0.5 * de[2], 0.0};
+    const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
+    if (n2 <= 1.0) q[3] = sqrt(1.0 - n2);
+    else {
+        q[3] = 1.0;
+        const double s = 1.0 / sqrt(1.0 + n2);
+        for (int c = 0; c < 4; ++c) q[c] *= s;
+    }
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double RqT[9] = {1 - 2 * (y * y + z * z), 2 * (x * y + z * w), 2 * (x * z - y * w),
+                           2 * (x * y - z * w), 1 - 2 * (x * x + z * z), 2 * (y * z + x * w),
+                           2 * (x * z + y * w), 2 * (y * z - x * w), 1 - 2 * (x * x + y * y)};
+    double R[9];
+    am_mul(ext, RqT, R);
+    for (int c = 0; c < 9; ++c) ext[c] = R[c];
+    for (int c = 0; c < 3; ++c) ext[9 + c] += de[3 + c];
 }
 
 // The new parameters (1-d: param = obs_anchor (u, v, 1), rho = invDepth; 3-d: param = invParam (alpha, beta, rho), rho = param[2])

@@ -9,9 +9,14 @@
 //   k_frame_head    processModel's covariance propagation (:800-816) + stateAugmentation (:962-1010) in one pass, and the pull of
 //                   the frame's inputs out of the pinned arena (tracks, derived index arrays, in-state feature records)
 //   k_cov_remove_fac  marginalisation (:2935-2951) of the covariance AND of its resident square-root factor in one launch
+// With the life cycle of the in-state features (orcvio_msckf_io_step_frame_ex): the lost features' removal (rmLostFeaturesCov,
+// :3776-3828) is an index map on k_frame_head's enumeration of its output (LostMap; k_fac_head for the factor of a frame without
+// propagation), and the changed features' step (measurementUpdate_hybrid's feature loop :1842-1889, the IMU extrinsics' increment
+// :4512-4517) rides in the launch that carries k_pose_step (feature_step_body; k_event_step as a launch of its own).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "feature_anchor.hpp"
 #include "io_ops.hpp"
 
 namespace orcvio_amd {
@@ -53,18 +58,20 @@ __device__ __forceinline__ void dev_mat3_mul(const double* A, const double* B, d
 // Thread 0 also copies the status words info[0..15] of the update that has just run into `keep` (the second update's commit
 // refuses itself when the first was refused: EpilogueArgs.info_also).
 struct PoseStepArgs { const double* src; double* dst; int N, stride; const double* dx; int leg, apply, left, discard_large; const int* info; int* keep; };
-__device__ __forceinline__ void pose_step_body(const double* __restrict__ src, double* __restrict__ dst, int N, int stride, const double* __restrict__ dx,
-                                               int leg, int apply, int left, int discard_large, const int* __restrict__ info, int* __restrict__ keep, const int c) {
-    if (c < 16 && keep) keep[c] = info ? info[c] : 0;   // (info == nullptr: the frame had no first update)
-    if (c >= N) return;
-    double r[28];
-    for (int i = 0; i < 28; ++i) r[i] = src[(size_t)c * stride + i];
+// does the increment take place: apply, unless discard_large_update discards dx (:4479-4494)
+__device__ __forceinline__ bool pose_step_applies(const double* __restrict__ dx, int apply, int discard_large) {
     bool app = apply != 0;
     if (app && discard_large) {
         const double nv = sqrt(dx[3] * dx[3] + dx[4] * dx[4] + dx[5] * dx[5]);
         const double np = sqrt(dx[6] * dx[6] + dx[7] * dx[7] + dx[8] * dx[8]);
         if (nv > 1.0 || np > 1.5) app = false;
     }
+    return app;
+}
+// record c of the second update's window into r[28]
+__device__ __forceinline__ void pose_step_record(const double* __restrict__ src, int stride, const double* __restrict__ dx, int leg, bool app, int left,
+                                                 const int c, double* r) {
+    for (int i = 0; i < 28; ++i) r[i] = src[(size_t)c * stride + i];
     if (app) {
         double Rt[9];
         const double* da = dx + leg + 6 * c;
@@ -73,10 +80,101 @@ __device__ __forceinline__ void pose_step_body(const double* __restrict__ src, d
         if (left) dev_mat3_mul(Rt, r, r); else dev_mat3_mul(r, Rt, r);
         r[9] += da[3]; r[10] += da[4]; r[11] += da[5];
     }
+}
+__device__ __forceinline__ void pose_step_body(const double* __restrict__ src, double* __restrict__ dst, int N, int stride, const double* __restrict__ dx,
+                                               int leg, int apply, int left, int discard_large, const int* __restrict__ info, int* __restrict__ keep, const int c) {
+    if (c < 16 && keep) keep[c] = info ? info[c] : 0;   // (info == nullptr: the frame had no first update)
+    if (c >= N) return;
+    double r[28];
+    pose_step_record(src, stride, dx, leg, pose_step_applies(dx, apply, discard_large), left, c, r);
     for (int i = 0; i < 28; ++i) dst[(size_t)c * stride + i] = r[i];
+}
+
+// ---- the feature step of a frame whose in-state features change anchor (orcvio_msckf_io_step_frame_ex) ---------------------------------
+// One wavefront, lane q = change q (k <= 16): what k_cov_change_anchors reads -- the changed features' p_w | p_fej and the IMU's
+// extrinsics -- into device memory, as the reference's state holds them when pruneImuStateBuffer runs (measurementUpdate_hybrid
+// :1842-1889, incrementState_IMUCam :4512-4517).
+//   ps.apply == 0              the caller's p_w and extrinsics as they are (the separate calls with no host increment in between)
+//   ps.apply != 0              the feature's parameters from its slam_features record (rec) take their entries of dx, p_w follows from the
+//                              OLD anchor's pose as the pose step leaves it (the same arithmetic: pose_step_record); the extrinsics
+//                              take dx[15:21].  A discarded dx (discard_large_update) leaves poses and extrinsics alone but the
+//                              parameters are STILL incremented (the feature loop runs after incrementState_IMUCam's early return).
+//   a refused first update     (status words [2] / [3]) increments nothing: the record's p_w, the given extrinsics
+//   a lost hand-off            (word [8]) nothing is written: the call runs the frame's updates and this step again
+// A non-finite p_w (an incremented inverse depth of zero) raises *status: k_cov_change_anchors then leaves P and S alone.
+#define FS_MAX_K 16
+enum { FS_EXT = 6 * FS_MAX_K, FS_DOUBLES = 6 * FS_MAX_K + 12 };   // [k][6] p_w | p_fej, then R_b2c 9 | t_c_b 3
+struct FeatureStepArgs {
+    int k, idp, base;         // changes (0: no step), parameter width, first feature column leg + 6 N (AFTER the frame's removals)
+    const int* chg_i;         // [k][4] slot, old anchor, new anchor, record in slam_features (host-coherent)
+    const double* chg_d;      // [FS_DOUBLES] as the caller gave them (host-coherent)
+    const double* slam;       // the records: param 3 | inv_depth 1 | p_w 3 | .. [cap]
+    int cap;
+    double* out;              // [FS_DOUBLES] device
+    int* status;              // device word
+};
+__device__ __forceinline__ void feature_step_body(const FeatureStepArgs& f, const PoseStepArgs& ps, const int q) {
+    const bool lost = ps.info && ps.info[8] != 0;
+    const bool refused = ps.info && (ps.info[2] != 0 || ps.info[3] != 0);
+    bool bad = false;
+    if (q < f.k && !lost) {
+        const int slot = f.chg_i[4 * q], old = f.chg_i[4 * q + 1], rec = f.chg_i[4 * q + 3];
+        double pw[3];
+        if (!ps.apply) { pw[0] = f.chg_d[6 * q]; pw[1] = f.chg_d[6 * q + 1]; pw[2] = f.chg_d[6 * q + 2]; }
+        else if (refused) { pw[0] = f.slam[(size_t)4 * f.cap + 3 * rec]; pw[1] = f.slam[(size_t)4 * f.cap + 3 * rec + 1]; pw[2] = f.slam[(size_t)4 * f.cap + 3 * rec + 2]; }
+        else {
+            double r[28];
+            pose_step_record(ps.src, ps.stride, ps.dx, ps.leg, pose_step_applies(ps.dx, ps.apply, ps.discard_large), ps.left, old, r);
+            const double par[3] = {f.slam[3 * rec], f.slam[3 * rec + 1], f.slam[3 * rec + 2]};
+            feature_increment(r, par, f.idp == 1 ? f.slam[(size_t)3 * f.cap + rec] : par[2], ps.dx + f.base + f.idp * slot, f.idp, pw);
+            bad = !(pw[0] - pw[0] == 0.0) || !(pw[1] - pw[1] == 0.0) || !(pw[2] - pw[2] == 0.0);
+        }
+        for (int c = 0; c < 3; ++c) { f.out[6 * q + c] = pw[c]; f.out[6 * q + 3 + c] = f.chg_d[6 * q + 3 + c]; }
+    }
+    if (q == FS_MAX_K && !lost) {   // (a lane of its own for the extrinsics)
+        double ext[12];
+        for (int c = 0; c < 12; ++c) ext[c] = f.chg_d[FS_EXT + c];
+        if (!refused && pose_step_applies(ps.dx, ps.apply, ps.discard_large)) extrinsic_increment(ps.dx + 15, ext);
+        for (int c = 0; c < 12; ++c) f.out[FS_EXT + c] = ext[c];
+    }
+    const bool any = __ballot(bad) != 0ull;
+    if (q == 0) *f.status = any ? 1 : 0;
 }
 __global__ __launch_bounds__(64) void k_pose_step(PoseStepArgs p) {
     pose_step_body(p.src, p.dst, p.N, p.stride, p.dx, p.leg, p.apply, p.left, p.discard_large, p.info, p.keep, threadIdx.x);
+}
+// the two steps as a launch of their own (the unfused and the repair path, a frame without a second update): wavefront 0 the poses,
+// wavefront 1 the changed features
+__global__ __launch_bounds__(128) void k_event_step(PoseStepArgs p, FeatureStepArgs f) {
+    const int t = threadIdx.x;
+    if (t < 64) pose_step_body(p.src, p.dst, p.N, p.stride, p.dx, p.leg, p.apply, p.left, p.discard_large, p.info, p.keep, t);
+    else feature_step_body(f, p, t - 64);
+}
+
+// ---- in-state features that leave the state in front of the frame's first update (rmLostFeaturesCov, :3776-3828) as an index map ----
+// The lost slots as a bit set by value: output index o (the state AFTER the removal) -> its index BEFORE it.  Everything behind a
+// removed feature, later features included, moves up; what stands behind the features moves up by all of them.
+#define FH_LOST_WORDS 8
+struct LostMap {
+    int count;    // removed features (0: no map)
+    int fbase;    // first feature state
+    int idp;      // states per feature
+    int nkeep;    // features that stay
+    unsigned long long bits[FH_LOST_WORDS];   // bit s: slot s (numbered before the removal) leaves
+};
+__device__ __forceinline__ int lost_unmap(const LostMap& L, int o) {
+    if (L.count == 0 || o < L.fbase) return o;
+    const int k = o - L.fbase, slot = k / L.idp, r = k - slot * L.idp;
+    if (slot >= L.nkeep) return o + L.idp * L.count;
+    int s = slot, w = 0;   // the (s + 1)-th slot that stays
+    for (; w < FH_LOST_WORDS - 1; ++w) {
+        const int z = 64 - __popcll(L.bits[w]);
+        if (s < z) break;
+        s -= z;
+    }
+    unsigned long long fr = ~L.bits[w];
+    for (int i = 0; i < s; ++i) fr &= fr - 1ull;
+    return L.fbase + L.idp * (64 * w + __ffsll(fr) - 1) + r;
 }
 
 
@@ -96,6 +194,8 @@ struct FrameHeadArgs {
     const char* src[FH_SEGS]; char* dst[FH_SEGS]; unsigned bytes[FH_SEGS];
     int pose_block;             // ingest workgroup that also runs the pose step of the frame's second update (-1: none)
     PoseStepArgs ps;
+    FeatureStepArgs fs;         // ... and, in its second wavefront, the step of the features that change anchor (fs.k == 0: none)
+    LostMap lost;               // covariance part: out (m x m) is what propagation + augmentation give WITHOUT the lost features' rows / columns
 };
 
 // The arithmetic of k_cov_propagate_rows / k_cov_propagate_finish / k_cov_augment (cov_ops.hpp), element by element in the same order --
@@ -108,12 +208,16 @@ struct FrameHeadArgs {
 //   region 2  (a, b) in L_out x C_out   T(sa, sb) = sum_l Phi(sa, l) P(l, sb), written to (a, b) and (b, a)
 //   region 3  (a, b) in C_out x C_out   P(sa, sb), symmetrised as the augmentation does
 // Only regions 1 and 2 (a fifth of the matrix) read Phi from the pinned arena.
+// a.lost (LostMap): the enumeration runs over the state AFTER the removal of the lost in-state features (m counts it); every output
+// index goes through lost_unmap before its source is looked up -- the removed rows and columns are never formed, what stands behind
+// them moves up: the bits of cov_propagate -> cov_augment -> cov_remove_features.
 template <int LEG>   // 22 or 46 (leg_dim): the products over the IMU block unroll completely -- their loads in flight together, the sums in the same order
 __global__ __launch_bounds__(256) void k_frame_head(FrameHeadArgs a) {
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= a.nb_cov) {
         const int w = b - a.nb_cov;
         if (w == a.pose_block && t < 64) pose_step_body(a.ps.src, a.ps.dst, a.ps.N, a.ps.stride, a.ps.dx, a.ps.leg, a.ps.apply, a.ps.left, a.ps.discard_large, a.ps.info, a.ps.keep, t);
+        if (w == a.pose_block && a.fs.k > 0 && t >= 64 && t < 128) feature_step_body(a.fs, a.ps, t - 64);
         int p0 = 0;   // pieces of the segments before this one
         for (int sgi = 0; sgi < a.nseg; ++sgi) {
             const unsigned bytes = a.bytes[sgi];
@@ -175,7 +279,9 @@ __global__ __launch_bounds__(256) void k_frame_head(FrameHeadArgs a) {
     else if (e < E1 + E2) { region = 2; const int q = e - E1; oa = Lout(q / nC); ob = Cout(q % nC); }
     else { region = 3; const int q = e - E1 - E2; if (nL == 0) { oa = q / m; ob = q - oa * m; } else { oa = Cout(q / nC); ob = Cout(q % nC); } }
     bool na, nb;
-    const int sa = src(oa, na), sb = src(ob, nb);
+    // (oa, ob) number the output; with lost features the propagated + augmented element behind it is (lost_unmap(oa), lost_unmap(ob)):
+    // a gather, the removed rows and columns are never formed
+    const int sa = src(lost_unmap(a.lost, oa), na), sb = src(lost_unmap(a.lost, ob), nb);
     if (region == 1) {
         double x = a.Q[sa * leg + sb], y = a.Q[sb * leg + sa];
 #pragma unroll
@@ -196,6 +302,19 @@ __global__ __launch_bounds__(256) void k_frame_head(FrameHeadArgs a) {
         else v = p2;
         a.out[(size_t)oa * m + ob] = v;
     }
+}
+
+// the factor's rows of a frame WITHOUT propagation whose in-state features leave: k_fac_augment's copy (pose < 0: no augmentation) with
+// the lost features' rows left out -- k_fac_augment -> k_fac_remove as one gather (m: states after the removal)
+__global__ __launch_bounds__(256) void k_fac_head(const double* __restrict__ F, int ld, int k, int pose, LostMap lost, int m,
+                                                  double* __restrict__ out, int ldo) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= k * m) return;
+    const int i = idx / m, j = idx - i * m;
+    const int p = lost_unmap(lost, j);
+    const bool nj = pose >= 0 && p >= pose && p < pose + 6;
+    const int sj = pose < 0 ? p : (nj ? (p - pose < 3 ? p - pose : p - pose + 3) : (p < pose ? p : p - 6));
+    out[(size_t)i * ldo + j] = F[(size_t)i * ld + sj];
 }
 
 // ---- marginalisation of the covariance and of its resident factor in one launch (k_cov_remove + k_fac_remove, cov_ops.hpp) ----------

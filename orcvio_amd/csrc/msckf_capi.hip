@@ -301,6 +301,9 @@ struct orcvio_msckf_handle {
     // orcvio_msckf_io_step_frame (capi_step.inc): the second update of a frame goes through an arena pair of its own, swapped in and out
     char *d_in2 = nullptr, *h_stage2 = nullptr, *h_stage2_dev = nullptr;
     bool arena_swapped = false;
+    // orcvio_msckf_io_step_frame_ex: staging of the frame's feature events, of their own (step_events, capi_step.inc) -- the propagation
+    // scratch and the index map the separate cov_* calls stage in are in use inside a frame
+    char *h_evt = nullptr, *h_evt_dev = nullptr, *d_evt = nullptr;
     int* d_step_words = nullptr;        // [0..15] status words of the frame's first update, kept for the second update's commit (info_also)
     std::vector<int> step_row_ptr;      // the second update's row offsets
     long long cnt_step_frames = 0, cnt_step_repairs = 0;   // frames through orcvio_msckf_io_step_frame; updates of such frames run again after a lost hand-off

@@ -462,6 +462,72 @@ def make_stream(flags: "Flags", sigma_px=None, cycle: int = 8, seed: int = 0, n_
     return frames, np.ascontiguousarray(P0)
 
 
+@dataclasses.dataclass
+class LifecycleChange:
+    """One in-state feature of a lifecycle frame whose anchor clone leaves: its slot in feature_states AFTER the frame's removals,
+    old and new anchor (window ranks), Feature::position and Feature::position_FEJ as the state holds them in front of the frame."""
+    slot: int
+    old: int
+    new: int
+    p_w: np.ndarray
+    p_fej: np.ndarray = None
+
+
+def _reanchor(win: "Window", f: SlamFeature, a: int) -> SlamFeature:
+    """The same feature anchored at clone a: its parameters are those of its position p_w in that clone's camera frame."""
+    R_c2w = win.R_b2w[a] @ win.R_b2c[a].T
+    t_c_w = win.t_b_w[a] + win.R_b2w[a] @ win.t_c_b[a]
+    pc = R_c2w.T @ (f.p_w - t_c_w)
+    inv = np.array([pc[0] / pc[2], pc[1] / pc[2], 1.0 / pc[2]])
+    return dataclasses.replace(f, anchor=int(a), inv_param=inv, obs_anchor=np.array([inv[0], inv[1], 1.0]), inv_depth=float(inv[2]))
+
+
+def make_lifecycle_stream(flags: "Flags", sigma_px=None, cycle: int = 8, seed: int = 0, n_slam: int = 16, idp: int = 1, leg: int = LEG_DIM,
+                          min_slam: int = 8):
+    """make_stream-shaped frames whose in-state features have the hybrid filter's life cycle (reference removeLostFeatures ->
+    rmLostFeaturesCov, src/orcvio.cpp:2233, :3776-3828; pruneImuStateBuffer's re-anchoring, :2664-2720).  The stream starts with
+    n_slam in-state features; from the second frame on 0-2 of them are lost per frame (one or two in the second, so that every
+    stream has a removal; never below min_slam), slots and n_extra follow; no feature enters.  On every 20-clone frame the features
+    anchored in the leaving clones [0, 1] change anchor -- if the drawn anchors leave none there, one feature is re-anchored into a
+    leaving clone -- to the newest clone (idp 3) or to a surviving clone that is not the newest (idp 1).  Each frame dict is
+    make_stream's (w, slam, prune, Phi, Q, remove; w and slam are those AFTER the frame's removals) plus n_feature_states (before
+    the removals), lost (slots before the removals, ascending), changes (LifecycleChange), R_b2c / t_c_b (the IMU's extrinsics in
+    front of the frame: the newest clone's).  Returns (frames, P0); deterministic per seed."""
+    rng = np.random.default_rng(seed)
+    lrng = np.random.default_rng(60_000 + seed)   # (the life cycle's own draws)
+    frames = []
+    nf = n_slam
+    for k in range(cycle):
+        N = 20 if k % 2 else 19
+        F = int(rng.integers(20, 201))
+        w0 = make_window(N=N, F=F, seed=1000 + k, track_len=(3, 6), flags=flags, outlier_frac=0.05, sigma_px=sigma_px)
+        n_lost = 0 if k == 0 else int(lrng.integers(1 if k == 1 else 0, 3))
+        n_lost = max(0, min(n_lost, nf - min_slam))
+        lost = sorted(int(x) for x in lrng.choice(nf, n_lost, replace=False))
+        nf_before, nf = nf, nf - n_lost
+        w = with_extra_states(w0, idp * nf, seed=k)
+        slam = make_slam_features(w, nf, seed=k, outlier_frac=0.1, sigma_px=sigma_px)
+        prune, changes = None, []
+        if N == 20:
+            sub = subset_tracks(w, [0, 1], min_obs=2)
+            if int(sub.obs_ptr[-1]) > 0:
+                prune = sub
+            if not any(f.anchor in (0, 1) for f in slam):
+                j = int(lrng.integers(0, nf))
+                slam[j] = _reanchor(w, slam[j], int(lrng.integers(0, 2)))
+            for j, f in enumerate(slam):
+                if f.anchor in (0, 1):
+                    new = N - 1 if idp == 3 else int(lrng.integers(2, N - 1))
+                    changes.append(LifecycleChange(slot=j, old=int(f.anchor), new=new, p_w=f.p_w.copy(), p_fej=f.p_fej.copy()))
+        Phi = np.eye(leg) + 0.002 * rng.standard_normal((leg, leg))
+        G = rng.standard_normal((leg, 12))
+        frames.append(dict(w=w, slam=slam, prune=prune, Phi=np.ascontiguousarray(Phi), Q=np.ascontiguousarray(1e-7 * G @ G.T),
+                           remove=[0, 1] if N == 20 else [], n_feature_states=nf_before, lost=lost, changes=changes,
+                           R_b2c=w.R_b2c[N - 1].copy(), t_c_b=w.t_c_b[N - 1].copy()))
+    P0 = with_extra_states(make_window(N=18, F=1, seed=5, flags=flags), idp * n_slam, seed=1).P
+    return frames, np.ascontiguousarray(P0)
+
+
 def pack_poses(win: "Window") -> np.ndarray:
     """[N][28] pose records of the input arena (include/orcvio_msckf.h ORCVIO_POSE_STRIDE)."""
     p = np.zeros((win.N, 28))
