@@ -1354,6 +1354,17 @@ def debug_read(upd: MsckfUpdater, which: str):
     ldz = int(dims[6])
     if which == 'dims':
         return dict(n=n, NA=NA, NAP=NAP, NP=NP, m_tot=m_tot, Mmax=int(dims[5]), ldz=ldz, reg_path=int(dims[7]))
+    if which == 'dense':   # [dense_rows][NAP]: H(:, 15 : 15 + NA) | r | 0 -- the rows handed over, then those of the entering features
+        dd = np.zeros(2, dtype=np.int32)
+        rc = lib.orcvio_msckf_debug_read(upd.h, 14, dd.ctypes.data_as(C.c_void_p), dd.nbytes)
+        if rc != 0:
+            raise MsckfError(rc, 'debug_read dense dims')
+        out = np.zeros((int(dd[0]), int(dd[1])))
+        if out.size:
+            rc = lib.orcvio_msckf_debug_read(upd.h, 13, out.ctypes.data_as(C.c_void_p), out.nbytes)
+            if rc != 0:
+                raise MsckfError(rc, 'debug_read dense')
+        return out
     shapes = {'Hs': (0, (m_tot, NAP)), 'Ab': (1, (NAP, NAP)), 'A': (2, (NAP, NAP)), 'RP': (3, (NP, NP)),
               'M': (4, (NP, NP)), 'RM': (5, (NP, NP)), 'Z': (6, (n, ldz)), 'U': (8, (NP, NP))}
     code, shape = shapes[which]

@@ -6,7 +6,9 @@
 #ifdef ORCVIO_DEBUG_HOOKS
 // ---- debug access to intermediate device buffers (tests only; not part of the public header) ---
 // which: 0 Hs [m_tot x NAP], 1 Ab, 2 A (summed block), 3 RP, 4 M, 5 RM, 6 Z, 8 U, 7 dims -> int32[8],
-//        11 {fac_valid, fac_n, fac_k, res_n} -> int32[4], 12 the resident factor [fac_k][fac_n]
+//        11 {fac_valid, fac_n, fac_k, res_n} -> int32[4], 12 the resident factor [fac_k][fac_n],
+//        13 the dense rows [dense_rows][NAP] (caller-projected rows, then the rows of the entering features: zero U part, V part),
+//        14 {dense_rows, NAP} -> int32[2]
 int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst, int64_t max_bytes) {
     if (!h || !dst) return ORCVIO_ERR_INVALID;
     HIPCHK(hipSetDevice(h->device));
@@ -48,6 +50,13 @@ int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst
             if ((size_t)max_bytes < (size_t)h->fac_k * h->fac_n * sizeof(double)) { g_last_error = "debug_read: buffer too small"; return ORCVIO_ERR_INVALID; }
             HIPCHK(hipMemcpy2D(dst, sizeof(double) * h->fac_n, h->d_Sres, sizeof(double) * h->fac_ld, sizeof(double) * h->fac_n, h->fac_k,
                                hipMemcpyDeviceToHost));
+            return ORCVIO_OK;
+        }
+        case 13: src = h->d_dense; bytes = (size_t)h->dense_rows * h->NAP * sizeof(double); break;
+        case 14: {
+            int32_t dd[2] = {h->dense_rows, h->NAP};
+            if ((size_t)max_bytes < sizeof(dd)) return ORCVIO_ERR_INVALID;
+            std::memcpy(dst, dd, sizeof(dd));
             return ORCVIO_OK;
         }
         case 7: {

@@ -231,10 +231,10 @@ def test_entering_features_rows_on_the_device(upd, idp, fej):
     assert rel(got['P_new'], ref['P_new']) < 1e-10
     if not fej:   # ... and against the restatement of the reference's whole hybrid update
         full = mh.hybrid_update_full(w, slam, new, idp)
-        if full['new_accept'] == list(range(len(new))):
-            dx_new, P = capi.augment_state(idp, g1, g2, gr, w.flags.noise_feature ** 2, got['dx'], got['P_new'])
-            assert rel(np.concatenate([got['dx'], dx_new]), full['dx']) < TOL
-            assert rel(P, full['P_new']) < TOL
+        assert full['new_accept'] == list(range(len(new)))   # (every entering feature passes its gate: the comparison below always runs)
+        dx_new, P = capi.augment_state(idp, g1, g2, gr, w.flags.noise_feature ** 2, got['dx'], got['P_new'])
+        assert rel(np.concatenate([got['dx'], dx_new]), full['dx']) < TOL
+        assert rel(P, full['P_new']) < TOL
 
 
 def test_dense_rows_alone(upd):
