@@ -895,6 +895,20 @@ class MsckfUpdater:
         out['accept'] = int(out['accept'][0])
         return out
 
+    def objects_local_tracks(self, flags, n_clones, objs, P, R_b2c, t_c_b, obj_left, new_bbox, vio_left, fix_D=False):
+        """The first half of update_object_tracks alone: the rows of the tracks evaluated on the device and compressed into the handle's
+        own block (debug_read 'Ab' of the diagnostics build: sum over the objects of X^T (I - Q_f Q_f^T) X); returns the local dof."""
+        fl = make_flags(flags)
+        ef, arr, keep = self._object_tracks(objs, R_b2c, t_c_b, obj_left, new_bbox, vio_left, fix_D)
+        Pc = None if P is None else np.ascontiguousarray(P, dtype=np.float64)
+        dof = C.c_int32(0)
+        rc = self.lib.orcvio_msckf_objects_local_tracks(self.h, C.byref(fl), C.byref(ef), n_clones, arr, len(objs), _d(Pc), None, C.byref(dof), None)
+        if rc != 0:
+            raise MsckfError(rc, 'orcvio_msckf_objects_local_tracks')
+        self.n = flags.leg_dim + 6 * n_clones + self.n_extra
+        self.sync()
+        return int(dof.value)
+
     def update_frame(self, win, oflags, objs, R_b2c, t_c_b, obj_left, new_bbox, vio_left, fix_D=False, commit_objects=True):
         """orcvio_msckf_io_update_frame: the feature update of `win` on the resident covariance (arena written in place, committed
         inside the launch) and the object update of `objs` on the covariance it leaves, the objects' compression beside the
@@ -1354,6 +1368,12 @@ def debug_read(upd: MsckfUpdater, which: str):
     ldz = int(dims[6])
     if which == 'dims':
         return dict(n=n, NA=NA, NAP=NAP, NP=NP, m_tot=m_tot, Mmax=int(dims[5]), ldz=ldz, reg_path=int(dims[7]))
+    if which == 'obj_fused':   # did the last object update take the one-launch compression (k_obj_fused)?
+        v = np.zeros(1, dtype=np.int32)
+        rc = lib.orcvio_msckf_debug_read(upd.h, 15, v.ctypes.data_as(C.c_void_p), v.nbytes)
+        if rc != 0:
+            raise MsckfError(rc, 'debug_read obj_fused')
+        return int(v[0])
     if which == 'dense':   # [dense_rows][NAP]: H(:, 15 : 15 + NA) | r | 0 -- the rows handed over, then those of the entering features
         dd = np.zeros(2, dtype=np.int32)
         rc = lib.orcvio_msckf_debug_read(upd.h, 14, dd.ctypes.data_as(C.c_void_p), dd.nbytes)

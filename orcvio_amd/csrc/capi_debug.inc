@@ -8,7 +8,8 @@
 // which: 0 Hs [m_tot x NAP], 1 Ab, 2 A (summed block), 3 RP, 4 M, 5 RM, 6 Z, 8 U, 7 dims -> int32[8],
 //        11 {fac_valid, fac_n, fac_k, res_n} -> int32[4], 12 the resident factor [fac_k][fac_n],
 //        13 the dense rows [dense_rows][NAP] (caller-projected rows, then the rows of the entering features: zero U part, V part),
-//        14 {dense_rows, NAP} -> int32[2]
+//        14 {dense_rows, NAP} -> int32[2],
+//        15 did the last object update take the one-launch compression (k_obj_fused)? -> int32
 int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst, int64_t max_bytes) {
     if (!h || !dst) return ORCVIO_ERR_INVALID;
     HIPCHK(hipSetDevice(h->device));
@@ -57,6 +58,11 @@ int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst
             int32_t dd[2] = {h->dense_rows, h->NAP};
             if ((size_t)max_bytes < sizeof(dd)) return ORCVIO_ERR_INVALID;
             std::memcpy(dst, dd, sizeof(dd));
+            return ORCVIO_OK;
+        }
+        case 15: {   // the route of the last object update: 1 k_obj_fused, 0 the three-launch pipeline
+            if ((size_t)max_bytes < sizeof(int32_t)) return ORCVIO_ERR_INVALID;
+            *reinterpret_cast<int32_t*>(dst) = h->obj_last_fused ? 1 : 0;
             return ORCVIO_OK;
         }
         case 7: {
