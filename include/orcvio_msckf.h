@@ -882,6 +882,60 @@ int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msc
                                         int32_t n_clones, const double* poses, const double* R_b2c, const double* t_c_b,
                                         const orcvio_msckf_anchor_change* changes, int32_t count, double* new_param, double* new_inv_depth);
 
+/* ---- Zero-velocity frames on the resident covariance (measurementUpdate_ZUPT_vpq, src/orcvio.cpp:3326-3454) --------------------------
+ * On a frame the zero-velocity check accepts (checkZUPTFeat / checkZUPTIMU, :3081-3320: images and IMU samples, the caller's), the
+ * reference runs a 9-row update on the current velocity and on the pose difference of the two newest clones instead of the MSCKF
+ * updates, and marginalises the previous clone (:2641-2645).  The Jacobian's sparsity is fixed (:3329-3334), so nothing of size 9 x n
+ * is passed: the call takes the residual and the three variances.
+ *   cov_zupt         the update on the resident covariance: with Y = H P (three combinations of 15 rows of P), M = Y H^T + R = C C^T and
+ *                    V = C^-1 Y:  dx = V^T C^-1 r,  P+ = (P + P^T)/2 - V^T V  -- the reference's (I - K H) P followed by (P + P^T)/2 for a
+ *                    symmetric prior.  With ORCVIO_OPT_SCHMIDT_STATES = k the trailing 6 k x 6 k block of P+ is the prior's
+ *                    (:3432-3441); dx covers every state, as the reference's K r does.  The resident dimension must be
+ *                    leg_dim + 6 n_clones + ORCVIO_OPT_EXTRA_STATES (which counts the nuisance states).  dx [n] is the caller's, for
+ *                    orcvio_msckf_increment_state and the in-state features' parameters (:3391-3428); the covariance is updated whether
+ *                    or not the caller's increment later discards a large dx (:3389, then :3431-3447).
+ *                    The resident square-root factor: valid on entry and no nuisance states -> S+ of the same shape with
+ *                    S+ S+^T = P+ (array form: nine Householder reflectors bring [R^1/2 | H S] to lower-triangular form from the right
+ *                    and are applied to every row of S); with nuisance states, or without a valid factor, it is invalid afterwards.
+ *                    The factor is also invalid afterwards when it has more than 448 columns (what the reflectors hold in LDS; a
+ *                    factor of cov_prefactor, cov_augment or a committed update has at most n <= 232 plus a few).
+ *                    Refused on the device (ORCVIO_ERR_NOT_SPD, *applied = 0, dx = 0, P and its factor exactly as before): M not
+ *                    positive definite, or a non-finite entry in one of the 15 rows of P that enter H P (rows 3..5 and the twelve
+ *                    rows of the two newest clones).  The gate reads those rows whole; the other entries of P are NOT examined: a
+ *                    NaN or Inf elsewhere in P passes through (symmetrised) into P+, as it passes through every other cov_* call.
+ *                    A HIP error while waiting (ORCVIO_ERR_HIP / _TIMEOUT): the prior and its factor stay resident, nothing applied.
+ *                    Refused before anything is enqueued (ORCVIO_ERR_INVALID, nothing done): a null argument, leg_dim not 22 / 46,
+ *                    n_clones < 2, a dimension that does not match, a variance that is not finite or <= 0, a non-finite r, a
+ *                    communicator on the handle.
+ *   cov_zupt_frame   ONE stationary frame: the launches of cov_propagate (Phi, Q not NULL), cov_augment (augment != 0), cov_zupt and
+ *                    cov_remove_clones of the clone at window rank n_clones - 2 (remove_previous != 0), back to back on the handle's
+ *                    stream; the calling thread waits once.  Results bit-identical to the four separate calls.  zupt.n_clones is the
+ *                    window AFTER this frame's augmentation.  A validation failure leaves nothing done; a refusal on the device leaves
+ *                    propagation, augmentation and marginalisation standing (*applied = 0, ORCVIO_ERR_NOT_SPD).  *n_after: the resident
+ *                    dimension behind the frame.  The factor behind a refused frame: kept where cov_zupt would have kept it
+ *                    (valid on entry to the update, no nuisance states, at most 448 columns); in the other cases -- nuisance states
+ *                    declared, or more than 448 columns -- it is DROPPED although P is the prior's: conservative, the next update
+ *                    factors P again.  A HIP error behind the update's launches (ORCVIO_ERR_HIP / _TIMEOUT from the row deletion or
+ *                    the wait) leaves NOTHING resident: the outcome is unknown and the row deletion may have reused the prior's buffer,
+ *                    so every cov_* call refuses until orcvio_msckf_cov_set.
+ * Frames on which an in-state feature is lost or changes its anchor use the separate calls in the reference's order: cov_propagate,
+ * cov_augment, cov_zupt, cov_remove_features, cov_change_anchors, cov_remove_clones -- all of which keep the factor. */
+typedef struct orcvio_msckf_zupt {
+    int32_t leg_dim;        /* 22 or 46 */
+    int32_t n_clones;       /* N >= 2: the window with this frame's clone in it */
+    double  r[9];           /* r_v, r_p, r_q as :3337-3368 forms them */
+    double  noise_v, noise_p, noise_q;   /* VARIANCES (the yaml's std squared, :119-121) */
+} orcvio_msckf_zupt;
+int32_t orcvio_msckf_cov_zupt(orcvio_msckf_handle* h, const orcvio_msckf_zupt* zupt, double* dx /* [n] */, int32_t* applied);
+
+typedef struct orcvio_msckf_zupt_frame {
+    orcvio_msckf_zupt zupt;   /* n_clones AFTER this frame's augmentation */
+    const double* Phi; const double* Q;   /* NULL, NULL: no propagation */
+    int32_t augment;
+    int32_t remove_previous;  /* != 0: the clone at window rank N-2 is marginalised behind the update (:2641-2645) */
+} orcvio_msckf_zupt_frame;
+int32_t orcvio_msckf_cov_zupt_frame(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame* frame, double* dx, int32_t* applied, int32_t* n_after);
+
 /* ---- One filter frame in one call WITH the life cycle of the in-state features (hybrid filter) ------------------------------------
  * orcvio_msckf_io_step_frame plus the frame's feature events, in the reference's order (processFeatures, src/orcvio.cpp:567-594):
  *   1 propagation   2 augmentation   3 REMOVAL of the lost in-state features (removeLostFeatures -> rmLostFeaturesCov, :2233,

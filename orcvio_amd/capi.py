@@ -44,6 +44,7 @@ EXPORTS = [
     'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect',
     'orcvio_msckf_objects_refined', 'orcvio_msckf_counters', 'orcvio_msckf_comm_details', 'orcvio_msckf_profile_sharded',
     'orcvio_msckf_io_step_frame', 'orcvio_msckf_io_step_frame_ex', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
+    'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame',
 ]
 
 
@@ -108,6 +109,17 @@ class TriangulationConfig(C.Structure):
 
 class TriangulationResult(C.Structure):
     _fields_ = [('valid', _ip), ('p_w', _dp), ('inv_param', _dp), ('flags', _ip), ('cost', _dp)]
+
+
+class Zupt(C.Structure):
+    """orcvio_msckf_zupt: the zero-velocity update's residual and VARIANCES (include/orcvio_msckf.h)."""
+    _fields_ = [('leg_dim', C.c_int32), ('n_clones', C.c_int32), ('r', C.c_double * 9), ('noise_v', C.c_double),
+                ('noise_p', C.c_double), ('noise_q', C.c_double)]
+
+
+class ZuptFrame(C.Structure):
+    """orcvio_msckf_zupt_frame: one stationary frame (include/orcvio_msckf.h)."""
+    _fields_ = [('zupt', Zupt), ('Phi', _dp), ('Q', _dp), ('augment', C.c_int32), ('remove_previous', C.c_int32)]
 
 
 class MsckfState(C.Structure):
@@ -191,6 +203,8 @@ def _bind(lib):
     lib.orcvio_msckf_cov_remove_features.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip, C.c_int32]
     lib.orcvio_msckf_cov_change_anchors.argtypes = [C.c_void_p, C.POINTER(MsckfFlags), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
                                                     C.POINTER(AnchorChange), C.c_int32, _dp, _dp]
+    lib.orcvio_msckf_cov_zupt.argtypes = [C.c_void_p, C.POINTER(Zupt), _dp, _ip]
+    lib.orcvio_msckf_cov_zupt_frame.argtypes = [C.c_void_p, C.POINTER(ZuptFrame), _dp, _ip, _ip]
     lib.orcvio_msckf_upload_nuisance_poses.argtypes = [C.c_void_p, C.c_void_p]
     lib.orcvio_msckf_update_object_tracks.argtypes = [C.c_void_p, C.POINTER(MsckfFlags), C.POINTER(ObjectEvalFlags), C.c_int32,
                                                       C.POINTER(ObjectTrackC), C.c_int32, _dp, C.POINTER(MsckfResult)]
@@ -1105,6 +1119,48 @@ class MsckfUpdater:
                                                            arr, k, _d(param), _d(rho)), 'orcvio_msckf_cov_change_anchors')
         return param[:k], rho[:k]
 
+    @staticmethod
+    def _zupt_struct(leg_dim, n_clones, r, noises):
+        z = Zupt()
+        z.leg_dim, z.n_clones = int(leg_dim), int(n_clones)
+        z.r[:] = [float(x) for x in np.asarray(r, dtype=np.float64).reshape(9)]
+        z.noise_v, z.noise_p, z.noise_q = (float(x) for x in noises)
+        return z
+
+    def cov_zupt(self, leg_dim, n_clones, r, noises, raise_on_refusal=True):
+        """orcvio_msckf_cov_zupt: measurementUpdate_ZUPT_vpq on the resident covariance (its factor kept).  r [9]; noises: the three
+        VARIANCES (v, p, q).  Returns dict(dx [n], applied, rc)."""
+        z = self._zupt_struct(leg_dim, n_clones, r, noises)
+        n = C.c_int32(0)
+        self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), None), 'orcvio_msckf_cov_get')
+        dx = np.zeros(max(n.value, 1))
+        applied = C.c_int32(-1)
+        rc = self.lib.orcvio_msckf_cov_zupt(self.h, C.byref(z), _d(dx), C.byref(applied))
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_zupt')
+        return dict(dx=dx[:n.value], applied=int(applied.value), rc=rc)
+
+    def cov_zupt_frame(self, leg_dim, n_clones, r, noises, Phi=None, Q=None, augment=True, remove_previous=True, raise_on_refusal=True):
+        """orcvio_msckf_cov_zupt_frame: one stationary frame in one call (propagate, augment, the zero-velocity update, the previous
+        clone marginalised).  n_clones: the window AFTER the augmentation.  Returns dict(dx, applied, n_after, rc)."""
+        f = ZuptFrame()
+        f.zupt = self._zupt_struct(leg_dim, n_clones, r, noises)
+        keep = []
+        if Phi is not None:
+            keep.append(np.ascontiguousarray(Phi, dtype=np.float64)); f.Phi = _d(keep[-1])
+        if Q is not None:
+            keep.append(np.ascontiguousarray(Q, dtype=np.float64)); f.Q = _d(keep[-1])
+        f.augment, f.remove_previous = int(bool(augment)), int(bool(remove_previous))
+        n = C.c_int32(0)
+        self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), None), 'orcvio_msckf_cov_get')
+        nu = n.value + (6 if augment else 0)
+        dx = np.zeros(max(nu, 1))
+        applied, n_after = C.c_int32(-1), C.c_int32(-1)
+        rc = self.lib.orcvio_msckf_cov_zupt_frame(self.h, C.byref(f), _d(dx), C.byref(applied), C.byref(n_after))
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame')
+        return dict(dx=dx[:nu], applied=int(applied.value), n_after=int(n_after.value), rc=rc)
+
     def set_object_dof_rank(self, on: bool):
         """ORCVIO_OPT_OBJECT_DOF: 1 = the object gate counts rows - rank(H_f) degrees of freedom (default rows - columns)."""
         self._chk(self.lib.orcvio_msckf_set_option(self.h, 11, int(bool(on))), 'orcvio_msckf_set_option')
@@ -1350,6 +1406,39 @@ def increment_window(win, dx):
         raise MsckfError(1, 'orcvio_msckf_increment_state')
     return dataclasses.replace(win, R_b2w=R, t_b_w=t, R_b2c=np.ascontiguousarray(win.R_b2c, dtype=np.float64).copy(),
                                t_c_b=np.ascontiguousarray(win.t_c_b, dtype=np.float64).copy()), rc == 1
+
+
+def _rotation_to_quaternion(R):
+    """The reference's rotationToQuaternion (math_utils.hpp): (x, y, z, w), Hamilton, scalar part >= 0."""
+    R = np.asarray(R, dtype=np.float64)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    k = int(np.argmax([R[0, 0], R[1, 1], R[2, 2], tr]))
+    q = np.zeros(4)
+    if k == 3:
+        q[3] = np.sqrt(1.0 + tr) / 2.0
+        q[:3] = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / (4.0 * q[3])
+    else:
+        a, b = (k + 1) % 3, (k + 2) % 3
+        q[k] = np.sqrt(1.0 + 2.0 * R[k, k] - tr) / 2.0
+        q[a] = (R[k, a] + R[a, k]) / (4.0 * q[k])
+        q[b] = (R[k, b] + R[b, k]) / (4.0 * q[k])
+        q[3] = (R[b, a] - R[a, b]) / (4.0 * q[k])
+    if q[3] < 0:
+        q = -q
+    return q / np.linalg.norm(q)
+
+
+def zupt_residual(v, R_prev, p_prev, R_cur, p_cur):
+    """r [9] of the zero-velocity update as measurementUpdate_ZUPT_vpq forms it (src/orcvio.cpp:3337-3368): -v, -(p_cur - p_prev) and
+    the vector part of q_cur (x) q_prev* (Hamilton quaternions of the two newest clones' orientations, rotationToQuaternion).
+    Pure numpy: no device, no library call."""
+    qc, qp = _rotation_to_quaternion(R_cur), _rotation_to_quaternion(R_prev)
+    vc, wc, vp, wp = qc[:3], qc[3], -qp[:3], qp[3]   # (q_prev conjugated)
+    r = np.zeros(9)
+    r[0:3] = -np.asarray(v, dtype=np.float64)
+    r[3:6] = -(np.asarray(p_cur, dtype=np.float64) - np.asarray(p_prev, dtype=np.float64))
+    r[6:9] = wc * vp + wp * vc + np.cross(vc, vp)
+    return r
 
 
 def chi2_quantile(dof, prob=0.95):

@@ -1,0 +1,109 @@
+// capi_zupt.inc -- part of msckf_capi.hip (ONE translation unit: included there, in this order; not compiled on its own).
+// zero-velocity frames on the resident covariance (measurementUpdate_ZUPT_vpq, src/orcvio.cpp:3326-3454; zupt_ops.hpp).
+
+// Everything that can be refused before a launch.  `n` is the resident dimension the update will see.
+static int zupt_validate(const orcvio_msckf_handle* h, const orcvio_msckf_zupt* z, int n, const char* who) {
+    if (h->comm || h->ipc) { g_last_error = std::string(who) + ": not with a communicator on the handle"; return ORCVIO_ERR_INVALID; }
+    if (z->leg_dim != 22 && z->leg_dim != 46) { g_last_error = std::string(who) + ": leg_dim must be 22 or 46"; return ORCVIO_ERR_INVALID; }
+    if (z->n_clones < 2) { g_last_error = std::string(who) + ": the update needs the two newest clones (n_clones >= 2)"; return ORCVIO_ERR_INVALID; }
+    if (6 * h->n_nui > h->n_extra && h->n_nui > 0) { g_last_error = std::string(who) + ": ORCVIO_OPT_EXTRA_STATES counts the nuisance states of ORCVIO_OPT_SCHMIDT_STATES"; return ORCVIO_ERR_INVALID; }
+    if (h->res_n == 0 || n > h->n_max || (long)z->leg_dim + 6L * z->n_clones + h->n_extra != (long)n) {
+        g_last_error = std::string(who) + ": leg_dim + 6 n_clones + ORCVIO_OPT_EXTRA_STATES is not the resident dimension"; return ORCVIO_ERR_INVALID;
+    }
+    const double var[3] = {z->noise_v, z->noise_p, z->noise_q};
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(var[k]) || !(var[k] > 0.0)) { g_last_error = std::string(who) + ": the variances must be finite and positive"; return ORCVIO_ERR_INVALID; }
+    if (!all_finite(z->r, 9)) { g_last_error = std::string(who) + ": non-finite residual"; return ORCVIO_ERR_INVALID; }
+    return ORCVIO_OK;
+}
+
+// dx [n] and the status word of the launch: in the propagation scratch (46 n_max + 2 46^2 doubles), which nothing behind the update reads
+static inline double* zupt_dx(orcvio_msckf_handle* h) { return h->d_covT; }
+static inline int* zupt_status(orcvio_msckf_handle* h) { return reinterpret_cast<int*>(h->d_covT + h->n_max); }
+
+// The launches: P+ and dx into the spare covariance buffer, S+ into the spare factor buffer; the buffers change roles on the host.
+// A refusal on the device leaves bit copies there, so what is enqueued behind this reads the prior.
+static int zupt_enqueue(orcvio_msckf_handle* h, const orcvio_msckf_zupt* z) {
+    const int n = h->res_n;
+    hipStream_t s = h->stream;
+    ZuptArgs a;
+    for (int k = 0; k < 9; ++k) a.r[k] = z->r[k];
+    a.noise[0] = z->noise_v; a.noise[1] = z->noise_p; a.noise[2] = z->noise_q;
+    a.n = n; a.b = z->leg_dim + 6 * z->n_clones; a.nui6 = 6 * h->n_nui;
+    const int nt = (n + ZUPT_TILE - 1) / ZUPT_TILE;
+    hipLaunchKernelGGL(k_zupt_cov, dim3(nt, nt), dim3(256), 0, s, (const double*)h->d_Pres, a, h->d_Ptmp, zupt_dx(h), zupt_status(h));
+    HIPCHK(hipGetLastError());
+    if (h->fac_valid && h->fac_n == n && h->n_nui == 0 && h->fac_k <= ZUPT_KMAX) {
+        hipLaunchKernelGGL(k_zupt_fac, dim3((n + ZUPT_FAC_ROWS - 1) / ZUPT_FAC_ROWS), dim3(256), 0, s, (const double*)h->d_Sres, h->fac_ld, h->fac_k, a,
+                           (const int*)zupt_status(h), h->d_Stmp);
+        HIPCHK(hipGetLastError());
+        fac_adopt(h, n, h->fac_k, h->fac_ld, 0);   // (tail 0: the rows >= 15 are no longer zero in the trailing columns)
+    } else h->fac_valid = false;   // (nuisance states: the restored block breaks P = S S^T)
+    std::swap(h->d_Pres, h->d_Ptmp);
+    return ORCVIO_OK;
+}
+
+// the one wait: dx [n_dx] and the status word
+static int zupt_collect(orcvio_msckf_handle* h, int n_dx, double* dx, int* refused) {
+    int st = 0;
+    const FetchCopy fc[] = {{dx, zupt_dx(h), sizeof(double) * (size_t)n_dx}, {&st, zupt_status(h), sizeof(int)}};
+    const int rc = fetch_copies(h, h->stream, fc, 2);
+    if (rc != ORCVIO_OK) return rc;
+    *refused = st != 0;
+    return ORCVIO_OK;
+}
+
+int32_t orcvio_msckf_cov_zupt(orcvio_msckf_handle* h, const orcvio_msckf_zupt* z, double* dx, int32_t* applied) {
+    if (!h || !z || !dx || !applied) { g_last_error = "cov_zupt: null argument"; return ORCVIO_ERR_INVALID; }
+    { const int rv = zupt_validate(h, z, h->res_n, "cov_zupt"); if (rv != ORCVIO_OK) return rv; }
+    HIPCHK(hipSetDevice(h->device));
+    const CovState before = cov_state(h);
+    { const int rc = zupt_enqueue(h, z); if (rc != ORCVIO_OK) { cov_restore(h, before); return rc; } }
+    int refused = 0;
+    // (a failed wait: the outcome is unknown, but the launches wrote the spare buffers only -- the prior and its factor stand)
+    { const int rc = zupt_collect(h, h->res_n, dx, &refused); if (rc != ORCVIO_OK) { cov_restore(h, before); return rc; } }
+    *applied = refused ? 0 : 1;
+    if (refused) {   // nothing is swapped: P, its factor and their bookkeeping are the prior's own
+        cov_restore(h, before);
+        g_last_error = "cov_zupt: H P H^T + R not positive definite, or a non-finite covariance: nothing applied";
+        return ORCVIO_ERR_NOT_SPD;
+    }
+    return ORCVIO_OK;
+}
+
+int32_t orcvio_msckf_cov_zupt_frame(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame* f, double* dx, int32_t* applied, int32_t* n_after) {
+    if (!h || !f || !dx || !applied || !n_after) { g_last_error = "cov_zupt_frame: null argument"; return ORCVIO_ERR_INVALID; }
+    if ((f->Phi == nullptr) != (f->Q == nullptr)) { g_last_error = "cov_zupt_frame: Phi and Q come together"; return ORCVIO_ERR_INVALID; }
+    const orcvio_msckf_zupt* z = &f->zupt;
+    const int n = h->res_n + (f->augment ? 6 : 0);   // what the update sees
+    { const int rv = zupt_validate(h, z, n, "cov_zupt_frame"); if (rv != ORCVIO_OK) return rv; }
+    // (with the dimensions above, cov_propagate, cov_augment and cov_remove_clones have nothing left to refuse)
+    if (f->augment && h->n_extra > h->res_n - 15) { g_last_error = "cov_zupt_frame: more extra states than the resident covariance has"; return ORCVIO_ERR_INVALID; }
+    HIPCHK(hipSetDevice(h->device));
+    int rc = ORCVIO_OK;
+    if (f->Phi) rc = orcvio_msckf_cov_propagate(h, z->leg_dim, f->Phi, f->Q);
+    if (rc == ORCVIO_OK && f->augment) rc = orcvio_msckf_cov_augment(h);
+    if (rc != ORCVIO_OK) return rc;
+    const int tail_before = h->fac_tail;
+    rc = zupt_enqueue(h, z);
+    if (rc != ORCVIO_OK) return rc;   // (a launch that failed: nothing changed roles, propagation and augmentation stand)
+    if (f->remove_previous) {
+        const int32_t prev = z->n_clones - 2;
+        rc = orcvio_msckf_cov_remove_clones(h, z->leg_dim, &prev, 1);
+    }
+    int refused = 0;
+    if (rc == ORCVIO_OK) rc = zupt_collect(h, n, dx, &refused);
+    if (rc != ORCVIO_OK) {   // a HIP error behind the update: its outcome is unknown and the row deletion may have overwritten the prior's
+        h->res_n = 0;        // buffer, so NOTHING is resident any more -- the caller sets the covariance again (cov_set)
+        h->fac_valid = false;
+        return rc;
+    }
+    *n_after = h->res_n;
+    *applied = refused ? 0 : 1;
+    if (refused) {   // the spare buffers took bit copies of the prior and of its factor, whose zero trailing columns are still zero
+        if (h->fac_valid) h->fac_tail = tail_before;
+        g_last_error = "cov_zupt_frame: H P H^T + R not positive definite, or a non-finite covariance: the update was not applied";
+        return ORCVIO_ERR_NOT_SPD;
+    }
+    return ORCVIO_OK;
+}

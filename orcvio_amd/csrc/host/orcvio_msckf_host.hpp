@@ -155,6 +155,52 @@ inline int planAnchorChanges(const StateServer& ss, const MapServer& map_server,
     return ORCVIO_OK;
 }
 
+// rotationToQuaternion (include/orcvio/utils/math_utils.hpp:188-227): (x, y, z, w), Hamilton, the branch on the largest of the diagonal
+// and the trace, the scalar part made non-negative, normalised.  R row-major.
+inline void rotationToQuaternion(const double* R, double q[4]) {
+    const double tr = R[0] + R[4] + R[8];
+    const double score[4] = {R[0], R[4], R[8], tr};
+    int m = 0;
+    for (int k = 1; k < 4; ++k) if (score[k] > score[m]) m = k;
+    if (m == 0) {
+        q[0] = std::sqrt(1 + 2 * R[0] - tr) / 2.0;
+        q[1] = (R[1] + R[3]) / (4 * q[0]); q[2] = (R[2] + R[6]) / (4 * q[0]); q[3] = (R[7] - R[5]) / (4 * q[0]);
+    } else if (m == 1) {
+        q[1] = std::sqrt(1 + 2 * R[4] - tr) / 2.0;
+        q[0] = (R[1] + R[3]) / (4 * q[1]); q[2] = (R[5] + R[7]) / (4 * q[1]); q[3] = (R[2] - R[6]) / (4 * q[1]);
+    } else if (m == 2) {
+        q[2] = std::sqrt(1 + 2 * R[8] - tr) / 2.0;
+        q[0] = (R[2] + R[6]) / (4 * q[2]); q[1] = (R[5] + R[7]) / (4 * q[2]); q[3] = (R[3] - R[1]) / (4 * q[2]);
+    } else {
+        q[3] = std::sqrt(1 + tr) / 2.0;
+        q[0] = (R[7] - R[5]) / (4 * q[3]); q[1] = (R[2] - R[6]) / (4 * q[3]); q[2] = (R[3] - R[1]) / (4 * q[3]);
+    }
+    if (q[3] < 0) for (int k = 0; k < 4; ++k) q[k] = -q[k];
+    const double nrm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int k = 0; k < 4; ++k) q[k] /= nrm;
+}
+
+// The residual of the zero-velocity update (src/orcvio.cpp:3337-3368): r_v = -velocity, r_p = -(p_curr - p_prev) of the clones
+// imu_state.id and imu_state.id - 1, r_q = the vector part of q_curr (x) q_prev* (Eigen's Hamilton product).
+inline std::vector<double> zuptResidual(const StateServer& ss) {
+    std::vector<double> r(9, 0.0);
+    const IMUState_Aug& cur = ss.imu_states_augment.at(ss.imu_state.id);
+    const IMUState_Aug& prev = ss.imu_states_augment.at(ss.imu_state.id - 1);
+    for (int k = 0; k < 3; ++k) {
+        r[k] = -ss.imu_state.velocity[k];
+        r[3 + k] = -(cur.position[k] - prev.position[k]);
+    }
+    double qc[4], qp[4];
+    rotationToQuaternion(cur.orientation, qc);
+    rotationToQuaternion(prev.orientation, qp);
+    const double aw = qc[3], ax = qc[0], ay = qc[1], az = qc[2];
+    const double bw = qp[3], bx = -qp[0], by = -qp[1], bz = -qp[2];   // (conjugate)
+    r[6] = aw * bx + ax * bw + ay * bz - az * by;
+    r[7] = aw * by + ay * bw + az * bx - ax * bz;
+    r[8] = aw * bz + az * bw + ax * by - ay * bx;
+    return r;
+}
+
 struct UpdateOutcome {
     int status = ORCVIO_OK;
     bool updated = false;          // an update was applied to state_cov
@@ -870,7 +916,9 @@ class MsckfBackend {
     }
 
     // OrcVIO::incrementState_IMUCam (src/orcvio.cpp:4468-4567)
-    bool incrementState_IMUCam(StateServer& ss, const std::vector<double>& delta_x) const {
+    bool incrementState_IMUCam(StateServer& ss, const std::vector<double>& delta_x) const { return incrementStateWith(flags, ss, delta_x); }
+    // (the same without a backend: host arithmetic only)
+    static bool incrementStateWith(const orcvio_msckf_flags& flags, StateServer& ss, const std::vector<double>& delta_x) {
         const int N = (int)ss.imu_states_augment.size();
         std::vector<double> R(9 * N), t(3 * N), Rc(9 * N), tc(3 * N);
         int i = 0;
@@ -905,6 +953,58 @@ class MsckfBackend {
             ++i;
         }
         return true;
+    }
+
+    // ---- zero-velocity frames (measurementUpdate_ZUPT_vpq, src/orcvio.cpp:3326-3454) on the resident covariance ---------------
+    // The host half behind orcvio_msckf_cov_zupt's dx: incrementState_IMUCam (:3389), then the in-state features' loop (:3391-3428)
+    // -- 3-d: invParam += dx, 1-d: invDepth += dx; `position` from the anchor's camera pose (a clone of the window, or a nuisance
+    // state under use_schmidt).  The loop runs whether or not the large-update test discarded dx (its return is inside
+    // incrementState_IMUCam).  Returns whether the state was incremented; throws if a feature's anchor is nowhere (:3405).
+    static bool applyZuptIncrement(const orcvio_msckf_flags& flags, StateServer& ss, MapServer& map_server, const std::vector<double>& delta_x,
+                                   int idp_dim, bool use_schmidt) {
+        const bool incremented = incrementStateWith(flags, ss, delta_x);
+        const int base_cntr = flags.leg_dim + 6 * (int)ss.imu_states_augment.size();
+        for (int i = 0; i < (int)ss.feature_states.size(); ++i) {
+            Feature& f = map_server.at(ss.feature_states[i]);
+            const IMUState_Aug* a = nullptr;
+            if (use_schmidt && std::find(ss.nui_ids.begin(), ss.nui_ids.end(), f.id_anchor) != ss.nui_ids.end()) a = &ss.nui_imu_states.at(f.id_anchor);
+            else if (ss.imu_states_augment.count(f.id_anchor)) a = &ss.imu_states_augment.at(f.id_anchor);
+            else throw std::runtime_error("zuptUpdate: an in-state feature's anchor is neither in the window nor a nuisance state");
+            double p_c[3];
+            if (idp_dim == 3) {
+                for (int k = 0; k < 3; ++k) f.invParam[k] += delta_x[base_cntr + 3 * i + k];
+                p_c[0] = f.invParam[0] / f.invParam[2]; p_c[1] = f.invParam[1] / f.invParam[2]; p_c[2] = 1.0 / f.invParam[2];
+            } else {
+                f.invDepth += delta_x[base_cntr + i];
+                p_c[0] = f.obs_anchor[0] / f.invDepth; p_c[1] = f.obs_anchor[1] / f.invDepth; p_c[2] = 1.0 / f.invDepth;
+            }
+            for (int k = 0; k < 3; ++k)
+                f.position[k] = a->orientation_cam[3 * k] * p_c[0] + a->orientation_cam[3 * k + 1] * p_c[1] + a->orientation_cam[3 * k + 2] * p_c[2] + a->position_cam[k];
+        }
+        return incremented;
+    }
+    // The whole update of a frame the zero-velocity check accepted: residual, orcvio_msckf_cov_zupt on the resident covariance (the
+    // noises are VARIANCES; ORCVIO_OPT_EXTRA_STATES / _SCHMIDT_STATES declare what is behind the clones), the increments above.
+    // The covariance is updated whether or not the increment discards a large dx, as the reference's is (:3389, :3431-3447).
+    UpdateOutcome zuptUpdate(StateServer& ss, MapServer& map_server, double noise_v, double noise_p, double noise_q, int idp_dim = 1,
+                             bool use_schmidt = false) {
+        UpdateOutcome out;
+        orcvio_msckf_zupt z{};
+        z.leg_dim = flags.leg_dim; z.n_clones = (int32_t)ss.imu_states_augment.size();
+        z.noise_v = noise_v; z.noise_p = noise_p; z.noise_q = noise_q;
+        if (z.n_clones < 2) { out.status = ORCVIO_ERR_INVALID; return out; }
+        const std::vector<double> r = zuptResidual(ss);
+        std::memcpy(z.r, r.data(), sizeof(z.r));
+        int32_t n = 0;
+        out.status = orcvio_msckf_cov_get(h_, &n, nullptr);
+        if (out.status != ORCVIO_OK) return out;
+        out.delta_x.assign((size_t)n, 0.0);
+        int32_t applied = 0;
+        out.status = orcvio_msckf_cov_zupt(h_, &z, out.delta_x.data(), &applied);
+        out.updated = applied != 0;
+        if (out.status != ORCVIO_OK) return out;
+        out.state_incremented = applyZuptIncrement(flags, ss, map_server, out.delta_x, idp_dim, use_schmidt);
+        return out;
     }
 
     // System::processObjects -> removeLostObjects straight from object TRACKS (state at the LM optimum + observations: what

@@ -21,6 +21,7 @@
 #include "feature_split.hpp"
 #include "triangulate.hpp"
 #include "cov_ops.hpp"
+#include "zupt_ops.hpp"
 #include "ekf_rows.hpp"
 #include "object_rows.hpp"
 #include "object_fused.hpp"
@@ -404,6 +405,7 @@ const char* orcvio_msckf_last_error(void) { return g_last_error.c_str(); }
 #include "capi_ipc.inc"   // the second transport of the communicator: HIP IPC + shared memory (several ranks per device possible)
 #include "capi_comm.inc"   // the handle's RCCL communicator, bounded waits, the sharded updates
 #include "capi_cov.inc"   // per-kernel profile, the device-resident covariance and its square-root factor
+#include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: the 9-row update, the factor kept, the one-call stationary frame
 #include "capi_frame.inc"   // one frame in one call: feature update + object update, the objects' compression beside the features' solve
 #include "capi_step.inc"   // one FILTER frame in one call: propagate, augment, update, prune update, marginalise on the resident covariance
 #include "capi_state.inc"   // triangulation, incrementState_IMUCam (host arithmetic)

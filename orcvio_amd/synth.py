@@ -528,6 +528,50 @@ def make_lifecycle_stream(flags: "Flags", sigma_px=None, cycle: int = 8, seed: i
     return frames, np.ascontiguousarray(P0)
 
 
+ZUPT_NOISES = (1e-2 ** 2, 1e-2 ** 2, 3.4e-2 ** 2)   # the shipped zupt_noise_v / _p / _q (std in the yaml), as VARIANCES
+
+
+def make_zupt_stream(flags: "Flags", n_frames: int = 30, seed: int = 0, n_slam: int = 12, idp: int = 1, leg: int = LEG_DIM,
+                     stationary=((3, 9), (14, 17), (22, 27)), propagate_stationary: bool = True, F_range=(20, 81)):
+    """A filter stream with stationary segments (frames k with a <= k < b for (a, b) in `stationary`): on those the zero-velocity
+    check would accept, so the frame carries no tracks but the residual of measurementUpdate_ZUPT_vpq -- Phi close to identity, Q
+    small, the previous clone marginalised behind the update (src/orcvio.cpp:567-594, :2641-2645).  Moving frames are make_stream's:
+    a window one clone larger than the covariance in front of it, lost tracks, `n_slam` in-state features, and at 20 clones the prune
+    update on the two oldest clones with their marginalisation.
+    Returns (frames, P0): a moving frame is dict(zupt=None, w, slam, prune, Phi, Q, remove); a stationary one
+    dict(zupt=dict(r, n_clones, noises), w=None, Phi, Q (None, None without propagate_stationary), remove_previous=True)."""
+    rng = np.random.default_rng(seed)
+    frames = []
+    N_cur = 18
+    for k in range(n_frames):
+        still = any(a <= k < b for a, b in stationary)
+        G = rng.standard_normal((leg, 12))
+        if still:
+            Phi = np.eye(leg) + 1e-5 * rng.standard_normal((leg, leg))
+            Q = 1e-10 * G @ G.T
+            r = np.concatenate([2e-3 * rng.standard_normal(3), 1e-3 * rng.standard_normal(3), 5e-4 * rng.standard_normal(3)])
+            frames.append(dict(zupt=dict(r=r, n_clones=N_cur + 1, noises=ZUPT_NOISES), w=None, slam=None, prune=None,
+                               Phi=np.ascontiguousarray(Phi) if propagate_stationary else None,
+                               Q=np.ascontiguousarray(Q) if propagate_stationary else None, remove=[], remove_previous=True))
+            continue   # (one clone in, the previous one out: the window keeps its size)
+        N = N_cur + 1
+        F = int(rng.integers(*F_range))
+        w0 = make_window(N=N, F=F, seed=3000 + k, track_len=(3, 6), flags=flags, outlier_frac=0.05)
+        w = with_extra_states(w0, idp * n_slam, seed=k)
+        slam = make_slam_features(w, n_slam, seed=k, outlier_frac=0.1)
+        prune = None
+        if N == 20:
+            sub = subset_tracks(w, [0, 1], min_obs=2)
+            if int(sub.obs_ptr[-1]) > 0:
+                prune = sub
+        Phi = np.eye(leg) + 0.002 * rng.standard_normal((leg, leg))
+        frames.append(dict(zupt=None, w=w, slam=slam, prune=prune, Phi=np.ascontiguousarray(Phi), Q=np.ascontiguousarray(1e-7 * G @ G.T),
+                           remove=[0, 1] if N == 20 else []))
+        N_cur = 18 if N == 20 else N
+    P0 = with_extra_states(make_window(N=18, F=1, seed=5, flags=flags), idp * n_slam, seed=1).P
+    return frames, np.ascontiguousarray(P0)
+
+
 def pack_poses(win: "Window") -> np.ndarray:
     """[N][28] pose records of the input arena (include/orcvio_msckf.h ORCVIO_POSE_STRIDE)."""
     p = np.zeros((win.N, 28))
