@@ -436,8 +436,8 @@ int32_t orcvio_msckf_update_objects(orcvio_msckf_handle* h, const orcvio_msckf_f
  * src/obj/ObjectResJacCam.cpp:153-519, src/obj/ObjectLM.cpp:250-632) followed by
  * OrcVIO::constructObjectResidualJacobians (src/orcvio.cpp:2017-2151), evaluated on the device.  Output rows are
  * interleaved per in-window frame [keypoint rows ; 4 bbox rows] and can be passed to
- * orcvio_msckf_update_objects as they are.  The LM *solver* is not part of this library: the caller supplies
- * the state at which the rows are evaluated.
+ * orcvio_msckf_update_objects as they are.  The state at which the rows are evaluated is the caller's: the optimum of
+ * orcvio_msckf_object_lm below (the LM solver on the device), or one the caller has found by other means.
  * The rows are evaluated with UNIT residual weights and the Huber loss OFF: the functors' `residual_weight` and
  * `use_valid` / huber arguments (src/obj/ObjectResJacCam.cpp:535, 567-576; src/obj/ObjectLM.cpp:775-811) are ones / infinity
  * at every shipped call site (include/orcvio/obj/ObjectFeatureInitializer.h:40, ObjectLM.h:301), so no entry point exposes them. */
@@ -474,6 +474,65 @@ typedef struct orcvio_object_track {
 int32_t orcvio_msckf_object_rows_eval(orcvio_msckf_handle* h, const orcvio_object_eval_flags* flags,
                                       const orcvio_object_track* obj, int32_t cap_rows, int32_t* n_rows,
                                       int32_t* row_clone, double* Hx6, double* Hf, double* res);
+
+/* The object optimiser: replaces ObjectFeatureInitializer::single_levenberg_marquardt (src/obj/ObjectFeatureInitializer.cpp:346-440)
+ * for every object of a frame in ONE launch, one workgroup per object, the whole iteration on the device.
+ *
+ * Problem (ObjectLM::operator(), src/obj/ObjectLM.cpp:761-788; Huber off as above).  State x = (wTo, shape v, keypoints m_k), 9 + 3K
+ * degrees of freedom in the column order [pose 6 | shape 3 | 3 per keypoint]; cost c = |r|^2 over, with F = n_frames,
+ *   residual_weights[0] x the keypoint reprojection rows (a NaN detection is not a row),
+ *   residual_weights[1] x the 4 bbox rows of every frame (use_new_bbox_residual 0 / 1 / 2 as in orcvio_object_eval_flags),
+ *   residual_weights[2] x (m_k - mean_kps_k), repeated once per frame (ErrorDeformRegularization, :652-684),
+ *   residual_weights[3] x (v - mean_shape),   repeated once per frame (ErrorQuadVRegularization, :732-743).
+ * EVERY frame of the track is used, in the window or not: frame_clone is not read (it may be NULL).
+ * Retraction: pose exp(xi) wTo (use_left_perturbation = 1) or wTo exp(xi) (0), xi = (upsilon, omega) in Sophus order; shape and
+ * keypoints additive.  The start's wTo MUST BE RIGID (rotation block orthonormal to rounding, last row 0 0 0 1): the left and the
+ * right iteration move a non-rigid matrix along different orbits (a float32 pose, orthonormal to 1e-7, ends 3e-5 apart).
+ *
+ * Iteration -- NOT MINPACK's trajectory (the reference's Eigen LM carries a custom scaled_norm): only the optimum is comparable.
+ * With A = J^T J, g = J^T r:  D_j = max over the iterations so far of sqrt(A_jj);  (A + lambda D^2) delta = -g, lambda_0 = 1e-3;
+ * pred = -2 g^T delta - delta^T A delta.  status 1 (converged) when pred <= ptol c, tested before the trial point is evaluated;
+ * otherwise rho = (c - c+) / pred: accepted if rho > 1e-4 with lambda <- max(lambda max(1/3, 1 - (2 rho - 1)^3), 1e-12), else
+ * lambda <- 4 lambda.  status 2 (stalled) when lambda > 1e12; status 3 after max_iter solves; status 4 when a number stops being
+ * finite or a pivot of the damped system is not positive (the last accepted state is returned).  A keypoint detected in no frame
+ * has only its regulariser and stays at its mean (it needs residual_weights[2] > 0).
+ *
+ * Limits: 1 <= K <= 16 (K = 0, the bbox-only extension, is refused: the reference's lite mode is another functor), 1 <= F <= 128,
+ * n_tracks <= the handle's max_features, max_iter 1..100000.  A violation or a non-finite input (start, prior, camera pose, bbox,
+ * config) returns ORCVIO_ERR_INVALID / ORCVIO_ERR_CAPACITY before anything is enqueued.  A per-object status other than 1 is NOT an
+ * error of the call.  Synchronous: one launch, one wait; staging of its own -- neither the resident covariance nor the arena of an
+ * open orcvio_msckf_io_begin is touched.
+ *
+ * Intended sequence: point a track's wTo / shape / kps at the arrays of its result and pass the SAME track records to
+ * orcvio_msckf_update_object_tracks (or to orcvio_msckf_object_rows_eval for the reference's fvec_all / fjac_*). */
+typedef struct orcvio_object_lm_config {
+    int32_t use_left_perturbation, use_new_bbox_residual;
+    double  residual_weights[4];
+    int32_t max_iter;
+    double  ptol;
+} orcvio_object_lm_config;
+
+/* weights 1, 1, 1, 1; max_iter 60; ptol 1e-18; left perturbation; the old bbox residual */
+void orcvio_msckf_object_lm_config_default(orcvio_object_lm_config* cfg);
+
+typedef struct orcvio_object_lm_prior {
+    const double* mean_shape;   /* [3]     */
+    const double* mean_kps;     /* [K][3]  */
+} orcvio_object_lm_prior;
+
+typedef struct orcvio_object_lm_result {
+    double* wTo;                /* [16]   caller-owned, as are shape [3] and kps [K][3] */
+    double* shape;
+    double* kps;
+    double cost0, cost;         /* |r|^2 at the start and at the returned state */
+    int32_t iterations;         /* damped solves that went on to a trial point (accepted or not) */
+    int32_t evaluations;        /* evaluations of the cost (the start's included) */
+    int32_t status;             /* 1 converged, 2 stalled, 3 iteration cap, 4 non-finite */
+} orcvio_object_lm_result;
+
+int32_t orcvio_msckf_object_lm(orcvio_msckf_handle* h, const orcvio_object_lm_config* cfg,
+                               const orcvio_object_track* tracks, const orcvio_object_lm_prior* priors,
+                               int32_t n_tracks, orcvio_object_lm_result* results);
 
 /* ---- staged, device-resident form (what bench.py times; also the multi-GPU path) ----
  * upload:      copy window / tracks / P to the handle's device buffers (host -> HBM);

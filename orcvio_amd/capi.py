@@ -30,7 +30,7 @@ EXPORTS = [
     'orcvio_msckf_block_ptr', 'orcvio_msckf_run_finish', 'orcvio_msckf_run_update',
     'orcvio_msckf_sync', 'orcvio_msckf_download', 'orcvio_msckf_profile_update',
     'orcvio_msckf_increment_state', 'orcvio_msckf_set_option', 'orcvio_msckf_run_local_to',
-    'orcvio_msckf_object_rows_eval', 'orcvio_msckf_triangulation_config_default', 'orcvio_msckf_triangulate',
+    'orcvio_msckf_object_rows_eval', 'orcvio_msckf_object_lm', 'orcvio_msckf_object_lm_config_default', 'orcvio_msckf_triangulation_config_default', 'orcvio_msckf_triangulate',
     'orcvio_msckf_triangulate_uploaded', 'orcvio_msckf_objects_local', 'orcvio_msckf_objects_finish',
     'orcvio_msckf_objects_download', 'orcvio_msckf_cov_set', 'orcvio_msckf_cov_get', 'orcvio_msckf_cov_propagate',
     'orcvio_msckf_cov_augment', 'orcvio_msckf_cov_remove_clones', 'orcvio_msckf_cov_commit', 'orcvio_msckf_cov_prefactor', 'orcvio_msckf_upload_new_features', 'orcvio_msckf_download_new_feature_blocks', 'orcvio_msckf_upload_nuisance_poses',
@@ -77,6 +77,21 @@ class ObjectEvalFlags(C.Structure):
 class ObjectTrackC(C.Structure):
     _fields_ = [('n_keypoints', C.c_int32), ('n_frames', C.c_int32), ('wTo', _dp), ('shape', _dp), ('kps', _dp),
                 ('frame_wTc', _dp), ('frame_zs', _dp), ('frame_bbox', _dp), ('frame_clone', _ip)]
+
+
+class ObjectLMConfig(C.Structure):
+    """orcvio_object_lm_config (include/orcvio_msckf.h)."""
+    _fields_ = [('use_left_perturbation', C.c_int32), ('use_new_bbox_residual', C.c_int32), ('residual_weights', C.c_double * 4),
+                ('max_iter', C.c_int32), ('ptol', C.c_double)]
+
+
+class ObjectLMPrior(C.Structure):
+    _fields_ = [('mean_shape', _dp), ('mean_kps', _dp)]
+
+
+class ObjectLMResult(C.Structure):
+    _fields_ = [('wTo', _dp), ('shape', _dp), ('kps', _dp), ('cost0', C.c_double), ('cost', C.c_double),
+                ('iterations', C.c_int32), ('evaluations', C.c_int32), ('status', C.c_int32)]
 
 
 class ObjectLMMsg(C.Structure):
@@ -908,6 +923,53 @@ class MsckfUpdater:
         out['gamma'] = float(out['gamma'][0])
         out['accept'] = int(out['accept'][0])
         return out
+
+    def object_lm(self, objs, mean_shapes, mean_kps, left, new_bbox, weights, max_iter=None, ptol=None):
+        """orcvio_msckf_object_lm: Levenberg-Marquardt over every object track of `objs` (synth.ObjectTrack-shaped, their state the
+        start) in one launch.  mean_shapes [n][3] / mean_kps [n][K][3]: the priors of the two regularisers, one per object.
+        Returns (tracks, stats): synth.ObjectTrack copies at the optimum (frames shared with the inputs) and per object
+        dict(cost0, cost, iterations, evaluations, status)."""
+        cfg = ObjectLMConfig()
+        self.lib.orcvio_msckf_object_lm_config_default.argtypes = [C.POINTER(ObjectLMConfig)]
+        self.lib.orcvio_msckf_object_lm_config_default.restype = None
+        self.lib.orcvio_msckf_object_lm_config_default(C.byref(cfg))
+        cfg.use_left_perturbation = int(left)
+        cfg.use_new_bbox_residual = int(new_bbox)
+        cfg.residual_weights[:] = [float(w) for w in weights]
+        if max_iter is not None:
+            cfg.max_iter = int(max_iter)
+        if ptol is not None:
+            cfg.ptol = float(ptol)
+        _, arr, keep = self._object_tracks(objs, np.eye(3), np.zeros(3), left, new_bbox, 0, False)
+        n = len(objs)
+        priors = (ObjectLMPrior * max(n, 1))()
+        results = (ObjectLMResult * max(n, 1))()
+        outs = []
+        for k, obj in enumerate(objs):
+            K = arr[k].n_keypoints
+            ms = np.ascontiguousarray(mean_shapes[k], dtype=np.float64).reshape(3)
+            mk = np.ascontiguousarray(np.asarray(mean_kps[k], dtype=np.float64).reshape(-1, 3))
+            if mk.shape[0] != K:
+                raise ValueError('object_lm: mean_kps[%d] has %d keypoints, the track %d' % (k, mk.shape[0], K))
+            o = (np.zeros((4, 4)), np.zeros(3), np.zeros((max(K, 1), 3)))
+            keep += [ms, mk]
+            outs.append(o)
+            priors[k] = ObjectLMPrior(_d(ms), _d(mk))
+            results[k].wTo, results[k].shape, results[k].kps = _d(o[0]), _d(o[1]), _d(o[2])
+        self.lib.orcvio_msckf_object_lm.argtypes = [C.c_void_p, C.POINTER(ObjectLMConfig), C.POINTER(ObjectTrackC),
+                                                    C.POINTER(ObjectLMPrior), C.c_int32, C.POINTER(ObjectLMResult)]
+        self.lib.orcvio_msckf_object_lm.restype = C.c_int32
+        rc = self.lib.orcvio_msckf_object_lm(self.h, C.byref(cfg), arr, priors, n, results)
+        if rc != 0:
+            raise MsckfError(rc, 'orcvio_msckf_object_lm')
+        from . import synth
+        tracks, stats = [], []
+        for k, obj in enumerate(objs):
+            K = arr[k].n_keypoints
+            tracks.append(synth.ObjectTrack(wTo=outs[k][0], shape=outs[k][1], kps=outs[k][2][:K].copy(), frames=obj.frames))
+            stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
+                              evaluations=int(results[k].evaluations), status=int(results[k].status)))
+        return tracks, stats
 
     def objects_local_tracks(self, flags, n_clones, objs, P, R_b2c, t_c_b, obj_left, new_bbox, vio_left, fix_D=False):
         """The first half of update_object_tracks alone: the rows of the tracks evaluated on the device and compressed into the handle's

@@ -241,6 +241,8 @@ static void free_all(orcvio_msckf_handle* h) {
         if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_obj_stage) (void)hipHostFree(h->h_obj_stage);
+    if (h->h_lm) (void)hipHostFree(h->h_lm);
+    if (h->d_lm) (void)hipFree(h->d_lm);
     if (h->h_stage2) (void)hipHostFree(h->h_stage2);
     if (h->d_in2) (void)hipFree(h->d_in2);
     if (h->d_step_words) (void)hipFree(h->d_step_words);

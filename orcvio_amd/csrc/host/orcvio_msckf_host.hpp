@@ -1038,6 +1038,86 @@ class MsckfBackend {
         return out;
     }
 
+    // ---- ObjectInitNode -> ObjectFeatureInitializer::single_levenberg_marquardt (src/obj/ObjectFeatureInitializer.cpp:346-440) ------
+    // The object optimiser on the device (orcvio_msckf_object_lm).  As in the reference the iteration starts at the pose of
+    // `objectstate` (single_object_initialization's, which must be RIGID), the mean shape and the mean keypoints -- the members
+    // below, the initializer's -- and on success the optimum is written back: pose, ellipsoid, keypoints in the OBJECT frame (the
+    // reference's object_keypoints_shape_global_frame is wTo times them).  Every frame of `feat` is used.  Returns lm.info() ==
+    // Success: status 1; the counters and the other statuses are left in `objectstate` either way.  fvec_all / fjac_* of the
+    // reference's export block come from orcvio_msckf_object_rows_eval at the returned state.
+    struct ObjectFeatureTrack {
+        int n_keypoints = 0;
+        std::vector<double> frame_wTc;    // [F][16] camera -> world
+        std::vector<double> frame_zs;     // [F][K][2] normalised detections, NaN = not detected
+        std::vector<double> frame_bbox;   // [F][4] xmin, ymin, xmax, ymax
+        int frames() const { return (int)(frame_bbox.size() / 4); }
+    };
+    struct ObjectState {
+        double object_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        double ellipsoid_shape[3] = {0, 0, 0};
+        std::vector<double> object_keypoints;   // [K][3], object frame
+        double cost0 = 0, cost = 0;
+        int iterations = 0, evaluations = 0, lm_status = 0, status = ORCVIO_OK;
+    };
+    std::vector<double> object_mean_shape = {0, 0, 0};   // [3]
+    std::vector<double> object_keypoints_mean;           // [K][3]
+    double residual_weights[4] = {1, 1, 1, 1};
+    int object_lm_max_iter = 60;
+    double object_lm_ptol = 1e-18;
+
+    // every object of a frame in ONE launch; returns the call's status, objectstates[k].lm_status the per-object one
+    int levenberg_marquardt(const std::vector<const ObjectFeatureTrack*>& feats, std::vector<ObjectState>& objectstates,
+                            const bool use_left_perturbation_flag, const int use_new_bbox_residual_flag) {
+        const size_t n = feats.size();
+        if (objectstates.size() != n) return ORCVIO_ERR_INVALID;
+        orcvio_object_lm_config cfg;
+        orcvio_msckf_object_lm_config_default(&cfg);
+        cfg.use_left_perturbation = use_left_perturbation_flag ? 1 : 0;
+        cfg.use_new_bbox_residual = use_new_bbox_residual_flag;
+        for (int i = 0; i < 4; ++i) cfg.residual_weights[i] = residual_weights[i];
+        cfg.max_iter = object_lm_max_iter;
+        cfg.ptol = object_lm_ptol;
+        std::vector<orcvio_object_track> tracks(n);
+        std::vector<orcvio_object_lm_prior> priors(n);
+        std::vector<orcvio_object_lm_result> results(n);
+        std::vector<std::vector<double>> out(n);
+        for (size_t k = 0; k < n; ++k) {
+            const ObjectFeatureTrack& f = *feats[k];
+            const int K = f.n_keypoints, F = f.frames();
+            if (K < 0 || object_keypoints_mean.size() != (size_t)3 * K || object_mean_shape.size() != 3 ||
+                f.frame_bbox.size() != (size_t)4 * F || f.frame_wTc.size() != (size_t)16 * F || f.frame_zs.size() != (size_t)2 * K * F) {
+                for (ObjectState& o : objectstates) o.status = ORCVIO_ERR_INVALID;   // (nothing was launched)
+                return ORCVIO_ERR_INVALID;
+            }
+            out[k].assign(19 + (size_t)3 * K, 0.0);
+            tracks[k] = orcvio_object_track{K, F, objectstates[k].object_pose, object_mean_shape.data(), object_keypoints_mean.data(),
+                                            f.frame_wTc.data(), f.frame_zs.data(), f.frame_bbox.data(), nullptr};
+            priors[k] = orcvio_object_lm_prior{object_mean_shape.data(), object_keypoints_mean.data()};
+            results[k] = orcvio_object_lm_result{};
+            results[k].wTo = out[k].data(); results[k].shape = out[k].data() + 16; results[k].kps = out[k].data() + 19;
+        }
+        const int rc = orcvio_msckf_object_lm(h_, &cfg, tracks.data(), priors.data(), (int32_t)n, results.data());
+        for (size_t k = 0; k < n; ++k) {
+            ObjectState& o = objectstates[k];
+            o.status = rc;
+            if (rc != ORCVIO_OK) continue;
+            o.cost0 = results[k].cost0; o.cost = results[k].cost;
+            o.iterations = results[k].iterations; o.evaluations = results[k].evaluations; o.lm_status = results[k].status;
+            if (o.lm_status != 1) continue;   // (the reference leaves objectstate as it was when the LM did not succeed, :380-384)
+            std::memcpy(o.object_pose, out[k].data(), sizeof(o.object_pose));
+            std::memcpy(o.ellipsoid_shape, out[k].data() + 16, sizeof(o.ellipsoid_shape));
+            o.object_keypoints.assign(out[k].begin() + 19, out[k].end());
+        }
+        return rc;
+    }
+    bool single_levenberg_marquardt(const ObjectFeatureTrack& feat, ObjectState& objectstate, const bool use_left_perturbation_flag,
+                                    const int use_new_bbox_residual_flag) {
+        std::vector<ObjectState> st(1, objectstate);
+        const int rc = levenberg_marquardt({&feat}, st, use_left_perturbation_flag, use_new_bbox_residual_flag);
+        objectstate = st[0];
+        return rc == ORCVIO_OK && objectstate.lm_status == 1;
+    }
+
     // ---- one frame: System::imageCallback's processFeatures update followed by processObjects (System.cpp:548-554) ----------
     // With the covariance resident and one GPU this is ONE library call (orcvio_msckf_io_update_frame): the object tracks'
     // compression runs beside the feature update's solve.  `eval_flags` carries the extrinsics the object rows are evaluated

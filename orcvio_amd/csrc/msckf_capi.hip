@@ -25,6 +25,7 @@
 #include "ekf_rows.hpp"
 #include "object_rows.hpp"
 #include "object_fused.hpp"
+#include "object_lm.hpp"
 #include "io_ops.hpp"
 #include "frame_ops.hpp"
 #include <immintrin.h>
@@ -268,6 +269,8 @@ struct orcvio_msckf_handle {
     bool pub_pending = false;          // the results of the last one-shot object update are on their way to the pinned block (k_epilogue): wait on h_flag
     char *h_obj_stage = nullptr, *d_obj_in = nullptr;   // input arena of an object update: pinned mirror + device copy (grown on demand)
     size_t obj_stage_cap = 0;
+    char *h_lm = nullptr, *d_lm = nullptr;             // staging of orcvio_msckf_object_lm, its own (an open io_begin's arena and the object update's staging stay as they are): pinned [inputs | outputs] + device copy
+    size_t lm_cap = 0;
     std::vector<ObjUse> obj_use;        // (objects_local_tracks: per-track records, kept across calls: no allocation per frame)
     std::vector<int> obj_fnr;           // rows of every frame of the track being staged
     std::vector<signed char> obj_nv;    // (objects_tracks_scan) detected keypoints of every frame of every usable track: the ONE pass over the observations
@@ -405,6 +408,7 @@ const char* orcvio_msckf_last_error(void) { return g_last_error.c_str(); }
 #include "capi_ipc.inc"   // the second transport of the communicator: HIP IPC + shared memory (several ranks per device possible)
 #include "capi_comm.inc"   // the handle's RCCL communicator, bounded waits, the sharded updates
 #include "capi_cov.inc"   // per-kernel profile, the device-resident covariance and its square-root factor
+#include "capi_object_lm.inc"   // the object optimiser: batched Levenberg-Marquardt over object tracks, one workgroup per object
 #include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: the 9-row update, the factor kept, the one-call stationary frame
 #include "capi_frame.inc"   // one frame in one call: feature update + object update, the objects' compression beside the features' solve
 #include "capi_step.inc"   // one FILTER frame in one call: propagate, augment, update, prune update, marginalise on the resident covariance

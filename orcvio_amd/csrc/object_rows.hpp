@@ -56,10 +56,10 @@ __device__ __forceinline__ void mat4_vec(const double* T, const double* x, doubl
 // Every lane of the wavefront must call it (it holds a ballot).  emit(row_in_frame, r, hx6, hpose, hshape | nullptr, kp | -1,
 // hkp | nullptr, nrows_of_frame) is called once per row by the lane that owns it: hx6 = J_cam D (the row's six window columns),
 // hpose / hshape / hkp the structural non-zeros of its H_f row.
+// object_rows_lane_at takes `live` from its caller (k_object_lm: every frame of the track, in the window or not; frame_clone is not
+// read), object_rows_lane from the frame's clone.
 template <class Emit>
-__device__ __forceinline__ void object_rows_lane(const ObjEvalArgs& p, const int f, const int t, const int lpf, Emit&& emit) {
-    const int clone = f >= 0 ? p.frame_clone[f] : -1;
-    const bool live = clone >= 0;
+__device__ __forceinline__ void object_rows_lane_at(const ObjEvalArgs& p, const int f, const bool live, const int t, const int lpf, Emit&& emit) {
     const int K = p.K;
     const int fq = live ? f : 0;
     // frame transforms
@@ -227,6 +227,12 @@ __device__ __forceinline__ void object_rows_lane(const ObjEvalArgs& p, const int
         }
         out(2 * nvalid + j, r, jc, hp, hs, -1, nullptr);
     }
+}
+
+template <class Emit>
+__device__ __forceinline__ void object_rows_lane(const ObjEvalArgs& p, const int f, const int t, const int lpf, Emit&& emit) {
+    const int clone = f >= 0 ? p.frame_clone[f] : -1;
+    object_rows_lane_at(p, f, clone >= 0, t, lpf, emit);
 }
 
 // One wavefront per in-window frame, rows to the compact row arrays in device memory (k_object_rows / k_object_rows_batch).

@@ -115,7 +115,7 @@ class H5:
 
 def main():
     out = os.path.join(ROOT, 'tests', 'golden')
-    for fn in ('test_error_feature_quadric.h5', 'test_error_bbox_quadric.h5'):
+    for fn in ('test_error_feature_quadric.h5', 'test_error_bbox_quadric.h5', 'test_error_deform_reg.h5', 'test_error_mean_shape_reg.h5'):
         data = H5(os.path.join(REF, fn)).read_all()
         np.savez_compressed(os.path.join(out, 'ref_' + fn[:-3] + '.npz'), **data)
         print(fn, {k: v.shape for k, v in data.items()})
