@@ -534,6 +534,65 @@ int32_t orcvio_msckf_object_lm(orcvio_msckf_handle* h, const orcvio_object_lm_co
                                const orcvio_object_track* tracks, const orcvio_object_lm_prior* priors,
                                int32_t n_tracks, orcvio_object_lm_result* results);
 
+/* The start of an object track: replaces ObjectFeatureInitializer::single_object_initialization
+ * (src/obj/ObjectFeatureInitializer.cpp:33-198) for every object of a frame in ONE launch (k_object_init, one workgroup per object).
+ *
+ * Keypoints.  Keypoint k is USED if the number of frames in which both of its coordinates are finite is strictly greater than
+ * min_obs (ObjectFeature.cpp:118).  A used keypoint is triangulated linearly over those frames (single_triangulation_common,
+ * src/feat/FeatureInitializer.cpp:6-111): anchor = the LAST of them (per keypoint), rows Bperp_i p = Bperp_i p_CiinA, solved by the
+ * normal equations (the reference: a pivoted QR; forward error cond(A)^2 eps instead of cond(A) eps), p_FinG = R_GtoA^T p + p_AinG;
+ * kp_cond = cond(A), the reference's condA.
+ * Alignment.  If the number of used keypoints is strictly greater than min_kps, findTransform (:265-344) over the used keypoints in
+ * increasing id: scale = ratio of the summed chords between CONSECUTIVE used keypoints, Cov = in out^T of the centred sets
+ * (out divided by scale), its 3 x 3 SVD (one-sided Jacobi on the device), R = V diag(1, 1, sign det(V U^T)) U^T,
+ * t_kabsch = scale (out_ctr / scale - R in_ctr).  The reference's literal result [scale R | t_kabsch] is NOT rigid; it is returned
+ * in pieces (R_kabsch, t_kabsch, scale; sigma = the singular values of Cov) and wTo is one of three RIGID forms:
+ *   pose_form 1  the reference as shipped (estimate_SE2_pose_flag = true, poseSE32SE2, se3_ops.hpp:272-300):
+ *                yaw = pi / atan2(T10, T00), 0 if that is not finite; translation (t_kabsch x, t_kabsch y, 0);
+ *   pose_form 2  the same with yaw = atan2(T10, T00) (opt-in correction, as use_new_bbox_residual = 2 is);
+ *   pose_form 0  rigid SE(3): R_kabsch and out_ctr - R in_ctr on the unscaled points (an extension).
+ * status 1 initialised; 2 too few usable keypoints (wTo = identity, as the reference returns); 4 a number stopped being finite
+ * (wTo = identity).  No conditioning threshold is applied: sigma and kp_cond are reported, the caller judges.
+ *
+ * Of a track, n_keypoints, n_frames, frame_wTc and frame_zs are read; wTo, shape, kps, frame_bbox and frame_clone are not and may
+ * be NULL.  Limits and refusals as orcvio_msckf_object_lm's (1 <= K <= 16, 1 <= F <= 128, n_tracks <= max_features, null pointers,
+ * a non-finite camera pose or mean keypoint; pose_form outside 0..2, a negative threshold), before anything is enqueued.  A NaN
+ * detection is data.  Synchronous: one upload, one launch, one download, one wait, on the optimiser's own staging. */
+typedef struct orcvio_object_init_config {
+    int32_t pose_form, min_obs, min_kps;
+} orcvio_object_init_config;
+
+/* the reference's values: pose_form 1, min_obs 3, min_kps 3 */
+void orcvio_msckf_object_init_config_default(orcvio_object_init_config* cfg);
+
+typedef struct orcvio_object_init_result {
+    double* wTo;                /* [16]    caller-owned, as are the four arrays below                                */
+    double* kps_world;          /* [K][3]  valid_shape_global_frame; NaN where the keypoint is not used              */
+    int32_t* kp_used;           /* [K]     1 / 0                                                                     */
+    int32_t* kp_obs;            /* [K]     frames with a finite detection                                            */
+    double* kp_cond;            /* [K]     cond(A) of the triangulation; NaN where the keypoint is not used          */
+    double R_kabsch[9], t_kabsch[3], scale;   /* the reference's literal matrix is [scale R_kabsch | t_kabsch]       */
+    double sigma[3];            /* singular values of Cov, descending                                                */
+    int32_t n_used;
+    int32_t status;             /* 1 initialised, 2 too few usable keypoints, 4 non-finite                           */
+} orcvio_object_init_result;
+
+/* mean_kps_per_track [n_tracks]: pointers to [K][3], the class's mean keypoints in the object frame */
+int32_t orcvio_msckf_object_init(orcvio_msckf_handle* h, const orcvio_object_init_config* cfg,
+                                 const orcvio_object_track* tracks, const double* const* mean_kps_per_track,
+                                 int32_t n_tracks, orcvio_object_init_result* results);
+
+/* Initialisation and optimisation in ONE call: packs and uploads once, k_object_init writes each track's start (its wTo, the mean
+ * shape, the mean keypoints: the reference's LMObjectState start) into the staged block, k_object_lm follows on the same stream, both
+ * result blocks come back in one download behind one wait.  An object whose initialisation did not end with status 1 is not
+ * optimised: its LM status is 0, its LM arrays hold the identity, the mean shape and the mean keypoints, its costs and counters 0.
+ * The tracks' wTo, shape, kps and frame_clone are not read and may be NULL; frame_bbox is.  Equal, bit for bit, to
+ * orcvio_msckf_object_init followed by orcvio_msckf_object_lm from its wTo and the means. */
+int32_t orcvio_msckf_object_init_lm(orcvio_msckf_handle* h, const orcvio_object_init_config* init_cfg,
+                                    const orcvio_object_lm_config* lm_cfg, const orcvio_object_track* tracks,
+                                    const orcvio_object_lm_prior* priors, int32_t n_tracks,
+                                    orcvio_object_init_result* init_results, orcvio_object_lm_result* lm_results);
+
 /* ---- staged, device-resident form (what bench.py times; also the multi-GPU path) ----
  * upload:      copy window / tracks / P to the handle's device buffers (host -> HBM);
  * run_local:   Jacobians -> nullspace -> gate -> stacked [H'|r'] -> Gram compression.

@@ -30,7 +30,8 @@ EXPORTS = [
     'orcvio_msckf_block_ptr', 'orcvio_msckf_run_finish', 'orcvio_msckf_run_update',
     'orcvio_msckf_sync', 'orcvio_msckf_download', 'orcvio_msckf_profile_update',
     'orcvio_msckf_increment_state', 'orcvio_msckf_set_option', 'orcvio_msckf_run_local_to',
-    'orcvio_msckf_object_rows_eval', 'orcvio_msckf_object_lm', 'orcvio_msckf_object_lm_config_default', 'orcvio_msckf_triangulation_config_default', 'orcvio_msckf_triangulate',
+    'orcvio_msckf_object_rows_eval', 'orcvio_msckf_object_lm', 'orcvio_msckf_object_lm_config_default',
+    'orcvio_msckf_object_init', 'orcvio_msckf_object_init_lm', 'orcvio_msckf_object_init_config_default', 'orcvio_msckf_triangulation_config_default', 'orcvio_msckf_triangulate',
     'orcvio_msckf_triangulate_uploaded', 'orcvio_msckf_objects_local', 'orcvio_msckf_objects_finish',
     'orcvio_msckf_objects_download', 'orcvio_msckf_cov_set', 'orcvio_msckf_cov_get', 'orcvio_msckf_cov_propagate',
     'orcvio_msckf_cov_augment', 'orcvio_msckf_cov_remove_clones', 'orcvio_msckf_cov_commit', 'orcvio_msckf_cov_prefactor', 'orcvio_msckf_upload_new_features', 'orcvio_msckf_download_new_feature_blocks', 'orcvio_msckf_upload_nuisance_poses',
@@ -92,6 +93,17 @@ class ObjectLMPrior(C.Structure):
 class ObjectLMResult(C.Structure):
     _fields_ = [('wTo', _dp), ('shape', _dp), ('kps', _dp), ('cost0', C.c_double), ('cost', C.c_double),
                 ('iterations', C.c_int32), ('evaluations', C.c_int32), ('status', C.c_int32)]
+
+
+class ObjectInitConfig(C.Structure):
+    """orcvio_object_init_config (include/orcvio_msckf.h)."""
+    _fields_ = [('pose_form', C.c_int32), ('min_obs', C.c_int32), ('min_kps', C.c_int32)]
+
+
+class ObjectInitResult(C.Structure):
+    _fields_ = [('wTo', _dp), ('kps_world', _dp), ('kp_used', _ip), ('kp_obs', _ip), ('kp_cond', _dp),
+                ('R_kabsch', C.c_double * 9), ('t_kabsch', C.c_double * 3), ('scale', C.c_double), ('sigma', C.c_double * 3),
+                ('n_used', C.c_int32), ('status', C.c_int32)]
 
 
 class ObjectLMMsg(C.Structure):
@@ -970,6 +982,110 @@ class MsckfUpdater:
             stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
                               evaluations=int(results[k].evaluations), status=int(results[k].status)))
         return tracks, stats
+
+    def _object_init_args(self, objs, mean_kps, pose_form, min_obs, min_kps, with_bbox):
+        """Track records with only what the initialiser reads (wTo / shape / kps / frame_clone NULL), its config and result records."""
+        cfg = ObjectInitConfig()
+        self.lib.orcvio_msckf_object_init_config_default.argtypes = [C.POINTER(ObjectInitConfig)]
+        self.lib.orcvio_msckf_object_init_config_default.restype = None
+        self.lib.orcvio_msckf_object_init_config_default(C.byref(cfg))
+        if pose_form is not None:
+            cfg.pose_form = int(pose_form)
+        if min_obs is not None:
+            cfg.min_obs = int(min_obs)
+        if min_kps is not None:
+            cfg.min_kps = int(min_kps)
+        n = len(objs)
+        arr = (ObjectTrackC * max(n, 1))()
+        results = (ObjectInitResult * max(n, 1))()
+        keep, outs, mks = [], [], []
+        for k, obj in enumerate(objs):
+            mk = np.ascontiguousarray(np.asarray(mean_kps[k], dtype=np.float64).reshape(-1, 3))
+            K = mk.shape[0]
+            wTc = np.ascontiguousarray(np.stack([fr['wTc'] for fr in obj.frames]), dtype=np.float64)
+            zs = np.ascontiguousarray(np.stack([np.asarray(fr['zs'], dtype=np.float64).reshape(-1, 2) for fr in obj.frames]))
+            if zs.shape[1] != K:
+                raise ValueError('object_init: mean_kps[%d] has %d keypoints, the track %d' % (k, K, zs.shape[1]))
+            bb = np.ascontiguousarray(np.stack([fr['bbox'] for fr in obj.frames]), dtype=np.float64) if with_bbox else None
+            o = dict(wTo=np.zeros((4, 4)), kps_world=np.zeros((max(K, 1), 3)), kp_used=np.zeros(max(K, 1), dtype=np.int32),
+                     kp_obs=np.zeros(max(K, 1), dtype=np.int32), kp_cond=np.zeros(max(K, 1)))
+            keep += [mk, wTc, zs, bb]
+            outs.append(o)
+            mks.append(mk)
+            arr[k] = ObjectTrackC(K, len(obj.frames), None, None, None, _d(wTc), _d(zs), _d(bb), None)
+            results[k].wTo, results[k].kps_world, results[k].kp_cond = _d(o['wTo']), _d(o['kps_world']), _d(o['kp_cond'])
+            results[k].kp_used, results[k].kp_obs = _i(o['kp_used']), _i(o['kp_obs'])
+        return cfg, arr, results, outs, mks, keep
+
+    @staticmethod
+    def _object_init_outs(results, outs):
+        res = []
+        for k, o in enumerate(outs):
+            r = results[k]
+            res.append(dict(o, R=np.array(r.R_kabsch[:]).reshape(3, 3), t=np.array(r.t_kabsch[:]), scale=float(r.scale),
+                            sigma=np.array(r.sigma[:]), n_used=int(r.n_used), status=int(r.status)))
+        return res
+
+    def object_init(self, objs, mean_kps, pose_form=None, min_obs=None, min_kps=None):
+        """orcvio_msckf_object_init: the start pose of every object track of `objs` (synth.ObjectTrack-shaped: their frames' wTc and
+        zs are read) in one launch -- keypoint triangulation, Kabsch alignment of mean_kps [n][K][3] onto the triangulated keypoints,
+        the pose form of include/orcvio_msckf.h.  Returns per object dict(wTo, kps_world, kp_used, kp_obs, kp_cond, R, t, scale,
+        sigma, n_used, status)."""
+        cfg, arr, results, outs, mks, keep = self._object_init_args(objs, mean_kps, pose_form, min_obs, min_kps, False)
+        n = len(objs)
+        ptrs = (_dp * max(n, 1))(*[_d(m) for m in mks])
+        self.lib.orcvio_msckf_object_init.argtypes = [C.c_void_p, C.POINTER(ObjectInitConfig), C.POINTER(ObjectTrackC), C.POINTER(_dp),
+                                                      C.c_int32, C.POINTER(ObjectInitResult)]
+        self.lib.orcvio_msckf_object_init.restype = C.c_int32
+        rc = self.lib.orcvio_msckf_object_init(self.h, C.byref(cfg), arr, ptrs, n, results)
+        if rc != 0:
+            raise MsckfError(rc, 'orcvio_msckf_object_init')
+        return self._object_init_outs(results, outs)
+
+    def object_init_lm(self, objs, mean_shapes, mean_kps, left, new_bbox, weights, max_iter=None, ptol=None, pose_form=None, min_obs=None,
+                       min_kps=None):
+        """orcvio_msckf_object_init_lm: object_init and object_lm from its start (the pose, the mean shape, the mean keypoints) in ONE
+        call.  Returns (inits, tracks, stats): object_init's list, and object_lm's two; an object whose initialisation did not end
+        with status 1 has LM status 0, the identity and the means."""
+        icfg, arr, iresults, iouts, mks, keep = self._object_init_args(objs, mean_kps, pose_form, min_obs, min_kps, True)
+        cfg = ObjectLMConfig()
+        self.lib.orcvio_msckf_object_lm_config_default.argtypes = [C.POINTER(ObjectLMConfig)]
+        self.lib.orcvio_msckf_object_lm_config_default.restype = None
+        self.lib.orcvio_msckf_object_lm_config_default(C.byref(cfg))
+        cfg.use_left_perturbation = int(left)
+        cfg.use_new_bbox_residual = int(new_bbox)
+        cfg.residual_weights[:] = [float(w) for w in weights]
+        if max_iter is not None:
+            cfg.max_iter = int(max_iter)
+        if ptol is not None:
+            cfg.ptol = float(ptol)
+        n = len(objs)
+        priors = (ObjectLMPrior * max(n, 1))()
+        results = (ObjectLMResult * max(n, 1))()
+        outs = []
+        for k in range(n):
+            K = arr[k].n_keypoints
+            ms = np.ascontiguousarray(mean_shapes[k], dtype=np.float64).reshape(3)
+            o = (np.zeros((4, 4)), np.zeros(3), np.zeros((max(K, 1), 3)))
+            keep.append(ms)
+            outs.append(o)
+            priors[k] = ObjectLMPrior(_d(ms), _d(mks[k]))
+            results[k].wTo, results[k].shape, results[k].kps = _d(o[0]), _d(o[1]), _d(o[2])
+        self.lib.orcvio_msckf_object_init_lm.argtypes = [C.c_void_p, C.POINTER(ObjectInitConfig), C.POINTER(ObjectLMConfig),
+                                                         C.POINTER(ObjectTrackC), C.POINTER(ObjectLMPrior), C.c_int32,
+                                                         C.POINTER(ObjectInitResult), C.POINTER(ObjectLMResult)]
+        self.lib.orcvio_msckf_object_init_lm.restype = C.c_int32
+        rc = self.lib.orcvio_msckf_object_init_lm(self.h, C.byref(icfg), C.byref(cfg), arr, priors, n, iresults, results)
+        if rc != 0:
+            raise MsckfError(rc, 'orcvio_msckf_object_init_lm')
+        from . import synth
+        tracks, stats = [], []
+        for k, obj in enumerate(objs):
+            K = arr[k].n_keypoints
+            tracks.append(synth.ObjectTrack(wTo=outs[k][0], shape=outs[k][1], kps=outs[k][2][:K].copy(), frames=obj.frames))
+            stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
+                              evaluations=int(results[k].evaluations), status=int(results[k].status)))
+        return self._object_init_outs(iresults, iouts), tracks, stats
 
     def objects_local_tracks(self, flags, n_clones, objs, P, R_b2c, t_c_b, obj_left, new_bbox, vio_left, fix_D=False):
         """The first half of update_object_tracks alone: the rows of the tracks evaluated on the device and compressed into the handle's

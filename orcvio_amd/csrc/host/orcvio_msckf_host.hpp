@@ -10,12 +10,14 @@
 // flatten -> C call -> apply sequence implemented here.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <iterator>
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../../include/orcvio_msckf.h"
@@ -1065,9 +1067,86 @@ class MsckfBackend {
     int object_lm_max_iter = 60;
     double object_lm_ptol = 1e-18;
 
+    // ---- ObjectInitNode -> ObjectFeatureInitializer::single_object_initialization (src/obj/ObjectFeatureInitializer.cpp:33-198) ------
+    // The start of an object track on the device (orcvio_msckf_object_init): keypoint triangulation, Kabsch alignment of
+    // object_keypoints_mean onto the triangulated keypoints, the pose in the form object_init_pose_form (1: the reference as shipped).
+    struct ObjectInit {
+        double wTq[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // rigid; the identity unless init_status == 1
+        double R_kabsch[9] = {0}, t_kabsch[3] = {0}, scale = 0, sigma[3] = {0};   // findTransform's literal matrix is [scale R | t]
+        std::vector<double> valid_shape_global_frame;   // [K][3], NaN where the keypoint is not used
+        std::vector<int32_t> kp_used, kp_obs;           // [K]
+        std::vector<double> kp_cond;                    // [K] cond(A) of the triangulation
+        int n_used = 0, init_status = 0, status = ORCVIO_OK;
+    };
+    int object_init_pose_form = 1, object_init_min_obs = 3, object_init_min_kps = 3;
+
+    void object_init_results(const std::vector<const ObjectFeatureTrack*>& feats, std::vector<ObjectInit>& inits,
+                             std::vector<orcvio_object_init_result>& res) const {
+        const size_t n = feats.size();
+        inits.assign(n, ObjectInit{});
+        res.assign(n, orcvio_object_init_result{});
+        for (size_t k = 0; k < n; ++k) {
+            const size_t K = (size_t)(feats[k]->n_keypoints > 0 ? feats[k]->n_keypoints : 0);
+            ObjectInit& o = inits[k];
+            o.valid_shape_global_frame.assign(3 * K + 1, 0.0); o.kp_used.assign(K + 1, 0); o.kp_obs.assign(K + 1, 0); o.kp_cond.assign(K + 1, 0.0);
+            res[k].wTo = o.wTq; res[k].kps_world = o.valid_shape_global_frame.data(); res[k].kp_used = o.kp_used.data();
+            res[k].kp_obs = o.kp_obs.data(); res[k].kp_cond = o.kp_cond.data();
+        }
+    }
+    static void object_init_finish(int rc, const std::vector<orcvio_object_init_result>& res, std::vector<ObjectInit>& inits) {
+        for (size_t k = 0; k < inits.size(); ++k) {
+            ObjectInit& o = inits[k];
+            o.valid_shape_global_frame.pop_back(); o.kp_used.pop_back(); o.kp_obs.pop_back(); o.kp_cond.pop_back();   // (the spare element kept the pointers valid)
+            o.status = rc;
+            if (rc != ORCVIO_OK) continue;
+            std::memcpy(o.R_kabsch, res[k].R_kabsch, sizeof(o.R_kabsch));
+            std::memcpy(o.t_kabsch, res[k].t_kabsch, sizeof(o.t_kabsch));
+            std::memcpy(o.sigma, res[k].sigma, sizeof(o.sigma));
+            o.scale = res[k].scale; o.n_used = res[k].n_used; o.init_status = res[k].status;
+        }
+    }
+
+    // every object of a frame in ONE launch; returns the call's status, inits[k].init_status the per-object one
+    int object_initialization(const std::vector<const ObjectFeatureTrack*>& feats, std::vector<ObjectInit>& inits) {
+        const size_t n = feats.size();
+        const orcvio_object_init_config icfg{object_init_pose_form, object_init_min_obs, object_init_min_kps};
+        std::vector<orcvio_object_track> tracks(n);
+        std::vector<const double*> mean(n, object_keypoints_mean.data());
+        for (size_t k = 0; k < n; ++k) {
+            const ObjectFeatureTrack& f = *feats[k];
+            const int K = f.n_keypoints, F = (int)(f.frame_wTc.size() / 16);
+            if (K < 0 || object_keypoints_mean.size() != (size_t)3 * K || f.frame_wTc.size() != (size_t)16 * F ||
+                f.frame_zs.size() != (size_t)2 * K * F) {
+                inits.assign(n, ObjectInit{});
+                for (ObjectInit& o : inits) o.status = ORCVIO_ERR_INVALID;   // (nothing was launched)
+                return ORCVIO_ERR_INVALID;
+            }
+            tracks[k] = orcvio_object_track{K, F, nullptr, nullptr, nullptr, f.frame_wTc.data(), f.frame_zs.data(), nullptr, nullptr};
+        }
+        std::vector<orcvio_object_init_result> res;
+        object_init_results(feats, inits, res);
+        const int rc = orcvio_msckf_object_init(h_, &icfg, tracks.data(), mean.data(), (int32_t)n, res.data());
+        object_init_finish(rc, res, inits);
+        return rc;
+    }
+    // the reference's call: (init_success_flag, wTq); everything else it leaves in members is in `init`
+    std::tuple<bool, std::array<double, 16>> single_object_initialization(const ObjectFeatureTrack& feat, ObjectInit* init = nullptr) {
+        std::vector<ObjectInit> one;
+        const int rc = object_initialization({&feat}, one);
+        std::array<double, 16> wTq;
+        std::memcpy(wTq.data(), one[0].wTq, sizeof(one[0].wTq));
+        const bool ok = rc == ORCVIO_OK && one[0].init_status == 1;
+        if (init) *init = one[0];
+        return std::make_tuple(ok, wTq);
+    }
+
     // every object of a frame in ONE launch; returns the call's status, objectstates[k].lm_status the per-object one
+    // initialize_on_device: the start is not objectstates[k].object_pose but single_object_initialization's, found in the SAME call
+    // (orcvio_msckf_object_init_lm: one upload, two launches, one wait); `inits`, if given, receives what object_initialization returns.
+    // An object that could not be initialised has lm_status 0 and keeps its state.
     int levenberg_marquardt(const std::vector<const ObjectFeatureTrack*>& feats, std::vector<ObjectState>& objectstates,
-                            const bool use_left_perturbation_flag, const int use_new_bbox_residual_flag) {
+                            const bool use_left_perturbation_flag, const int use_new_bbox_residual_flag,
+                            const bool initialize_on_device = false, std::vector<ObjectInit>* inits = nullptr) {
         const size_t n = feats.size();
         if (objectstates.size() != n) return ORCVIO_ERR_INVALID;
         orcvio_object_lm_config cfg;
@@ -1096,7 +1175,18 @@ class MsckfBackend {
             results[k] = orcvio_object_lm_result{};
             results[k].wTo = out[k].data(); results[k].shape = out[k].data() + 16; results[k].kps = out[k].data() + 19;
         }
-        const int rc = orcvio_msckf_object_lm(h_, &cfg, tracks.data(), priors.data(), (int32_t)n, results.data());
+        int rc;
+        if (initialize_on_device) {
+            const orcvio_object_init_config icfg{object_init_pose_form, object_init_min_obs, object_init_min_kps};
+            std::vector<ObjectInit> local;
+            std::vector<ObjectInit>& oi = inits ? *inits : local;
+            std::vector<orcvio_object_init_result> ires;
+            object_init_results(feats, oi, ires);
+            rc = orcvio_msckf_object_init_lm(h_, &icfg, &cfg, tracks.data(), priors.data(), (int32_t)n, ires.data(), results.data());
+            object_init_finish(rc, ires, oi);
+        } else {
+            rc = orcvio_msckf_object_lm(h_, &cfg, tracks.data(), priors.data(), (int32_t)n, results.data());
+        }
         for (size_t k = 0; k < n; ++k) {
             ObjectState& o = objectstates[k];
             o.status = rc;

@@ -179,6 +179,16 @@ __global__ __launch_bounds__(OBJ_LM_NT) void k_object_lm(ObjLmArgs a) {
     const ObjLmTrack tr = a.tracks[o];
     const int K = tr.K;
     const double* __restrict__ in = a.in;
+    if (tr.pad != 0) {   // the skip word of orcvio_msckf_object_init_lm: no start, no iteration -- the identity, the means, status 0
+        double* out = a.out + (size_t)o * OBJ_LM_OUT;
+        for (int i = tid; i < OBJ_LM_OUT; i += OBJ_LM_NT) {
+            double v = 0.0;
+            if (i < 16) v = (i % 5 == 0) ? 1.0 : 0.0;
+            else if (i < 19 + 3 * K) v = in[tr.off + 3 + 3 * K + i];
+            out[i] = v;
+        }
+        return;          // (workgroup-uniform)
+    }
     for (int i = tid; i < OBJ_LM_STATE; i += OBJ_LM_NT) {
         double v = 0.0;
         if (i < 16) v = in[tr.off + i];

@@ -18,7 +18,7 @@ namespace orcvio_amd {
 struct ObjLmTrack {             // one object of the launch (offset in doubles into the staged input block)
     int K, F;
     int off;                    // wTo 16 | shape 3 | kps 3K | mean_shape 3 | mean_kps 3K | frame_wTc 16F | frame_zs 2KF | frame_bbox 4F
-    int pad;
+    int pad;                    // the skip word: 0 from the host; k_object_init stores 1 where k_object_lm must not optimise
 };
 
 inline size_t obj_lm_track_doubles(int K, int F) { return 22 + (size_t)6 * K + (size_t)F * (20 + 2 * K); }
