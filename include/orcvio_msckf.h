@@ -497,7 +497,7 @@ int32_t orcvio_msckf_object_rows_eval(orcvio_msckf_handle* h, const orcvio_objec
  * finite or a pivot of the damped system is not positive (the last accepted state is returned).  A keypoint detected in no frame
  * has only its regulariser and stays at its mean (it needs residual_weights[2] > 0).
  *
- * Limits: 1 <= K <= 16 (K = 0, the bbox-only extension, is refused: the reference's lite mode is another functor), 1 <= F <= 128,
+ * Limits: 1 <= K <= 16 (K = 0 is refused here: the reference's lite mode is another functor, orcvio_msckf_object_lm_lite below), 1 <= F <= 128,
  * n_tracks <= the handle's max_features, max_iter 1..100000.  A violation or a non-finite input (start, prior, camera pose, bbox,
  * config) returns ORCVIO_ERR_INVALID / ORCVIO_ERR_CAPACITY before anything is enqueued.  A per-object status other than 1 is NOT an
  * error of the call.  Synchronous: one launch, one wait; staging of its own -- neither the resident covariance nor the arena of an
@@ -592,6 +592,84 @@ int32_t orcvio_msckf_object_init_lm(orcvio_msckf_handle* h, const orcvio_object_
                                     const orcvio_object_lm_config* lm_cfg, const orcvio_object_track* tracks,
                                     const orcvio_object_lm_prior* priors, int32_t n_tracks,
                                     orcvio_object_init_result* init_results, orcvio_object_lm_result* lm_results);
+
+/* ---- the LITE object mapper: bbox-only tracks (n_keypoints = 0), the reference's use_bbox_only_flag branch ----
+ * Replaces ObjectFeatureInitializer::single_object_initialization_lite (src/obj/ObjectFeatureInitializer.cpp:495-584) and
+ * single_levenberg_marquardt_lite (:442-493, the ObjectLMLite functor: src/obj/ObjectLMLite.cpp) for every object of a frame at once.
+ * What comes back goes into orcvio_msckf_update_object_tracks as a track with n_keypoints = 0.
+ *
+ * The optimiser (orcvio_msckf_object_lm_lite; k_object_lm_lite: one WAVEFRONT per object, no workgroup barrier, no LDS).
+ * Problem (ObjectLMLite::operator(), ObjectLMLite.cpp:389-415; Huber off).  State x = (wTo, shape v): 9 degrees of freedom in the
+ * column order [pose 6 | shape 3]; cost c = |r|^2 over, with F = n_frames,
+ *   residual_weights[0] x the 4 bbox rows of every frame (the rows of orcvio_msckf_object_lm; use_new_bbox_residual 0 / 1 / 2),
+ *   residual_weights[1] x (v - mean_shape), repeated F - 1 times: the reference LITERALLY (include/orcvio/obj/ObjectLMLite.h:288-297,
+ *                         NErrors = 3 (zb.size() - 1) under a "TODO FIXME why -1"), so a one-frame track has no regulariser;
+ *                         reg_every_frame = 1 (opt-in correction, as use_new_bbox_residual = 2 is): F times.
+ * The two weights are in the REFERENCE'S OWN ORDER: ObjectLMLite reads the initialiser's four-vector from index 0, so the bbox rows
+ * get residual_weights(0) and the regulariser residual_weights(1) -- not the (1) and (3) of the full functor.  Every shipped call
+ * site passes ones.  Retraction and iteration: exactly those of orcvio_msckf_object_lm (lambda_0 = 1e-3, the running-maximum
+ * scaling D, pred, the rho rule, status 1..4), on the 9 x 9 system.  The start's wTo must be rigid.
+ * The bbox-only optimum is NOT unique in wTo (the ellipsoid is invariant under the half-turns about its axes); the cost depends on
+ * wTo diag(v^2, -1) wTo^T, which is what two runs can be compared by.
+ * Of a track, n_keypoints (must be 0), n_frames, wTo, shape, frame_wTc and frame_bbox are read; kps, frame_zs and frame_clone are
+ * not and may be NULL.  Of a prior, mean_shape; mean_kps may be NULL.  Of a result, wTo and shape are written; kps may be NULL and is
+ * not written: a lite track has no keypoints (the reference's lite state zeroes its keypoints on the first step,
+ * ObjectLMLite.cpp:74-90, so its object_keypoints_shape_global_frame is the object origin repeated).
+ * Limits: n_keypoints = 0, 1 <= F <= 128, n_tracks <= max_features, max_iter 1..100000; a violation, a null pointer or a non-finite
+ * pose, box, mean or config value returns ORCVIO_ERR_INVALID / ORCVIO_ERR_CAPACITY before anything is enqueued.  A batch equals one
+ * object per call bit for bit.  Synchronous, on the optimiser's own staging. */
+typedef struct orcvio_object_lite_config {
+    int32_t use_left_perturbation, use_new_bbox_residual;
+    double  residual_weights[2];    /* bbox rows, shape regulariser */
+    int32_t reg_every_frame;        /* 0: F - 1 repeats of the regulariser (the reference); 1: F */
+    int32_t max_iter;
+    double  ptol;
+} orcvio_object_lite_config;
+
+/* weights 1, 1; reg_every_frame 0; max_iter 60; ptol 1e-18; left perturbation; the old bbox residual */
+void orcvio_msckf_object_lite_config_default(orcvio_object_lite_config* cfg);
+
+int32_t orcvio_msckf_object_lm_lite(orcvio_msckf_handle* h, const orcvio_object_lite_config* cfg,
+                                    const orcvio_object_track* tracks, const orcvio_object_lm_prior* priors,
+                                    int32_t n_tracks, orcvio_object_lm_result* results);
+
+/* The start (orcvio_msckf_object_init_lite; k_object_init_lite: one thread per object), from the FIRST frame alone:
+ * (R_GtoA, p_AinG) = frame 0's camera, A = diag((mean_shape o bbox_scale)^2), the four lines l of frame 0's box in the scale
+ * poly2lineh(bbox2poly(.)) gives them (the bbox rows' lines; the ratio is not invariant to a per-line scaling), b = (cx, cy, 1) the
+ * box's centre, B = R_GtoA:
+ *   d = 1 / sqrt( b^T (sum l l^T) b / sum l^T B A B^T l ),   wPq = d B^T b + p_AinG,   rotation = identity.
+ * pose_form as in orcvio_msckf_object_init: 1 = poseSE32SE2 as shipped (on an identity rotation: yaw 0, translation (x, y, 0)),
+ * 2 coincides with 1 here, 0 keeps the full translation.  status 1, or 4 when wPq is not finite (the reference's allFinite; wTo =
+ * identity).  d is returned with the pose.  Only n_keypoints (must be 0), n_frames, frame_wTc[0], frame_bbox[0] and the mean shape
+ * are read.  Limits and refusals as orcvio_msckf_object_lm_lite's; pose_form outside 0..2 or a non-finite bbox_scale is refused. */
+typedef struct orcvio_object_init_lite_config {
+    int32_t pose_form;
+    double  bbox_scale[3];          /* the reference's empirical_bbox_scale: ones as shipped (.8, .6, .7 commented out for KITTI) */
+} orcvio_object_init_lite_config;
+
+/* pose_form 1, bbox_scale 1, 1, 1 */
+void orcvio_msckf_object_init_lite_config_default(orcvio_object_init_lite_config* cfg);
+
+typedef struct orcvio_object_init_lite_result {
+    double* wTo;                    /* [16] caller-owned */
+    double d;                       /* the depth along the centre ray */
+    int32_t status;                 /* 1 initialised, 4 non-finite */
+} orcvio_object_init_lite_result;
+
+/* mean_shape_per_track [n_tracks]: pointers to [3] */
+int32_t orcvio_msckf_object_init_lite(orcvio_msckf_handle* h, const orcvio_object_init_lite_config* cfg,
+                                      const orcvio_object_track* tracks, const double* const* mean_shape_per_track,
+                                      int32_t n_tracks, orcvio_object_init_lite_result* results);
+
+/* Both in ONE call: packs and uploads once, k_object_init_lite writes each track's start (its wTo and the mean shape: the
+ * reference's LMObjectStateLite start) into the staged block, k_object_lm_lite follows on the same stream, both result blocks come
+ * back in one download behind one wait.  An object whose start failed (status 4) is not optimised: its LM status is 0, its LM
+ * arrays hold the identity and the mean shape, its costs and counters 0.  The tracks' wTo and shape are not read and may be NULL.
+ * Equal, bit for bit, to orcvio_msckf_object_init_lite followed by orcvio_msckf_object_lm_lite from its wTo and the mean shape. */
+int32_t orcvio_msckf_object_init_lm_lite(orcvio_msckf_handle* h, const orcvio_object_init_lite_config* init_cfg,
+                                         const orcvio_object_lite_config* lm_cfg, const orcvio_object_track* tracks,
+                                         const orcvio_object_lm_prior* priors, int32_t n_tracks,
+                                         orcvio_object_init_lite_result* init_results, orcvio_object_lm_result* lm_results);
 
 /* ---- staged, device-resident form (what bench.py times; also the multi-GPU path) ----
  * upload:      copy window / tracks / P to the handle's device buffers (host -> HBM);

@@ -32,6 +32,8 @@ EXPORTS = [
     'orcvio_msckf_increment_state', 'orcvio_msckf_set_option', 'orcvio_msckf_run_local_to',
     'orcvio_msckf_object_rows_eval', 'orcvio_msckf_object_lm', 'orcvio_msckf_object_lm_config_default',
     'orcvio_msckf_object_init', 'orcvio_msckf_object_init_lm', 'orcvio_msckf_object_init_config_default', 'orcvio_msckf_triangulation_config_default', 'orcvio_msckf_triangulate',
+    'orcvio_msckf_object_init_lite', 'orcvio_msckf_object_lm_lite', 'orcvio_msckf_object_init_lm_lite', 'orcvio_msckf_object_lite_config_default',
+    'orcvio_msckf_object_init_lite_config_default',
     'orcvio_msckf_triangulate_uploaded', 'orcvio_msckf_objects_local', 'orcvio_msckf_objects_finish',
     'orcvio_msckf_objects_download', 'orcvio_msckf_cov_set', 'orcvio_msckf_cov_get', 'orcvio_msckf_cov_propagate',
     'orcvio_msckf_cov_augment', 'orcvio_msckf_cov_remove_clones', 'orcvio_msckf_cov_commit', 'orcvio_msckf_cov_prefactor', 'orcvio_msckf_upload_new_features', 'orcvio_msckf_download_new_feature_blocks', 'orcvio_msckf_upload_nuisance_poses',
@@ -104,6 +106,21 @@ class ObjectInitResult(C.Structure):
     _fields_ = [('wTo', _dp), ('kps_world', _dp), ('kp_used', _ip), ('kp_obs', _ip), ('kp_cond', _dp),
                 ('R_kabsch', C.c_double * 9), ('t_kabsch', C.c_double * 3), ('scale', C.c_double), ('sigma', C.c_double * 3),
                 ('n_used', C.c_int32), ('status', C.c_int32)]
+
+
+class ObjectLiteConfig(C.Structure):
+    """orcvio_object_lite_config (include/orcvio_msckf.h)."""
+    _fields_ = [('use_left_perturbation', C.c_int32), ('use_new_bbox_residual', C.c_int32), ('residual_weights', C.c_double * 2),
+                ('reg_every_frame', C.c_int32), ('max_iter', C.c_int32), ('ptol', C.c_double)]
+
+
+class ObjectInitLiteConfig(C.Structure):
+    """orcvio_object_init_lite_config (include/orcvio_msckf.h)."""
+    _fields_ = [('pose_form', C.c_int32), ('bbox_scale', C.c_double * 3)]
+
+
+class ObjectInitLiteResult(C.Structure):
+    _fields_ = [('wTo', _dp), ('d', C.c_double), ('status', C.c_int32)]
 
 
 class ObjectLMMsg(C.Structure):
@@ -1086,6 +1103,133 @@ class MsckfUpdater:
             stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
                               evaluations=int(results[k].evaluations), status=int(results[k].status)))
         return self._object_init_outs(iresults, iouts), tracks, stats
+
+    # ---- the lite (bbox-only) object mapper ------------------------------------------------------------------------------------
+    def _lite_tracks(self, objs, with_start):
+        """Track records with n_keypoints = 0 and only what the lite calls read (kps / frame_zs / frame_clone NULL; wTo and shape
+        too where the start is the device's)."""
+        n = len(objs)
+        arr = (ObjectTrackC * max(n, 1))()
+        keep = []
+        for k, obj in enumerate(objs):
+            wTc = np.ascontiguousarray(np.stack([fr['wTc'] for fr in obj.frames]), dtype=np.float64)
+            bb = np.ascontiguousarray(np.stack([fr['bbox'] for fr in obj.frames]), dtype=np.float64)
+            wTo = np.ascontiguousarray(obj.wTo, dtype=np.float64) if with_start else None
+            shape = np.ascontiguousarray(obj.shape, dtype=np.float64) if with_start else None
+            keep += [wTc, bb, wTo, shape]
+            arr[k] = ObjectTrackC(0, len(obj.frames), _d(wTo), _d(shape), None, _d(wTc), None, _d(bb), None)
+        return arr, keep
+
+    def _lite_config(self, left, new_bbox, weights, reg_every_frame, max_iter, ptol):
+        cfg = ObjectLiteConfig()
+        self.lib.orcvio_msckf_object_lite_config_default.argtypes = [C.POINTER(ObjectLiteConfig)]
+        self.lib.orcvio_msckf_object_lite_config_default.restype = None
+        self.lib.orcvio_msckf_object_lite_config_default(C.byref(cfg))
+        cfg.use_left_perturbation = int(left)
+        cfg.use_new_bbox_residual = int(new_bbox)
+        cfg.residual_weights[:] = [float(w) for w in weights]
+        cfg.reg_every_frame = int(reg_every_frame)
+        if max_iter is not None:
+            cfg.max_iter = int(max_iter)
+        if ptol is not None:
+            cfg.ptol = float(ptol)
+        return cfg
+
+    def _lite_init_config(self, pose_form, bbox_scale):
+        cfg = ObjectInitLiteConfig()
+        self.lib.orcvio_msckf_object_init_lite_config_default.argtypes = [C.POINTER(ObjectInitLiteConfig)]
+        self.lib.orcvio_msckf_object_init_lite_config_default.restype = None
+        self.lib.orcvio_msckf_object_init_lite_config_default(C.byref(cfg))
+        if pose_form is not None:
+            cfg.pose_form = int(pose_form)
+        if bbox_scale is not None:
+            cfg.bbox_scale[:] = [float(v) for v in bbox_scale]
+        return cfg
+
+    @staticmethod
+    def _lite_lm_records(n, mean_shapes, keep):
+        priors = (ObjectLMPrior * max(n, 1))()
+        results = (ObjectLMResult * max(n, 1))()
+        outs = []
+        for k in range(n):
+            ms = np.ascontiguousarray(mean_shapes[k], dtype=np.float64).reshape(3)
+            o = (np.zeros((4, 4)), np.zeros(3))
+            keep.append(ms)
+            outs.append(o)
+            priors[k] = ObjectLMPrior(_d(ms), None)
+            results[k].wTo, results[k].shape, results[k].kps = _d(o[0]), _d(o[1]), None
+        return priors, results, outs
+
+    @staticmethod
+    def _lite_lm_outs(objs, results, outs):
+        """Bbox-only tracks (kps [0][3], the frames shared with the inputs: update_object_tracks takes them as they are) and the statistics."""
+        from . import synth
+        tracks, stats = [], []
+        for k, obj in enumerate(objs):
+            tracks.append(synth.ObjectTrack(wTo=outs[k][0], shape=outs[k][1], kps=np.zeros((0, 3)), frames=obj.frames))
+            stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
+                              evaluations=int(results[k].evaluations), status=int(results[k].status)))
+        return tracks, stats
+
+    def object_lm_lite(self, objs, mean_shapes, left, new_bbox, weights=(1.0, 1.0), reg_every_frame=0, max_iter=None, ptol=None):
+        """orcvio_msckf_object_lm_lite: the 9-dof Levenberg-Marquardt over every bbox-only track of `objs` (synth.ObjectTrack-shaped:
+        wTo and shape are the start, the frames' wTc and bbox are read; kps and zs are ignored) in one launch, one wavefront per
+        object.  weights: (bbox rows, shape regulariser).  Returns (tracks, stats) as object_lm does, the tracks without keypoints."""
+        cfg = self._lite_config(left, new_bbox, weights, reg_every_frame, max_iter, ptol)
+        arr, keep = self._lite_tracks(objs, True)
+        n = len(objs)
+        priors, results, outs = self._lite_lm_records(n, mean_shapes, keep)
+        self.lib.orcvio_msckf_object_lm_lite.argtypes = [C.c_void_p, C.POINTER(ObjectLiteConfig), C.POINTER(ObjectTrackC),
+                                                         C.POINTER(ObjectLMPrior), C.c_int32, C.POINTER(ObjectLMResult)]
+        self.lib.orcvio_msckf_object_lm_lite.restype = C.c_int32
+        rc = self.lib.orcvio_msckf_object_lm_lite(self.h, C.byref(cfg), arr, priors, n, results)
+        if rc != 0:
+            raise MsckfError(rc, 'orcvio_msckf_object_lm_lite')
+        return self._lite_lm_outs(objs, results, outs)
+
+    def object_init_lite(self, objs, mean_shapes, pose_form=None, bbox_scale=None):
+        """orcvio_msckf_object_init_lite: the start pose of every bbox-only track from its first frame's camera and box.  Returns per
+        object dict(wTo, d, status)."""
+        cfg = self._lite_init_config(pose_form, bbox_scale)
+        arr, keep = self._lite_tracks(objs, False)
+        n = len(objs)
+        ms = [np.ascontiguousarray(m, dtype=np.float64).reshape(3) for m in mean_shapes]
+        ptrs = (_dp * max(n, 1))(*[_d(m) for m in ms])
+        results = (ObjectInitLiteResult * max(n, 1))()
+        outs = [np.zeros((4, 4)) for _ in range(n)]
+        for k in range(n):
+            results[k].wTo = _d(outs[k])
+        self.lib.orcvio_msckf_object_init_lite.argtypes = [C.c_void_p, C.POINTER(ObjectInitLiteConfig), C.POINTER(ObjectTrackC), C.POINTER(_dp),
+                                                           C.c_int32, C.POINTER(ObjectInitLiteResult)]
+        self.lib.orcvio_msckf_object_init_lite.restype = C.c_int32
+        rc = self.lib.orcvio_msckf_object_init_lite(self.h, C.byref(cfg), arr, ptrs, n, results)
+        if rc != 0:
+            raise MsckfError(rc, 'orcvio_msckf_object_init_lite')
+        return [dict(wTo=outs[k], d=float(results[k].d), status=int(results[k].status)) for k in range(n)]
+
+    def object_init_lm_lite(self, objs, mean_shapes, left, new_bbox, weights=(1.0, 1.0), reg_every_frame=0, max_iter=None, ptol=None,
+                            pose_form=None, bbox_scale=None):
+        """orcvio_msckf_object_init_lm_lite: object_init_lite and object_lm_lite from its start (the pose, the mean shape) in ONE call.
+        Returns (inits, tracks, stats); an object whose start failed has LM status 0, the identity and the mean shape."""
+        icfg = self._lite_init_config(pose_form, bbox_scale)
+        cfg = self._lite_config(left, new_bbox, weights, reg_every_frame, max_iter, ptol)
+        arr, keep = self._lite_tracks(objs, False)
+        n = len(objs)
+        priors, results, outs = self._lite_lm_records(n, mean_shapes, keep)
+        iresults = (ObjectInitLiteResult * max(n, 1))()
+        iouts = [np.zeros((4, 4)) for _ in range(n)]
+        for k in range(n):
+            iresults[k].wTo = _d(iouts[k])
+        self.lib.orcvio_msckf_object_init_lm_lite.argtypes = [C.c_void_p, C.POINTER(ObjectInitLiteConfig), C.POINTER(ObjectLiteConfig),
+                                                              C.POINTER(ObjectTrackC), C.POINTER(ObjectLMPrior), C.c_int32,
+                                                              C.POINTER(ObjectInitLiteResult), C.POINTER(ObjectLMResult)]
+        self.lib.orcvio_msckf_object_init_lm_lite.restype = C.c_int32
+        rc = self.lib.orcvio_msckf_object_init_lm_lite(self.h, C.byref(icfg), C.byref(cfg), arr, priors, n, iresults, results)
+        if rc != 0:
+            raise MsckfError(rc, 'orcvio_msckf_object_init_lm_lite')
+        inits = [dict(wTo=iouts[k], d=float(iresults[k].d), status=int(iresults[k].status)) for k in range(n)]
+        tracks, stats = self._lite_lm_outs(objs, results, outs)
+        return inits, tracks, stats
 
     def objects_local_tracks(self, flags, n_clones, objs, P, R_b2c, t_c_b, obj_left, new_bbox, vio_left, fix_D=False):
         """The first half of update_object_tracks alone: the rows of the tracks evaluated on the device and compressed into the handle's

@@ -1208,6 +1208,131 @@ class MsckfBackend {
         return rc == ORCVIO_OK && objectstate.lm_status == 1;
     }
 
+    // ---- ObjectInitNode with use_bbox_only_flag: ObjectFeatureInitializer::single_object_initialization_lite and
+    // single_levenberg_marquardt_lite (src/obj/ObjectFeatureInitializer.cpp:495-584, :442-493; ObjectInitNode.cpp:1115-1166) ----------
+    // The lite mapper on the device (orcvio_msckf_object_init_lite / _object_lm_lite / _object_init_lm_lite).  Of a track only
+    // frame_wTc and frame_bbox are read (n_keypoints and frame_zs are ignored: a lite track has no keypoints, object_keypoints comes
+    // back empty).  The weights are the initializer's four-vector read from index 0 as ObjectLMLite reads it: residual_weights[0] on
+    // the bbox rows, [1] on the shape regulariser, which repeats F - 1 times unless object_lite_reg_every_frame.
+    struct ObjectInitLite {
+        double wTq[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // the identity unless init_status == 1
+        double d = 0;                                                       // the depth along the first box's centre ray
+        int init_status = 0, status = ORCVIO_OK;
+    };
+    double object_lite_bbox_scale[3] = {1, 1, 1};   // the reference's empirical_bbox_scale
+    int object_lite_reg_every_frame = 0;
+
+    bool object_lite_tracks(const std::vector<const ObjectFeatureTrack*>& feats, const std::vector<ObjectState>* starts,
+                            std::vector<orcvio_object_track>& tracks) const {
+        const size_t n = feats.size();
+        tracks.assign(n, orcvio_object_track{});
+        if (object_mean_shape.size() != 3) return false;
+        for (size_t k = 0; k < n; ++k) {
+            const ObjectFeatureTrack& f = *feats[k];
+            const int F = f.frames();
+            if (f.frame_bbox.size() != (size_t)4 * F || f.frame_wTc.size() != (size_t)16 * F) return false;
+            tracks[k] = orcvio_object_track{0, F, starts ? (*starts)[k].object_pose : nullptr, starts ? object_mean_shape.data() : nullptr, nullptr,
+                                            f.frame_wTc.data(), nullptr, f.frame_bbox.data(), nullptr};
+        }
+        return true;
+    }
+
+    // every object of a frame in ONE launch; returns the call's status, inits[k].init_status the per-object one
+    int object_initialization_lite(const std::vector<const ObjectFeatureTrack*>& feats, std::vector<ObjectInitLite>& inits) {
+        const size_t n = feats.size();
+        inits.assign(n, ObjectInitLite{});
+        std::vector<orcvio_object_track> tracks;
+        if (!object_lite_tracks(feats, nullptr, tracks)) {
+            for (ObjectInitLite& o : inits) o.status = ORCVIO_ERR_INVALID;   // (nothing was launched)
+            return ORCVIO_ERR_INVALID;
+        }
+        const orcvio_object_init_lite_config icfg{object_init_pose_form, {object_lite_bbox_scale[0], object_lite_bbox_scale[1], object_lite_bbox_scale[2]}};
+        std::vector<const double*> mean(n, object_mean_shape.data());
+        std::vector<orcvio_object_init_lite_result> res(n);
+        for (size_t k = 0; k < n; ++k) res[k].wTo = inits[k].wTq;
+        const int rc = orcvio_msckf_object_init_lite(h_, &icfg, tracks.data(), mean.data(), (int32_t)n, res.data());
+        for (size_t k = 0; k < n; ++k) {
+            inits[k].status = rc;
+            if (rc == ORCVIO_OK) { inits[k].d = res[k].d; inits[k].init_status = res[k].status; }
+        }
+        return rc;
+    }
+    // the reference's call: (init_success_flag, wTq)
+    std::tuple<bool, std::array<double, 16>> single_object_initialization_lite(const ObjectFeatureTrack& feat, ObjectInitLite* init = nullptr) {
+        std::vector<ObjectInitLite> one;
+        const int rc = object_initialization_lite({&feat}, one);
+        std::array<double, 16> wTq;
+        std::memcpy(wTq.data(), one[0].wTq, sizeof(one[0].wTq));
+        if (init) *init = one[0];
+        return std::make_tuple(rc == ORCVIO_OK && one[0].init_status == 1, wTq);
+    }
+
+    // every object of a frame in ONE launch, as levenberg_marquardt; initialize_on_device: the start is
+    // single_object_initialization_lite's, found in the SAME call (orcvio_msckf_object_init_lm_lite).  An object whose start failed
+    // has lm_status 0 and keeps its state.
+    int levenberg_marquardt_lite(const std::vector<const ObjectFeatureTrack*>& feats, std::vector<ObjectState>& objectstates,
+                                 const bool use_left_perturbation_flag, const int use_new_bbox_residual_flag,
+                                 const bool initialize_on_device = false, std::vector<ObjectInitLite>* inits = nullptr) {
+        const size_t n = feats.size();
+        if (objectstates.size() != n) return ORCVIO_ERR_INVALID;
+        orcvio_object_lite_config cfg;
+        orcvio_msckf_object_lite_config_default(&cfg);
+        cfg.use_left_perturbation = use_left_perturbation_flag ? 1 : 0;
+        cfg.use_new_bbox_residual = use_new_bbox_residual_flag;
+        cfg.residual_weights[0] = residual_weights[0]; cfg.residual_weights[1] = residual_weights[1];
+        cfg.reg_every_frame = object_lite_reg_every_frame;
+        cfg.max_iter = object_lm_max_iter;
+        cfg.ptol = object_lm_ptol;
+        std::vector<orcvio_object_track> tracks;
+        if (!object_lite_tracks(feats, initialize_on_device ? nullptr : &objectstates, tracks)) {
+            for (ObjectState& o : objectstates) o.status = ORCVIO_ERR_INVALID;   // (nothing was launched)
+            return ORCVIO_ERR_INVALID;
+        }
+        std::vector<orcvio_object_lm_prior> priors(n, orcvio_object_lm_prior{object_mean_shape.data(), nullptr});
+        std::vector<orcvio_object_lm_result> results(n);
+        std::vector<std::array<double, 19>> out(n);
+        for (size_t k = 0; k < n; ++k) {
+            out[k].fill(0.0);
+            results[k] = orcvio_object_lm_result{};
+            results[k].wTo = out[k].data(); results[k].shape = out[k].data() + 16;
+        }
+        int rc;
+        if (initialize_on_device) {
+            const orcvio_object_init_lite_config icfg{object_init_pose_form, {object_lite_bbox_scale[0], object_lite_bbox_scale[1], object_lite_bbox_scale[2]}};
+            std::vector<ObjectInitLite> local;
+            std::vector<ObjectInitLite>& oi = inits ? *inits : local;
+            oi.assign(n, ObjectInitLite{});
+            std::vector<orcvio_object_init_lite_result> ires(n);
+            for (size_t k = 0; k < n; ++k) ires[k].wTo = oi[k].wTq;
+            rc = orcvio_msckf_object_init_lm_lite(h_, &icfg, &cfg, tracks.data(), priors.data(), (int32_t)n, ires.data(), results.data());
+            for (size_t k = 0; k < n; ++k) {
+                oi[k].status = rc;
+                if (rc == ORCVIO_OK) { oi[k].d = ires[k].d; oi[k].init_status = ires[k].status; }
+            }
+        } else {
+            rc = orcvio_msckf_object_lm_lite(h_, &cfg, tracks.data(), priors.data(), (int32_t)n, results.data());
+        }
+        for (size_t k = 0; k < n; ++k) {
+            ObjectState& o = objectstates[k];
+            o.status = rc;
+            if (rc != ORCVIO_OK) continue;
+            o.cost0 = results[k].cost0; o.cost = results[k].cost;
+            o.iterations = results[k].iterations; o.evaluations = results[k].evaluations; o.lm_status = results[k].status;
+            if (o.lm_status != 1) continue;   // (the reference leaves objectstate as it was when the LM did not succeed, :476-480)
+            std::memcpy(o.object_pose, out[k].data(), sizeof(o.object_pose));
+            std::memcpy(o.ellipsoid_shape, out[k].data() + 16, sizeof(o.ellipsoid_shape));
+            o.object_keypoints.clear();
+        }
+        return rc;
+    }
+    bool single_levenberg_marquardt_lite(const ObjectFeatureTrack& feat, ObjectState& objectstate, const bool use_left_perturbation_flag,
+                                         const int use_new_bbox_residual_flag) {
+        std::vector<ObjectState> st(1, objectstate);
+        const int rc = levenberg_marquardt_lite({&feat}, st, use_left_perturbation_flag, use_new_bbox_residual_flag);
+        objectstate = st[0];
+        return rc == ORCVIO_OK && objectstate.lm_status == 1;
+    }
+
     // ---- one frame: System::imageCallback's processFeatures update followed by processObjects (System.cpp:548-554) ----------
     // With the covariance resident and one GPU this is ONE library call (orcvio_msckf_io_update_frame): the object tracks'
     // compression runs beside the feature update's solve.  `eval_flags` carries the extrinsics the object rows are evaluated
