@@ -1003,6 +1003,38 @@ int32_t orcvio_msckf_triangulate(orcvio_msckf_handle* h, const orcvio_triangulat
 int32_t orcvio_msckf_triangulate_uploaded(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg,
                                           const int32_t* is_initialized, void* stream);
 
+/* The same INSIDE the in-place update: arms the NEXT update on the open arena (orcvio_msckf_io_update, _io_submit, or the
+ * first update of orcvio_msckf_io_step_frame / _io_step_frame_ex) to triangulate its own tracks on the device, on the
+ * update's stream behind the pull of the arena and in front of the first kernel that reads a position -- what
+ * OrcVIO::removeLostFeatures does before it updates (src/orcvio.cpp:2258-2270, :2296-2312, :2325-2327).  Call it between
+ * orcvio_msckf_io_begin and that update.  The arming holds for ONE update: the update consumes it, a later update on the same
+ * arena is a plain one unless the call is made again; a new orcvio_msckf_io_begin drops it.
+ *   mode[j]  ORCVIO_TRI_KEEP          the arena's p_w[j] is used as it is (the reference's is_initialized feature, :2260)
+ *            ORCVIO_TRI_ALL           checkMotion + initializePosition over all listed observations (a lost feature)
+ *            ORCVIO_TRI_ALL_BUT_LAST  the same over all but the LAST listed observation (if_tracked_now / curr_id,
+ *                                     include/orcvio/feat/feature.hpp:358-359, :414): the newest observation enters the update,
+ *                                     not the triangulation; a track with fewer than two observations left is ORCVIO_TRI_NO_MOTION
+ *   mode == NULL: every track ORCVIO_TRI_ALL.
+ * The arena's p_w of a track that is not KEEP is never read (it may hold anything, NaN included).  A track that fails takes
+ * no part in the update, as behind orcvio_msckf_triangulate_uploaded: accept = 0, gamma = NaN, its rows count nowhere.
+ * out: pointers into pinned host memory of the handle, filled when the update's own wait returns (no second wait, no
+ * copy call) and valid until the next armed update or orcvio_msckf_destroy.  A KEEP track reports valid = 1, flags = 0, its
+ * p_w echoed, NaN in inv_param and cost.
+ * ORCVIO_ERR_INVALID, nothing armed and *out untouched: no open arena, a pending orcvio_msckf_io_submit, a mode outside
+ * 0..2, a NULL or non-finite config (or negative iteration counts), an object update in the arena, a communicator on
+ * the handle.  The prune update of the frame calls still takes its positions from the caller
+ * (initializePosition_AssignAnchor, :2782-2791, uses observations the prune tracks do not list). */
+enum { ORCVIO_TRI_KEEP = 0, ORCVIO_TRI_ALL = 1, ORCVIO_TRI_ALL_BUT_LAST = 2 };
+typedef struct orcvio_msckf_io_tri {
+    const int32_t* valid;     /* [F] 1: the track has a position (given or triangulated) and took part in the update */
+    const int32_t* flags;     /* [F] ORCVIO_TRI_NO_MOTION / _NEG_DEPTH / _BIG_PROJ bits                              */
+    const double* p_w;        /* [F][3] */
+    const double* inv_param;  /* [F][3] */
+    const double* cost;       /* [F]    */
+} orcvio_msckf_io_tri;
+int32_t orcvio_msckf_io_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg,
+                                    const int32_t* mode /* [F] or NULL */, orcvio_msckf_io_tri* out);
+
 /* ---- Device-resident covariance ------------------------------------------
  * The three places besides the update where the reference touches state_cov, on a copy of P that stays in HBM, so that
  * P does not cross PCIe every frame.  n = leg_dim + 6 * (clones in the window); no EKF-SLAM / nuisance states.

@@ -44,7 +44,7 @@ EXPORTS = [
     'orcvio_msckf_comm_unique_id', 'orcvio_msckf_comm_init', 'orcvio_msckf_comm_destroy', 'orcvio_msckf_comm_info',
     'orcvio_msckf_run_update_sharded', 'orcvio_msckf_update_features_sharded', 'orcvio_msckf_update_object_tracks_sharded',
     'orcvio_msckf_comm_barrier', 'orcvio_msckf_comm_allreduce_max', 'orcvio_msckf_io_begin', 'orcvio_msckf_io_update',
-    'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect',
+    'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect', 'orcvio_msckf_io_triangulate',
     'orcvio_msckf_objects_refined', 'orcvio_msckf_counters', 'orcvio_msckf_comm_details', 'orcvio_msckf_profile_sharded',
     'orcvio_msckf_io_step_frame', 'orcvio_msckf_io_step_frame_ex', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
     'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame',
@@ -153,6 +153,14 @@ class TriangulationConfig(C.Structure):
 
 class TriangulationResult(C.Structure):
     _fields_ = [('valid', _ip), ('p_w', _dp), ('inv_param', _dp), ('flags', _ip), ('cost', _dp)]
+
+
+class MsckfIoTri(C.Structure):
+    _fields_ = [('valid', C.POINTER(C.c_int32)), ('flags', C.POINTER(C.c_int32)), ('p_w', C.POINTER(C.c_double)),
+                ('inv_param', C.POINTER(C.c_double)), ('cost', C.POINTER(C.c_double))]
+
+
+TRI_KEEP, TRI_ALL, TRI_ALL_BUT_LAST = 0, 1, 2
 
 
 class Zupt(C.Structure):
@@ -267,6 +275,7 @@ def _bind(lib):
     lib.orcvio_msckf_io_begin.argtypes = [C.c_void_p, C.POINTER(MsckfFlags), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MsckfIo)]
     lib.orcvio_msckf_io_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip]
     lib.orcvio_msckf_io_submit.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.orcvio_msckf_io_triangulate.argtypes = [C.c_void_p, C.POINTER(TriangulationConfig), _ip, C.POINTER(MsckfIoTri)]
     lib.orcvio_msckf_io_collect.argtypes = [C.c_void_p, _ip]
     lib.orcvio_msckf_io_step_frame.argtypes = [C.c_void_p, C.POINTER(FrameStep), C.POINTER(FrameResult)]
     lib.orcvio_msckf_io_step_frame_ex.argtypes = [C.c_void_p, C.POINTER(FrameStep), C.POINTER(FrameEvents), C.POINTER(FrameResultEx)]
@@ -732,6 +741,20 @@ class MsckfUpdater:
         stats = np.zeros(8, dtype=np.int32)
         self._chk(self.lib.orcvio_msckf_io_update(self.h, int(bool(want_P)), int(bool(commit)), _i(stats)), 'orcvio_msckf_io_update')
         return stats
+
+    def io_triangulate(self, cfg=None, mode=None):
+        """orcvio_msckf_io_triangulate: arms the next update on the open arena (io_update, io_submit, the first update of
+        io_step_frame / io_step_frame_ex) to triangulate its tracks on the device.  mode: None (every track TRI_ALL) or [F] of TRI_KEEP /
+        TRI_ALL / TRI_ALL_BUT_LAST.  Returns numpy VIEWS of the handle's pinned block (valid, flags, p_w, solution, cost), filled when that
+        update returns.  cfg: as for triangulate(); cfg=False passes NULL (a refusal)."""
+        c = None if cfg is False else self._tri_config(cfg)
+        md = None if mode is None else np.ascontiguousarray(mode, dtype=np.int32)
+        out = MsckfIoTri()
+        self._chk(self.lib.orcvio_msckf_io_triangulate(self.h, None if c is None else C.byref(c), _i(md), C.byref(out)), 'orcvio_msckf_io_triangulate')
+        F = self.F
+        view = lambda ptr, shape: np.ctypeslib.as_array(ptr, shape=shape)
+        return dict(valid=view(out.valid, (max(F, 1),))[:F], flags=view(out.flags, (max(F, 1),))[:F], p_w=view(out.p_w, (max(F, 1), 3))[:F],
+                    solution=view(out.inv_param, (max(F, 1), 3))[:F], cost=view(out.cost, (max(F, 1),))[:F])
 
     def io_submit(self, want_P=True, commit=False):
         """orcvio_msckf_io_submit: the update on what stands in the arena is launched; io_collect() waits for it."""
@@ -1317,7 +1340,7 @@ class MsckfUpdater:
         return P
 
     def io_step_frame_ex(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
-                         n_feature_states=0, lost=(), changes=(), R_b2c=None, t_c_b=None, literal_3d=0, raise_on_refusal=True):
+                         n_feature_states=0, lost=(), changes=(), R_b2c=None, t_c_b=None, literal_3d=0, raise_on_refusal=True, triangulate=None):
         """orcvio_msckf_io_step_frame_ex: io_step_frame plus the frame's feature events.  `win` and set_extra_states are those AFTER the
         removals; lost: slots in feature_states before the call (ascending), n_feature_states their count before the removals;
         changes: objects with slot (after the removals), old, new, p_w, p_fej; R_b2c / t_c_b: the IMU's current extrinsics.
@@ -1334,16 +1357,22 @@ class MsckfUpdater:
         tb = None if t_c_b is None else np.ascontiguousarray(t_c_b, dtype=np.float64).reshape(3)
         ev = FrameEvents(int(idp_dim), int(literal_3d), int(n_feature_states), _i(ls) if len(ls) else None, len(ls), arr if k else None, k,
                          _d(Rb), _d(tb))
-        return self.io_step_frame(win, Phi, Q, augment, slam, idp_dim, prune, prune_apply_dx, remove, raise_on_refusal, _events=(ev, k, (ls, arr, Rb, tb)))
+        return self.io_step_frame(win, Phi, Q, augment, slam, idp_dim, prune, prune_apply_dx, remove, raise_on_refusal, _events=(ev, k, (ls, arr, Rb, tb)),
+                                  triangulate=triangulate)
 
     def io_step_frame(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
-                      raise_on_refusal=True, _events=None):
+                      raise_on_refusal=True, _events=None, triangulate=None):
         """orcvio_msckf_io_step_frame: ONE filter frame on the resident covariance -- propagation, augmentation, the update on `win`'s
         tracks (+ the in-state features `slam`), the prune update on `prune`'s tracks (a synth.Window sharing win's poses), the
         marginalisation of `remove`.  Returns dict(dx, gamma, accept, stats, prune_dx, prune_gamma, prune_accept, prune_stats, n_after,
-        status_first, status_prune, repaired) with copies of the results."""
+        status_first, status_prune, repaired) with copies of the results.  triangulate: None, True or dict(cfg=, mode=) -- the first
+        update triangulates its tracks on the device (io_triangulate); the dict then has tri = copies of valid, flags, p_w, solution, cost."""
         io = self.io_begin(win.flags, win.N, win.F, int(win.obs_ptr[-1]), with_P=2)
         self.io_fill(io, win, with_P=False)
+        tri = None
+        if triangulate:
+            targ = triangulate if isinstance(triangulate, dict) else {}
+            tri = self.io_triangulate(targ.get('cfg'), targ.get('mode'))
         keep = []
         st = FrameStep()
         st.leg_dim = int(win.flags.leg_dim)
@@ -1390,6 +1419,8 @@ class MsckfUpdater:
             par = arr(rex.new_param, 3 * k, np.float64)
             extra = dict(new_param=None if par is None else par.reshape(k, 3), new_inv_depth=arr(rex.new_inv_depth, k, np.float64),
                          status_changes=int(rex.status_changes))
+        if tri is not None:
+            extra['tri'] = {k: v.copy() for k, v in tri.items()}
         return dict(**extra, rc=rc, dx=arr(res.dx, n, np.float64), gamma=arr(res.gamma, win.F, np.float64), accept=arr(res.accept, win.F, np.int32),
                     stats=np.array(res.stats[:], dtype=np.int32), prune_dx=arr(res.prune_dx, n, np.float64),
                     prune_gamma=arr(res.prune_gamma, F2, np.float64), prune_accept=arr(res.prune_accept, F2, np.int32),

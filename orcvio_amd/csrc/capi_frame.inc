@@ -192,6 +192,7 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     if (!h || !res_f || !res_o || !oflags || !efl || n_tracks < 0) { g_last_error = std::string(who) + ": null argument"; return ORCVIO_ERR_INVALID; }
     if (h->io_submitted) { g_last_error = std::string(who) + ": an update submitted with orcvio_msckf_io_submit has not been collected"; return ORCVIO_ERR_INVALID; }
     if (!h->io_open || h->io_with_P) { g_last_error = std::string(who) + ": call orcvio_msckf_io_begin with with_P = 0 first (the frame runs on the resident covariance)"; return ORCVIO_ERR_INVALID; }
+    if (h->tri_armed) { g_last_error = std::string(who) + ": the arena is armed by orcvio_msckf_io_triangulate (io_update, io_submit and the io_step_frame calls carry it; open the arena again for this call)"; return ORCVIO_ERR_INVALID; }
     if (res_f->P_out || res_f->K || res_f->G || res_f->H_thin || res_f->r_thin) { g_last_error = std::string(who) + ": the feature half returns dx, gamma, accept and stats (P+ stays resident)"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     static const bool overlap = [] { const char* e = getenv("ORCVIO_FRAME_OVERLAP"); return !e || atoi(e) != 0; }();   // 0: the two calls in sequence

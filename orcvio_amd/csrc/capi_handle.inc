@@ -244,6 +244,8 @@ static void free_all(orcvio_msckf_handle* h) {
     if (h->h_lm) (void)hipHostFree(h->h_lm);
     if (h->d_lm) (void)hipFree(h->d_lm);
     if (h->h_stage2) (void)hipHostFree(h->h_stage2);
+    if (h->h_tri) (void)hipHostFree(h->h_tri);
+    if (h->d_tri_words) (void)hipFree(h->d_tri_words);
     if (h->d_in2) (void)hipFree(h->d_in2);
     if (h->d_step_words) (void)hipFree(h->d_step_words);
     if (h->h_evt) (void)hipHostFree(h->h_evt);

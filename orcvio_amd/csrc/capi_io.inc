@@ -149,11 +149,33 @@ int32_t orcvio_msckf_download(orcvio_msckf_handle* h, orcvio_msckf_result* res) 
 // ONE graph launch per update: k_ingest (pinned arena -> HBM) -> the update's kernels -> k_epilogue (results -> host-coherent
 // memory, [the commit of P+ and its square-root factor], then the flag).  No copy-engine transfer, no stream
 // synchronisation: the calling thread spins on the flag.
+static int launch_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg, bool have_init, bool mark_skip, hipStream_t s,
+                              bool io, bool with_mode);   // (capi_state.inc)
+// An update armed by orcvio_msckf_io_triangulate: from here on it runs as behind orcvio_msckf_triangulate_uploaded (d_skip is read by
+// every form of the front end).  Called behind upload_finalize, which resets both words; the arming is consumed.
+static inline void tri_consume(orcvio_msckf_handle* h, UpdateCall& c) {
+    if (!h->tri_armed) return;
+    h->tri_armed = false;
+    c.tri = true;
+    h->skip_active = true; h->tri_live = true;
+    // nothing but the tracks in this update: without a single valid one it is refused on the device the way a refused first update
+    // refuses the frame's second (info_also: P and its factor stay, bit for bit) -- and is no error: stats[3] = 0
+    h->tri_refuse_empty = h->F > 0 && h->ekf_F == 0 && h->dense_rows == 0 && h->new_F == 0 && !c.info_also;
+    if (h->tri_refuse_empty) c.info_also = h->d_tri_words;
+}
 static unsigned long long io_signature(const orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool commit, const UpdateCall& c, bool finpub = false) {
     unsigned long long sig = launch_signature(h, s, h->h_stage_dev, (long)(0x100 | (want_P ? 1 : 0) | (commit ? 2 : 0) | (finpub ? 4 : 0)), c);
     auto mix = [&](unsigned long long v) { sig = (sig ^ v) * 1099511628211ull; };
     mix((unsigned long long)upload_bytes(h)); mix((unsigned long long)h->io_poses); mix((unsigned long long)(size_t)h->d_Stmp); mix((unsigned long long)(size_t)h->d_Pres);
     mix(h->factor_opt); mix((unsigned long long)h->outs_small); mix((unsigned long long)(size_t)h->d_Ptmp); mix(h->finpub_opt);
+    mix(c.tri); mix(h->tri_live);
+    if (c.tri) {   // (a captured k_triangulate has the config by value and the mode pointer frozen in it)
+        const orcvio_triangulation_config& t = h->tri_cfg;
+        const double d[6] = {t.translation_threshold, t.huber_epsilon, t.estimation_precision, t.initial_damping, t.cost_threshold, t.init_final_dist_threshold};
+        for (double v : d) { unsigned long long bits; std::memcpy(&bits, &v, 8); mix(bits); }
+        mix((unsigned long long)t.outer_loop_max_iteration); mix((unsigned long long)t.inner_loop_max_iteration);
+        mix(h->tri_with_mode); mix((unsigned long long)(size_t)h->h_tri_dev); mix((unsigned long long)(size_t)c.info_also);
+    }
     return sig;
 }
 
@@ -177,7 +199,10 @@ static int io_enqueue(orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool c
     h->last_finpub_commit = c.fin_pub && commit;
     // inputs: the derived index arrays at the head of the arena (the caller-written part behind them went ahead: ingest_raw)
     int rc = ORCVIO_OK;
-    if (!c.already_ingested) rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, early_ingest() ? h->io_poses : upload_bytes(h));
+    // (tri_live without c.tri: the repeat of an armed update -- the positions in HBM are the device's own, the arena's are not read again)
+    if (!c.already_ingested) rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, early_ingest() || (h->tri_live && !c.tri) ? h->io_poses : upload_bytes(h));
+    // the armed update's triangulation: ONE launch behind the pull of the arena, in front of the first kernel that reads p_w or d_skip
+    if (rc == ORCVIO_OK && c.tri) rc = launch_triangulate(h, &h->tri_cfg, false, true, s, true, h->tri_with_mode);
     if (rc == ORCVIO_OK) rc = enqueue_update(h, s, c);
     if (rc != ORCVIO_OK || c.fin_pub) return rc;
     // ONE launch behind the update: the results to host-coherent memory, the commit (refused on the device if the update is),
@@ -296,6 +321,7 @@ static int io_run(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* sta
 static int io_run_forked(orcvio_msckf_handle* h, int32_t* stats) {
     UpdateCall c;
     c.retry_forked = true;
+    if (h->tri_live && h->tri_refuse_empty) c.info_also = h->d_tri_words;   // (the word of the attempt that triangulated stands)
     return io_run(h, false, true, stats, c);
 }
 static int io_finish(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats) {
@@ -380,6 +406,7 @@ int32_t orcvio_msckf_io_update(orcvio_msckf_handle* h, int32_t want_P, int32_t c
     h->pw_missing = false;
     h->io_open = true;   // ... and may run the next update of the same shape without a new io_begin
     UpdateCall c;
+    tri_consume(h, c);
     return io_run(h, want_P != 0, commit != 0, stats, c);
 }
 
@@ -395,6 +422,7 @@ int32_t orcvio_msckf_io_submit(orcvio_msckf_handle* h, int32_t want_P, int32_t c
     h->pw_missing = false;
     h->io_open = true;
     UpdateCall c;
+    tri_consume(h, c);
     rc = io_launch(h, want_P != 0, commit != 0, c);
     if (rc != ORCVIO_OK) return rc;
     h->io_submitted = true; h->io_sub_P = want_P != 0; h->io_sub_commit = commit != 0;

@@ -9,9 +9,21 @@ void orcvio_msckf_triangulation_config_default(orcvio_triangulation_config* c) {
     c->init_final_dist_threshold = 5.0;
 }
 
-static int launch_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg, bool have_init, bool mark_skip, hipStream_t s) {
+// io: the launch inside an armed in-place update (orcvio_msckf_io_triangulate) -- the modes out of the handle's pinned block (with_mode),
+// the results published into it
+static int launch_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg, bool have_init, bool mark_skip, hipStream_t s,
+                              bool io, bool with_mode) {
     if (h->F == 0) return ORCVIO_OK;
-    TriArgs a;
+    TriArgs a{};
+    if (io) {
+        const TriBlock b = tri_block_layout(h->maxF);
+        char* d = h->h_tri_dev;
+        a.mode = with_mode ? reinterpret_cast<const int*>(d + b.mode) : nullptr;
+        a.pub_valid = reinterpret_cast<int*>(d + b.valid); a.pub_flags = reinterpret_cast<int*>(d + b.flags);
+        a.pub_cost = reinterpret_cast<double*>(d + b.cost); a.pub_pw = reinterpret_cast<double*>(d + b.p_w);
+        a.pub_sol = reinterpret_cast<double*>(d + b.inv_param);
+        a.words = h->d_tri_words;
+    }
     a.poses = h->d_poses; a.obs_ptr = h->d_obs_ptr; a.obs_clone = h->d_obs_clone; a.obs_z = h->d_obs_z;
     a.is_init = have_init ? h->d_tri_init : nullptr;
     a.p_w = h->d_pw; a.valid = h->d_tri_valid; a.flags = h->d_tri_flags; a.solution = h->d_tri_sol; a.cost = h->d_tri_cost;
@@ -36,10 +48,44 @@ int32_t orcvio_msckf_triangulate_uploaded(orcvio_msckf_handle* h, const orcvio_t
         const AuxCopy cp[] = {{h->d_tri_init, is_initialized, sizeof(int) * (size_t)h->F}};   // (the caller's memory: through the bounce buffer)
         { const int rc = aux_copies(h, s, cp, 1); if (rc != ORCVIO_OK) return rc; }
     }
-    int rc = launch_triangulate(h, cfg, is_initialized != nullptr, true, s);
+    int rc = launch_triangulate(h, cfg, is_initialized != nullptr, true, s, false, false);
     if (rc != ORCVIO_OK) return rc;
     h->skip_active = true;
     h->pw_missing = false;
+    return ORCVIO_OK;
+}
+
+// Arms the next update on the open arena (capi_io.inc tri_consume / io_enqueue): nothing is enqueued here.  The modes are copied into
+// the handle's pinned block, out of which the kernel reads them; the config is kept by value.
+int32_t orcvio_msckf_io_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg, const int32_t* mode, orcvio_msckf_io_tri* out) {
+    const char* who = "orcvio_msckf_io_triangulate: ";
+    if (!h || !out) { g_last_error = std::string(who) + "null argument"; return ORCVIO_ERR_INVALID; }
+    if (!h->io_open) { g_last_error = std::string(who) + "call orcvio_msckf_io_begin first"; return ORCVIO_ERR_INVALID; }
+    if (h->io_submitted) { g_last_error = std::string(who) + "an update submitted with orcvio_msckf_io_submit has not been collected"; return ORCVIO_ERR_INVALID; }
+    if (h->objects_mode) { g_last_error = std::string(who) + "the arena holds an object update"; return ORCVIO_ERR_INVALID; }
+    if (h->comm || h->ipc) { g_last_error = std::string(who) + "not with a communicator on the handle"; return ORCVIO_ERR_INVALID; }
+    const TriBlock b = tri_block_layout(h->maxF);
+    if (!h->h_tri) {
+        if (!tri_config_ok(cfg)) { g_last_error = std::string(who) + "a NULL or non-finite config (iteration counts must not be negative)"; return ORCVIO_ERR_INVALID; }
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipHostMalloc(&h->h_tri, b.bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->h_tri_dev), h->h_tri, 0));
+        std::memset(h->h_tri, 0, b.bytes);
+        HIPCHK(hipMalloc(&h->d_tri_words, 64));
+        HIPCHK(hipMemset(h->d_tri_words, 0, 64));
+    }
+    // (every reader and writer of the block on the device belongs to an update whose wait has returned: io_submitted is refused above)
+    const char* why = "";
+    const int rc = tri_arm_stage(cfg, mode, h->F, h->maxF, h->h_tri, &why);
+    if (rc != ORCVIO_OK) { g_last_error = std::string(who) + why; return rc; }
+    h->tri_cfg = *cfg;
+    h->tri_with_mode = mode != nullptr;
+    h->tri_armed = true;
+    out->valid = reinterpret_cast<const int32_t*>(h->h_tri + b.valid);
+    out->flags = reinterpret_cast<const int32_t*>(h->h_tri + b.flags);
+    out->cost = reinterpret_cast<const double*>(h->h_tri + b.cost);
+    out->p_w = reinterpret_cast<const double*>(h->h_tri + b.p_w);
+    out->inv_param = reinterpret_cast<const double*>(h->h_tri + b.inv_param);
     return ORCVIO_OK;
 }
 
@@ -69,6 +115,7 @@ int32_t orcvio_msckf_triangulate(orcvio_msckf_handle* h, const orcvio_triangulat
     hipStream_t s = h->stream;
     // this call owns the track buffers: whatever was uploaded for an update is gone
     h->uploaded = false; h->ran = false; h->skip_active = false; h->objects_mode = false; h->io_open = false;
+    h->tri_armed = false; h->tri_live = false; h->tri_refuse_empty = false;
     h->N = N; h->F = F; h->nobs = nobs;
     HIPCHK(hipStreamSynchronize(s));
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }
@@ -92,7 +139,7 @@ int32_t orcvio_msckf_triangulate(orcvio_msckf_handle* h, const orcvio_triangulat
         const int rc = aux_copies(h, s, cp, (int)(sizeof(cp) / sizeof(cp[0])));
         if (rc != ORCVIO_OK) return rc;
     }
-    int rc = launch_triangulate(h, cfg, is_initialized != nullptr, false, s);
+    int rc = launch_triangulate(h, cfg, is_initialized != nullptr, false, s, false, false);
     if (rc != ORCVIO_OK) return rc;
     if (F > 0) {
         // results: into ONE pinned block by asynchronous copies, one synchronisation, then into the caller's arrays

@@ -478,12 +478,16 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     // (a frame without lost features and without in-state features has no first update: the covariance bookkeeping and, if there is one,
     //  the prune update are the whole frame -- the reference's removeLostFeatures returns before any arithmetic, src/orcvio.cpp:2440-2446)
     const bool first = FA > 0 || h->ekf_F > 0;
+    bool tri_frame_empty = false;
+    bool tri_frame = false;   // the first update triangulates its own tracks (orcvio_msckf_io_triangulate)
     unsigned long long pubA = 0;
     h->ekf_side_used = false;
     if (first) {
         UpdateCall c;
         c.ekf_side = fused;           // (the in-state rows beside k_front: enqueue_update)
         c.already_ingested = fused;   // (k_frame_head has pulled the whole arena)
+        tri_consume(h, c);            // (armed: k_triangulate behind the head, in front of the tracks' launch)
+        tri_frame = c.tri; tri_frame_empty = h->tri_refuse_empty;
         rc = io_enqueue(h, s, false, true, c, true);
         h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h, false);
         if (rc != ORCVIO_OK) {
@@ -587,6 +591,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             if (rc == ORCVIO_OK) { h->io_open = true; rc = upload_finalize(h, who); }
             if (rc == ORCVIO_OK) {
                 h->pw_missing = false;
+                if (tri_frame) { h->skip_active = true; h->tri_live = true; h->tri_refuse_empty = tri_frame_empty; }   // (the positions and d_skip of the lost attempt stand in HBM)
                 rc = io_run_forked(h, res->stats);
             }
             res->repaired++; h->cnt_step_repairs++;

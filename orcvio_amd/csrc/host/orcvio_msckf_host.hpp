@@ -849,6 +849,63 @@ class MsckfBackend {
         return ok;
     }
 
+    // removeLostFeatures' triangulation AND update in one call (src/orcvio.cpp:2258-2270, :2296-2312, :2325-2327, :2497-2560): the
+    // listed features are flattened into the arena with a mode each -- is_initialized: the position stands (ORCVIO_TRI_KEEP); still
+    // tracked (its last observation in the window is curr_id's): triangulated without that observation, which enters the update all
+    // the same (ORCVIO_TRI_ALL_BUT_LAST); otherwise over every observation in the window (ORCVIO_TRI_ALL) -- and ONE armed in-place
+    // update (orcvio_msckf_io_triangulate + orcvio_msckf_io_update) triangulates and updates on the device.  Written back: what
+    // initializePositions writes back.  erase_ids: the features without a valid position, which the reference erases from the map.
+    // accepted / gamma of the outcome are per listed feature (0 / NaN for the erased ones).
+    UpdateOutcome triangulateAndUpdate(StateServer& ss, MapServer& map_server, const std::vector<FeatureIDType>& ids, StateIDType curr_id,
+                                       std::vector<FeatureIDType>* erase_ids) {
+        UpdateOutcome out;
+        if (erase_ids) erase_ids->clear();
+        if (ids.empty()) return out;
+        const int F = (int)ids.size();
+        std::vector<int32_t> mode(ids.size(), ORCVIO_TRI_ALL);
+        std::vector<StateIDType> anchor(ids.size(), -1);
+        for (int k = 0; k < F; ++k) {
+            const Feature& f = map_server.at(ids[k]);
+            StateIDType last = -1, before = -1;   // the last two observations the arena lists (fillArena: the clones of the window)
+            for (const auto& ob : f.observations)
+                if (ss.imu_states_augment.count(ob.first)) { before = last; last = ob.first; }
+            if (f.is_initialized) mode[k] = ORCVIO_TRI_KEEP;
+            else if (last == curr_id) { mode[k] = ORCVIO_TRI_ALL_BUT_LAST; anchor[k] = before; }
+            else anchor[k] = last;
+        }
+        orcvio_msckf_io io{};
+        orcvio_msckf_io_tri tri{};
+        int nn = 0;
+        out.status = fillArena(ss, map_server, ids, {}, !resident_covariance, &io, &nn);
+        if (out.status == ORCVIO_OK) out.status = orcvio_msckf_io_triangulate(h_, &optimization_config, mode.data(), &tri);
+        if (out.status != ORCVIO_OK) return out;
+        int32_t stats[8] = {0};
+        out.status = orcvio_msckf_io_update(h_, resident_covariance ? 0 : 1, resident_covariance ? 1 : 0, stats);
+        if (out.status != ORCVIO_OK) return out;
+        for (int k = 0; k < F; ++k) {
+            if (mode[k] == ORCVIO_TRI_KEEP) continue;
+            Feature& f = map_server.at(ids[k]);
+            f.failed_by_neg_dpth = (tri.flags[k] & ORCVIO_TRI_NEG_DEPTH) != 0;
+            f.failed_by_big_proj = (tri.flags[k] & ORCVIO_TRI_BIG_PROJ) != 0;
+            if (!tri.valid[k]) { if (erase_ids) erase_ids->push_back(ids[k]); continue; }
+            std::memcpy(f.position_FEJ, f.position, sizeof(f.position));   // (not initialised before: feature.hpp:431-432)
+            f.is_initialized = true;
+            std::memcpy(f.position, tri.p_w + 3 * (size_t)k, sizeof(f.position));
+            std::memcpy(f.invParam, tri.inv_param + 3 * (size_t)k, sizeof(f.invParam));
+            f.id_anchor = anchor[k];
+            f.invDepth = tri.inv_param[3 * (size_t)k + 2];
+        }
+        out.accepted.assign(io.accept, io.accept + F);
+        out.gamma.assign(io.gamma, io.gamma + F);
+        out.delta_x.assign(io.dx, io.dx + nn);
+        out.updated = stats[3] != 0;
+        if (out.updated) {
+            if (!resident_covariance) ss.state_cov.assign(io.P_out, io.P_out + (size_t)nn * nn);
+            out.state_incremented = incrementState_IMUCam(ss, out.delta_x);
+        }
+        return out;
+    }
+
     // ---- objects --------------------------------------------------------------------------------
     // OrcVIO::constructObjectResidualJacobians (src/orcvio.cpp:2017-2151) in compact form: returns false if
     // no frame of the object is in the window.  jacobian_wrt_sensor_state: rows x 6 row-major, ordered

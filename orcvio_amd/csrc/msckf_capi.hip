@@ -20,6 +20,7 @@
 #include "msckf_kernels.hpp"
 #include "feature_split.hpp"
 #include "triangulate.hpp"
+#include "triangulate_arm.hpp"
 #include "cov_ops.hpp"
 #include "zupt_ops.hpp"
 #include "ekf_rows.hpp"
@@ -191,6 +192,14 @@ struct orcvio_msckf_handle {
     bool pw_missing = false;            // uploaded without positions: triangulate_uploaded must run before the update
     int *d_tri_valid = nullptr, *d_tri_flags = nullptr, *d_tri_init = nullptr;
     double *d_tri_sol = nullptr, *d_tri_cost = nullptr;
+    // orcvio_msckf_io_triangulate: the next update on the open arena triangulates its own tracks (one-shot; the update consumes it)
+    char *h_tri = nullptr, *h_tri_dev = nullptr;   // pinned [mode | valid | flags | cost | p_w | inv_param] (triangulate_arm.hpp), on first use
+    bool tri_armed = false, tri_with_mode = false;
+    orcvio_triangulation_config tri_cfg{};
+    int* d_tri_words = nullptr;         // [16] status block of the armed launch (TriArgs.words): [2] != 0 = no track is valid -- the update's info_also
+    bool tri_refuse_empty = false;      // the current armed update has nothing but its tracks: without a valid one it leaves P and its factor alone
+    bool tri_live = false;              // the positions of the current upload were made on the device by an armed update: a repeat of that update
+                                        // (a lost hand-off) keeps them and d_skip -- it pulls the derived index arrays only and does not triangulate again
     int* d_flag = nullptr;              // step counter of that launch (inside the d_info allocation, own 128-byte line)
     // device buffers
     double *d_poses = nullptr, *d_pw = nullptr, *d_obs_z = nullptr, *d_obs_zvel = nullptr, *d_P = nullptr;
@@ -342,6 +351,7 @@ struct UpdateCall {
     bool fin_frame = false;             // the chained frame call is enqueueing its feature half (finish_fused_active)
     bool ekf_side = false;              // the step call's first update: the in-state rows beside k_front, on the side stream
     bool already_ingested = false;      // k_frame_head has pulled the arena of this update (io_enqueue skips its ingest launch)
+    bool tri = false;                   // armed by orcvio_msckf_io_triangulate: k_triangulate behind the pull of the arena (io_enqueue; h->tri_cfg, h->tri_with_mode)
     unsigned* mark_M_word = nullptr;    // ST_FORM_M / ST_POTRF_M store mark_M_val there once M is formed, and put the pointer back to null: the caller
     unsigned mark_M_val = 0u;           //  sees from its record whether the mark went out
     const unsigned* join_wait = nullptr;   // the ST_FORM_U product polls this counter (the frame call's object half) ...

@@ -6,6 +6,11 @@
 // the three-parameter (alpha, beta, rho) Levenberg-Marquardt in the last camera's frame is a handful of wave
 // reductions per iteration; every lane carries the same (alpha, beta, rho), lambda and loop counters, so the
 // reference's do-while control flow is wave-uniform.
+//
+// Inside the in-place update (orcvio_msckf_io_triangulate) the launch also gets a mode per track -- keep the given position, use every
+// listed observation, or every one but the last (a feature that is still tracked: its newest observation enters the update, not the
+// triangulation) -- and publishes every track's results into pinned host memory, ahead of the flag the update raises later on the same
+// stream: the storing lane issues a system-scope fence, as k_cov_change_anchors and k_finish_pub do.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -25,6 +30,15 @@ struct TriArgs {
     double* solution;         // [F][3] (alpha, beta, rho) in the last camera's frame
     double* cost;             // [F]
     int* skip;                // [F] or nullptr: 1 where the track must not enter the update
+    const int* mode;          // [F] or nullptr (every track 1): 0 keep p_w[j] as it is, 1 all listed observations, 2 all but the last
+    int* pub_valid;           // not nullptr: host-coherent copies of the five results ([F], [F], [F], [F][3], [F][3]), stored by the
+    int* pub_flags;           //  lane that stores the results, with a system-scope fence behind them
+    double* pub_cost;
+    double* pub_pw;
+    double* pub_sol;
+    int* words;               // not nullptr: [2] <- 1 when NO track of the launch is valid, else 0 (read as a status block by the update's
+                              //  finish: an update without a single track leaves P and its factor alone, as removeLostFeatures returns
+                              //  before any arithmetic, src/orcvio.cpp:2440-2446); [4] valid tracks, [5] arrivals: zero between launches
     double translation_threshold, huber_epsilon, estimation_precision, initial_damping, cost_threshold, init_final_dist_threshold;
     int outer_max, inner_max;
     int F;
@@ -49,17 +63,54 @@ __device__ __forceinline__ double tri_wave_sum(double x) {
     return __hiloint2double(hi, lo);
 }
 
+// one lane: a track's results as they stand in HBM (p_w included) into the pinned block
+__device__ __forceinline__ void tri_publish(const TriArgs& p, int j, int valid, int flags, double cost, double s0, double s1, double s2,
+                                            double w0, double w1, double w2) {
+    if (!p.pub_valid) return;
+    p.pub_valid[j] = valid; p.pub_flags[j] = flags; p.pub_cost[j] = cost;
+    p.pub_sol[3 * j] = s0; p.pub_sol[3 * j + 1] = s1; p.pub_sol[3 * j + 2] = s2;
+    p.pub_pw[3 * j] = w0; p.pub_pw[3 * j + 1] = w1; p.pub_pw[3 * j + 2] = w2;
+    __threadfence_system();
+}
+// one lane, once per track, behind its results: the block that arrives last decides words[2]
+__device__ __forceinline__ void tri_arrive(const TriArgs& p, int valid) {
+    if (!p.words) return;
+    if (valid) __hip_atomic_fetch_add(p.words + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int old = __hip_atomic_fetch_add(p.words + 5, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (old == p.F - 1) {
+        const int nv = __hip_atomic_load(p.words + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        p.words[2] = nv == 0 ? 1 : 0;
+        __hip_atomic_store(p.words + 4, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(p.words + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// one lane: a track that is not triangulated (too few observations, no motion) -- its position stays what it was
+__device__ __forceinline__ void tri_refuse(const TriArgs& p, int j) {
+    p.valid[j] = 0; p.flags[j] = 1; p.cost[j] = NAN;
+    p.solution[3 * j] = p.solution[3 * j + 1] = p.solution[3 * j + 2] = NAN;
+    if (p.skip) p.skip[j] = 1;
+    if (p.pub_valid) tri_publish(p, j, 0, 1, NAN, NAN, NAN, NAN, p.p_w[3 * j], p.p_w[3 * j + 1], p.p_w[3 * j + 2]);
+    tri_arrive(p, 0);
+}
+
 __global__ __launch_bounds__(64) void k_triangulate(TriArgs p) {
     const int j = blockIdx.x, t = threadIdx.x;
     const int lo = p.obs_ptr[j];
-    const int M = p.obs_ptr[j + 1] - lo;
+    const int md = p.mode ? p.mode[j] : 1;
+    if (md == 0) {   // the position is given: the track takes part as it is
+        if (t == 0) {
+            p.valid[j] = 1; p.flags[j] = 0; p.cost[j] = NAN;
+            p.solution[3 * j] = p.solution[3 * j + 1] = p.solution[3 * j + 2] = NAN;
+            if (p.skip) p.skip[j] = 0;
+            if (p.pub_valid) tri_publish(p, j, 1, 0, NAN, NAN, NAN, NAN, p.p_w[3 * j], p.p_w[3 * j + 1], p.p_w[3 * j + 2]);
+            tri_arrive(p, 1);
+        }
+        return;
+    }
+    const int M = p.obs_ptr[j + 1] - lo - (md == 2 ? 1 : 0);   // observations the triangulation uses: lanes 0 .. M-1
     const bool init = p.is_init && p.is_init[j] != 0;
     if (M < 2) {   // nothing to triangulate from (the reference never gets here: least_Obs_Num, src/orcvio.cpp:2252)
-        if (t == 0) {
-            p.valid[j] = 0; p.flags[j] = 1; p.cost[j] = NAN;
-            p.solution[3 * j] = p.solution[3 * j + 1] = p.solution[3 * j + 2] = NAN;
-            if (p.skip) p.skip[j] = 1;
-        }
+        if (t == 0) tri_refuse(p, j);
         return;
     }
     const bool live = t < M;
@@ -103,11 +154,7 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs p) {
         }
         mo = __shfl(mo, 0);
         if (!(mo > p.translation_threshold)) {
-            if (t == 0) {
-                p.valid[j] = 0; p.flags[j] = 1; p.cost[j] = NAN;
-                p.solution[3 * j] = p.solution[3 * j + 1] = p.solution[3 * j + 2] = NAN;
-                if (p.skip) p.skip[j] = 1;
-            }
+            if (t == 0) tri_refuse(p, j);
             return;
         }
     }
@@ -226,11 +273,18 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs p) {
         p.flags[j] = fl;
         p.cost[j] = total;
         p.solution[3 * j] = x0; p.solution[3 * j + 1] = x1; p.solution[3 * j + 2] = x2;
+        double w[3] = {0.0, 0.0, 0.0};
+        if (p.pub_valid && !ok && init) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) w[a] = p.p_w[3 * j + a];
+        }
         if (ok || !init) {   // position = T_c_w_last * final_position (feature.hpp:433); an initialised feature keeps its prior on failure
 #pragma unroll
-            for (int a = 0; a < 3; ++a) p.p_w[3 * j + a] = ok ? (Rl[3 * a] * f0 + Rl[3 * a + 1] * f1 + Rl[3 * a + 2] * f2 + tl[a]) : NAN;
+            for (int a = 0; a < 3; ++a) p.p_w[3 * j + a] = w[a] = ok ? (Rl[3 * a] * f0 + Rl[3 * a + 1] * f1 + Rl[3 * a + 2] * f2 + tl[a]) : NAN;
         }
         if (p.skip) p.skip[j] = ok ? 0 : 1;
+        tri_publish(p, j, ok ? 1 : 0, fl, total, x0, x1, x2, w[0], w[1], w[2]);
+        tri_arrive(p, ok ? 1 : 0);
     }
 }
 
