@@ -976,52 +976,81 @@ class MsckfUpdater:
         out['accept'] = int(out['accept'][0])
         return out
 
+    # ---- the object mapper: what the four LM-bearing calls share -----------------------------------------------------------------
+    def _lm_config(self, left, new_bbox, weights, max_iter, ptol, reg_every_frame=None):
+        """ObjectLMConfig (four weights), or with reg_every_frame ObjectLiteConfig (two weights): the library's defaults, then the
+        caller's values."""
+        lite = reg_every_frame is not None
+        cls = ObjectLiteConfig if lite else ObjectLMConfig
+        default = self.lib.orcvio_msckf_object_lite_config_default if lite else self.lib.orcvio_msckf_object_lm_config_default
+        cfg = cls()
+        default.argtypes = [C.POINTER(cls)]
+        default.restype = None
+        default(C.byref(cfg))
+        cfg.use_left_perturbation = int(left)
+        cfg.use_new_bbox_residual = int(new_bbox)
+        cfg.residual_weights[:] = [float(w) for w in weights]
+        if lite:
+            cfg.reg_every_frame = int(reg_every_frame)
+        if max_iter is not None:
+            cfg.max_iter = int(max_iter)
+        if ptol is not None:
+            cfg.ptol = float(ptol)
+        return cfg
+
+    @staticmethod
+    def _lm_records(n, mean_shapes, mean_kps, keep):
+        """The prior and result records of an optimiser and the arrays its results land in, per object (wTo, shape, kps).
+        mean_kps: one contiguous [K][3] array per object, or None for bbox-only tracks (no keypoint pointers at all)."""
+        priors = (ObjectLMPrior * max(n, 1))()
+        results = (ObjectLMResult * max(n, 1))()
+        outs = []
+        for k in range(n):
+            ms = np.ascontiguousarray(mean_shapes[k], dtype=np.float64).reshape(3)
+            keep.append(ms)
+            if mean_kps is None:
+                o = (np.zeros((4, 4)), np.zeros(3), None)
+                priors[k] = ObjectLMPrior(_d(ms), None)
+            else:
+                o = (np.zeros((4, 4)), np.zeros(3), np.zeros((max(mean_kps[k].shape[0], 1), 3)))
+                priors[k] = ObjectLMPrior(_d(ms), _d(mean_kps[k]))
+            outs.append(o)
+            results[k].wTo, results[k].shape, results[k].kps = _d(o[0]), _d(o[1]), _d(o[2])
+        return priors, results, outs
+
+    @staticmethod
+    def _lm_outs(objs, arr, results, outs):
+        """(tracks, stats) of an optimiser: synth.ObjectTrack copies at the optimum (kps [0][3] for a bbox-only track; the frames
+        shared with the inputs: update_object_tracks takes them as they are) and the statistics."""
+        from . import synth
+        tracks, stats = [], []
+        for k, obj in enumerate(objs):
+            kps = np.zeros((0, 3)) if outs[k][2] is None else outs[k][2][:arr[k].n_keypoints].copy()
+            tracks.append(synth.ObjectTrack(wTo=outs[k][0], shape=outs[k][1], kps=kps, frames=obj.frames))
+            stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
+                              evaluations=int(results[k].evaluations), status=int(results[k].status)))
+        return tracks, stats
+
     def object_lm(self, objs, mean_shapes, mean_kps, left, new_bbox, weights, max_iter=None, ptol=None):
         """orcvio_msckf_object_lm: Levenberg-Marquardt over every object track of `objs` (synth.ObjectTrack-shaped, their state the
         start) in one launch.  mean_shapes [n][3] / mean_kps [n][K][3]: the priors of the two regularisers, one per object.
         Returns (tracks, stats): synth.ObjectTrack copies at the optimum (frames shared with the inputs) and per object
         dict(cost0, cost, iterations, evaluations, status)."""
-        cfg = ObjectLMConfig()
-        self.lib.orcvio_msckf_object_lm_config_default.argtypes = [C.POINTER(ObjectLMConfig)]
-        self.lib.orcvio_msckf_object_lm_config_default.restype = None
-        self.lib.orcvio_msckf_object_lm_config_default(C.byref(cfg))
-        cfg.use_left_perturbation = int(left)
-        cfg.use_new_bbox_residual = int(new_bbox)
-        cfg.residual_weights[:] = [float(w) for w in weights]
-        if max_iter is not None:
-            cfg.max_iter = int(max_iter)
-        if ptol is not None:
-            cfg.ptol = float(ptol)
+        cfg = self._lm_config(left, new_bbox, weights, max_iter, ptol)
         _, arr, keep = self._object_tracks(objs, np.eye(3), np.zeros(3), left, new_bbox, 0, False)
         n = len(objs)
-        priors = (ObjectLMPrior * max(n, 1))()
-        results = (ObjectLMResult * max(n, 1))()
-        outs = []
-        for k, obj in enumerate(objs):
-            K = arr[k].n_keypoints
-            ms = np.ascontiguousarray(mean_shapes[k], dtype=np.float64).reshape(3)
-            mk = np.ascontiguousarray(np.asarray(mean_kps[k], dtype=np.float64).reshape(-1, 3))
-            if mk.shape[0] != K:
-                raise ValueError('object_lm: mean_kps[%d] has %d keypoints, the track %d' % (k, mk.shape[0], K))
-            o = (np.zeros((4, 4)), np.zeros(3), np.zeros((max(K, 1), 3)))
-            keep += [ms, mk]
-            outs.append(o)
-            priors[k] = ObjectLMPrior(_d(ms), _d(mk))
-            results[k].wTo, results[k].shape, results[k].kps = _d(o[0]), _d(o[1]), _d(o[2])
+        mks = [np.ascontiguousarray(np.asarray(mean_kps[k], dtype=np.float64).reshape(-1, 3)) for k in range(n)]
+        for k, mk in enumerate(mks):
+            if mk.shape[0] != arr[k].n_keypoints:
+                raise ValueError('object_lm: mean_kps[%d] has %d keypoints, the track %d' % (k, mk.shape[0], arr[k].n_keypoints))
+        priors, results, outs = self._lm_records(n, mean_shapes, mks, keep)
         self.lib.orcvio_msckf_object_lm.argtypes = [C.c_void_p, C.POINTER(ObjectLMConfig), C.POINTER(ObjectTrackC),
                                                     C.POINTER(ObjectLMPrior), C.c_int32, C.POINTER(ObjectLMResult)]
         self.lib.orcvio_msckf_object_lm.restype = C.c_int32
         rc = self.lib.orcvio_msckf_object_lm(self.h, C.byref(cfg), arr, priors, n, results)
         if rc != 0:
             raise MsckfError(rc, 'orcvio_msckf_object_lm')
-        from . import synth
-        tracks, stats = [], []
-        for k, obj in enumerate(objs):
-            K = arr[k].n_keypoints
-            tracks.append(synth.ObjectTrack(wTo=outs[k][0], shape=outs[k][1], kps=outs[k][2][:K].copy(), frames=obj.frames))
-            stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
-                              evaluations=int(results[k].evaluations), status=int(results[k].status)))
-        return tracks, stats
+        return self._lm_outs(objs, arr, results, outs)
 
     def _object_init_args(self, objs, mean_kps, pose_form, min_obs, min_kps, with_bbox):
         """Track records with only what the initialiser reads (wTo / shape / kps / frame_clone NULL), its config and result records."""
@@ -1088,29 +1117,9 @@ class MsckfUpdater:
         call.  Returns (inits, tracks, stats): object_init's list, and object_lm's two; an object whose initialisation did not end
         with status 1 has LM status 0, the identity and the means."""
         icfg, arr, iresults, iouts, mks, keep = self._object_init_args(objs, mean_kps, pose_form, min_obs, min_kps, True)
-        cfg = ObjectLMConfig()
-        self.lib.orcvio_msckf_object_lm_config_default.argtypes = [C.POINTER(ObjectLMConfig)]
-        self.lib.orcvio_msckf_object_lm_config_default.restype = None
-        self.lib.orcvio_msckf_object_lm_config_default(C.byref(cfg))
-        cfg.use_left_perturbation = int(left)
-        cfg.use_new_bbox_residual = int(new_bbox)
-        cfg.residual_weights[:] = [float(w) for w in weights]
-        if max_iter is not None:
-            cfg.max_iter = int(max_iter)
-        if ptol is not None:
-            cfg.ptol = float(ptol)
+        cfg = self._lm_config(left, new_bbox, weights, max_iter, ptol)
         n = len(objs)
-        priors = (ObjectLMPrior * max(n, 1))()
-        results = (ObjectLMResult * max(n, 1))()
-        outs = []
-        for k in range(n):
-            K = arr[k].n_keypoints
-            ms = np.ascontiguousarray(mean_shapes[k], dtype=np.float64).reshape(3)
-            o = (np.zeros((4, 4)), np.zeros(3), np.zeros((max(K, 1), 3)))
-            keep.append(ms)
-            outs.append(o)
-            priors[k] = ObjectLMPrior(_d(ms), _d(mks[k]))
-            results[k].wTo, results[k].shape, results[k].kps = _d(o[0]), _d(o[1]), _d(o[2])
+        priors, results, outs = self._lm_records(n, mean_shapes, mks, keep)
         self.lib.orcvio_msckf_object_init_lm.argtypes = [C.c_void_p, C.POINTER(ObjectInitConfig), C.POINTER(ObjectLMConfig),
                                                          C.POINTER(ObjectTrackC), C.POINTER(ObjectLMPrior), C.c_int32,
                                                          C.POINTER(ObjectInitResult), C.POINTER(ObjectLMResult)]
@@ -1118,13 +1127,7 @@ class MsckfUpdater:
         rc = self.lib.orcvio_msckf_object_init_lm(self.h, C.byref(icfg), C.byref(cfg), arr, priors, n, iresults, results)
         if rc != 0:
             raise MsckfError(rc, 'orcvio_msckf_object_init_lm')
-        from . import synth
-        tracks, stats = [], []
-        for k, obj in enumerate(objs):
-            K = arr[k].n_keypoints
-            tracks.append(synth.ObjectTrack(wTo=outs[k][0], shape=outs[k][1], kps=outs[k][2][:K].copy(), frames=obj.frames))
-            stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
-                              evaluations=int(results[k].evaluations), status=int(results[k].status)))
+        tracks, stats = self._lm_outs(objs, arr, results, outs)
         return self._object_init_outs(iresults, iouts), tracks, stats
 
     # ---- the lite (bbox-only) object mapper ------------------------------------------------------------------------------------
@@ -1143,20 +1146,9 @@ class MsckfUpdater:
             arr[k] = ObjectTrackC(0, len(obj.frames), _d(wTo), _d(shape), None, _d(wTc), None, _d(bb), None)
         return arr, keep
 
+    # (_lite_config and _lite_init_config are kept under these names and signatures: tests/test_gpu_object_lite.py builds raw calls with them)
     def _lite_config(self, left, new_bbox, weights, reg_every_frame, max_iter, ptol):
-        cfg = ObjectLiteConfig()
-        self.lib.orcvio_msckf_object_lite_config_default.argtypes = [C.POINTER(ObjectLiteConfig)]
-        self.lib.orcvio_msckf_object_lite_config_default.restype = None
-        self.lib.orcvio_msckf_object_lite_config_default(C.byref(cfg))
-        cfg.use_left_perturbation = int(left)
-        cfg.use_new_bbox_residual = int(new_bbox)
-        cfg.residual_weights[:] = [float(w) for w in weights]
-        cfg.reg_every_frame = int(reg_every_frame)
-        if max_iter is not None:
-            cfg.max_iter = int(max_iter)
-        if ptol is not None:
-            cfg.ptol = float(ptol)
-        return cfg
+        return self._lm_config(left, new_bbox, weights, max_iter, ptol, reg_every_frame)
 
     def _lite_init_config(self, pose_form, bbox_scale):
         cfg = ObjectInitLiteConfig()
@@ -1169,80 +1161,60 @@ class MsckfUpdater:
             cfg.bbox_scale[:] = [float(v) for v in bbox_scale]
         return cfg
 
-    @staticmethod
-    def _lite_lm_records(n, mean_shapes, keep):
-        priors = (ObjectLMPrior * max(n, 1))()
-        results = (ObjectLMResult * max(n, 1))()
-        outs = []
+    def _lite_init_args(self, n, pose_form, bbox_scale):
+        """The lite initialiser's config, its result records and the arrays its poses land in."""
+        cfg = self._lite_init_config(pose_form, bbox_scale)
+        results = (ObjectInitLiteResult * max(n, 1))()
+        outs = [np.zeros((4, 4)) for _ in range(n)]
         for k in range(n):
-            ms = np.ascontiguousarray(mean_shapes[k], dtype=np.float64).reshape(3)
-            o = (np.zeros((4, 4)), np.zeros(3))
-            keep.append(ms)
-            outs.append(o)
-            priors[k] = ObjectLMPrior(_d(ms), None)
-            results[k].wTo, results[k].shape, results[k].kps = _d(o[0]), _d(o[1]), None
-        return priors, results, outs
+            results[k].wTo = _d(outs[k])
+        return cfg, results, outs
 
     @staticmethod
-    def _lite_lm_outs(objs, results, outs):
-        """Bbox-only tracks (kps [0][3], the frames shared with the inputs: update_object_tracks takes them as they are) and the statistics."""
-        from . import synth
-        tracks, stats = [], []
-        for k, obj in enumerate(objs):
-            tracks.append(synth.ObjectTrack(wTo=outs[k][0], shape=outs[k][1], kps=np.zeros((0, 3)), frames=obj.frames))
-            stats.append(dict(cost0=float(results[k].cost0), cost=float(results[k].cost), iterations=int(results[k].iterations),
-                              evaluations=int(results[k].evaluations), status=int(results[k].status)))
-        return tracks, stats
+    def _lite_init_outs(results, outs):
+        return [dict(wTo=o, d=float(results[k].d), status=int(results[k].status)) for k, o in enumerate(outs)]
 
     def object_lm_lite(self, objs, mean_shapes, left, new_bbox, weights=(1.0, 1.0), reg_every_frame=0, max_iter=None, ptol=None):
         """orcvio_msckf_object_lm_lite: the 9-dof Levenberg-Marquardt over every bbox-only track of `objs` (synth.ObjectTrack-shaped:
         wTo and shape are the start, the frames' wTc and bbox are read; kps and zs are ignored) in one launch, one wavefront per
         object.  weights: (bbox rows, shape regulariser).  Returns (tracks, stats) as object_lm does, the tracks without keypoints."""
-        cfg = self._lite_config(left, new_bbox, weights, reg_every_frame, max_iter, ptol)
+        cfg = self._lm_config(left, new_bbox, weights, max_iter, ptol, reg_every_frame)
         arr, keep = self._lite_tracks(objs, True)
         n = len(objs)
-        priors, results, outs = self._lite_lm_records(n, mean_shapes, keep)
+        priors, results, outs = self._lm_records(n, mean_shapes, None, keep)
         self.lib.orcvio_msckf_object_lm_lite.argtypes = [C.c_void_p, C.POINTER(ObjectLiteConfig), C.POINTER(ObjectTrackC),
                                                          C.POINTER(ObjectLMPrior), C.c_int32, C.POINTER(ObjectLMResult)]
         self.lib.orcvio_msckf_object_lm_lite.restype = C.c_int32
         rc = self.lib.orcvio_msckf_object_lm_lite(self.h, C.byref(cfg), arr, priors, n, results)
         if rc != 0:
             raise MsckfError(rc, 'orcvio_msckf_object_lm_lite')
-        return self._lite_lm_outs(objs, results, outs)
+        return self._lm_outs(objs, arr, results, outs)
 
     def object_init_lite(self, objs, mean_shapes, pose_form=None, bbox_scale=None):
         """orcvio_msckf_object_init_lite: the start pose of every bbox-only track from its first frame's camera and box.  Returns per
         object dict(wTo, d, status)."""
-        cfg = self._lite_init_config(pose_form, bbox_scale)
         arr, keep = self._lite_tracks(objs, False)
         n = len(objs)
+        cfg, results, outs = self._lite_init_args(n, pose_form, bbox_scale)
         ms = [np.ascontiguousarray(m, dtype=np.float64).reshape(3) for m in mean_shapes]
         ptrs = (_dp * max(n, 1))(*[_d(m) for m in ms])
-        results = (ObjectInitLiteResult * max(n, 1))()
-        outs = [np.zeros((4, 4)) for _ in range(n)]
-        for k in range(n):
-            results[k].wTo = _d(outs[k])
         self.lib.orcvio_msckf_object_init_lite.argtypes = [C.c_void_p, C.POINTER(ObjectInitLiteConfig), C.POINTER(ObjectTrackC), C.POINTER(_dp),
                                                            C.c_int32, C.POINTER(ObjectInitLiteResult)]
         self.lib.orcvio_msckf_object_init_lite.restype = C.c_int32
         rc = self.lib.orcvio_msckf_object_init_lite(self.h, C.byref(cfg), arr, ptrs, n, results)
         if rc != 0:
             raise MsckfError(rc, 'orcvio_msckf_object_init_lite')
-        return [dict(wTo=outs[k], d=float(results[k].d), status=int(results[k].status)) for k in range(n)]
+        return self._lite_init_outs(results, outs)
 
     def object_init_lm_lite(self, objs, mean_shapes, left, new_bbox, weights=(1.0, 1.0), reg_every_frame=0, max_iter=None, ptol=None,
                             pose_form=None, bbox_scale=None):
         """orcvio_msckf_object_init_lm_lite: object_init_lite and object_lm_lite from its start (the pose, the mean shape) in ONE call.
         Returns (inits, tracks, stats); an object whose start failed has LM status 0, the identity and the mean shape."""
-        icfg = self._lite_init_config(pose_form, bbox_scale)
-        cfg = self._lite_config(left, new_bbox, weights, reg_every_frame, max_iter, ptol)
+        cfg = self._lm_config(left, new_bbox, weights, max_iter, ptol, reg_every_frame)
         arr, keep = self._lite_tracks(objs, False)
         n = len(objs)
-        priors, results, outs = self._lite_lm_records(n, mean_shapes, keep)
-        iresults = (ObjectInitLiteResult * max(n, 1))()
-        iouts = [np.zeros((4, 4)) for _ in range(n)]
-        for k in range(n):
-            iresults[k].wTo = _d(iouts[k])
+        icfg, iresults, iouts = self._lite_init_args(n, pose_form, bbox_scale)
+        priors, results, outs = self._lm_records(n, mean_shapes, None, keep)
         self.lib.orcvio_msckf_object_init_lm_lite.argtypes = [C.c_void_p, C.POINTER(ObjectInitLiteConfig), C.POINTER(ObjectLiteConfig),
                                                               C.POINTER(ObjectTrackC), C.POINTER(ObjectLMPrior), C.c_int32,
                                                               C.POINTER(ObjectInitLiteResult), C.POINTER(ObjectLMResult)]
@@ -1250,9 +1222,8 @@ class MsckfUpdater:
         rc = self.lib.orcvio_msckf_object_init_lm_lite(self.h, C.byref(icfg), C.byref(cfg), arr, priors, n, iresults, results)
         if rc != 0:
             raise MsckfError(rc, 'orcvio_msckf_object_init_lm_lite')
-        inits = [dict(wTo=iouts[k], d=float(iresults[k].d), status=int(iresults[k].status)) for k in range(n)]
-        tracks, stats = self._lite_lm_outs(objs, results, outs)
-        return inits, tracks, stats
+        tracks, stats = self._lm_outs(objs, arr, results, outs)
+        return self._lite_init_outs(iresults, iouts), tracks, stats
 
     def objects_local_tracks(self, flags, n_clones, objs, P, R_b2c, t_c_b, obj_left, new_bbox, vio_left, fix_D=False):
         """The first half of update_object_tracks alone: the rows of the tracks evaluated on the device and compressed into the handle's

@@ -1197,6 +1197,30 @@ class MsckfBackend {
         return std::make_tuple(ok, wTq);
     }
 
+  private:
+    // the members into either optimiser config behind its defaults: orcvio_object_lm_config takes the four weights,
+    // orcvio_object_lite_config the first two (its reg_every_frame is the caller's)
+    template <class Cfg>
+    void object_lm_config_fill(Cfg& cfg, const bool use_left_perturbation_flag, const int use_new_bbox_residual_flag) const {
+        cfg.use_left_perturbation = use_left_perturbation_flag ? 1 : 0;
+        cfg.use_new_bbox_residual = use_new_bbox_residual_flag;
+        for (size_t i = 0; i < sizeof(cfg.residual_weights) / sizeof(double); ++i) cfg.residual_weights[i] = residual_weights[i];
+        cfg.max_iter = object_lm_max_iter;
+        cfg.ptol = object_lm_ptol;
+    }
+    // an optimiser's result record (its arrays in out: wTo 16 | shape 3 | kps n_kps) back into the state
+    static void object_lm_write_back(const int rc, const orcvio_object_lm_result& r, const double* out, const size_t n_kps, ObjectState& o) {
+        o.status = rc;
+        if (rc != ORCVIO_OK) return;
+        o.cost0 = r.cost0; o.cost = r.cost;
+        o.iterations = r.iterations; o.evaluations = r.evaluations; o.lm_status = r.status;
+        if (o.lm_status != 1) return;   // (the reference leaves objectstate as it was when the LM did not succeed, :380-384, :476-480)
+        std::memcpy(o.object_pose, out, sizeof(o.object_pose));
+        std::memcpy(o.ellipsoid_shape, out + 16, sizeof(o.ellipsoid_shape));
+        o.object_keypoints.assign(out + 19, out + 19 + n_kps);
+    }
+
+  public:
     // every object of a frame in ONE launch; returns the call's status, objectstates[k].lm_status the per-object one
     // initialize_on_device: the start is not objectstates[k].object_pose but single_object_initialization's, found in the SAME call
     // (orcvio_msckf_object_init_lm: one upload, two launches, one wait); `inits`, if given, receives what object_initialization returns.
@@ -1208,11 +1232,7 @@ class MsckfBackend {
         if (objectstates.size() != n) return ORCVIO_ERR_INVALID;
         orcvio_object_lm_config cfg;
         orcvio_msckf_object_lm_config_default(&cfg);
-        cfg.use_left_perturbation = use_left_perturbation_flag ? 1 : 0;
-        cfg.use_new_bbox_residual = use_new_bbox_residual_flag;
-        for (int i = 0; i < 4; ++i) cfg.residual_weights[i] = residual_weights[i];
-        cfg.max_iter = object_lm_max_iter;
-        cfg.ptol = object_lm_ptol;
+        object_lm_config_fill(cfg, use_left_perturbation_flag, use_new_bbox_residual_flag);
         std::vector<orcvio_object_track> tracks(n);
         std::vector<orcvio_object_lm_prior> priors(n);
         std::vector<orcvio_object_lm_result> results(n);
@@ -1244,17 +1264,7 @@ class MsckfBackend {
         } else {
             rc = orcvio_msckf_object_lm(h_, &cfg, tracks.data(), priors.data(), (int32_t)n, results.data());
         }
-        for (size_t k = 0; k < n; ++k) {
-            ObjectState& o = objectstates[k];
-            o.status = rc;
-            if (rc != ORCVIO_OK) continue;
-            o.cost0 = results[k].cost0; o.cost = results[k].cost;
-            o.iterations = results[k].iterations; o.evaluations = results[k].evaluations; o.lm_status = results[k].status;
-            if (o.lm_status != 1) continue;   // (the reference leaves objectstate as it was when the LM did not succeed, :380-384)
-            std::memcpy(o.object_pose, out[k].data(), sizeof(o.object_pose));
-            std::memcpy(o.ellipsoid_shape, out[k].data() + 16, sizeof(o.ellipsoid_shape));
-            o.object_keypoints.assign(out[k].begin() + 19, out[k].end());
-        }
+        for (size_t k = 0; k < n; ++k) object_lm_write_back(rc, results[k], out[k].data(), out[k].size() - 19, objectstates[k]);
         return rc;
     }
     bool single_levenberg_marquardt(const ObjectFeatureTrack& feat, ObjectState& objectstate, const bool use_left_perturbation_flag,
@@ -1294,24 +1304,38 @@ class MsckfBackend {
         return true;
     }
 
-    // every object of a frame in ONE launch; returns the call's status, inits[k].init_status the per-object one
-    int object_initialization_lite(const std::vector<const ObjectFeatureTrack*>& feats, std::vector<ObjectInitLite>& inits) {
-        const size_t n = feats.size();
+  private:
+    // the lite initialiser's config from the members; its result records, the poses landing in `inits`; the records back into `inits`
+    orcvio_object_init_lite_config object_init_lite_config() const {
+        return orcvio_object_init_lite_config{object_init_pose_form, {object_lite_bbox_scale[0], object_lite_bbox_scale[1], object_lite_bbox_scale[2]}};
+    }
+    static void object_init_lite_results(const size_t n, std::vector<ObjectInitLite>& inits, std::vector<orcvio_object_init_lite_result>& res) {
         inits.assign(n, ObjectInitLite{});
-        std::vector<orcvio_object_track> tracks;
-        if (!object_lite_tracks(feats, nullptr, tracks)) {
-            for (ObjectInitLite& o : inits) o.status = ORCVIO_ERR_INVALID;   // (nothing was launched)
-            return ORCVIO_ERR_INVALID;
-        }
-        const orcvio_object_init_lite_config icfg{object_init_pose_form, {object_lite_bbox_scale[0], object_lite_bbox_scale[1], object_lite_bbox_scale[2]}};
-        std::vector<const double*> mean(n, object_mean_shape.data());
-        std::vector<orcvio_object_init_lite_result> res(n);
+        res.assign(n, orcvio_object_init_lite_result{});
         for (size_t k = 0; k < n; ++k) res[k].wTo = inits[k].wTq;
-        const int rc = orcvio_msckf_object_init_lite(h_, &icfg, tracks.data(), mean.data(), (int32_t)n, res.data());
-        for (size_t k = 0; k < n; ++k) {
+    }
+    static void object_init_lite_finish(const int rc, const std::vector<orcvio_object_init_lite_result>& res, std::vector<ObjectInitLite>& inits) {
+        for (size_t k = 0; k < inits.size(); ++k) {
             inits[k].status = rc;
             if (rc == ORCVIO_OK) { inits[k].d = res[k].d; inits[k].init_status = res[k].status; }
         }
+    }
+
+  public:
+    // every object of a frame in ONE launch; returns the call's status, inits[k].init_status the per-object one
+    int object_initialization_lite(const std::vector<const ObjectFeatureTrack*>& feats, std::vector<ObjectInitLite>& inits) {
+        const size_t n = feats.size();
+        std::vector<orcvio_object_init_lite_result> res;
+        object_init_lite_results(n, inits, res);
+        std::vector<orcvio_object_track> tracks;
+        if (!object_lite_tracks(feats, nullptr, tracks)) {
+            object_init_lite_finish(ORCVIO_ERR_INVALID, res, inits);   // (nothing was launched)
+            return ORCVIO_ERR_INVALID;
+        }
+        const orcvio_object_init_lite_config icfg = object_init_lite_config();
+        std::vector<const double*> mean(n, object_mean_shape.data());
+        const int rc = orcvio_msckf_object_init_lite(h_, &icfg, tracks.data(), mean.data(), (int32_t)n, res.data());
+        object_init_lite_finish(rc, res, inits);
         return rc;
     }
     // the reference's call: (init_success_flag, wTq)
@@ -1334,12 +1358,8 @@ class MsckfBackend {
         if (objectstates.size() != n) return ORCVIO_ERR_INVALID;
         orcvio_object_lite_config cfg;
         orcvio_msckf_object_lite_config_default(&cfg);
-        cfg.use_left_perturbation = use_left_perturbation_flag ? 1 : 0;
-        cfg.use_new_bbox_residual = use_new_bbox_residual_flag;
-        cfg.residual_weights[0] = residual_weights[0]; cfg.residual_weights[1] = residual_weights[1];
+        object_lm_config_fill(cfg, use_left_perturbation_flag, use_new_bbox_residual_flag);
         cfg.reg_every_frame = object_lite_reg_every_frame;
-        cfg.max_iter = object_lm_max_iter;
-        cfg.ptol = object_lm_ptol;
         std::vector<orcvio_object_track> tracks;
         if (!object_lite_tracks(feats, initialize_on_device ? nullptr : &objectstates, tracks)) {
             for (ObjectState& o : objectstates) o.status = ORCVIO_ERR_INVALID;   // (nothing was launched)
@@ -1355,31 +1375,17 @@ class MsckfBackend {
         }
         int rc;
         if (initialize_on_device) {
-            const orcvio_object_init_lite_config icfg{object_init_pose_form, {object_lite_bbox_scale[0], object_lite_bbox_scale[1], object_lite_bbox_scale[2]}};
+            const orcvio_object_init_lite_config icfg = object_init_lite_config();
             std::vector<ObjectInitLite> local;
             std::vector<ObjectInitLite>& oi = inits ? *inits : local;
-            oi.assign(n, ObjectInitLite{});
-            std::vector<orcvio_object_init_lite_result> ires(n);
-            for (size_t k = 0; k < n; ++k) ires[k].wTo = oi[k].wTq;
+            std::vector<orcvio_object_init_lite_result> ires;
+            object_init_lite_results(n, oi, ires);
             rc = orcvio_msckf_object_init_lm_lite(h_, &icfg, &cfg, tracks.data(), priors.data(), (int32_t)n, ires.data(), results.data());
-            for (size_t k = 0; k < n; ++k) {
-                oi[k].status = rc;
-                if (rc == ORCVIO_OK) { oi[k].d = ires[k].d; oi[k].init_status = ires[k].status; }
-            }
+            object_init_lite_finish(rc, ires, oi);
         } else {
             rc = orcvio_msckf_object_lm_lite(h_, &cfg, tracks.data(), priors.data(), (int32_t)n, results.data());
         }
-        for (size_t k = 0; k < n; ++k) {
-            ObjectState& o = objectstates[k];
-            o.status = rc;
-            if (rc != ORCVIO_OK) continue;
-            o.cost0 = results[k].cost0; o.cost = results[k].cost;
-            o.iterations = results[k].iterations; o.evaluations = results[k].evaluations; o.lm_status = results[k].status;
-            if (o.lm_status != 1) continue;   // (the reference leaves objectstate as it was when the LM did not succeed, :476-480)
-            std::memcpy(o.object_pose, out[k].data(), sizeof(o.object_pose));
-            std::memcpy(o.ellipsoid_shape, out[k].data() + 16, sizeof(o.ellipsoid_shape));
-            o.object_keypoints.clear();
-        }
+        for (size_t k = 0; k < n; ++k) object_lm_write_back(rc, results[k], out[k].data(), 0, objectstates[k]);   // (no keypoints: object_keypoints comes back empty)
         return rc;
     }
     bool single_levenberg_marquardt_lite(const ObjectFeatureTrack& feat, ObjectState& objectstate, const bool use_left_perturbation_flag,

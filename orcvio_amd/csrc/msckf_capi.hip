@@ -420,9 +420,7 @@ const char* orcvio_msckf_last_error(void) { return g_last_error.c_str(); }
 #include "capi_ipc.inc"   // the second transport of the communicator: HIP IPC + shared memory (several ranks per device possible)
 #include "capi_comm.inc"   // the handle's RCCL communicator, bounded waits, the sharded updates
 #include "capi_cov.inc"   // per-kernel profile, the device-resident covariance and its square-root factor
-#include "capi_object_lm.inc"   // the object optimiser: batched Levenberg-Marquardt over object tracks, one workgroup per object
-#include "capi_object_init.inc"   // the start of an object track: keypoint triangulation and Kabsch alignment, alone or in front of the optimiser
-#include "capi_object_lite.inc"   // the lite (bbox-only) object mapper: the start from the first box, the 9-dof optimiser, one wavefront per object
+#include "capi_object_mapper.inc"   // the object mapper: the start and the Levenberg-Marquardt refinement of object tracks, with keypoints and bbox-only
 #include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: the 9-row update, the factor kept, the one-call stationary frame
 #include "capi_frame.inc"   // one frame in one call: feature update + object update, the objects' compression beside the features' solve
 #include "capi_step.inc"   // one FILTER frame in one call: propagate, augment, update, prune update, marginalise on the resident covariance

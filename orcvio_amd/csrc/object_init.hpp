@@ -4,7 +4,7 @@
 // single_triangulation_common (src/feat/FeatureInitializer.cpp:6-111), findTransform (:265-344) and poseSE32SE2
 // (include/orcvio/utils/se3_ops.hpp:272-300).
 //
-// One workgroup per object, as k_object_lm; it reads the optimiser's staged block (object_lm_pack.hpp) and writes the start -- its
+// One workgroup per object, as k_object_lm; it reads the optimiser's staged block (object_mapper_pack.hpp) and writes the start -- its
 // pose, the mean shape, the mean keypoints -- into the block's first 19 + 3K doubles, so k_object_lm can follow on the same stream.
 // Triangulation: wavefront w takes keypoints w, w + 4, ..; lane <-> frame, a second pass for frames 64..127.  Each row pair
 //   Bperp_i = [-b2 0 b0; 0 b2 -b1],  b = R_AtoCi^T (u, v, 1) / |.|
@@ -13,7 +13,7 @@
 // Alignment: one lane, K <= 16 points from LDS; the 3 x 3 SVD is a one-sided Jacobi with a fixed number of sweeps.
 // No workgroup waits for another; every loop is bounded by K, by the two frame passes or by OBJ_INIT_SWEEPS.
 #pragma once
-#include "object_init_pack.hpp"   // the layout of the staged blocks
+#include "object_mapper_pack.hpp"   // the layout of the staged blocks
 #include "triangulate.hpp"        // tri_wave_sum
 
 namespace orcvio_amd {

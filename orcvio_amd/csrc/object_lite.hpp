@@ -16,15 +16,13 @@
 // overflow.
 // k_object_init_lite: one thread per object (a dozen products of 3-vectors).
 #pragma once
-#include "object_lite_pack.hpp"   // the layout of the staged blocks
-#include "object_lm.hpp"          // obj_lm_se3_exp
-#include "object_rows.hpp"
+#include "object_mapper_pack.hpp"   // the layout of the staged blocks
+#include "object_lm_step.hpp"       // what k_object_lm uses as well: obj_lm_se3_exp, obj_lm_sym, the status codes
 
 namespace orcvio_amd {
 
 #define OBJ_LITE_NT 256           // threads per workgroup
 #define OBJ_LITE_WPB 4            // objects (wavefronts) per workgroup
-#define OBJ_LITE_ACC 55           // 45 products of nine columns (upper triangle by rows), 9 gradient entries, the cost
 
 struct ObjLiteArgs {
     const ObjLmTrack* tracks;
@@ -61,7 +59,7 @@ __device__ __forceinline__ void obj_lite_eval(const ObjLiteArgs& a, const int F,
     const double w0 = a.w[0];
 
 #pragma unroll
-    for (int i = 0; i < OBJ_LITE_ACC; ++i) S[i] = 0.0;
+    for (int i = 0; i < OBJ_LM_ACC; ++i) S[i] = 0.0;
     for (int f0 = 0; f0 < F; f0 += 16) {   // (wave-uniform bound: every lane reaches the ballot inside)
         const int f = f0 + grp;
         const bool live = f < F;
@@ -88,7 +86,7 @@ __device__ __forceinline__ void obj_lite_eval(const ObjLiteArgs& a, const int F,
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) {
 #pragma unroll
-        for (int i = 0; i < OBJ_LITE_ACC; ++i) S[i] += __shfl_xor(S[i], s);
+        for (int i = 0; i < OBJ_LM_ACC; ++i) S[i] += __shfl_xor(S[i], s);
     }
     // the regulariser without rows: wreg = w1^2 x repeats on the shape's diagonal, wreg (v - mean) in the gradient
     double reg = 0.0;
@@ -102,6 +100,8 @@ __device__ __forceinline__ void obj_lite_eval(const ObjLiteArgs& a, const int F,
     S[54] += reg;
 }
 
+// (The pieces of the step are written out here and again in k_object_lm, not shared helpers: behind helpers the emitted code of one
+// kernel or the other moved -- object_lm_step.hpp says which piece did what.)
 __global__ __launch_bounds__(OBJ_LITE_NT) void k_object_lm_lite(ObjLiteArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int o = (int)blockIdx.x * OBJ_LITE_WPB + wave;
@@ -129,13 +129,13 @@ __global__ __launch_bounds__(OBJ_LITE_NT) void k_object_lm_lite(ObjLiteArgs a) {
     for (int i = 0; i < 9; ++i) D[i] = 0.0;
     const double wreg = a.w[1] * a.w[1] * (double)(a.reg_every_frame ? F : F - 1);
 
-    double S[OBJ_LITE_ACC], Sn[OBJ_LITE_ACC];
+    double S[OBJ_LM_ACC], Sn[OBJ_LM_ACC];
     obj_lite_eval(a, F, blk, x, mean, wreg, S);
     const double cost0 = S[54];
-    int iterations = 0, evaluations = 1, status = 3;
+    int iterations = 0, evaluations = 1, status = OBJ_LM_ST_ITER_CAP;
     double lam = 1e-3;
     bool stop = false;
-    if (!isfinite(cost0)) { status = 4; stop = true; }
+    if (!isfinite(cost0)) { status = OBJ_LM_ST_NONFINITE; stop = true; }
 
     for (int it = 0; it < a.max_iter && !stop; ++it) {
         // (A + lambda D^2) delta = -g by a Cholesky in registers: L (lower, by rows) in place of the damped matrix
@@ -190,8 +190,8 @@ __global__ __launch_bounds__(OBJ_LITE_NT) void k_object_lm_lite(ObjLiteArgs a) {
             quad += dl[i] * s;
         }
         const double pred = -2.0 * gd - quad;
-        if (bad || !isfinite(pred)) { status = 4; break; }
-        if (pred <= a.ptol * S[54]) { status = 1; break; }
+        if (bad || !isfinite(pred)) { status = OBJ_LM_ST_NONFINITE; break; }
+        if (pred <= a.ptol * S[54]) { status = OBJ_LM_ST_CONVERGED; break; }
         {
             double E[16];
             obj_lm_se3_exp(dl, E);
@@ -208,17 +208,17 @@ __global__ __launch_bounds__(OBJ_LITE_NT) void k_object_lm_lite(ObjLiteArgs a) {
         obj_lite_eval(a, F, blk, xn, mean, wreg, Sn);
         ++evaluations; ++iterations;
         const double cn = Sn[54];
-        if (!isfinite(cn)) { status = 4; break; }
+        if (!isfinite(cn)) { status = OBJ_LM_ST_NONFINITE; break; }
         const double rho = (S[54] - cn) / pred;
         if (rho > 1e-4) {
 #pragma unroll
             for (int i = 0; i < 19; ++i) x[i] = xn[i];
 #pragma unroll
-            for (int i = 0; i < OBJ_LITE_ACC; ++i) S[i] = Sn[i];
+            for (int i = 0; i < OBJ_LM_ACC; ++i) S[i] = Sn[i];
             const double q = 2.0 * rho - 1.0;
             lam = fmax(lam * fmax(1.0 / 3.0, 1.0 - q * q * q), 1e-12);
         } else lam *= 4.0;
-        if (lam > 1e12) { status = 2; stop = true; }
+        if (lam > 1e12) { status = OBJ_LM_ST_STALLED; stop = true; }
     }
     if (lane == 0) {
 #pragma unroll

@@ -14,12 +14,12 @@
 // is factored by a 9 x 9 Cholesky, the blocks are back-substituted.  The two regularisers add w^2 F to the diagonal and
 // w^2 F (x - mean) to the gradient: they need no rows.
 #pragma once
-#include "object_lm_pack.hpp"   // ObjLmTrack, the limits, the layout of the staged blocks
+#include "object_mapper_pack.hpp"   // ObjLmTrack, the limits, the layout of the staged blocks
+#include "object_lm_step.hpp"       // what k_object_lm_lite uses as well: obj_lm_se3_exp, obj_lm_sym, the status codes
 
 namespace orcvio_amd {
 
 #define OBJ_LM_NT 256           // threads per workgroup (four wavefronts)
-#define OBJ_LM_ACC 55           // per-lane accumulators: 45 products of nine columns, 9 gradient entries, the cost
 #define OBJ_LM_STATE 68         // wTo 16 | shape 3 | kps 48 (| 1 unused)
 
 struct ObjLmArgs {
@@ -39,35 +39,6 @@ struct ObjLmSys {
     double gk[OBJ_LM_MAXK][3];
     double c;
 };
-
-__device__ __forceinline__ int obj_lm_sym(int i, int j) { return i * 9 - i * (i - 1) / 2 + (j - i); }   // i <= j, upper triangle by rows
-
-// Sophus SE3d::exp, tangent (upsilon, omega): R = exp(omega), t = V upsilon (the thresholds of oracle/mirror_objects.se3_exp)
-__device__ inline void obj_lm_se3_exp(const double* xi, double* T) {
-    const double* u = xi;
-    const double* w = xi + 3;
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
-    const double W[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-    double W2[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-    double a, b, ra, rb;
-    if (th < 1e-10) { ra = 1.0; rb = 0.5; a = 0.5; b = 1.0 / 6.0; }
-    else {
-        const double s = sin(th), c = cos(th);
-        ra = s / th; rb = (1.0 - c) / th2; a = rb; b = (th - s) / (th2 * th);
-    }
-    for (int i = 0; i < 3; ++i) {
-        double V[3];
-        for (int j = 0; j < 3; ++j) {
-            const double e = (i == j) ? 1.0 : 0.0;
-            T[4 * i + j] = e + ra * W[3 * i + j] + rb * W2[3 * i + j];
-            V[j] = e + a * W[3 * i + j] + b * W2[3 * i + j];
-        }
-        T[4 * i + 3] = V[0] * u[0] + V[1] * u[1] + V[2] * u[2];
-    }
-    T[12] = T[13] = T[14] = 0.0; T[15] = 1.0;
-}
 
 // A, g and c of the state at `x` (LDS) into `S` (LDS).  Every thread of the workgroup calls it; it ends behind a barrier.
 __device__ __forceinline__ void obj_lm_eval(const ObjLmArgs& a, const ObjLmTrack tr, const double* __restrict__ in, const double* x,
@@ -164,6 +135,8 @@ __device__ __forceinline__ void obj_lm_eval(const ObjLmArgs& a, const ObjLmTrack
     __syncthreads();
 }
 
+// (The pieces of the step are written out here and again in k_object_lm_lite, not shared helpers: behind helpers the emitted code of
+// one kernel or the other moved -- object_lm_step.hpp says which piece did what.)
 __global__ __launch_bounds__(OBJ_LM_NT) void k_object_lm(ObjLmArgs a) {
     __shared__ double sX[2][OBJ_LM_STATE];            // the accepted state and the trial state
     __shared__ double sPrior[3 + 3 * OBJ_LM_MAXK];    // mean shape | mean keypoints
@@ -197,13 +170,13 @@ __global__ __launch_bounds__(OBJ_LM_NT) void k_object_lm(ObjLmArgs a) {
     }
     for (int i = tid; i < 3 + 3 * OBJ_LM_MAXK; i += OBJ_LM_NT) sPrior[i] = i < 3 + 3 * K ? in[tr.off + 19 + 3 * K + i] : 0.0;
     for (int i = tid; i < 9 + 3 * OBJ_LM_MAXK; i += OBJ_LM_NT) { sD[i] = 0.0; sDelta[i] = 0.0; }
-    if (tid == 0) { sLam = 1e-3; sCtl[0] = 0; sCtl[1] = 0; sCtl[2] = 3; sCtl[3] = 0; }
+    if (tid == 0) { sLam = 1e-3; sCtl[0] = 0; sCtl[1] = 0; sCtl[2] = OBJ_LM_ST_ITER_CAP; sCtl[3] = 0; }
     __syncthreads();
 
     int cur = 0, iterations = 0, evaluations = 1;
     obj_lm_eval(a, tr, in, sX[0], sPrior, sRole, &sS[0]);
     const double cost0 = sS[0].c;
-    if (!isfinite(cost0)) { if (tid == 0) { sCtl[2] = 4; sCtl[0] = 1; } }
+    if (!isfinite(cost0)) { if (tid == 0) { sCtl[2] = OBJ_LM_ST_NONFINITE; sCtl[0] = 1; } }
     __syncthreads();
     bool stop = sCtl[0] != 0;
 
@@ -327,8 +300,8 @@ __global__ __launch_bounds__(OBJ_LM_NT) void k_object_lm(ObjLmArgs a) {
             for (int k = 0; k < K; ++k) { gd += sQ[k][0]; quad += sQ[k][1]; }
             const double pred = -2.0 * gd - quad;
             sQ[0][0] = pred;
-            if (sCtl[3] != 0 || !isfinite(pred)) { sCtl[2] = 4; sCtl[0] = 1; }
-            else if (pred <= a.ptol * S->c) { sCtl[2] = 1; sCtl[0] = 1; }
+            if (sCtl[3] != 0 || !isfinite(pred)) { sCtl[2] = OBJ_LM_ST_NONFINITE; sCtl[0] = 1; }
+            else if (pred <= a.ptol * S->c) { sCtl[2] = OBJ_LM_ST_CONVERGED; sCtl[0] = 1; }
             else {
                 double E[16];
                 obj_lm_se3_exp(sDelta, E);
@@ -349,7 +322,7 @@ __global__ __launch_bounds__(OBJ_LM_NT) void k_object_lm(ObjLmArgs a) {
             const double c = S->c, cn = sS[cur ^ 1].c;
             double lam = sLam;
             sCtl[1] = 0;
-            if (!isfinite(cn)) { sCtl[2] = 4; sCtl[0] = 1; }
+            if (!isfinite(cn)) { sCtl[2] = OBJ_LM_ST_NONFINITE; sCtl[0] = 1; }
             else {
                 const double rho = (c - cn) / pred;
                 if (rho > 1e-4) {
@@ -357,7 +330,7 @@ __global__ __launch_bounds__(OBJ_LM_NT) void k_object_lm(ObjLmArgs a) {
                     const double q = 2.0 * rho - 1.0;
                     lam = fmax(lam * fmax(1.0 / 3.0, 1.0 - q * q * q), 1e-12);
                 } else lam *= 4.0;
-                if (lam > 1e12) { sCtl[2] = 2; sCtl[0] = 1; }
+                if (lam > 1e12) { sCtl[2] = OBJ_LM_ST_STALLED; sCtl[0] = 1; }
                 sLam = lam;
             }
         }

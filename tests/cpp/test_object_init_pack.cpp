@@ -1,13 +1,14 @@
-// Host half of orcvio_msckf_object_init / orcvio_msckf_object_init_lm (orcvio_amd/csrc/object_init_pack.hpp: validation, packing,
+// Host half of orcvio_msckf_object_init / orcvio_msckf_object_init_lm (orcvio_amd/csrc/object_mapper_pack.hpp: validation, packing,
 // unpacking) on its own, built with -fsanitize=address,undefined by tests/test_object_init_mirror.py: every buffer is a heap block of
 // exactly the size the layout asks for, so a write or read past it is reported.  No device, no library.
 #include <cassert>
 #include <cstdio>
+#include <cstring>
 #include <limits>
 #include <memory>
 #include <vector>
 
-#include "../../orcvio_amd/csrc/object_init_pack.hpp"
+#include "../../orcvio_amd/csrc/object_mapper_pack.hpp"
 
 using namespace orcvio_amd;
 
@@ -39,6 +40,94 @@ static bool same(double a, double b) { return a == b || (a != a && b != b); }   
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); return 1; } } while (0)
 
+// Doubly faulty inputs: which of two simultaneous faults the two validators report.  One pair from each two refusal classes (null
+// argument, config, capacity of the handle, the per-track checks) and pairs within the per-track checks, for both entry points.  The
+// expected code and text of every row were recorded by running the same inputs through the validators of the three pack headers this
+// header replaced.
+static int double_faults() {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<Case> cs;
+    const int shapes[][2] = {{3, 4}, {16, 128}, {12, 47}, {5, 2}, {2, 3}};
+    for (auto& s : shapes) cs.emplace_back(s[0], s[1], 1000.0 * cs.size());
+    Case nan_pose(2, 3, 50.0), nan_bbox(12, 47, 60.0), nan_shape(5, 2, 70.0);
+    nan_pose.wTc[7] = nan; nan_bbox.bb.back() = nan; nan_shape.ms[1] = nan;
+    struct Args {
+        orcvio_object_init_config c{1, 3, 3};
+        orcvio_object_lm_config lc{1, 0, {1, 1, 1, 1}, 60, 1e-18};
+        std::vector<orcvio_object_track> t;
+        std::vector<const double*> m;
+        std::vector<orcvio_object_lm_prior> p;
+        std::vector<orcvio_object_init_result> r;
+        std::vector<orcvio_object_lm_result> l;
+        int n = 0;
+        bool no_cfg = false, no_lm_cfg = false, no_tracks = false, no_means = false, no_priors = false, no_results = false, no_lm_results = false;
+    };
+    struct Row { bool lm; const char* name; int rc; const char* why; void (*change)(Args&, const Case&, const Case&, const Case&); };
+    #define CH [](Args& a, const Case& np, const Case& nb, const Case& ns)
+    #define UNUSED (void)np; (void)nb; (void)ns;
+    const Row rows[] = {
+        // orcvio_msckf_object_init
+        {false, "null results + bad config", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_results = true; a.c.pose_form = 3; }},
+        {false, "null means + too many tracks", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_means = true; a.n = 65; }},
+        {false, "null config + a track without frames", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_cfg = true; a.t[0].n_frames = 0; }},
+        {false, "bad config + too many tracks", ORCVIO_ERR_INVALID, "config: pose_form 0..2, min_obs >= 0, min_kps >= 0", CH { UNUSED a.c.min_obs = -1; a.n = 65; }},
+        {false, "bad config + a track without keypoints", ORCVIO_ERR_INVALID, "config: pose_form 0..2, min_obs >= 0, min_kps >= 0", CH { UNUSED a.c.min_kps = -1; a.t[2].n_keypoints = 0; }},
+        {false, "too many tracks + 17 keypoints", ORCVIO_ERR_CAPACITY, "more tracks than the handle's capacity (max_features)", CH { UNUSED a.n = 65; a.t[0].n_keypoints = 17; }},
+        {false, "null result array + non-finite pose, one track", ORCVIO_ERR_INVALID, "null pointer in a track, mean keypoints or result",
+         CH { UNUSED a.t[4] = np.track(false); a.m[4] = np.mk.data(); a.r[4].kp_obs = nullptr; }},
+        {false, "no keypoints + 129 frames, one track", ORCVIO_ERR_INVALID, "a track without keypoints (the bbox-only initialiser is another function: not served)",
+         CH { UNUSED a.t[3].n_keypoints = 0; a.t[3].n_frames = 129; }},
+        {false, "non-finite pose in track 4 + null mean in track 1", ORCVIO_ERR_INVALID, "null pointer in a track, mean keypoints or result",
+         CH { UNUSED a.t[4] = np.track(false); a.m[4] = np.mk.data(); a.m[1] = nullptr; }},
+        {false, "no frames in track 3 + non-finite pose in track 4", ORCVIO_ERR_INVALID, "a track without frames",
+         CH { UNUSED a.t[4] = np.track(false); a.m[4] = np.mk.data(); a.t[3].n_frames = 0; }},
+        // orcvio_msckf_object_init_lm
+        {true, "null lm results + bad lm config", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_lm_results = true; a.lc.max_iter = 0; }},
+        {true, "null results + bad lm config", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.no_results = true; a.lc.max_iter = 0; }},
+        {true, "null init config + bad lm config", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.no_cfg = true; a.lc.ptol = -1.0; }},
+        {true, "null tracks + bad init config", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_tracks = true; a.c.pose_form = -1; }},
+        {true, "bad lm config + bad init config", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.lc.use_new_bbox_residual = 3; a.c.pose_form = 3; }},
+        {true, "no tracks + bad init config", ORCVIO_ERR_INVALID, "config: pose_form 0..2, min_obs >= 0, min_kps >= 0", CH { UNUSED a.n = 0; a.c.pose_form = 3; }},
+        {true, "no tracks + null init config", ORCVIO_ERR_INVALID, "config: pose_form 0..2, min_obs >= 0, min_kps >= 0", CH { UNUSED a.n = 0; a.no_cfg = true; }},
+        {true, "no tracks + bad lm config + bad init config", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.n = 0; a.lc.max_iter = 0; a.c.pose_form = 3; }},
+        {true, "negative count + bad init config", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.n = -1; a.c.pose_form = 3; }},
+        {true, "bad init config + too many tracks", ORCVIO_ERR_INVALID, "config: pose_form 0..2, min_obs >= 0, min_kps >= 0", CH { UNUSED a.c.min_obs = -1; a.n = 65; }},
+        {true, "bad lm config + a track without frames", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.lc.max_iter = 100001; a.t[0].n_frames = 0; }},
+        {true, "too many tracks + null bbox", ORCVIO_ERR_CAPACITY, "more tracks than the handle's capacity (max_features)", CH { UNUSED a.n = 65; a.t[0].frame_bbox = nullptr; }},
+        {true, "null bbox + null init result array, one track", ORCVIO_ERR_INVALID, "null pointer in a track, mean keypoints or result",
+         CH { UNUSED a.t[1].frame_bbox = nullptr; a.r[1].kp_cond = nullptr; }},
+        {true, "null lm result array + non-finite pose, one track", ORCVIO_ERR_INVALID, "null pointer in a track, prior or result of the optimiser",
+         CH { UNUSED a.t[4] = np.track(true); a.p[4] = np.prior(); a.l[4].kps = nullptr; }},
+        {true, "non-finite bbox + non-finite pose, one track", ORCVIO_ERR_INVALID, "non-finite number in a camera pose or a mean keypoint",
+         CH { UNUSED a.t[4] = np.track(true); a.p[4] = np.prior(); a.t[4].frame_bbox = nb.bb.data(); }},
+        {true, "non-finite mean shape in track 3 + null mean shape in track 4", ORCVIO_ERR_INVALID, "non-finite number in a mean shape or a bounding box",
+         CH { UNUSED a.t[3] = ns.track(true); a.p[3] = ns.prior(); a.p[4].mean_shape = nullptr; }},
+        {true, "non-finite bbox in track 2 + 129 frames in track 3", ORCVIO_ERR_INVALID, "non-finite number in a mean shape or a bounding box",
+         CH { UNUSED a.t[2] = nb.track(true); a.p[2] = nb.prior(); a.t[3].n_frames = 129; }},
+    };
+    #undef CH
+    #undef UNUSED
+    int failed = 0;
+    for (const Row& row : rows) {
+        Args a;
+        for (auto& c : cs) { a.t.push_back(c.track(row.lm)); a.m.push_back(c.mk.data()); a.p.push_back(c.prior()); a.r.push_back(c.result()); a.l.push_back(c.lm_result()); }
+        a.n = (int)cs.size();
+        row.change(a, nan_pose, nan_bbox, nan_shape);
+        const char* why = nullptr;
+        size_t nd = 1;
+        const int rc = row.lm ? obj_init_lm_validate(a.no_cfg ? nullptr : &a.c, a.no_lm_cfg ? nullptr : &a.lc, a.no_tracks ? nullptr : a.t.data(),
+                                                     a.no_priors ? nullptr : a.p.data(), a.n, a.no_results ? nullptr : a.r.data(),
+                                                     a.no_lm_results ? nullptr : a.l.data(), 64, &why, &nd)
+                              : obj_init_validate(a.no_cfg ? nullptr : &a.c, a.no_tracks ? nullptr : a.t.data(), a.no_means ? nullptr : a.m.data(), a.n,
+                                                  a.no_results ? nullptr : a.r.data(), 64, &why, &nd);
+        if (rc != row.rc || nd != 0 || !why || std::strcmp(why, row.why) != 0) {
+            std::printf("FAILED double fault '%s' (%s): %d \"%s\"\n", row.name, row.lm ? "object_init_lm" : "object_init", rc, why ? why : "(null)");
+            ++failed;
+        }
+    }
+    return failed;
+}
+
 int main() {
     const orcvio_object_init_config cfg{1, 3, 3};
     const orcvio_object_lm_config lcfg{1, 0, {1, 1, 1, 1}, 60, 1e-18};
@@ -68,7 +157,8 @@ int main() {
         std::unique_ptr<ObjLmTrack[]> recs(new ObjLmTrack[n]);
         std::unique_ptr<double[]> in(new double[nd]);
         for (size_t i = 0; i < nd; ++i) in[i] = -7.0;
-        obj_init_pack(with_lm ? tracks_lm.data() : tracks.data(), with_lm ? nullptr : mean.data(), with_lm ? priors.data() : nullptr, n, recs.get(), in.get());
+        const ObjMapIo io = with_lm ? obj_io_init(nullptr, priors.data(), results.data(), lm_results.data()) : obj_io_init(mean.data(), nullptr, results.data(), nullptr);
+        obj_map_pack(io, with_lm ? tracks_lm.data() : tracks.data(), n, recs.get(), in.get());
         size_t off = 0;
         for (int q = 0; q < n; ++q) {
             const Case& c = cs[q];
@@ -171,6 +261,7 @@ int main() {
     CHECK(obj_init_lm_validate(&cfg, &lcfg, tracks_lm.data(), priors.data(), n, results.data(), nullptr, 64, &why, &nd3) == ORCVIO_ERR_INVALID);
     CHECK(obj_init_lm_validate(&cfg, &lcfg, tracks_lm.data(), priors.data(), 65, results.data(), lm_results.data(), 64, &why, &nd3) == ORCVIO_ERR_CAPACITY);
     CHECK(obj_init_lm_validate(&cfg, &lcfg, nullptr, nullptr, 0, nullptr, nullptr, 64, &why, &nd3) == ORCVIO_OK && nd3 == 0);
+    CHECK(double_faults() == 0);
     std::printf("object init pack ok\n");
     return 0;
 }

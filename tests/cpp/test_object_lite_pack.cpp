@@ -1,13 +1,14 @@
-// Host half of the lite object mapper (orcvio_amd/csrc/object_lite_pack.hpp: validation, packing, unpacking) on its own, built with
+// Host half of the lite object mapper (orcvio_amd/csrc/object_mapper_pack.hpp: validation, packing, unpacking) on its own, built with
 // -fsanitize=address,undefined by tests/test_object_lite_pack.py: every buffer is a heap block of exactly the size the layout asks
 // for, so a write or read past it is reported; what the calls do not read (kps, frame_zs, frame_clone, mean_kps, the result's kps)
 // is NULL.  No device, no library.
 #include <cstdio>
+#include <cstring>
 #include <limits>
 #include <memory>
 #include <vector>
 
-#include "../../orcvio_amd/csrc/object_lite_pack.hpp"
+#include "../../orcvio_amd/csrc/object_mapper_pack.hpp"
 
 using namespace orcvio_amd;
 
@@ -28,6 +29,94 @@ struct Case {
 };
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); return 1; } } while (0)
+
+// Doubly faulty inputs: which of two simultaneous faults the three validators report.  One pair from each two refusal classes (null
+// argument, config, capacity of the handle, the per-track checks) and pairs within the per-track checks, for each entry point.  The
+// expected code and text of every row were recorded by running the same inputs through the validators of the three pack headers this
+// header replaced.
+static int double_faults() {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<Case> cs;
+    for (int F : {4, 128, 47, 2, 17}) cs.emplace_back(F, 1000.0 * cs.size());
+    Case nan_pose(3, 50.0), nan_start(128, 60.0);
+    nan_pose.wTc[7] = nan; nan_start.shape[2] = nan;
+    struct Args {
+        orcvio_object_lite_config c{1, 0, {1, 1}, 0, 60, 1e-18};
+        orcvio_object_init_lite_config ic{1, {1, 1, 1}};
+        std::vector<orcvio_object_track> t;
+        std::vector<const double*> m;
+        std::vector<orcvio_object_lm_prior> p;
+        std::vector<orcvio_object_init_lite_result> ir;
+        std::vector<orcvio_object_lm_result> r;
+        int n = 0;
+        bool no_cfg = false, no_init_cfg = false, no_tracks = false, no_means = false, no_priors = false, no_init_results = false, no_results = false;
+    };
+    enum { LM, INIT, INIT_LM };
+    struct Row { int call; const char* name; int rc; const char* why; void (*change)(Args&, const Case&, const Case&); };
+    #define CH [](Args& a, const Case& np, const Case& ns)
+    #define UNUSED (void)np; (void)ns;
+    const Row rows[] = {
+        // orcvio_msckf_object_lm_lite
+        {LM, "null results + bad config", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_results = true; a.c.max_iter = 0; }},
+        {LM, "null priors + too many tracks", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_priors = true; a.n = 65; }},
+        {LM, "null config + a track with keypoints", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_cfg = true; a.t[0].n_keypoints = 1; }},
+        {LM, "bad config + too many tracks", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.c.ptol = -1.0; a.n = 65; }},
+        {LM, "bad config + a track without frames", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.c.residual_weights[1] = 1.0 / 0.0; a.t[2].n_frames = 0; }},
+        {LM, "too many tracks + a track with keypoints", ORCVIO_ERR_CAPACITY, "more tracks than the handle's capacity (max_features)", CH { UNUSED a.n = 65; a.t[0].n_keypoints = 2; }},
+        {LM, "keypoints + 129 frames, one track", ORCVIO_ERR_INVALID, "a track with keypoints (the lite mapper serves bbox-only tracks: n_keypoints = 0)", CH { UNUSED a.t[3].n_keypoints = 1; a.t[3].n_frames = 129; }},
+        {LM, "null start + non-finite pose, one track", ORCVIO_ERR_INVALID, "null pointer in a track, mean shape or result", CH { UNUSED a.t[4] = np.track(); a.p[4] = np.prior(); a.t[4].shape = nullptr; }},
+        {LM, "non-finite start in track 1 + null result in track 3", ORCVIO_ERR_INVALID, "non-finite number in a start value, mean shape, camera pose or bounding box", CH { UNUSED a.t[1] = ns.track(); a.p[1] = ns.prior(); a.r[3].wTo = nullptr; }},
+        {LM, "non-finite pose in track 4 + 129 frames in track 1", ORCVIO_ERR_CAPACITY, "more than 128 frames", CH { UNUSED a.t[4] = np.track(); a.p[4] = np.prior(); a.t[1].n_frames = 129; }},
+        // orcvio_msckf_object_init_lite
+        {INIT, "null means + bad config", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_means = true; a.ic.pose_form = 3; }},
+        {INIT, "null results + too many tracks", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_init_results = true; a.n = 65; }},
+        {INIT, "negative count + a track without frames", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.n = -1; a.t[0].n_frames = 0; }},
+        {INIT, "bad config + too many tracks", ORCVIO_ERR_INVALID, "config: pose_form 0..2, finite bbox_scale", CH { UNUSED a.ic.bbox_scale[0] = 1.0 / 0.0; a.n = 65; }},
+        {INIT, "bad config + null bbox", ORCVIO_ERR_INVALID, "config: pose_form 0..2, finite bbox_scale", CH { UNUSED a.ic.pose_form = -1; a.t[2].frame_bbox = nullptr; }},
+        {INIT, "too many tracks + a track without frames", ORCVIO_ERR_CAPACITY, "more tracks than the handle's capacity (max_features)", CH { UNUSED a.n = 65; a.t[0].n_frames = 0; }},
+        {INIT, "null result array + non-finite pose, one track", ORCVIO_ERR_INVALID, "null pointer in a track, mean shape or result", CH { UNUSED a.t[4] = np.track(false); a.m[4] = np.ms.data(); a.ir[4].wTo = nullptr; }},
+        {INIT, "non-finite start (not read) + null mean, one track", ORCVIO_ERR_INVALID, "null pointer in a track, mean shape or result", CH { UNUSED a.t[1] = ns.track(); a.m[1] = nullptr; }},
+        {INIT, "no frames + keypoints, one track", ORCVIO_ERR_INVALID, "a track with keypoints (the lite mapper serves bbox-only tracks: n_keypoints = 0)", CH { UNUSED a.t[3].n_frames = 0; a.t[3].n_keypoints = 3; }},
+        // orcvio_msckf_object_init_lm_lite
+        {INIT_LM, "null lm config + bad init config", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_cfg = true; a.ic.pose_form = 3; }},
+        {INIT_LM, "null lm results + too many tracks", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_results = true; a.n = 65; }},
+        {INIT_LM, "null init results + a track with keypoints", ORCVIO_ERR_INVALID, "null argument", CH { UNUSED a.no_init_results = true; a.t[0].n_keypoints = 1; }},
+        {INIT_LM, "bad init config + bad lm config", ORCVIO_ERR_INVALID, "config: pose_form 0..2, finite bbox_scale", CH { UNUSED a.ic.pose_form = 3; a.c.max_iter = 0; }},
+        {INIT_LM, "no tracks + bad init config + bad lm config", ORCVIO_ERR_INVALID, "config: pose_form 0..2, finite bbox_scale", CH { UNUSED a.n = 0; a.ic.pose_form = 3; a.c.max_iter = 0; }},
+        {INIT_LM, "no tracks + bad lm config", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.n = 0; a.c.use_new_bbox_residual = -1; }},
+        {INIT_LM, "bad lm config + too many tracks", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights", CH { UNUSED a.c.max_iter = 0; a.n = 65; }},
+        {INIT_LM, "bad init config + a track without frames", ORCVIO_ERR_INVALID, "config: pose_form 0..2, finite bbox_scale", CH { UNUSED a.ic.bbox_scale[2] = 0.0 / 0.0; a.t[1].n_frames = 0; }},
+        {INIT_LM, "too many tracks + null pose", ORCVIO_ERR_CAPACITY, "more tracks than the handle's capacity (max_features)", CH { UNUSED a.n = 65; a.t[0].frame_wTc = nullptr; }},
+        {INIT_LM, "null lm result array + non-finite pose, one track", ORCVIO_ERR_INVALID, "null pointer in a track, mean shape or result", CH { UNUSED a.t[4] = np.track(false); a.p[4] = np.prior(); a.r[4].shape = nullptr; }},
+        {INIT_LM, "non-finite pose in track 4 + null init result in track 0", ORCVIO_ERR_INVALID, "null pointer in a track, mean shape or result", CH { UNUSED a.t[4] = np.track(false); a.p[4] = np.prior(); a.ir[0].wTo = nullptr; }},
+        {INIT_LM, "non-finite pose in track 0 + 129 frames in track 2", ORCVIO_ERR_INVALID, "non-finite number in a start value, mean shape, camera pose or bounding box", CH { UNUSED a.t[0] = np.track(false); a.p[0] = np.prior(); a.t[2].n_frames = 129; }},
+    };
+    #undef CH
+    #undef UNUSED
+    int failed = 0;
+    for (const Row& row : rows) {
+        Args a;
+        for (auto& c : cs) { a.t.push_back(c.track(row.call == LM)); a.m.push_back(c.ms.data()); a.p.push_back(c.prior()); a.ir.push_back(c.iresult()); a.r.push_back(c.result()); }
+        a.n = (int)cs.size();
+        row.change(a, nan_pose, nan_start);
+        const char* why = nullptr;
+        size_t nd = 1;
+        const orcvio_object_lite_config* cfg = a.no_cfg ? nullptr : &a.c;
+        const orcvio_object_init_lite_config* icfg = a.no_init_cfg ? nullptr : &a.ic;
+        const orcvio_object_track* t = a.no_tracks ? nullptr : a.t.data();
+        const orcvio_object_lm_prior* p = a.no_priors ? nullptr : a.p.data();
+        const orcvio_object_init_lite_result* ir = a.no_init_results ? nullptr : a.ir.data();
+        const orcvio_object_lm_result* r = a.no_results ? nullptr : a.r.data();
+        const int rc = row.call == LM     ? obj_lite_lm_validate(cfg, t, p, a.n, r, 64, &why, &nd)
+                       : row.call == INIT ? obj_lite_init_validate(icfg, t, a.no_means ? nullptr : a.m.data(), a.n, ir, 64, &why, &nd)
+                                          : obj_lite_init_lm_validate(icfg, cfg, t, p, a.n, ir, r, 64, &why, &nd);
+        if (rc != row.rc || nd != 0 || !why || std::strcmp(why, row.why) != 0) {
+            std::printf("FAILED double fault '%s' (call %d): %d \"%s\"\n", row.name, row.call, rc, why ? why : "(null)");
+            ++failed;
+        }
+    }
+    return failed;
+}
 
 int main() {
     const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -58,7 +147,8 @@ int main() {
         std::unique_ptr<ObjLmTrack[]> recs(new ObjLmTrack[n]);
         std::unique_ptr<double[]> in(new double[want]);
         for (size_t i = 0; i < want; ++i) in[i] = -1.0;
-        obj_lite_pack(with_start ? tracks.data() : bare.data(), [&](int q) { return means[q]; }, n, with_start != 0, recs.get(), in.get());
+        const ObjMapIo io = with_start ? obj_io_lite(nullptr, means.data(), nullptr, results.data()) : obj_io_lite(nullptr, means.data(), iresults.data(), nullptr);
+        obj_map_pack(io, with_start ? tracks.data() : bare.data(), n, recs.get(), in.get());
         size_t off = 0;
         for (int q = 0; q < n; ++q) {
             const Case& c = cs[q];
@@ -137,6 +227,7 @@ int main() {
     CHECK(obj_lite_init_lm_validate(&icfg, &cfg, nullptr, nullptr, 0, nullptr, nullptr, 64, &why, &nd3) == ORCVIO_OK && nd3 == 0);
     CHECK(obj_lite_lm_validate(nullptr, tracks.data(), priors.data(), n, results.data(), 64, &why, &nd3) == ORCVIO_ERR_INVALID);
     CHECK(obj_lite_init_lm_validate(&icfg, nullptr, tracks.data(), priors.data(), n, iresults.data(), results.data(), 64, &why, &nd3) == ORCVIO_ERR_INVALID);
+    CHECK(double_faults() == 0);
     std::printf("object lite pack ok\n");
     return 0;
 }

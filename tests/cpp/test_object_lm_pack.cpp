@@ -1,13 +1,14 @@
-// Host half of orcvio_msckf_object_lm (orcvio_amd/csrc/object_lm_pack.hpp: validation, packing, unpacking) on its own, built with
+// Host half of orcvio_msckf_object_lm (orcvio_amd/csrc/object_mapper_pack.hpp: validation, packing, unpacking) on its own, built with
 // -fsanitize=address,undefined by tests/test_object_lm_pack.py: every buffer is a heap block of exactly the size the layout asks
 // for, so a write or read past it is reported.  No device, no library.
 #include <cassert>
 #include <cstdio>
+#include <cstring>
 #include <limits>
 #include <memory>
 #include <vector>
 
-#include "../../orcvio_amd/csrc/object_lm_pack.hpp"
+#include "../../orcvio_amd/csrc/object_mapper_pack.hpp"
 
 using namespace orcvio_amd;
 
@@ -28,6 +29,67 @@ struct Case {
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); return 1; } } while (0)
 
+// Doubly faulty inputs: which of two simultaneous faults the validator reports.  One pair from each two refusal classes (null
+// argument, config, capacity of the handle, the per-track checks) and pairs within the per-track checks.  The expected code and text
+// of every row were recorded by running the same inputs through the validators of the three pack headers this header replaced.
+static int double_faults() {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<Case> cs;
+    const int shapes[][2] = {{3, 4}, {16, 128}, {12, 47}, {5, 2}, {2, 3}};
+    for (auto& s : shapes) cs.emplace_back(s[0], s[1], 1000.0 * cs.size());
+    Case nan_pose(2, 3, 50.0), nan_start(16, 128, 60.0);
+    nan_pose.wTc[7] = nan; nan_start.kps.back() = nan;
+    struct Args {
+        orcvio_object_lm_config c{1, 0, {1, 1, 1, 1}, 60, 1e-18};
+        std::vector<orcvio_object_track> t;
+        std::vector<orcvio_object_lm_prior> p;
+        std::vector<orcvio_object_lm_result> r;
+        int n = 0;
+        bool no_cfg = false, no_tracks = false, no_priors = false, no_results = false;
+    };
+    struct Row { const char* name; int rc; const char* why; void (*change)(Args&, const Case&, const Case&); };
+    const Row rows[] = {
+        {"null results + bad config", ORCVIO_ERR_INVALID, "null argument", [](Args& a, const Case&, const Case&) { a.no_results = true; a.c.max_iter = 0; }},
+        {"null priors + too many tracks", ORCVIO_ERR_INVALID, "null argument", [](Args& a, const Case&, const Case&) { a.no_priors = true; a.n = 65; }},
+        {"null config + a track without frames", ORCVIO_ERR_INVALID, "null argument", [](Args& a, const Case&, const Case&) { a.no_cfg = true; a.t[0].n_frames = 0; }},
+        {"negative count + bad config", ORCVIO_ERR_INVALID, "null argument", [](Args& a, const Case&, const Case&) { a.n = -1; a.c.ptol = -1.0; }},
+        {"bad config + too many tracks", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights",
+         [](Args& a, const Case&, const Case&) { a.c.max_iter = 0; a.n = 65; }},
+        {"bad config + a track without keypoints", ORCVIO_ERR_INVALID, "config: max_iter 1..100000, finite ptol >= 0, use_new_bbox_residual 0..2, finite weights",
+         [](Args& a, const Case&, const Case&) { a.c.ptol = -1.0; a.t[2].n_keypoints = 0; }},
+        {"too many tracks + a track without frames", ORCVIO_ERR_CAPACITY, "more tracks than the handle's capacity (max_features)",
+         [](Args& a, const Case&, const Case&) { a.n = 65; a.t[0].n_frames = 0; }},
+        {"null bbox + non-finite start, one track", ORCVIO_ERR_INVALID, "null pointer in a track, prior or result",
+         [](Args& a, const Case&, const Case& ns) { a.t[1] = ns.track(); a.p[1] = ns.prior(); a.t[1].frame_bbox = nullptr; }},
+        {"null result + non-finite pose, one track", ORCVIO_ERR_INVALID, "null pointer in a track, prior or result",
+         [](Args& a, const Case& np, const Case&) { a.t[4] = np.track(); a.p[4] = np.prior(); a.r[4].shape = nullptr; }},
+        {"17 keypoints + no frames, one track", ORCVIO_ERR_INVALID, "a track without frames", [](Args& a, const Case&, const Case&) { a.t[2].n_keypoints = 17; a.t[2].n_frames = 0; }},
+        {"17 keypoints + 129 frames, one track", ORCVIO_ERR_CAPACITY, "more than 16 keypoints", [](Args& a, const Case&, const Case&) { a.t[2].n_keypoints = 17; a.t[2].n_frames = 129; }},
+        {"no keypoints + 129 frames, one track", ORCVIO_ERR_INVALID, "a track without keypoints (bbox-only tracks are the reference's lite functor: not served)",
+         [](Args& a, const Case&, const Case&) { a.t[3].n_keypoints = 0; a.t[3].n_frames = 129; }},
+        {"non-finite pose in track 4 + 129 frames in track 1", ORCVIO_ERR_CAPACITY, "more than 128 frames",
+         [](Args& a, const Case& np, const Case&) { a.t[4] = np.track(); a.p[4] = np.prior(); a.t[1].n_frames = 129; }},
+        {"non-finite start in track 1 + null prior in track 3", ORCVIO_ERR_INVALID, "non-finite number in a start value, prior, camera pose or bounding box",
+         [](Args& a, const Case&, const Case& ns) { a.t[1] = ns.track(); a.p[1] = ns.prior(); a.p[3].mean_kps = nullptr; }},
+    };
+    int failed = 0;
+    for (const Row& row : rows) {
+        Args a;
+        for (auto& c : cs) { a.t.push_back(c.track()); a.p.push_back(c.prior()); a.r.push_back(c.result()); }
+        a.n = (int)cs.size();
+        row.change(a, nan_pose, nan_start);
+        const char* why = nullptr;
+        size_t nd = 1;
+        const int rc = obj_lm_validate(a.no_cfg ? nullptr : &a.c, a.no_tracks ? nullptr : a.t.data(), a.no_priors ? nullptr : a.p.data(), a.n,
+                                       a.no_results ? nullptr : a.r.data(), 64, &why, &nd);
+        if (rc != row.rc || nd != 0 || !why || std::strcmp(why, row.why) != 0) {
+            std::printf("FAILED double fault '%s': %d \"%s\"\n", row.name, rc, why ? why : "(null)");
+            ++failed;
+        }
+    }
+    return failed;
+}
+
 int main() {
     orcvio_object_lm_config cfg{1, 0, {1, 1, 1, 1}, 60, 1e-18};
     std::vector<Case> cs;
@@ -47,7 +109,7 @@ int main() {
     // pack into blocks of exactly the announced size
     std::unique_ptr<ObjLmTrack[]> recs(new ObjLmTrack[n]);
     std::unique_ptr<double[]> in(new double[nd]);
-    obj_lm_pack(tracks.data(), priors.data(), n, recs.get(), in.get());
+    obj_map_pack(obj_io_lm(priors.data(), results.data()), tracks.data(), n, recs.get(), in.get());
     size_t off = 0;
     for (int q = 0; q < n; ++q) {
         const Case& c = cs[q];
@@ -104,6 +166,7 @@ int main() {
     CHECK(obj_lm_validate(&cfg, tracks.data(), priors.data(), 65, results.data(), 64, &why, &nd3) == ORCVIO_ERR_CAPACITY);   // (refused before track 6 would be read)
     CHECK(obj_lm_validate(&cfg, nullptr, nullptr, 0, nullptr, 64, &why, &nd3) == ORCVIO_OK && nd3 == 0);
     CHECK(obj_lm_validate(nullptr, tracks.data(), priors.data(), n, results.data(), 64, &why, &nd3) == ORCVIO_ERR_INVALID);
+    CHECK(double_faults() == 0);
     std::printf("object lm pack ok\n");
     return 0;
 }

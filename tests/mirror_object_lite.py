@@ -23,8 +23,8 @@ import dataclasses
 import numpy as np
 
 from oracle import mirror_objects as mo
-
-STATUS_CONVERGED, STATUS_STALLED, STATUS_MAX_ITER, STATUS_NON_FINITE = 1, 2, 3, 4
+import mirror_object_lm
+from mirror_object_lm import STATUS_CONVERGED, STATUS_STALLED, STATUS_MAX_ITER, STATUS_NON_FINITE   # noqa: F401 (re-exported)
 
 
 @dataclasses.dataclass
@@ -70,8 +70,6 @@ def retract(wTo, shape, d, left):
 def solve(obj, mean_shape, cfg: Config, first_accepted=False):
     """obj: synth.ObjectTrack-shaped start (wTo rigid; its kps and the frames' zs are ignored).  Returns dict(wTo, shape, cost0, cost,
     iterations, evaluations, status).  first_accepted: stop behind the first accepted trial point (status 3)."""
-    wTo = np.array(obj.wTo, dtype=np.float64)
-    shape = np.array(obj.shape, dtype=np.float64)
     mean_shape = np.asarray(mean_shape, dtype=np.float64)
     frames = bare_frames(obj.frames)
 
@@ -80,47 +78,9 @@ def solve(obj, mean_shape, cfg: Config, first_accepted=False):
             r, J = residual_jacobian(T, v, frames, mean_shape, cfg)
             return J.T @ J, J.T @ r, float(r @ r)
 
-    A, g, c = evaluate(wTo, shape)
-    out = dict(cost0=c, evaluations=1, iterations=0, status=STATUS_MAX_ITER)
-    lam = 1e-3
-    D = np.zeros(9)
-    if not np.isfinite(c):
-        out['status'] = STATUS_NON_FINITE
-    else:
-        for _ in range(cfg.max_iter):
-            D = np.maximum(D, np.sqrt(np.diag(A)))
-            with np.errstate(all='ignore'):
-                try:
-                    d = np.linalg.solve(A + lam * np.diag(D * D), -g)
-                except np.linalg.LinAlgError:
-                    d = np.full(9, np.nan)
-                pred = -2.0 * (g @ d) - d @ A @ d
-            if not np.isfinite(pred):
-                out['status'] = STATUS_NON_FINITE
-                break
-            if pred <= cfg.ptol * c:
-                out['status'] = STATUS_CONVERGED
-                break
-            Tn, vn = retract(wTo, shape, d, cfg.left)
-            An, gn, cn = evaluate(Tn, vn)
-            out['evaluations'] += 1
-            out['iterations'] += 1
-            if not np.isfinite(cn):
-                out['status'] = STATUS_NON_FINITE
-                break
-            rho = (c - cn) / pred
-            accepted = rho > 1e-4
-            if accepted:
-                wTo, shape, A, g, c = Tn, vn, An, gn, cn
-                lam = max(lam * max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3), 1e-12)
-            else:
-                lam *= 4.0
-            if lam > 1e12:
-                out['status'] = STATUS_STALLED
-                break
-            if accepted and first_accepted:
-                break
-    out.update(wTo=wTo, shape=shape, cost=c)
+    state0 = (np.array(obj.wTo, dtype=np.float64), np.array(obj.shape, dtype=np.float64))
+    (wTo, shape), out = mirror_object_lm.lm_iterate(evaluate, lambda st, d: retract(*st, d, cfg.left), state0, cfg.max_iter, cfg.ptol, first_accepted)
+    out.update(wTo=wTo, shape=shape)
     return out
 
 

@@ -75,28 +75,19 @@ def residual_jacobian(wTo, shape, kps, frames, mean_shape, mean_kps, cfg: Config
     return np.concatenate([wt * res, rd, rs]), np.vstack([wt[:, None] * Hf, Jd, Js])
 
 
-def solve(obj, mean_shape, mean_kps, cfg: Config):
-    """obj: synth.ObjectTrack-shaped start (wTo rigid).  Returns dict(wTo, shape, kps, cost0, cost, iterations, evaluations, status)."""
-    wTo = np.array(obj.wTo, dtype=np.float64)
-    shape = np.array(obj.shape, dtype=np.float64)
-    kps = np.array(obj.kps, dtype=np.float64).reshape(-1, 3)
-    mean_shape = np.asarray(mean_shape, dtype=np.float64)
-    mean_kps = np.asarray(mean_kps, dtype=np.float64).reshape(-1, 3)
-    frames = obj.frames
-
-    def evaluate(T, v, m):
-        with np.errstate(all='ignore'):
-            r, J = residual_jacobian(T, v, m, frames, mean_shape, mean_kps, cfg)
-            return J.T @ J, J.T @ r, float(r @ r)
-
-    A, g, c = evaluate(wTo, shape, kps)
+def lm_iterate(evaluate, retract, state0, max_iter, ptol, first_accepted=False):
+    """The iteration of include/orcvio_msckf.h over any state tuple: evaluate(*state) -> (A, g, c), retract(state, d) -> state.
+    Returns (state, dict(cost0, cost, iterations, evaluations, status)).  first_accepted: stop behind the first accepted trial
+    point (status 3)."""
+    state = state0
+    A, g, c = evaluate(*state)
     out = dict(cost0=c, evaluations=1, iterations=0, status=STATUS_MAX_ITER)
     lam = 1e-3
     D = np.zeros(len(g))
     if not np.isfinite(c):
         out['status'] = STATUS_NON_FINITE
     else:
-        for _ in range(cfg.max_iter):
+        for _ in range(max_iter):
             D = np.maximum(D, np.sqrt(np.diag(A)))
             with np.errstate(all='ignore'):
                 try:
@@ -107,26 +98,46 @@ def solve(obj, mean_shape, mean_kps, cfg: Config):
             if not np.isfinite(pred):
                 out['status'] = STATUS_NON_FINITE
                 break
-            if pred <= cfg.ptol * c:
+            if pred <= ptol * c:
                 out['status'] = STATUS_CONVERGED
                 break
-            Tn, vn, mn = retract(wTo, shape, kps, d, cfg.left)
-            An, gn, cn = evaluate(Tn, vn, mn)
+            trial = retract(state, d)
+            An, gn, cn = evaluate(*trial)
             out['evaluations'] += 1
             out['iterations'] += 1
             if not np.isfinite(cn):
                 out['status'] = STATUS_NON_FINITE
                 break
             rho = (c - cn) / pred
-            if rho > 1e-4:
-                wTo, shape, kps, A, g, c = Tn, vn, mn, An, gn, cn
+            accepted = rho > 1e-4
+            if accepted:
+                state, A, g, c = trial, An, gn, cn
                 lam = max(lam * max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3), 1e-12)
             else:
                 lam *= 4.0
             if lam > 1e12:
                 out['status'] = STATUS_STALLED
                 break
-    out.update(wTo=wTo, shape=shape, kps=kps, cost=c)
+            if accepted and first_accepted:
+                break
+    out['cost'] = c
+    return state, out
+
+
+def solve(obj, mean_shape, mean_kps, cfg: Config):
+    """obj: synth.ObjectTrack-shaped start (wTo rigid).  Returns dict(wTo, shape, kps, cost0, cost, iterations, evaluations, status)."""
+    mean_shape = np.asarray(mean_shape, dtype=np.float64)
+    mean_kps = np.asarray(mean_kps, dtype=np.float64).reshape(-1, 3)
+    frames = obj.frames
+
+    def evaluate(T, v, m):
+        with np.errstate(all='ignore'):
+            r, J = residual_jacobian(T, v, m, frames, mean_shape, mean_kps, cfg)
+            return J.T @ J, J.T @ r, float(r @ r)
+
+    state0 = (np.array(obj.wTo, dtype=np.float64), np.array(obj.shape, dtype=np.float64), np.array(obj.kps, dtype=np.float64).reshape(-1, 3))
+    (wTo, shape, kps), out = lm_iterate(evaluate, lambda st, d: retract(*st, d, cfg.left), state0, cfg.max_iter, cfg.ptol)
+    out.update(wTo=wTo, shape=shape, kps=kps)
     return out
 
 

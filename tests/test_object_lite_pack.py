@@ -1,4 +1,4 @@
-"""Host half of the lite object mapper (validation, packing, unpacking: orcvio_amd/csrc/object_lite_pack.hpp) as a stand-alone
+"""Host half of the lite object mapper (validation, packing, unpacking: orcvio_amd/csrc/object_mapper_pack.hpp) as a stand-alone
 program under AddressSanitizer and UndefinedBehaviorSanitizer, on the CPU (tests/cpp/test_object_lite_pack.cpp)."""
 import os
 import subprocess

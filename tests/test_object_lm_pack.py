@@ -1,4 +1,4 @@
-"""Host half of orcvio_msckf_object_lm (validation, packing, unpacking: orcvio_amd/csrc/object_lm_pack.hpp) as a stand-alone
+"""Host half of orcvio_msckf_object_lm (validation, packing, unpacking: orcvio_amd/csrc/object_mapper_pack.hpp) as a stand-alone
 program under AddressSanitizer and UndefinedBehaviorSanitizer, on the CPU (tests/cpp/test_object_lm_pack.cpp)."""
 import os
 import subprocess
