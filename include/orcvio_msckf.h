@@ -1220,7 +1220,6 @@ int32_t orcvio_msckf_io_step_frame_ex(orcvio_msckf_handle* h, const orcvio_msckf
 /* ---- Environment switches (read once per process; diagnostics and A/B measurements -- every one of them leaves the results unchanged) ----
  *   ORCVIO_COMM_TIMEOUT_S   bound of every wait another rank can strand, seconds (default 180)
  *   ORCVIO_IPC_WAIT_S       ipc transport: bound of the device-side wait for a peer's block, seconds (default 20, at most the above)
- *   ORCVIO_IPC_COARSE       1: ipc transport's gather buffer in plain (coarse-grained) hipMalloc memory instead of fine-grained / uncached
  *   ORCVIO_RCCL_LIB         path of the RCCL library to dlopen first (then librccl.so.1 / librccl.so by the loader's search -- an already
  *                           loaded one, e.g. torch's bundled copy, wins --, then /opt/rocm/lib)
  *   ORCVIO_FRAME_OVERLAP    0: orcvio_msckf_io_update_frame runs its two halves one behind the other
@@ -1230,32 +1229,20 @@ int32_t orcvio_msckf_io_step_frame_ex(orcvio_msckf_handle* h, const orcvio_msckf
  *                           M (M12 = M1 + L_a^T A' L_a: the same sequential update, by Woodbury) and runs on the objects' stream beside the
  *                           feature half's solve and commit -- 7 % of the config-3 frame; equal to the two calls to rounding (1e-10;
  *                           DESIGN.md 3.6), counted in orcvio_msckf_counters [6]
- *   ORCVIO_FRONT_U          1 (read at create): U = [A; b^T] L_a by the feature workgroups of k_front behind their Grams instead of the
- *                           k_gemm_asmA launch (bit-identical; measured 6 us slower per update: docs/LAB_NOTES.md); default 0
  *   ORCVIO_FUSE_FINISH      (read at create) P+ = s2 Z^T Z, dx and an object update's gate by finish workgroups of the factorisation + solve
  *                           launch instead of a k_finish_sqrt launch behind it (bit-identical either way): 1 (default) in the chained frame
  *                           call, both halves (0.167-0.170 -> 0.160 ms); 2 in every update whose solve takes the look-ahead form (measured
  *                           ~2 us slower per queued update); 0 never
- *   ORCVIO_FRAME_GRAPH      1: the frame call's feature half as a replayed launch graph (default: plain launches, with the objects'
- *                           compression enqueued in the middle of them: a graph's completion marker delays the object solve by ~14 us)
- *   ORCVIO_FRAME_EVENT_JOIN 1: the frame call's object solve joins the compression's stream with an event (default: its first product
- *                           polls the compression's completion word: a stream-level join costs ~10 us of dispatch even when long satisfied)
  *   ORCVIO_OBJ_FUSED        0: object tracks always through the three-launch compression over materialised rows (default 1: the one-launch
  *                           compression k_obj_fused whenever every track qualifies, orcvio_msckf_counters [5])
  *   ORCVIO_FUSED_STAMPS     phase stamps of k_obj_fused (object 0) on stderr
  *   ORCVIO_FUSED_TOL        k_obj_fused's pivot tolerance relative to the largest pivot (default 1e-10; tests of its verification step)
- *   ORCVIO_EARLY_INGEST     0: the whole arena is pulled by the ingest node of the launch graph (no early pull under the validation)
- *   ORCVIO_REV_PRIOR        0: plain Cholesky of the prior (M keeps its 15 IMU columns)
- *   ORCVIO_SPLIT_TRACKS     track count from which the tracks front end is two launches over E scratch in HBM (k_feature_e + k_feature_gate);
- *                           default 0 = never (round 5: no faster than k_feature at 2 000 tracks, 85 MB of scratch traffic per update)
- *   ORCVIO_FUSED_FRONT, ORCVIO_FUSED_SOLVE   0: the forked seven-launch front end / the two-launch solve (same as the options)
  *   ORCVIO_BLK2             0 (read at create): windows beyond the register-resident factorisations (n > 224: 34 .. 60 clones) through the LDS-panel
  *                           Cholesky and k_trsm_rl (0.95-2.1 ms per update) instead of the 2 x 2 block factorisation out of the register kernels
  *                           (0.26-0.41 ms); same results to rounding
- *   ORCVIO_LA_SOLVE         0 / 2 / 3: default of ORCVIO_OPT_LOOKAHEAD_SOLVE;  ORCVIO_LA_SPIN: polls before a wait inside k_potrf_solve_la gives up
+ *   ORCVIO_LA_SPIN          polls before a wait inside k_potrf_solve_la gives up
  *                           (default 4 M, seconds; 0 makes every hand-off fail at once: the test of the fall-back)
  *   ORCVIO_FRONT_SPIN, ORCVIO_IO_SPIN_SECONDS   bounds of the in-launch hand-off of k_front (polls) and of the host's flag spin
- *   ORCVIO_OBJ_INGEST, ORCVIO_OBJ_PUBLISH   object update: 0 = copy engine instead of the ingest kernel; 1 = results through the flag word
  *   ORCVIO_TIMING           host wall times of the parts of the one-shot calls on stderr
  *   ORCVIO_ASM_DBG, ORCVIO_POTRF_ABLATE, ORCVIO_POTRF_COLD   kernel diagnostics (scripts/gpu_*.py) */
 

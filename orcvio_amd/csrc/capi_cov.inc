@@ -410,11 +410,11 @@ int32_t orcvio_msckf_cov_prefactor(orcvio_msckf_handle* h) {
     const int ld = round_up(n + 1, 16);
     hipStream_t s = h->stream;
     // L(i, j) = R[j * ld + i] (k_potrf_reg writes the upper factor R, P = R^T R, full 16 x 16 tiles, zeros below the diagonal): the
-    // layout of the resident factor S (S(i, j) = d_Sres[i + j * fac_ld]).  With the reversed factorisation (rev_prior_opt) the
+    // layout of the resident factor S (S(i, j) = d_Sres[i + j * fac_ld]).  With the reversed factorisation the
     // factor comes out with its rows in reverse order: it is written to scratch and flipped into place, and its last 15 columns
     // are zero in the active rows (fac_tail)
     const double eps = 2.220446049250313e-16;
-    const bool rev = h->rev_prior_opt && h->fused_solve && n - 15 >= 16;
+    const bool rev = h->fused_solve && n - 15 >= 16;
     double* dst = rev ? h->d_KG : h->d_Stmp;   // (d_KG: scratch of the optional outputs, free between updates)
     { const int rp = launch_potrf_reg_slots(s, h->d_Pres, n, n, 8.0 * eps, dst, ld, h->d_DinvP, h->d_info, 1, rev ? 1 : 0); if (rp != ORCVIO_OK) return rp; }
     if (rev) hipLaunchKernelGGL(k_fac_flip, dim3((n * ld + 255) / 256), dim3(256), 0, s, (const double*)dst, ld, n, h->d_Stmp, ld);

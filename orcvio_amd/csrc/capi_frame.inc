@@ -229,12 +229,11 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     hipStream_t s = h->stream;
     h->last_stream = s;
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }
-    // ---- features: ONE graph launch (ingest, the five kernels, results + commit + flag), as orcvio_msckf_io_update(commit)
+    // ---- features: ingest, the five kernels, results + commit + flag, as orcvio_msckf_io_update(commit)
     // The feature half of a FRAME goes out as plain launches, not as a replayed graph: behind a hipGraphLaunch the stream's next plain
     // launch starts ~14 us late (the graph's completion marker; measured with and without the cross-stream join below), and the object
     // solve is such a launch -- 14 us of the frame.  Seven plain launches cost the host ~15 us more to enqueue, which it has (the
-    // device is busy with the tracks for 40 us).  ORCVIO_FRAME_GRAPH=1: the replayed graph, as orcvio_msckf_io_update takes it.
-    static const bool frame_graph = [] { const char* e = dbg_getenv("ORCVIO_FRAME_GRAPH"); return e && atoi(e) != 0; }();
+    // device is busy with the tracks for 40 us).
     // ... and the objects' compression is enqueued in the MIDDLE of them: right behind the tracks' launch (k_front: 40 us of device time),
     // ahead of the feature update's remaining five launches, which the host has 40 us to put out.  The compression then starts ~20 us
     // earlier and is done well before the feature half; possible when every object takes the one-launch compression (k_obj_fused), whose
@@ -250,19 +249,19 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     // (orcvio_msckf_io_stage_object_tracks ahead of this call: the scan and the staging of these very tracks are done -- ~14 us of host time
     //  that stood between the tracks' launch and the compression's)
     ObjPrestage* ps = h->prestage ? static_cast<ObjPrestage*>(h->prestage.get()) : nullptr;
-    const bool pre = ps && h->prestage_valid && !frame_graph && ps->tracks == tracks && ps->n_tracks == n_tracks && ps->N == oN && ps->leg_dim == oflags->leg_dim &&
+    const bool pre = ps && h->prestage_valid && ps->tracks == tracks && ps->n_tracks == n_tracks && ps->N == oN && ps->leg_dim == oflags->leg_dim &&
                      std::memcmp(&ps->efl, efl, sizeof(*efl)) == 0 && oNAP <= h->NAP_max;
     h->prestage_valid = false;   // (one use)
     if (pre) {
         early_pl = ps->pl; early_dof = ps->dof; early_Fmax = ps->Fmax; early_nd = ps->nd; early_ni = ps->ni;
         early = true;
         h->cnt_prestaged++;
-    } else if (!frame_graph && n_tracks > 0 && (oflags->leg_dim == 22 || oflags->leg_dim == 46) && oNAP <= h->NAP_max) {
+    } else if (n_tracks > 0 && (oflags->leg_dim == 22 || oflags->leg_dim == 46) && oNAP <= h->NAP_max) {
         if (objects_tracks_scan(h, oN, tracks, n_tracks, h->obj_use, early_pl, &early_dof, &early_Fmax, &early_nd, &early_ni) == ORCVIO_OK &&
             obj_fused_eligible(h, tracks, h->obj_use, oN, early_pl.no_max)) early = true;
     }
     // the chained object solve (above): opt-in, for frames whose objects all take the one-launch compression and commit in the call
-    bool chain = h->frame_chain && early && !frame_graph && commit_objects != 0 && !h->ekf_mode && h->n_extra == 0 && oflags->leg_dim == fflags.leg_dim &&
+    bool chain = h->frame_chain && early && commit_objects != 0 && !h->ekf_mode && h->n_extra == 0 && oflags->leg_dim == fflags.leg_dim &&
                  oflags->noise_feature == fflags.noise_feature &&   // (M12 = M1 + L_a^T A' L_a holds for ONE sigma)
                  fused_solve_active(h) && la_solve_active(h, (h->kf - h->tail + 15) / 16, false) && front_fused_active(h, false);
     const bool signal_done = !chain;   // (the chained solve runs on the compression's own stream: no completion word to poll)
@@ -290,8 +289,9 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     cf.fin_frame = chain;   // (its P+ / dx by finish workgroups of its solve launch: finish_fused_active)
     cf.info_keep = h->d_step_words;   // (its epilogue keeps a copy of its status words for the object half's commit)
     if (chain) { cf.mark_M_word = h->d_chain_words; cf.mark_M_val = w1; }   // (launch_solve_stage(ST_FORM_M) stores it)
-    if (frame_graph) rc = run_with_graph(h, h->g_io, io_signature(h, s, false, true, cf), s, [&](bool) { return io_enqueue(h, s, false, true, cf); });
-    else { cf.mid = early ? &mid : nullptr; rc = io_enqueue(h, s, false, true, cf); h->cnt_plain_runs++; }
+    cf.mid = early ? &mid : nullptr;
+    rc = io_enqueue(h, s, false, true, cf);
+    h->cnt_plain_runs++;
     h->A_deferred = front_defers_assembly(h, false);
     tmark(1);
     if (chain && rc == ORCVIO_OK) {   // the word behind the feature half's epilogue (its commit): a launch of its own, behind the kernel boundary
@@ -350,11 +350,9 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
         chain = false;
         // the object solve: behind the features' commit (stream order) AND the compression.  The one-launch compression ends with a
         // one-word launch (k_obj_done) that stores its sequence number; the solve's first product polls that word -- no stream-level join,
-        // which costs ~10 us of dispatch on this stream even when the event fired long ago (ORCVIO_FRAME_EVENT_JOIN=1: the event, as the
-        // general path takes it)
-        static const bool event_join = [] { const char* e = dbg_getenv("ORCVIO_FRAME_EVENT_JOIN"); return e && atoi(e) != 0; }();
+        // which costs ~10 us of dispatch on this stream even when the event fired long ago (the general path takes the event)
         UpdateCall co;   // the object half's solve
-        if (h->obj_last_fused && !event_join && signal_done) { co.join_wait = h->d_obj_done; co.join_expect = h->obj_done_total; }
+        if (h->obj_last_fused && signal_done) { co.join_wait = h->d_obj_done; co.join_expect = h->obj_done_total; }
         else {
             if (!early || !signal_done) HIPCHK(hipEventRecord(h->ev_obj, h->obj_stream));   // (!signal_done: the chain was dropped after the compression went out without its event)
             HIPCHK(hipStreamWaitEvent(s, h->ev_obj, 0));

@@ -196,16 +196,9 @@ static int fetch_copies(orcvio_msckf_handle* h, hipStream_t s, const FetchCopy* 
 
 // host-pinned (device-visible) -> HBM by a kernel instead of a copy-engine transfer: lower latency for the few hundred KB an
 // update moves, and it can be a node of a captured graph like any other launch
-static int launch_ingest(orcvio_msckf_handle* h, hipStream_t s, const void* src_dev, void* dst, size_t bytes, bool kernel = true,
+static int launch_ingest(orcvio_msckf_handle* h, hipStream_t s, const void* src_dev, void* dst, size_t bytes,
                          int* zero = nullptr, unsigned zero_mask = 0u) {
     if (bytes == 0) return ORCVIO_OK;
-    if (!kernel) {   // the copy engine (pinned memory: asynchronous)
-        HIPCHK(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyHostToDevice, s));
-        if (zero)
-            for (int i = 0; i < 32; ++i)
-                if (zero_mask >> i & 1u) HIPCHK(hipMemsetAsync(zero + i, 0, sizeof(int), s));
-        return ORCVIO_OK;
-    }
     const size_t n16 = (bytes + 15) / 16;
     int grid = (int)((n16 + 255) / 256);
     if (grid > 4 * h->n_cus) grid = 4 * h->n_cus;
@@ -213,19 +206,6 @@ static int launch_ingest(orcvio_msckf_handle* h, hipStream_t s, const void* src_
     hipLaunchKernelGGL(k_ingest, dim3(grid), dim3(256), 0, s, reinterpret_cast<const u32x4*>(src_dev), reinterpret_cast<u32x4*>(dst), n16, zero, zero_mask);
     HIPCHK(hipGetLastError());
     return ORCVIO_OK;
-}
-static bool obj_ingest_kernel() {   // diagnostics: ORCVIO_OBJ_INGEST=0 moves the inputs of an object update with the copy engine
-    static const bool v = [] { const char* e = dbg_getenv("ORCVIO_OBJ_INGEST"); return e ? atoi(e) != 0 : true; }();
-    return v;
-}
-// The results of a one-shot object update: device-to-host copy + stream synchronisation (default), or ORCVIO_OBJ_PUBLISH=1:
-// k_epilogue + the flag, as the feature updates do.  Measured on one box (scripts/gpu_obj_timing.py, config 3, median ms, host
-// buffers / resident prior): ingest kernel + copy out 0.2118 / 0.1625, ingest kernel + flag 0.2111 / 0.1684, copy engine both
-// ways 0.2175 / 0.1684 -- the object update is a chain of a dozen plain launches whose enqueue the host is still busy with
-// when the first kernels run, so the wake-up is not what it waits for.
-static bool obj_publish_kernel() {
-    static const bool v = [] { const char* e = dbg_getenv("ORCVIO_OBJ_PUBLISH"); return e ? atoi(e) != 0 : false; }();
-    return v;
 }
 // ---- create / destroy ---------------------------------------------------------------------
 static void free_all(orcvio_msckf_handle* h) {
@@ -236,7 +216,7 @@ static void free_all(orcvio_msckf_handle* h) {
                     h->d_W, h->d_Y, h->d_KG, h->d_Gobj, h->d_RF, h->d_DinvF, h->d_Yobj, h->d_objH,
                     h->d_obj_gamma, h->d_obj_i, h->d_obj_accept, h->d_T3, h->d_Xobs, h->d_S,
                     h->d_Pres, h->d_Ptmp, h->d_Sres, h->d_Stmp, h->d_covT, h->d_covmap, h->d_skip, h->d_tri_valid, h->d_tri_flags, h->d_tri_init, h->d_tri_sol, h->d_tri_cost, h->d_sync, h->d_la_rdy, h->d_U2, h->d_M2, h->d_RM2, h->d_DinvM2, h->d_Z2, h->d_outs2, h->d_chain_words, h->d_obj_done,
-                    h->d_ekf_i, h->d_ekf_d, h->d_ekf_E, h->d_Gekf, h->d_ekf_gamma, h->d_ekf_accept, h->d_slam, h->d_dense, h->d_Rf, h->d_new, h->d_aug, h->d_split};
+                    h->d_ekf_i, h->d_ekf_d, h->d_ekf_E, h->d_Gekf, h->d_ekf_gamma, h->d_ekf_accept, h->d_slam, h->d_dense, h->d_Rf, h->d_new, h->d_aug};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
@@ -297,22 +277,15 @@ int32_t orcvio_msckf_create(int32_t device, int32_t max_clones, int32_t max_feat
     auto* h = new orcvio_msckf_handle();
     h->device = device;
     h->n_cus = prop.multiProcessorCount;
-    if (const char* e = dbg_getenv("ORCVIO_FUSED_SOLVE")) h->fused_solve = atoi(e);   // diagnostics: defaults of the options
-    if (const char* e = dbg_getenv("ORCVIO_FUSED_FRONT")) h->front_fused = atoi(e);
-    if (const char* e = dbg_getenv("ORCVIO_LA_SOLVE")) h->la_solve = atoi(e);
     if (const char* e = getenv("ORCVIO_LA_SPIN")) h->la_spin = atoi(e);
-    if (const char* e = dbg_getenv("ORCVIO_FRONT_U")) h->front_u = atoi(e) != 0;
     if (const char* e = dbg_getenv("ORCVIO_FUSE_FINISH")) h->fuse_finish = atoi(e);
     if (const char* e = getenv("ORCVIO_FRAME_CHAIN")) h->frame_chain = atoi(e) != 0;
     if (const char* e = dbg_getenv("ORCVIO_BLK2")) h->blk2_opt = atoi(e) != 0;
     if (const char* e = dbg_getenv("ORCVIO_OBJ_FUSED")) h->obj_fused_opt = atoi(e);
     if (const char* e = getenv("ORCVIO_FRONT_SPIN")) h->front_spin_limit = atoi(e);
-    if (const char* e = dbg_getenv("ORCVIO_REV_PRIOR")) h->rev_prior_opt = atoi(e) != 0;
-    if (const char* e = dbg_getenv("ORCVIO_SPLIT_TRACKS")) h->split_min_tracks = atoi(e);
     if (const char* e = dbg_getenv("ORCVIO_STEP_FUSED")) h->step_fused = atoi(e) != 0;
     if (const char* e = dbg_getenv("ORCVIO_THIN_UPDATE")) h->thin_opt = atoi(e) != 0;
     if (const char* e = dbg_getenv("ORCVIO_STEP_EKF_SIDE")) h->ekf_side_opt = atoi(e) != 0;
-    if (const char* e = dbg_getenv("ORCVIO_USE_GRAPH")) h->use_graph = atoi(e) != 0;
     if (const char* e = dbg_getenv("ORCVIO_FINISH_PUB")) h->finpub_opt = atoi(e) != 0;
     if (const char* e = dbg_getenv("ORCVIO_EKF_ONE_LAUNCH")) h->ekf_one_launch = atoi(e) != 0;
     h->maxN = max_clones;
@@ -503,7 +476,6 @@ int32_t orcvio_msckf_set_option(orcvio_msckf_handle* h, int32_t option, int32_t 
 
 static int factor_layout_clean(orcvio_msckf_handle* h);
 static int launch_ekf(orcvio_msckf_handle* h, hipStream_t s);
-static int feature_split_reserve(orcvio_msckf_handle* h);
 static int io_wait(orcvio_msckf_handle* h, hipStream_t s, unsigned long long expected_pub = 0);
 static int comm_stream_wait(orcvio_msckf_handle* h, hipStream_t s, const char* who);
 static int ipc_check_lost(orcvio_msckf_handle* h, const char* who);
@@ -522,7 +494,7 @@ static void select_prior_factor(orcvio_msckf_handle* h, bool with_P) {
     h->kf = h->use_factor ? h->fac_k : h->n;
 }
 // ... and whether the factor in use ends in columns that are zero in the active rows (call when reg_path is known)
-static inline bool rev_prior_active(const orcvio_msckf_handle* h) { return h->rev_prior_opt && h->reg_path && h->fused_solve && !h->use_factor; }
+static inline bool rev_prior_active(const orcvio_msckf_handle* h) { return h->reg_path && h->fused_solve && !h->use_factor; }
 static void select_tail(orcvio_msckf_handle* h) {
     const int t = h->use_factor ? h->fac_tail : (rev_prior_active(h) ? 15 : 0);
     h->tail = (h->reg_path && h->fused_solve && t > 0 && h->kf - t >= 16) ? t : 0;

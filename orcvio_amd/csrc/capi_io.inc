@@ -199,8 +199,8 @@ static int io_enqueue(orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool c
     h->last_finpub_commit = c.fin_pub && commit;
     // inputs: the derived index arrays at the head of the arena (the caller-written part behind them went ahead: ingest_raw)
     int rc = ORCVIO_OK;
-    // (tri_live without c.tri: the repeat of an armed update -- the positions in HBM are the device's own, the arena's are not read again)
-    if (!c.already_ingested) rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, early_ingest() || (h->tri_live && !c.tri) ? h->io_poses : upload_bytes(h));
+    // (the repeat of an armed update -- tri_live without c.tri -- pulls no more either: the positions in HBM are the device's own)
+    if (!c.already_ingested) rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, h->io_poses);
     // the armed update's triangulation: ONE launch behind the pull of the arena, in front of the first kernel that reads p_w or d_skip
     if (rc == ORCVIO_OK && c.tri) rc = launch_triangulate(h, &h->tri_cfg, false, true, s, true, h->tri_with_mode);
     if (rc == ORCVIO_OK) rc = enqueue_update(h, s, c);

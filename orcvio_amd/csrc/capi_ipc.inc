@@ -17,7 +17,7 @@
 //                    is q as well -- a rank whose counter has slipped, or a slot still holding another update, is a lost block
 //     rank-ordered sum of the slots of generation p + replicated solve                             (kernel START = acquire)
 // The gather buffer is allocated fine-grained / uncached (hipExtMallocWithFlags, as RCCL allocates its exchange buffers) so that
-// no L2 of the owning device keeps lines of generation q - 2 (ORCVIO_IPC_COARSE=1: plain hipMalloc).
+// no L2 of the owning device keeps lines of generation q - 2 (plain hipMalloc when that allocation fails).
 // NOT VERIFIED ACROSS DEVICES: every test and soak so far is several ranks on ONE device (no multi-GPU box was available).
 // The counters: `seq` (one per sharded update), `dof_count` (one per sharded object update), `red_count` (one per host reduction)
 // advance at the TOP of the call that uses them, before any return only one rank can take, so that a rank-local failure (a HIP
@@ -206,17 +206,13 @@ static int ipc_init(orcvio_msckf_handle* h, const uint8_t* id, int rank, int wor
     ic->gen_stride = slot * world;
     {
         // fine-grained / uncached like RCCL's exchange buffers: no cache of the owning device keeps lines a peer has rewritten
-        const char* coarse = dbg_getenv("ORCVIO_IPC_COARSE");
         void* g = nullptr;
         hipIpcMemHandle_t mh;
-        hipError_t e = hipErrorUnknown;
-        if (!(coarse && coarse[0] == '1')) {
-            e = hipExtMallocWithFlags(&g, sizeof(double) * slot * world * 2, hipDeviceMallocUncached);
-            if (e == hipSuccess) { e = hipIpcGetMemHandle(&mh, g); if (e != hipSuccess) { (void)hipFree(g); g = nullptr; } }
-            ic->gather_uncached = (e == hipSuccess);
-            (void)hipGetLastError();
-        }
-        if (!g) {
+        hipError_t e = hipExtMallocWithFlags(&g, sizeof(double) * slot * world * 2, hipDeviceMallocUncached);
+        if (e == hipSuccess) { e = hipIpcGetMemHandle(&mh, g); if (e != hipSuccess) { (void)hipFree(g); g = nullptr; } }
+        ic->gather_uncached = (e == hipSuccess);
+        (void)hipGetLastError();
+        if (!g) {   // (the plain, coarse-grained allocation when the uncached one is not to be had)
             if (hipMalloc(&g, sizeof(double) * slot * world * 2) != hipSuccess) return fail(ORCVIO_ERR_HIP, "comm_init (ipc): hipMalloc(gather)");
             e = hipIpcGetMemHandle(&mh, g);
         }

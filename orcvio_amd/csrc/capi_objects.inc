@@ -237,7 +237,7 @@ static int objects_prior(orcvio_msckf_handle* h, hipStream_t s, const double* P,
     layout_outputs(h, n, 1);
     if (P) {
         std::memcpy(h->h_stage + h->io_P, P, sizeof(double) * (size_t)n * n);
-        const int ri = launch_ingest(h, s, h->h_stage_dev + h->io_P, h->d_P, sizeof(double) * (size_t)n * n, obj_ingest_kernel());
+        const int ri = launch_ingest(h, s, h->h_stage_dev + h->io_P, h->d_P, sizeof(double) * (size_t)n * n);
         if (ri != ORCVIO_OK) return ri;
         { const int rm = arena_mark_read(h, s); if (rm != ORCVIO_OK) return rm; }
     }
@@ -439,7 +439,7 @@ int32_t orcvio_msckf_objects_local(orcvio_msckf_handle* h, const orcvio_msckf_fl
     pl.d_hx = dd; pl.d_hf = dd + rows * 6;
     pl.d_ridx = di + o_ridx; pl.d_rowptr = di + o_rowptr; pl.d_groups = reinterpret_cast<ObjGroup*>(di + o_groups);
     pl.d_arrow = reinterpret_cast<ObjArrow*>(di + o_arrow); pl.d_kp_range = reinterpret_cast<int2*>(di + o_range); pl.d_kp_rows = di + o_kprows;
-    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, nd * 8 + (o_groups + (size_t)4 * ng) * 4, obj_ingest_kernel()); if (ri != ORCVIO_OK) return ri; }
+    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, nd * 8 + (o_groups + (size_t)4 * ng) * 4); if (ri != ORCVIO_OK) return ri; }
     return objects_pipeline(h, s, dst, pl);
 }
 
@@ -611,7 +611,7 @@ static int objects_fused_launch(orcvio_msckf_handle* h, hipStream_t s, double* d
     double* dd = reinterpret_cast<double*>(h->d_obj_in);
     int* di = reinterpret_cast<int*>(h->d_obj_in + nd * 8);
     // info[4], [5] (dropped pivots, objects through the flagged branch) and info[9..12] (shard status words): cleared by the ingest launch
-    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, nd * 8 + ni_tot * 4, obj_ingest_kernel(), h->d_info + 4, 0x1E3u); if (ri != ORCVIO_OK) return ri; }
+    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, nd * 8 + ni_tot * 4, h->d_info + 4, 0x1E3u); if (ri != ORCVIO_OK) return ri; }
     h->obj_status_cleared = true;
     prof_mark(h, s, "staging + k_ingest");
     ObjFusedArgs fa{};
@@ -888,7 +888,7 @@ int32_t orcvio_msckf_objects_local_tracks(orcvio_msckf_handle* h, const orcvio_m
     pl.d_ridx = di + o_ridx; pl.d_rowptr = di + o_rowptr; pl.d_groups = reinterpret_cast<ObjGroup*>(di + o_groups);
     pl.d_arrow = reinterpret_cast<ObjArrow*>(di + o_arrow); pl.d_kp_range = reinterpret_cast<int2*>(di + o_range); pl.d_kp_rows = di + o_kprows;
     const auto tt3 = std::chrono::steady_clock::now();
-    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, nd * 8 + (o_groups + (size_t)4 * ng) * 4, obj_ingest_kernel()); if (ri != ORCVIO_OK) return ri; }
+    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, nd * 8 + (o_groups + (size_t)4 * ng) * 4); if (ri != ORCVIO_OK) return ri; }
     (void)n_eval;
     // the rows, and in the same launch the zeroing of what the compression accumulates into (Cd, Sg, Hr: adjacent) and of the
     // two pivot counters.  After a merge for ORCVIO_OPT_REF_STACK_HF the scratch layout is another one: plain fills there.
@@ -1080,8 +1080,7 @@ int32_t orcvio_msckf_update_objects(orcvio_msckf_handle* h, const orcvio_msckf_f
     if (rc == ORCVIO_OK) rc = objects_rank_dof(h, h->stream, &dof);
     if (rc != ORCVIO_OK) return rc;
     rc = orcvio_msckf_objects_finish(h, h->d_A, 1, dof, nullptr);
-    if (rc == ORCVIO_OK) rc = obj_publish_kernel() ? publish_enqueue(h, h->stream, res->P_out != nullptr)   // results -> pinned block, then the flag
-                                                   : download_enqueue(h, h->stream, res->P_out != nullptr);
+    if (rc == ORCVIO_OK) rc = download_enqueue(h, h->stream, res->P_out != nullptr);
     if (rc != ORCVIO_OK) return rc;
     rc = orcvio_msckf_objects_download(h, res);
     h->objects_mode = false;
@@ -1101,8 +1100,7 @@ static int update_object_tracks_impl(orcvio_msckf_handle* h, const orcvio_msckf_
     if (rc != ORCVIO_OK) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     rc = objects_finish_checked(h, h->d_A, 1, dof, nullptr, c);
-    if (rc == ORCVIO_OK) rc = obj_publish_kernel() ? publish_enqueue(h, h->stream, res->P_out != nullptr)   // results -> pinned block, then the flag
-                                                   : download_enqueue(h, h->stream, res->P_out != nullptr);
+    if (rc == ORCVIO_OK) rc = download_enqueue(h, h->stream, res->P_out != nullptr);
     if (rc != ORCVIO_OK) return rc;
     const auto t2 = std::chrono::steady_clock::now();
     rc = orcvio_msckf_objects_download(h, res);

@@ -55,12 +55,7 @@ static inline size_t upload_bytes(const orcvio_msckf_handle* h) {
 // The caller-written part of the arena (poses, tracks, P: everything behind the derived index arrays) pulled into HBM by a launch
 // of its own, issued BEFORE the host validates the index arrays and derives the per-clone lists (upload_finalize, ~8 us at
 // config 2): the transfer runs under that host work, and the launch graph of the update only has the derived arrays left to fetch.
-static bool early_ingest() {   // diagnostics: ORCVIO_EARLY_INGEST=0 leaves the whole arena to the ingest node of the launch graph
-    static const bool v = [] { const char* e = dbg_getenv("ORCVIO_EARLY_INGEST"); return e ? atoi(e) != 0 : true; }();
-    return v;
-}
 static int ingest_raw(orcvio_msckf_handle* h, hipStream_t s) {
-    if (!early_ingest()) return ORCVIO_OK;
     return launch_ingest(h, s, h->h_stage_dev + h->io_poses, h->d_in + h->io_poses, upload_bytes(h) - h->io_poses);
 }
 
@@ -177,7 +172,7 @@ static int upload_finalize(orcvio_msckf_handle* h, const char* who) {
     h->ran = false;
     h->skip_active = false; h->tri_live = false; h->tri_refuse_empty = false;
     h->objects_mode = false;   // (a staged object update may have left it set)
-    return feature_split_reserve(h);
+    return ORCVIO_OK;
 }
 
 // the caller's arrays -> the arena (orcvio_msckf_upload and the copying one-shot calls)
@@ -255,48 +250,8 @@ static FeatArgs feature_args(const orcvio_msckf_handle* h) {
     return a;
 }
 
-// Many tracks (more than a few rounds of what the CUs hold co-resident): the two-kernel front end of feature_split.hpp --
-// k_feature_e (Jacobians, QR, E = J P J^T; four workgroups per CU) and k_feature_gate (one wavefront per track).  Not with a
-// materialised stack (the projected rows need the gate's verdict inside the track's workgroup).
-static bool feature_split_active(const orcvio_msckf_handle* h) {
-    return h->split_min_tracks > 0 && h->F >= h->split_min_tracks && !h->materialize && h->feat_ablate == 0 && (h->NAP + 63) / 64 <= 7 &&
-           feat_split_lds_bytes(h->Mmax, h->NAP, h->N) <= (size_t)40 * 1024;
-}
-// scratch of the split front end: reserved when the tracks are uploaded (never inside a captured launch sequence)
-static int feature_split_reserve(orcvio_msckf_handle* h) {
-    if (!feature_split_active(h)) return ORCVIO_OK;
-    const size_t need = (size_t)h->F * feat_split_track_doubles(h->Mmax);
-    if (need <= h->split_cap) return ORCVIO_OK;
-    HIPCHK(hipDeviceSynchronize());
-    if (h->d_split) (void)hipFree(h->d_split);
-    h->d_split = nullptr; h->split_cap = 0;
-    const size_t cap = need + need / 4;
-    HIPCHK(hipMalloc(&h->d_split, sizeof(double) * cap));
-    h->split_cap = cap;
-    h->graph_epoch++;   // captured graphs hold the freed pointer
-    return ORCVIO_OK;
-}
-static int launch_feature_split(orcvio_msckf_handle* h, hipStream_t s) {
-    const FeatArgs a = feature_args(h);
-    const size_t lds = feat_split_lds_bytes(h->Mmax, h->NAP, h->N);
-    dim3 grid(h->F), block(256);
-    switch ((h->NAP + 63) / 64) {
-        case 1: hipLaunchKernelGGL(k_feature_e<1>, grid, block, lds, s, a, h->d_split); break;
-        case 2: hipLaunchKernelGGL(k_feature_e<2>, grid, block, lds, s, a, h->d_split); break;
-        case 3: hipLaunchKernelGGL(k_feature_e<3>, grid, block, lds, s, a, h->d_split); break;
-        case 4: hipLaunchKernelGGL(k_feature_e<4>, grid, block, lds, s, a, h->d_split); break;
-        case 5: hipLaunchKernelGGL(k_feature_e<5>, grid, block, lds, s, a, h->d_split); break;
-        case 6: hipLaunchKernelGGL(k_feature_e<6>, grid, block, lds, s, a, h->d_split); break;
-        default: hipLaunchKernelGGL(k_feature_e<7>, grid, block, lds, s, a, h->d_split); break;
-    }
-    hipLaunchKernelGGL(k_feature_gate, dim3((h->F + 3) / 4), dim3(256), 0, s, a, (const double*)h->d_split);
-    HIPCHK(hipGetLastError());
-    return ORCVIO_OK;
-}
-
 static int launch_feature(orcvio_msckf_handle* h, hipStream_t s) {
     if (h->F == 0) return ORCVIO_OK;
-    if (feature_split_active(h) && h->d_split && (size_t)h->F * feat_split_track_doubles(h->Mmax) <= h->split_cap) return launch_feature_split(h, s);
     const FeatArgs a = feature_args(h);
     const size_t lds = feat_lds_bytes(h->Mmax, h->NAP, h->N);
     const int npass = (h->NAP + 63) / 64;
@@ -345,11 +300,6 @@ static int front_row_chunks(const orcvio_msckf_handle* h) {
 // after the Grams (one device-wide barrier instead of two, no assembly pass)
 static bool front_defers_assembly(const orcvio_msckf_handle* h, bool retry_forked) { return front_fused_active(h, retry_forked) && front_row_chunks(h) <= 4 && h->NA <= 192; }
 
-// ... and the product U = [A; b^T] L_a itself can run inside k_front, behind the Grams (FrontUArgs): when the prior is factored in the
-// look-ahead form (its step counter tells the feature workgroups which block rows of the factor are out) or its factor is resident
-static bool front_forms_U(const orcvio_msckf_handle* h, const UpdateCall& c) {
-    return h->front_u && front_defers_assembly(h, c.retry_forked) && (h->use_factor || front_far_workgroups(h) > 0) && !c.join_wait;
-}
 // compress_dst != nullptr: the compression (Grams + assembly of A into compress_dst) runs inside the same launch;
 // grams_only: ... without the assembly (the caller's next kernel is k_gemm_asmA)
 static int launch_front(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c, double* compress_dst, bool grams_only = false) {
@@ -363,19 +313,7 @@ static int launch_front(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c, do
     if (nfar > 0 && lds < sizeof(double) * la_lds_doubles<3>()) lds = sizeof(double) * la_lds_doubles<3>();
     const int team_doubles = (int)(team / sizeof(double));
     FrontGramArgs g{};
-    g.enabled = compress_dst != nullptr ? (grams_only ? (front_forms_U(h, c) ? 3 : 2) : 1) : 0;
-    c.front_did_U = g.enabled == 3;
-    FrontUArgs u{};
-    if (g.enabled == 3) {   // (launch_solve_stage(ST_FORM_U)'s product, deferred form)
-        const PriorFactor pf = prior_factor(h);
-        const int NA = h->NA, NAP = h->NAP;
-        u.aa = AsmArgs{h->d_S, h->N, h->flags.leg_dim - 15, NA, NAP, h->d_Gpart, front_row_chunks(h), (size_t)NAP * NAP, 0, extra_gram(h)};
-        u.B = pf.base + 15 * pf.sLi; u.sBk = pf.sLi; u.sBj = pf.sLj;
-        u.M = NA + 1; u.Nc = h->kf - h->tail; u.K = NA;
-        u.C = h->d_U; u.sCi = (long)h->NP; u.sCj = 1L;
-        u.done = h->d_sync + 48;
-        if (lds < sizeof(double) * 2 * ASM_LDS_DOUBLES) lds = sizeof(double) * 2 * ASM_LDS_DOUBLES;
-    }
+    g.enabled = compress_dst != nullptr ? (grams_only ? 2 : 1) : 0;
     const int t3rows = 3 * h->F;
     g.chunks = front_row_chunks(h);
     h->front_chunks = g.chunks;
@@ -399,12 +337,10 @@ static int launch_front(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c, do
     do {                                                                                                                        \
         static bool attr_set = false;                                                                                           \
         if (!attr_set) {                                                                                                        \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_front<NPS, NSL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024))); \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_front<NPS, NSL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024))); \
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_front<NPS, NSL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024))); \
             attr_set = true;                                                                                                    \
         }                                                                                                                       \
-        if (g.enabled == 3) hipLaunchKernelGGL((k_front<NPS, NSL, true>), grid, block, lds, s, a, q, team_doubles, g, u);       \
-        else hipLaunchKernelGGL((k_front<NPS, NSL, false>), grid, block, lds, s, a, q, team_doubles, g, u);                     \
+        hipLaunchKernelGGL((k_front<NPS, NSL>), grid, block, lds, s, a, q, team_doubles, g);                                    \
     } while (0)
     switch ((h->NAP + 63) / 64) {
         case 1: LAUNCH_FRONT(1, 4); break;
@@ -717,7 +653,6 @@ static int launch_solve_stage(orcvio_msckf_handle* h, hipStream_t s, int stage, 
             if (h->use_factor) return ORCVIO_OK;   // the factor is resident
             return launch_potrf(h, s, h->d_P, n, n, 8.0 * eps, h->d_RP, h->d_DinvP, h->d_info, rev_prior_active(h) ? 1 : 0);
         case ST_FORM_U:    // U[(NA+1) x kf] = [A; b^T] * L_a
-            if (h->A_deferred && c.front_did_U) return ORCVIO_OK;   // (k_front formed U behind its Grams: FrontUArgs)
             if (h->A_deferred) {   // A = scatter(S) - sum Gpart assembled inside the product (k_front left the Grams only)
                 AsmArgs aa{h->d_S, h->N, h->flags.leg_dim - 15, NA, NAP, h->d_Gpart, h->front_chunks, (size_t)NAP * NAP, asm_dbg(),
                            extra_gram(h)};
@@ -831,7 +766,7 @@ static unsigned long long launch_signature(const orcvio_msckf_handle* h, hipStre
     auto mix = [&](unsigned long long v) { sig = (sig ^ v) * 1099511628211ull; };
     mix(h->N); mix(h->F); mix(h->nobs); mix(h->m_tot); mix(h->thin_opt); mix(h->Mmax); mix(h->chunks); mix(h->s_chunks); mix(h->rows_per_chunk);
     mix(h->flags.leg_dim); mix(h->flags.use_larvio); mix(h->flags.use_left_perturbation); mix(h->flags.if_fej);
-    mix(h->flags.estimate_td); mix(h->materialize); mix(h->skip_active); mix(h->fused_solve); mix(h->la_solve); mix(h->la_spin); mix(h->front_u); mix(h->fuse_finish); mix(c.fin_frame); mix(h->front_fused); mix(h->front_blocked_by_comm); mix(h->feat_ablate); mix(h->ekf_F); mix(h->ekf_mode); mix(h->n_extra); mix(h->n_nui); mix(h->dense_rows);
+    mix(h->flags.estimate_td); mix(h->materialize); mix(h->skip_active); mix(h->fused_solve); mix(h->la_solve); mix(h->la_spin); mix(h->fuse_finish); mix(c.fin_frame); mix(h->front_fused); mix(h->front_blocked_by_comm); mix(h->feat_ablate); mix(h->ekf_F); mix(h->ekf_mode); mix(h->n_extra); mix(h->n_nui); mix(h->dense_rows);
     unsigned long long bits;
     double sg = h->flags.noise_feature;
     std::memcpy(&bits, &sg, 8); mix(bits);
@@ -844,7 +779,7 @@ static unsigned long long launch_signature(const orcvio_msckf_handle* h, hipStre
     // the resident square-root factor is double-buffered and every user of it is a captured kernel argument (prior_factor):
     // its address belongs to the signature (ADVICE r2, high: a same-shape update after cov_commit replayed the OTHER buffer)
     mix(h->use_factor ? (unsigned long long)(size_t)h->d_Sres : 0ull);
-    mix(h->tail); mix(rev_prior_active(h)); mix(feature_split_active(h)); mix((unsigned long long)(size_t)h->d_split);
+    mix(h->tail); mix(rev_prior_active(h));
     mix((unsigned long long)(size_t)s); mix((unsigned long long)(size_t)p0); mix((unsigned long long)extra);
     return sig;
 }
@@ -1057,7 +992,7 @@ static int enqueue_update(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c) 
     // out BEHIND k_front's: a wait enqueued ahead of what it waits for would stall a hardware queue the two streams happen to share (the
     // runtime maps any number of streams onto a few), and the host's time for four launches would stand in front of k_front.
     const bool ekf_side = c.ekf_side && h->ekf_side_opt && h->cnt_step_frames >= h->ekf_side_skip_until && !mid && h->ekf_F > 0 && h->dense_rows == 0 && h->ekf_one_launch && h->d_step_words &&
-                          front_defers_assembly(h, c.retry_forked) && !front_forms_U(h, c) && h->F > 0;
+                          front_defers_assembly(h, c.retry_forked) && h->F > 0;
     unsigned* side_words = ekf_side ? reinterpret_cast<unsigned*>(h->d_step_words) + 32 : nullptr;
     if (ekf_side) { c.front_mark = side_words; c.front_mark_val = ++h->ekf_side_seq; }
     else { const int re = launch_ekf(h, s); if (re != ORCVIO_OK) return re; }

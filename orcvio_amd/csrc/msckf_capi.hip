@@ -18,7 +18,6 @@
 
 #include <functional>
 #include "msckf_kernels.hpp"
-#include "feature_split.hpp"
 #include "triangulate.hpp"
 #include "triangulate_arm.hpp"
 #include "cov_ops.hpp"
@@ -43,7 +42,7 @@ static thread_local std::string g_last_error;
 
 // Environment switches.  The PRODUCT library reads ten, all documented in include/orcvio_msckf.h ("Environment"): the communicator's
 // transport and bounds, the bounds of the in-launch waits, the two numerics-relevant forms of the frame call.  Every ablation, stamp and
-// measured-slower path of the lab notes is read through dbg_getenv, which the product build compiles to "unset" (VERDICT r5 #6): those
+// reference path the tests compare the fused kernels against is read through dbg_getenv, which the product build compiles to "unset" (VERDICT r5 #6): those
 // switches exist in the diagnostics build only (liborcvio_msckf_dbg.so, -DORCVIO_DEBUG_HOOKS; tests/test_abi.py checks the strings).
 #ifdef ORCVIO_DEBUG_HOOKS
 static inline const char* dbg_getenv(const char* name) { return getenv(name); }
@@ -156,12 +155,11 @@ struct orcvio_msckf_handle {
     size_t obj_lds_budget = 0;          // dynamic LDS the border launch of the object update may take on THIS handle's device (0: not asked yet)
     bool arrow_opt = true;              // ORCVIO_OPT_OBJECT_QR: structured Householder QR of Hf (0: chol(Hf^T Hf), round 1's route)
     bool use_factor = false;            // the current upload's prior comes with its factor: no Cholesky of P
-    // The prior's Cholesky is taken of the REVERSED matrix (potrf_reg_body, rev): P = S S^T with S(i, c) = L'(n-1-i, c), whose
+    // The prior's Cholesky is taken of the REVERSED matrix (potrf_reg_body, rev; rev_prior_active): P = S S^T with S(i, c) = L'(n-1-i, c), whose
     // rows 15 .. n-1 (the states measurement rows touch) are zero in the last 15 columns -- M = s2 I + L_a^T A L_a is
     // diag(M', s2 I_15) and only M' (kf - 15) is formed and factored.  `tail` = those trailing columns of the factor in use
     // (15, or 0: LDS-panel path, unfused solve, a resident factor that has been through an augmentation); fac_tail = the same
     // for the resident factor (kept by commit / remove_clones / clones_to_nuisance, dropped by augment).
-    bool rev_prior_opt = true;          // ORCVIO_REV_PRIOR=0: the plain Cholesky (tail 0), same results
     int tail = 0, fac_tail = 0;
     // orcvio_msckf_io_update_frame: the object tracks' compression runs on a stream of its own beside the feature update's solve
     hipStream_t obj_stream = nullptr;
@@ -224,18 +222,10 @@ struct orcvio_msckf_handle {
     char* d_new = nullptr; size_t new_cap = 0, new_out_off = 0;   // entering features (orcvio_msckf_upload_new_features): inputs, then H_1 | H_2 | r_1
     int new_F = 0, new_idp = 3;
     double* d_Rf = nullptr;             // [maxF][6] R factor of every track's H_f (k_feature), for orcvio_msckf_augment_new_features
-    double* d_split = nullptr;          // scratch of the two-kernel front end for many tracks (feature_split.hpp): E and the gate's right-hand sides per track
-    size_t split_cap = 0;
-    int split_min_tracks = 0;           // ORCVIO_SPLIT_TRACKS: track count from which k_feature_e + k_feature_gate replace k_feature (0 = never: the
-                                        // default since round 5 -- at 2 000 tracks the two-launch form measured 0.208 ms against 0.211 for k_feature
-                                        // with E in LDS, inside the run-to-run spread, and moves 85 MB of E scratch through HBM per update for it)
     int* d_sync = nullptr;              // device-wide counter of k_front (own allocation, zero between launches)
     int* d_la_rdy = nullptr;            // k_potrf_solve_la: one word per block row a far workgroup brings forward (own 128-byte line, cleared by the k_gemm ahead of it); [16..31] / [32] the same and the step counter for chol(P) inside k_front; [48] the finish workgroups' counter (LaFin)
     int la_solve = 3;                   // look-ahead depth of the fused solve (0: k_potrf_solve, one workgroup holds the whole trailing matrix; 2 / 3: k_potrf_solve_la)
     size_t chain_fin_oo = 0;            // ... and where in the second outputs arena it put P++ (checked against the object half's layout)
-    bool front_u = false;               // ORCVIO_FRONT_U=1: U = [A; b^T] L_a by the feature workgroups of k_front, behind the Grams (FrontUArgs) instead of the
-                                        // k_gemm_asmA launch -- bit-identical, tested, and SLOWER (k_front 39.5 -> 54.9 us for a launch of 8.3 + gap: a
-                                        // second device-wide barrier, and 144 strips of A read past the caches): a measured negative, kept opt-in
     double chain_fin_thr = 0.0;         // ... and the threshold it used
     std::shared_ptr<void> prestage;     // ObjPrestage (capi_objects.inc): what orcvio_msckf_io_stage_object_tracks left for the next frame call
     unsigned long long cnt_prestaged = 0;   // frame calls that found their object tracks staged ahead
@@ -362,7 +352,6 @@ struct UpdateCall {
     // ---- left by one stage for a later stage of the same enqueue
     unsigned* front_mark = nullptr; unsigned front_mark_val = 0;       // enqueue_update -> launch_front: FrontGramArgs.started
     const unsigned* asm_wait = nullptr; unsigned asm_wait_val = 0;     // enqueue_update -> launch_solve_stage(ST_FORM_U): k_gemm_asmA_w
-    bool front_did_U = false;           // launch_front formed U behind its Grams (ORCVIO_FRONT_U): ST_FORM_U has nothing to launch
 };
 
 // ---- resident covariance / factor bookkeeping of the handle ---------------------------------------------------------------------

@@ -1838,12 +1838,11 @@ struct AsmArgs {
     const double* plus;   // optional Gram added to A (EKF-SLAM rows), lower tiles valid
 };
 // One 16 x 16 tile of C = [A; b^T] B with the strip of A assembled in LDS: the body of k_gemm_asmA, 256 threads (tid), LDS handed in
-// (sA: 16 x 193, sPartF: 3 x 4 x 64, sSharedF: 4 x 64 doubles).  PUB: the Grams, the clone tiles and B were stored by other workgroups
-// of THIS launch (k_front with the product inside, FrontUArgs): read past the caches.  !active: the barriers only (no store).
+// (sA: 16 x 193, sPartF: 3 x 4 x 64, sSharedF: 4 x 64 doubles).  !active: the barriers only (no store).
 constexpr int ASM_LDS_DOUBLES = 16 * 193 + 3 * 4 * 64 + 4 * 64;
 // PLUSW: aa.plus is being written by ANOTHER stream (k_gemm_asmA_w): its loads stand behind a poll of the completion word `wait`, issued
 // once every other load of the strip is in flight, and go past the caches (agent-scope loads: no acquire fence, nothing else is re-read).
-template <bool PUB, bool PLUSW = false>
+template <bool PLUSW>
 __device__ __forceinline__ void asm_gemm_tile(const AsmArgs& aa, const double* __restrict__ B, long sBk, long sBj, int M, int Nc, int K,
                                               double* __restrict__ C, long sCi, long sCj, const int tile_index, const bool active, const int tid,
                                               double* __restrict__ sA, double* __restrict__ sPartF, double* __restrict__ sSharedF,
@@ -1865,7 +1864,7 @@ __device__ __forceinline__ void asm_gemm_tile(const AsmArgs& aa, const double* _
 #pragma unroll
     for (int q = 0; q < GB; ++q) {
         const int k = kbeg + 4 * q + kk;
-        bv[q] = ld_sel<PUB>(pb + (long)(k < kend ? k : (kend > 0 ? kend - 1 : 0)) * sBk);
+        bv[q] = pb[(long)(k < kend ? k : (kend > 0 ? kend - 1 : 0)) * sBk];
     }
     // ---- the (ext|r) x (ext|r) entries sum EVERY clone tile: once per workgroup that owns such rows, 64 entries x N
     //      tiles over the 256 threads (clone c on thread group c % 4, then a fixed-order sum of the four partials)
@@ -1880,7 +1879,7 @@ __device__ __forceinline__ void asm_gemm_tile(const AsmArgs& aa, const double* _
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int cu = c + 4 * u;
-                const double v = ld_sel<PUB>(aa.S + (size_t)(cu < aa.N ? cu : aa.N - 1) * 256 + e16);
+                const double v = aa.S[(size_t)(cu < aa.N ? cu : aa.N - 1) * 256 + e16];
                 acc8[u] += cu < aa.N ? v : 0.0;
             }
         }
@@ -1922,11 +1921,11 @@ __device__ __forceinline__ void asm_gemm_tile(const AsmArgs& aa, const double* _
             if (!in || !use_S) n1 = 0;
             const int e16 = (ei >= ek) ? ei * 16 + ek : ek * 16 + ei;   // the S tiles hold both triangles: [max][min]
             cls[rr][j] = n1 == 2 ? (2 | ((ea * 8 + (ek == 13 ? 7 : ek)) << 2)) : n1;
-            sv[rr][j] = ld_sel<PUB>(aa.S + (n1 == 1 ? (unsigned)(c0 * 256 + e16) : 0u));
+            sv[rr][j] = aa.S[n1 == 1 ? (unsigned)(c0 * 256 + e16) : 0u];
             const unsigned src = rowoff + kc;
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (u < aa.nparts) gv[rr][j][u] = ld_sel<PUB>(aa.parts + (size_t)u * aa.stride + src);   // (wave-uniform count and base)
+                if (u < aa.nparts) gv[rr][j][u] = aa.parts[(size_t)u * aa.stride + src];   // (wave-uniform count and base)
             pv[rr][j] = 0.0;
             if (!PLUSW && aa.plus) pv[rr][j] = aa.plus[((ic >> 4) >= (int)(kc >> 4)) ? src : kc * (unsigned)aa.NAP + (unsigned)ic];
         }
@@ -1950,7 +1949,7 @@ __device__ __forceinline__ void asm_gemm_tile(const AsmArgs& aa, const double* _
             }
         }
     }
-    if (PUB || has_shared) __syncthreads();   // (workgroup-uniform in k_gemm_asmA: one tile per workgroup; the two teams of k_front hold different tiles)
+    if (has_shared) __syncthreads();   // (workgroup-uniform: one tile per workgroup)
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
         const int r = wave + 4 * rr;
@@ -2005,8 +2004,8 @@ __device__ __forceinline__ void asm_gemm_tile(const AsmArgs& aa, const double* _
 }
 
 // (k_gemm_asmA keeps its own copy of the body below rather than calling asm_gemm_tile<false>: through the shared function the compiler
-//  allocates it differently -- 66 spilled SGPRs instead of 7 -- and the launch takes 8.65 instead of 8.3 us; asm_gemm_tile serves the
-//  opt-in in-launch form of k_front only.  The two must stay the same arithmetic: test_U_inside_k_front_is_bit_identical_...)
+//  allocates it differently -- 66 spilled SGPRs instead of 7 -- and the launch takes 8.65 instead of 8.3 us; asm_gemm_tile serves
+//  k_gemm_asmA_w only.  The two must stay the same arithmetic.)
 __global__ __launch_bounds__(256) void k_gemm_asmA(AsmArgs aa, const double* __restrict__ B, long sBk, long sBj, int M, int Nc, int K,
                                                    double* __restrict__ C, long sCi, long sCj, int* __restrict__ clear) {
     // The 16 x K strip of A this tile needs is assembled into LDS first, with the k index along the lanes (coalesced
@@ -2160,7 +2159,7 @@ __global__ __launch_bounds__(256) void k_gemm_asmA_w(AsmArgs aa, const double* _
                                                      double* __restrict__ C, long sCi, long sCj, const unsigned* __restrict__ wait, unsigned expect,
                                                      int spin_limit, int* __restrict__ lost) {
     __shared__ double sU[ASM_LDS_DOUBLES];
-    asm_gemm_tile<false, true>(aa, B, sBk, sBj, M, Nc, K, C, sCi, sCj, (int)blockIdx.x, true, (int)threadIdx.x, sU, sU + 16 * 193, sU + 16 * 193 + 768,
+    asm_gemm_tile<true>(aa, B, sBk, sBj, M, Nc, K, C, sCi, sCj, (int)blockIdx.x, true, (int)threadIdx.x, sU, sU + 16 * 193, sU + 16 * 193 + 768,
                                wait, expect, spin_limit, lost);
 }
 
@@ -2184,7 +2183,7 @@ struct FrontPotrfArgs {
 // per CU by its LDS size), take (tile, chunk) / clone work items, meet again and assemble.  The factorisation in
 // workgroup 0 takes no part; it outlasts all of this, so the compression is free.
 struct FrontGramArgs {
-    int enabled;
+    int enabled;                  // 0: tracks only; 1: + both Grams and the assembly of A into A_dst; 2: + the Grams only (k_gemm_asmA assembles A)
     int chunks, rows_per_chunk;   // T3 row chunks of this launch (<= 8 x 80 rows each: one batch of loads per wavefront)
     double* Gpart; double* S; const int* clone_rows;
     int* counter;                 // zero between launches (the last workgroup through resets it)
@@ -2194,18 +2193,6 @@ struct FrontGramArgs {
     int spin_limit;               // polls of the flag line before a waiting workgroup gives up (a few tens of ms)
     unsigned* started;            // optional: workgroup 0 stores started_val here with its first instruction -- "everything enqueued in front
     unsigned started_val;         //   of this launch is complete", read by a wait launch on another stream (the frame call's in-state rows)
-};
-// U = [A; b^T] L_a inside the launch (g.enabled == 3): behind the Grams and a second device-wide barrier, every team takes one tile of U
-// with k_gemm_asmA's body -- same arithmetic, same bits -- as soon as the prior's factorisation has published the block row of R the
-// tile's columns of L_a come from (its step counter q.la_flag; nothing to wait for when the factor is resident).  The launch then ends
-// ~3 us later than the factorisation does, and the k_gemm_asmA launch behind it (8 us + a launch gap) is gone.  The factorising
-// workgroup puts its hand-off words back to zero only when every feature workgroup has said it is through (u.done).
-struct FrontUArgs {
-    AsmArgs aa;
-    const double* B; long sBk, sBj;
-    int M, Nc, K;
-    double* C; long sCi, sCj;
-    int* done;   // zero between launches
 };
 __device__ __forceinline__ void front_grid_barrier(int* counter, int target, int* lost, int spin_limit, unsigned long long* dbg = nullptr) {
     // Everything that crosses this barrier is written with write-through (sc1) stores and read with sc1 loads
@@ -2230,28 +2217,14 @@ __device__ __forceinline__ void front_grid_barrier(int* counter, int target, int
     }
     __syncthreads();
 }
-template <int NPASS, int NSLOT, bool WITH_U = false>   // WITH_U: the instantiation that can form U behind the Grams (g.enabled == 3, FrontUArgs)
-__global__ __launch_bounds__(512) void k_front(FeatArgs p, FrontPotrfArgs q, int team_doubles, FrontGramArgs g, FrontUArgs u) {
+template <int NPASS, int NSLOT>
+__global__ __launch_bounds__(512) void k_front(FeatArgs p, FrontPotrfArgs q, int team_doubles, FrontGramArgs g) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if (blockIdx.x == 0) {
         if (g.started && threadIdx.x == 0) __hip_atomic_store(g.started, g.started_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (q.skip) return;
         if (g.enabled && threadIdx.x == 0) (reinterpret_cast<unsigned long long*>(g.counter) + 8)[0] = wall_clock64();
-        if (WITH_U && q.nfar > 0 && g.enabled == 3) {   // (the feature workgroups read the step counter until their tiles of U are out)
-            potrf_la_chain_wg<3, false, true, true>(smem, LaIn{q.X, q.ldx, q.n, q.rev}, q.tol_rel, q.R, q.ldr, q.Dinv, q.info, q.la_flag, q.la_rdy, g.lost, q.la_spin, nullptr);
-            __syncthreads();
-            if ((threadIdx.x >> 6) == 4) {   // (the wavefront that stored the step counter)
-                const int l = threadIdx.x & 63, nfb = (int)gridDim.x - 1 - q.nfar;
-                int it = 0;
-                while (__hip_atomic_load(u.done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nfb && it < g.spin_limit) { __builtin_amdgcn_s_sleep(8); ++it; }
-                if (it >= g.spin_limit && l == 0) atomicAdd(g.lost, 1);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (l < 16) __hip_atomic_store(q.la_rdy + l, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (l == 16) __hip_atomic_store(q.la_flag, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (l == 17) __hip_atomic_store(u.done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        else if (q.nfar > 0) potrf_la_chain_wg<3, false, true>(smem, LaIn{q.X, q.ldx, q.n, q.rev}, q.tol_rel, q.R, q.ldr, q.Dinv, q.info, q.la_flag, q.la_rdy, g.lost, q.la_spin, nullptr);
+        if (q.nfar > 0) potrf_la_chain_wg<3, false, true>(smem, LaIn{q.X, q.ldx, q.n, q.rev}, q.tol_rel, q.R, q.ldr, q.Dinv, q.info, q.la_flag, q.la_rdy, g.lost, q.la_spin, nullptr);
         else potrf_reg_body<NSLOT, false>(smem, q.X, q.ldx, q.n, q.tol_rel, q.R, q.ldr, q.Dinv, q.info, 0, 0, nullptr, nullptr, 1, 0, q.rev);
         if (g.enabled && threadIdx.x == 0) (reinterpret_cast<unsigned long long*>(g.counter) + 8)[6] = wall_clock64();
         return;
@@ -2301,31 +2274,6 @@ __global__ __launch_bounds__(512) void k_front(FeatArgs p, FrontPotrfArgs q, int
     }
     FRONT_STAMP(3);
     int phases = 2;
-    if (WITH_U && g.enabled == 3) {   // ---- U = [A; b^T] L_a: one tile per team (FrontUArgs) ------------------------------------------
-        front_grid_barrier(g.counter, 2 * nfb, g.lost, g.spin_limit, me == 0 ? stamp + 7 : nullptr);
-        FRONT_STAMP(4);
-        const int ntj = (u.Nc + 15) >> 4, ntu = ((u.M + 15) >> 4) * ntj;
-        double* sU = smem + (size_t)team * ASM_LDS_DOUBLES;
-        for (int t0 = 2 * me; t0 < ntu; t0 += 2 * nfb) {
-            const int tile = t0 + team;
-            const bool active = tile < ntu;
-            if (!q.skip && active && local == 0) {   // block row (tile's column block) of R published?  (bounded; one lane polls, the barrier below)
-                const int need = tile % ntj + 1;
-                int it = 0;
-                while (__hip_atomic_load(q.la_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need && it < q.la_spin) { __builtin_amdgcn_s_sleep(4); ++it; }
-                if (it >= q.la_spin) { atomicAdd(g.lost, 1); }
-            }
-            __syncthreads();
-            asm_gemm_tile<true>(u.aa, u.B, u.sBk, u.sBj, u.M, u.Nc, u.K, u.C, u.sCi, u.sCj, active ? tile : 0, active, local, sU, sU + 16 * 193, sU + 16 * 193 + 768);
-            __syncthreads();   // (the strip and the partial tiles are reused by the next item)
-        }
-        FRONT_STAMP(5);
-        if (!q.skip && q.nfar > 0) {   // this workgroup reads the factorisation's words no more
-            __syncthreads();
-            if (threadIdx.x == 0) __hip_atomic_fetch_add(u.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        phases = 3;
-    }
     if (g.enabled == 1) {   // (enabled == 2: the consumer, k_gemm_asmA, assembles A on the fly)
         front_grid_barrier(g.counter, 2 * nfb, g.lost, g.spin_limit, me == 0 ? stamp + 7 : nullptr);
         FRONT_STAMP(4);

@@ -141,7 +141,12 @@ def test_the_product_library_reads_only_the_documented_environment_variables(bui
     assert prod <= documented, prod - documented
     assert {'ORCVIO_COMM_TRANSPORT', 'ORCVIO_LA_SPIN', 'ORCVIO_FRAME_CHAIN'} <= prod
     dbg = names(b.LIB_DBG)
-    assert {'ORCVIO_FUSE_FINISH', 'ORCVIO_BLK2', 'ORCVIO_SPLIT_TRACKS', 'ORCVIO_TIMING'} <= dbg
+    assert {'ORCVIO_FUSE_FINISH', 'ORCVIO_BLK2', 'ORCVIO_OBJ_FUSED', 'ORCVIO_TIMING'} <= dbg
+    # the switches of the retired paths (docs/LAB_NOTES.md) are gone from both
+    retired = {'ORCVIO_SPLIT_TRACKS', 'ORCVIO_FRONT_U', 'ORCVIO_FRAME_GRAPH', 'ORCVIO_FRAME_EVENT_JOIN', 'ORCVIO_OBJ_PUBLISH', 'ORCVIO_OBJ_INGEST',
+               'ORCVIO_EARLY_INGEST', 'ORCVIO_REV_PRIOR', 'ORCVIO_IPC_COARSE', 'ORCVIO_FUSED_FRONT', 'ORCVIO_FUSED_SOLVE', 'ORCVIO_LA_SOLVE',
+               'ORCVIO_USE_GRAPH'}
+    assert not (retired & prod) and not (retired & dbg), (retired & prod, retired & dbg)
 
 
 def test_the_committed_pmc_profile_is_of_these_sources():
