@@ -10,8 +10,10 @@ LIB_DIR = os.path.join(_HERE, 'lib')
 LIB = os.path.join(LIB_DIR, 'liborcvio_msckf.so')
 LIB_DBG = os.path.join(LIB_DIR, 'liborcvio_msckf_dbg.so')   # the same sources + the orcvio_msckf_debug_* test hooks
 SOURCES = ['msckf_capi.hip']
-# every file the one translation unit is made of: the C-ABI sections (capi_*.inc), the kernel headers, the public header
-DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.hpp', '.inc'))) + [os.path.join('..', '..', 'include', 'orcvio_msckf.h')]
+# every file the one translation unit is made of: the C-ABI sections (capi_*.inc), the kernel headers, the HIP-free headers under
+# host/ that it includes (not host/orcvio_msckf_host.hpp: the C++ shim over the C-ABI is no part of the library), the public header
+DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.hpp', '.inc'))) + \
+    [os.path.join('host', 'cov_book.hpp'), os.path.join('host', 'ipc_protocol.hpp'), os.path.join('..', '..', 'include', 'orcvio_msckf.h')]
 
 
 def _stale(lib) -> bool:

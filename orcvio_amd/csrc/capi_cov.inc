@@ -101,8 +101,48 @@ int32_t orcvio_msckf_cov_set(orcvio_msckf_handle* h, int32_t n, const double* P)
     HIPCHK(hipStreamSynchronize(h->stream));   // (a commit may still be writing the resident covariance: the flag of an in-place
                                                //  update rises when its RESULTS are out, not when its commit workgroups are done)
     HIPCHK(hipMemcpy(h->d_Pres, P, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    h->res_n = n;
-    h->fac_valid = false;   // a new covariance: its factor is not known
+    h->set(n);
+    return ORCVIO_OK;
+}
+
+// ---- the launches of an edit, ONE per kernel family: what to read and write comes in the record the edit's bookkeeping left
+// (CovBook, host/cov_book.hpp); Phi and Q are device pointers, their staging stays with the caller
+static int launch_cov_propagate(orcvio_msckf_handle* h, hipStream_t s, const CovEdit& e, int leg, const double* dPhi, const double* dQ) {
+    hipLaunchKernelGGL(k_cov_propagate_rows, dim3((leg * e.n + 255) / 256), dim3(256), 0, s, e.P, e.n, dPhi, leg, h->d_covT);
+    hipLaunchKernelGGL(k_cov_propagate_finish, dim3((e.n * e.n + 255) / 256), dim3(256), 0, s, e.P, e.n, dPhi, dQ, leg, (const double*)h->d_covT, e.Pout);
+    HIPCHK(hipGetLastError());
+    return ORCVIO_OK;
+}
+// the new clone goes in at `pose`: BEHIND the clones and IN FRONT of the feature / nuisance states (rest_rows, src/orcvio.cpp:976-1003)
+static int launch_cov_augment(orcvio_msckf_handle*, hipStream_t s, const CovEdit& e, int pose) {
+    hipLaunchKernelGGL(k_cov_augment, dim3((e.m * e.m + 255) / 256), dim3(256), 0, s, e.P, e.n, pose, e.Pout);
+    if (e.fac) hipLaunchKernelGGL(k_fac_augment, dim3((e.fac_k * e.m + 255) / 256), dim3(256), 0, s, e.S, e.ld_in, e.fac_k, e.n, pose, e.Sout, e.ld_out);
+    HIPCHK(hipGetLastError());
+    return ORCVIO_OK;
+}
+// new state i <- old state map[i], i < e.m (states removed, or a permutation): rows of S with it.  The map travels through the pinned
+// bounce buffer: nothing to wait for, and it may be a local of the caller (aux_copies has copied it when it returns)
+static int launch_cov_gather(orcvio_msckf_handle* h, hipStream_t s, const CovEdit& e, const std::vector<int>& map) {
+    const AuxCopy cp[] = {{h->d_covmap, map.data(), sizeof(int) * map.size()}};
+    const int rc = aux_copies(h, s, cp, 1);
+    if (rc != ORCVIO_OK) return rc;
+    hipLaunchKernelGGL(k_cov_remove, dim3((e.m * e.m + 255) / 256), dim3(256), 0, s, e.P, e.n, (const int*)h->d_covmap, e.m, e.Pout);   // (m = map.size())
+    if (e.fac) hipLaunchKernelGGL(k_fac_remove, dim3((e.fac_k * e.m + 255) / 256), dim3(256), 0, s, e.S, e.ld_in, e.fac_k, (const int*)h->d_covmap, e.m, e.Sout, e.ld_out);
+    HIPCHK(hipGetLastError());
+    return ORCVIO_OK;
+}
+struct AnchorLaunch {   // k_cov_change_anchors' inputs besides the covariance
+    int idp, literal_3d, if_fej, count, base, leg;
+    const double* poses; const double* ext; const int* chg_i; const double* chg_d;
+    double* par;
+};
+// Y = J P [k d][n] goes to the spare covariance buffer (n_max^2 >= k d n: k d <= n - base), overwritten as a whole by whatever writes it next
+static int launch_cov_change_anchors(orcvio_msckf_handle*, hipStream_t s, const CovEdit& e, const AnchorLaunch& a, const AnchorFrameArgs& fr) {
+    const auto kernel = a.idp == 3 ? k_cov_change_anchors<3> : k_cov_change_anchors<1>;
+    const int threads = a.idp == 3 ? AnchorThreads<3>::value : AnchorThreads<1>::value;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, s, const_cast<double*>(e.P), e.n, e.fac ? const_cast<double*>(e.S) : (double*)nullptr, e.ld_in, e.fac_k,
+                       a.poses, a.ext, a.chg_i, a.chg_d, a.count, a.base, a.leg, a.if_fej, a.literal_3d, a.par, e.Pout, fr);
+    HIPCHK(hipGetLastError());
     return ORCVIO_OK;
 }
 
@@ -121,7 +161,6 @@ int32_t orcvio_msckf_cov_propagate(orcvio_msckf_handle* h, int32_t leg, const do
     if (!h || !Phi || !Q || (leg != 22 && leg != 46) || h->res_n < leg) { g_last_error = "cov_propagate: invalid"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const int n = h->res_n;
     double* dPhi = h->d_covT + (size_t)46 * h->n_max;   // behind the Phi P rows: Phi, then Q
     double* dQ = dPhi + 46 * 46;
     {   // Phi and Q are caller memory: through the pinned bounce buffer, so that nothing has to be waited for
@@ -129,60 +168,31 @@ int32_t orcvio_msckf_cov_propagate(orcvio_msckf_handle* h, int32_t leg, const do
         const int rc = aux_copies(h, s, cp, 2);
         if (rc != ORCVIO_OK) return rc;
     }
-    hipLaunchKernelGGL(k_cov_propagate_rows, dim3((leg * n + 255) / 256), dim3(256), 0, s, h->d_Pres, n, dPhi, leg, h->d_covT);
-    hipLaunchKernelGGL(k_cov_propagate_finish, dim3((n * n + 255) / 256), dim3(256), 0, s, h->d_Pres, n, dPhi, dQ, leg, h->d_covT, h->d_Ptmp);
-    HIPCHK(hipGetLastError());
-    std::swap(h->d_Pres, h->d_Ptmp);
-    h->fac_valid = false;   // P_LL <- Phi P_LL Phi^T + Q: the factor of the sum is not a row operation on S
-    return ORCVIO_OK;
+    return launch_cov_propagate(h, s, h->propagate(), leg, dPhi, dQ);
 }
 
 int32_t orcvio_msckf_cov_augment(orcvio_msckf_handle* h) {
     if (!h || h->res_n < 9 || h->res_n + 6 > h->n_max) { g_last_error = "cov_augment: no resident covariance, or window full"; return ORCVIO_ERR_CAPACITY; }
     HIPCHK(hipSetDevice(h->device));
-    const int n = h->res_n, m = n + 6;
-    // the new clone goes BEHIND the clones and IN FRONT of the feature / nuisance states (rest_rows, src/orcvio.cpp:976-1003)
+    const int n = h->res_n;
     if (h->n_extra > n - 15) { g_last_error = "cov_augment: more extra states than the resident covariance has"; return ORCVIO_ERR_INVALID; }
-    hipLaunchKernelGGL(k_cov_augment, dim3((m * m + 255) / 256), dim3(256), 0, h->stream, h->d_Pres, n, n - h->n_extra, h->d_Ptmp);
-    HIPCHK(hipGetLastError());
-    std::swap(h->d_Pres, h->d_Ptmp);
-    h->res_n = m;
-    if (h->fac_valid && h->fac_n == n) {   // the new clone's rows of S are copies of the IMU's (theta, p) rows
-        const int ldo = round_up(m + 1, 16);
-        hipLaunchKernelGGL(k_fac_augment, dim3((h->fac_k * m + 255) / 256), dim3(256), 0, h->stream, h->d_Sres, h->fac_ld, h->fac_k, n,
-                           n - h->n_extra, h->d_Stmp, ldo);
-        HIPCHK(hipGetLastError());
-        fac_adopt(h, m, h->fac_k, ldo, 0);   // (tail 0: the new clone's rows are copies of IMU rows, not zero in the trailing columns)
-    } else h->fac_valid = false;
-    return ORCVIO_OK;
+    return launch_cov_augment(h, h->stream, h->augment(), n - h->n_extra);
 }
 
-// The states with drop[i] set leave the resident covariance (rows and columns deleted, the rest keeps its order); deleting
-// states deletes rows of the resident square-root factor, which is kept.
-static int cov_remove_rows(orcvio_msckf_handle* h, const std::vector<char>& drop) {
-    const int n = h->res_n;
+// The states in `map` (ascending) stay in the resident covariance, the others leave (rows and columns deleted); deleting states
+// deletes rows of the resident square-root factor, which is kept.
+static int cov_keep_states(orcvio_msckf_handle* h, const std::vector<int>& map) {
+    return launch_cov_gather(h, h->stream, h->gather((int)map.size()), map);
+}
+// the states that stay when the d rows of the listed in-state features (slots ascending, the features begin at `base`) leave a state of n
+static std::vector<int> lost_features_map(int n, int base, int d, const int32_t* slots, int count) {
     std::vector<int> map;
-    for (int i = 0; i < n; ++i)
-        if (!drop[i]) map.push_back(i);
-    const int m = (int)map.size();
-    hipStream_t s = h->stream;
-    {   // (the map is a local: through the pinned bounce buffer, nothing to wait for)
-        const AuxCopy cp[] = {{h->d_covmap, map.data(), sizeof(int) * (size_t)m}};
-        const int rc = aux_copies(h, s, cp, 1);
-        if (rc != ORCVIO_OK) return rc;
+    int q = 0;
+    for (int i = 0; i < n; ++i) {
+        while (q < count && base + d * (slots[q] + 1) <= i) ++q;
+        if (q == count || i < base + d * slots[q]) map.push_back(i);
     }
-    hipLaunchKernelGGL(k_cov_remove, dim3((m * m + 255) / 256), dim3(256), 0, s, h->d_Pres, n, h->d_covmap, m, h->d_Ptmp);
-    HIPCHK(hipGetLastError());
-    if (h->fac_valid && h->fac_n == n) {   // deleting states deletes rows of S
-        const int ldo = round_up(m + 1, 16);
-        hipLaunchKernelGGL(k_fac_remove, dim3((h->fac_k * m + 255) / 256), dim3(256), 0, s, h->d_Sres, h->fac_ld, h->fac_k, h->d_covmap, m,
-                           h->d_Stmp, ldo);
-        HIPCHK(hipGetLastError());
-        fac_adopt(h, m, h->fac_k, ldo, h->fac_tail);
-    } else h->fac_valid = false;
-    std::swap(h->d_Pres, h->d_Ptmp);
-    h->res_n = m;
-    return ORCVIO_OK;
+    return map;
 }
 
 int32_t orcvio_msckf_cov_remove_clones(orcvio_msckf_handle* h, int32_t leg, const int32_t* idx, int32_t count) {
@@ -195,7 +205,10 @@ int32_t orcvio_msckf_cov_remove_clones(orcvio_msckf_handle* h, int32_t leg, cons
         if (idx[k] < 0 || idx[k] >= N) { g_last_error = "cov_remove_clones: index out of the window"; return ORCVIO_ERR_INVALID; }
         for (int c = 0; c < 6; ++c) drop[leg + 6 * idx[k] + c] = 1;
     }
-    return cov_remove_rows(h, drop);
+    std::vector<int> map;
+    for (int i = 0; i < n; ++i)
+        if (!drop[i]) map.push_back(i);
+    return cov_keep_states(h, map);
 }
 
 // Schmidt branch of pruneImuStateBuffer (src/orcvio.cpp:2881-2920): the listed clones leave the window but STAY in the covariance
@@ -217,22 +230,7 @@ int32_t orcvio_msckf_cov_clones_to_nuisance(orcvio_msckf_handle* h, int32_t leg,
         std::rotate(map.begin() + start, map.begin() + start + 6, map.end());   // the block goes to the end, everything behind it moves up
         moved_before.push_back(idx[k]);
     }
-    hipStream_t s = h->stream;
-    {
-        const AuxCopy cp[] = {{h->d_covmap, map.data(), sizeof(int) * (size_t)n}};
-        const int rc = aux_copies(h, s, cp, 1);
-        if (rc != ORCVIO_OK) return rc;
-    }
-    hipLaunchKernelGGL(k_cov_remove, dim3((n * n + 255) / 256), dim3(256), 0, s, h->d_Pres, n, h->d_covmap, n, h->d_Ptmp);
-    HIPCHK(hipGetLastError());
-    if (h->fac_valid && h->fac_n == n) {
-        hipLaunchKernelGGL(k_fac_remove, dim3((h->fac_k * n + 255) / 256), dim3(256), 0, s, h->d_Sres, h->fac_ld, h->fac_k, h->d_covmap, n,
-                           h->d_Stmp, h->fac_ld);
-        HIPCHK(hipGetLastError());
-        fac_adopt(h, n, h->fac_k, h->fac_ld, h->fac_tail);
-    } else h->fac_valid = false;
-    std::swap(h->d_Pres, h->d_Ptmp);
-    return ORCVIO_OK;
+    return launch_cov_gather(h, h->stream, h->permute(), map);
 }
 
 // rmLostFeaturesCov (src/orcvio.cpp:3776-3828) on the resident covariance: the d rows and columns of the listed in-state features
@@ -248,10 +246,7 @@ int32_t orcvio_msckf_cov_remove_features(orcvio_msckf_handle* h, int32_t leg, in
         if (slots[q] < 0 || slots[q] >= n_feature_states || (q > 0 && slots[q] <= slots[q - 1])) { g_last_error = "cov_remove_features: slots must be ascending and in range"; return ORCVIO_ERR_INVALID; }
     if (count == 0) return ORCVIO_OK;
     HIPCHK(hipSetDevice(h->device));
-    std::vector<char> drop(n, 0);
-    for (int q = 0; q < count; ++q)
-        for (int c = 0; c < idp_dim; ++c) drop[base + idp_dim * slots[q] + c] = 1;
-    return cov_remove_rows(h, drop);
+    return cov_keep_states(h, lost_features_map(n, base, idp_dim, slots, count));
 }
 
 // The in-state branch of pruneImuStateBuffer (src/orcvio.cpp:2664-2720) for up to 16 features at once: new parameters in the new
@@ -261,6 +256,16 @@ static bool all_finite(const double* x, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(x[i])) return false;
     return true;
+}
+// one change as k_cov_change_anchors reads it: ci [4] slot | old anchor | new anchor | rec (the frame call: the feature's slam_features
+// record), cd [6] p_w | p_fej (p_w again without FEJ); the 12 doubles of the extrinsics R_b2c | t_c_b
+static inline void pack_anchor_change(const orcvio_msckf_anchor_change& c, bool if_fej, int rec, int* ci, double* cd) {
+    ci[0] = c.slot; ci[1] = c.old_anchor; ci[2] = c.new_anchor; ci[3] = rec;
+    for (int a = 0; a < 3; ++a) { cd[a] = c.p_w[a]; cd[3 + a] = if_fej ? c.p_fej[a] : c.p_w[a]; }
+}
+static inline void pack_extrinsics(const double* R_b2c, const double* t_c_b, double* ext) {
+    for (int a = 0; a < 9; ++a) ext[a] = R_b2c[a];
+    for (int a = 0; a < 3; ++a) ext[9 + a] = t_c_b[a];
 }
 int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags, int32_t idp_dim, int32_t literal_3d,
                                         int32_t n_clones, const double* poses, const double* R_b2c, const double* t_c_b,
@@ -283,12 +288,10 @@ int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msc
         if (c.old_anchor < 0 || c.old_anchor >= n_clones || c.new_anchor < 0 || c.new_anchor >= n_clones) { g_last_error = "cov_change_anchors: anchor outside the window"; return ORCVIO_ERR_INVALID; }
         if (c.old_anchor == c.new_anchor) { g_last_error = "cov_change_anchors: old anchor == new anchor"; return ORCVIO_ERR_INVALID; }
         if (!all_finite(c.p_w, 3) || (flags->if_fej && !all_finite(c.p_fej, 3))) { g_last_error = "cov_change_anchors: non-finite feature position"; return ORCVIO_ERR_INVALID; }
-        ci[ANCHOR_CHG_STRIDE * q] = c.slot; ci[ANCHOR_CHG_STRIDE * q + 1] = c.old_anchor; ci[ANCHOR_CHG_STRIDE * q + 2] = c.new_anchor;
-        for (int a = 0; a < 3; ++a) { cd[6 * q + a] = c.p_w[a]; cd[6 * q + 3 + a] = flags->if_fej ? c.p_fej[a] : c.p_w[a]; }
+        pack_anchor_change(c, flags->if_fej != 0, 0, &ci[ANCHOR_CHG_STRIDE * q], &cd[6 * q]);
     }
     double ext[12];
-    for (int a = 0; a < 9; ++a) ext[a] = R_b2c[a];
-    for (int a = 0; a < 3; ++a) ext[9 + a] = t_c_b[a];
+    pack_extrinsics(R_b2c, t_c_b, ext);
     if (!all_finite(ext, 12)) { g_last_error = "cov_change_anchors: non-finite extrinsics"; return ORCVIO_ERR_INVALID; }
     for (int i = 0; i < n_clones; ++i)
         if (!all_finite(poses + (size_t)i * ORCVIO_POSE_STRIDE, 27)) { g_last_error = "cov_change_anchors: non-finite pose record"; return ORCVIO_ERR_INVALID; }
@@ -305,16 +308,11 @@ int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msc
         const int rc = aux_copies(h, s, cp, 4);
         if (rc != ORCVIO_OK) return rc;
     }
-    const bool fac = h->fac_valid && h->fac_n == n;
-    // Y = J P [k d][n] goes to d_Ptmp (n_max^2 >= k d n: k d <= n - base)
-#define LAUNCH_CA(D) hipLaunchKernelGGL(k_cov_change_anchors<D>, dim3(1), dim3(AnchorThreads<D>::value), 0, s, h->d_Pres, n, fac ? h->d_Sres : (double*)nullptr, \
-                                        h->fac_ld, h->fac_k, (const double*)dposes, (const double*)dext, (const int*)h->d_covmap, (const double*)dcd, \
-                                        count, base, leg, flags->if_fej ? 1 : 0, literal_3d ? 1 : 0, dpar, h->d_Ptmp, AnchorFrameArgs{})
-    if (d == 3) LAUNCH_CA(3);
-    else LAUNCH_CA(1);
-#undef LAUNCH_CA
-    HIPCHK(hipGetLastError());
-    if (!fac) h->fac_valid = false;   // (T S touches rows >= 15 only: the factor's zero trailing columns, fac_tail, stay zero)
+    {
+        const AnchorLaunch a{d, literal_3d ? 1 : 0, flags->if_fej ? 1 : 0, count, base, leg, dposes, dext, h->d_covmap, dcd, dpar};
+        const int rc = launch_cov_change_anchors(h, s, h->change_anchors(), a, AnchorFrameArgs{});
+        if (rc != ORCVIO_OK) return rc;
+    }
     std::vector<double> par(4 * count);
     const FetchCopy fc[] = {{par.data(), dpar, sizeof(double) * par.size()}};
     const int rc = fetch_copies(h, s, fc, 1);
@@ -332,19 +330,19 @@ int32_t orcvio_msckf_cov_commit(orcvio_msckf_handle* h) {
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->last_stream ? h->last_stream : h->stream;
     const int n = h->n, kf = h->kf;
-    if (h->factor_opt && h->n_nui > 0) h->fac_valid = false;   // Schmidt: the nuisance block of P+ is the prior's, so P+ != s2 Z^T Z
-    if (h->last_update_thin) h->fac_valid = false;               // the direct form of a thin stack (k_thin_*) has no Z: no factor to keep
-    if (h->factor_opt && h->n_nui == 0 && !h->last_update_thin) {   // S+ = sigma Z^T (or the prior's own factor if a gated object update was rejected): read before Pres changes
+    // the rule of commit_bookkeeping (a Schmidt update and the direct form of a thin stack leave no factor), with P+ copied into the
+    // resident buffer instead of written into the spare one, and S+ made by a launch of its own
+    const FacAfter fa = update_fac_after(h);
+    if (fa == FacAfter::adopt) {   // S+ = sigma Z^T (or the prior's own factor if a gated object update was rejected): read before Pres changes
         const PriorFactor pf = prior_factor(h);
         hipLaunchKernelGGL(k_fac_commit, dim3((kf * n + 255) / 256), dim3(256), 0, s, h->d_Z, h->ldz, kf, n, h->flags.noise_feature,
                            h->last_update_objects ? h->d_obj_accept : (const int*)nullptr, pf.base, pf.sLi, pf.sLj, h->d_Stmp, h->ldz,
                            (const int*)(h->d_info + 2));
         HIPCHK(hipGetLastError());
-        fac_adopt(h, n, kf, h->ldz, h->tail);
     }
     HIPCHK(hipMemcpyAsync(h->d_Pres, h->d_Pout, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, s));
     if (s != h->stream) HIPCHK(hipStreamSynchronize(s));   // the other cov_* calls run on the handle's own stream
-    h->res_n = n;
+    h->commit_update(n, kf, h->ldz, h->tail, false, fa);
     return ORCVIO_OK;
 }
 
@@ -390,9 +388,7 @@ int32_t orcvio_msckf_cov_commit_new_features(orcvio_msckf_handle* h, double* dx_
     HIPCHK(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (bad) { g_last_error = "cov_commit_new_features: singular H_2"; return ORCVIO_ERR_NOT_SPD; }
-    std::swap(h->d_Pres, h->d_Ptmp);
-    h->res_n = nt;
-    h->fac_valid = false;   // (the factor of the augmented covariance would have d k more columns: not kept)
+    h->commit_new_features(nt);   // (the factor of the augmented covariance would have d k more columns: not kept)
     h->new_F = 0;
     return ORCVIO_OK;
 }
@@ -405,9 +401,8 @@ int32_t orcvio_msckf_cov_prefactor(orcvio_msckf_handle* h) {
     if (!h || h->res_n == 0) { g_last_error = "cov_prefactor: no resident covariance"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     const int n = h->res_n, nb = (n + 15) / 16;
-    if (!h->factor_opt || (h->fac_valid && h->fac_n == n)) return ORCVIO_OK;   // switched off, or the factor is known already
+    if (!h->factor_opt || h->fac_follows()) return ORCVIO_OK;   // switched off, or the factor is known already
     if (nb > 14 || nb * 16 > h->NP_max) return ORCVIO_OK;   // no register-resident factorisation of this size: the update factors P itself
-    const int ld = round_up(n + 1, 16);
     hipStream_t s = h->stream;
     // L(i, j) = R[j * ld + i] (k_potrf_reg writes the upper factor R, P = R^T R, full 16 x 16 tiles, zeros below the diagonal): the
     // layout of the resident factor S (S(i, j) = d_Sres[i + j * fac_ld]).  With the reversed factorisation the
@@ -415,10 +410,11 @@ int32_t orcvio_msckf_cov_prefactor(orcvio_msckf_handle* h) {
     // are zero in the active rows (fac_tail)
     const double eps = 2.220446049250313e-16;
     const bool rev = h->fused_solve && n - 15 >= 16;
+    const int ld = CovBook::ld_for(n);
     double* dst = rev ? h->d_KG : h->d_Stmp;   // (d_KG: scratch of the optional outputs, free between updates)
     { const int rp = launch_potrf_reg_slots(s, h->d_Pres, n, n, 8.0 * eps, dst, ld, h->d_DinvP, h->d_info, 1, rev ? 1 : 0); if (rp != ORCVIO_OK) return rp; }
     if (rev) hipLaunchKernelGGL(k_fac_flip, dim3((n * ld + 255) / 256), dim3(256), 0, s, (const double*)dst, ld, n, h->d_Stmp, ld);
     HIPCHK(hipGetLastError());
-    fac_adopt(h, n, n, ld, rev ? 15 : 0);
+    h->prefactor(rev);
     return ORCVIO_OK;
 }

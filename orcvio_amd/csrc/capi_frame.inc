@@ -141,8 +141,7 @@ static int frame_chain_finish(orcvio_msckf_handle* h, const ChainGeom& g, int do
     if (re != ORCVIO_OK) return re;
     h->pub_pending = true;
     h->pub_enqueued++;
-    fac_adopt(h, n, kf, ldz, g.tail);
-    h->res_n = n;
+    h->commit_update(n, kf, ldz, g.tail, false, FacAfter::adopt);
     h->ran = true; h->last_update_objects = true; h->last_run_kind = 2; h->last_sharded = false;
     h->last_stream = sb;
     h->cnt_chained++;

@@ -54,20 +54,13 @@ static int step_validate_tracks(const orcvio_msckf_handle* h, const orcvio_msckf
 // launch, the removed clones by value (k_cov_remove_fac) -- orcvio_msckf_cov_remove_clones' arithmetic (a gather), no index map to copy
 static int step_remove(orcvio_msckf_handle* h, int leg, const int32_t* idx, int count) {
     if (!h->step_fused) return orcvio_msckf_cov_remove_clones(h, leg, idx, count);
-    const int n = h->res_n, m = n - 6 * count;
     RemoveArgs r{};
     r.leg = leg; r.count = count;
     for (int k = 0; k < count; ++k) r.clone[k] = idx[k];   // (ascending: remove_map walks the list with the index already shifted by the earlier removals)
-    const bool fac = h->fac_valid && h->fac_n == n;
-    const int ldo = round_up(m + 1, 16);
-    const int nb_P = (m * m + 255) / 256, nb_F = fac ? (h->fac_k * m + 255) / 256 : 0;
-    hipLaunchKernelGGL(k_cov_remove_fac, dim3(nb_P + nb_F), dim3(256), 0, h->stream, (const double*)h->d_Pres, n, m, r, h->d_Ptmp, nb_P,
-                       (const double*)h->d_Sres, h->fac_ld, fac ? h->fac_k : 0, h->d_Stmp, ldo);
+    const CovEdit e = h->gather(h->res_n - 6 * count);
+    const int nb_P = (e.m * e.m + 255) / 256, nb_F = e.fac ? (e.fac_k * e.m + 255) / 256 : 0;
+    hipLaunchKernelGGL(k_cov_remove_fac, dim3(nb_P + nb_F), dim3(256), 0, h->stream, e.P, e.n, e.m, r, e.Pout, nb_P, e.S, e.ld_in, e.fac ? e.fac_k : 0, e.Sout, e.ld_out);
     HIPCHK(hipGetLastError());
-    if (fac) fac_adopt(h, m, h->fac_k, ldo, h->fac_tail);
-    else h->fac_valid = false;
-    std::swap(h->d_Pres, h->d_Ptmp);
-    h->res_n = m;
     return ORCVIO_OK;
 }
 
@@ -111,8 +104,7 @@ struct StepEvents {   // validated; k == 0 and lost.count == 0: a frame without 
 static inline int* evt_status_host(const orcvio_msckf_handle* h) { return reinterpret_cast<int*>(h->h_evt + EVT_H_STATUS); }
 // k_cov_change_anchors on the resident covariance as the stream leaves it at this point, its inputs the feature step's outputs
 static int launch_change_anchors(orcvio_msckf_handle* h, hipStream_t s, const StepEvents& e, const double* poses, const int* first_info, bool wire, bool publish) {
-    const int n = h->res_n, leg = h->flags.leg_dim, base = leg + 6 * h->N;
-    const bool fac = h->fac_valid && h->fac_n == n;
+    const int leg = h->flags.leg_dim, base = leg + 6 * h->N;
     const double* dev = reinterpret_cast<const double*>(h->d_evt);
     AnchorFrameArgs fr{};
     fr.refuse = reinterpret_cast<const int*>(h->d_evt + EVT_D_STATUS);
@@ -121,16 +113,10 @@ static int launch_change_anchors(orcvio_msckf_handle* h, hipStream_t s, const St
     fr.par_host = reinterpret_cast<double*>(h->h_evt_dev + EVT_H_PAR);
     fr.status_host = reinterpret_cast<int*>(h->h_evt_dev + EVT_H_STATUS);
     if (publish) { fr.seq = h->d_seq; fr.flag = h->h_flag_dev; }
-    // (Y = J P goes to the spare covariance buffer: the buffer the commit in front has just left, overwritten as a whole by whatever writes it next)
-#define LAUNCH_CA(D) hipLaunchKernelGGL(k_cov_change_anchors<D>, dim3(1), dim3(AnchorThreads<D>::value), 0, s, h->d_Pres, n, fac ? h->d_Sres : (double*)nullptr, \
-                                        h->fac_ld, h->fac_k, poses, dev + FS_EXT, reinterpret_cast<const int*>(h->h_evt_dev), dev, e.k, base, leg, \
-                                        h->flags.if_fej ? 1 : 0, e.literal_3d ? 1 : 0, reinterpret_cast<double*>(h->d_evt + EVT_D_PAR), h->d_Ptmp, fr)
-    if (e.idp == 3) LAUNCH_CA(3);
-    else LAUNCH_CA(1);
-#undef LAUNCH_CA
-    HIPCHK(hipGetLastError());
-    if (!fac) h->fac_valid = false;
-    return ORCVIO_OK;
+    // (Y = J P goes to the spare covariance buffer: the buffer the commit in front has just left)
+    const AnchorLaunch a{e.idp, e.literal_3d ? 1 : 0, h->flags.if_fej ? 1 : 0, e.k, base, leg, poses, dev + FS_EXT, reinterpret_cast<const int*>(h->h_evt_dev), dev,
+                         reinterpret_cast<double*>(h->d_evt + EVT_D_PAR)};
+    return launch_cov_change_anchors(h, s, h->change_anchors(), a, fr);
 }
 
 struct StepSecond {   // what the second update of the frame needs besides the handle
@@ -272,11 +258,9 @@ static int step_validate_events(orcvio_msckf_handle* h, const orcvio_msckf_frame
         if (rec >= 0 && sf->anchor[rec] != c.old_anchor) return bad("change: the feature's slam_features record is anchored elsewhere than old_anchor");
         if (derive && rec < 0) return bad("change: with prune_apply_dx the changed feature needs its slam_features record (every in-state feature is tracked)");
         if ((!derive && !all_finite(c.p_w, 3)) || (h->flags.if_fej && !all_finite(c.p_fej, 3))) return bad("change: non-finite feature position");
-        ci[4 * q] = c.slot; ci[4 * q + 1] = c.old_anchor; ci[4 * q + 2] = c.new_anchor; ci[4 * q + 3] = rec < 0 ? 0 : rec;
-        for (int a = 0; a < 3; ++a) { cd[6 * q + a] = c.p_w[a]; cd[6 * q + 3 + a] = h->flags.if_fej ? c.p_fej[a] : c.p_w[a]; }
+        pack_anchor_change(c, h->flags.if_fej != 0, rec < 0 ? 0 : rec, ci + ANCHOR_CHG_STRIDE * q, cd + 6 * q);
     }
-    for (int a = 0; a < 9; ++a) cd[FS_EXT + a] = ev->R_b2c[a];
-    for (int a = 0; a < 3; ++a) cd[FS_EXT + 9 + a] = ev->t_c_b[a];
+    pack_extrinsics(ev->R_b2c, ev->t_c_b, cd + FS_EXT);
     if (!all_finite(cd + FS_EXT, 12)) return bad("non-finite extrinsics");
     const double* poses = reinterpret_cast<const double*>(h->h_stage + h->io_poses);
     for (int i = 0; i < N; ++i)
@@ -330,7 +314,12 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     // ---- the covariance's bookkeeping ahead of the first update: propagation and augmentation.  The handle's fields are set first and
     // the launches recorded; they go out once the first update's tracks have passed their checks (a validation failure leaves nothing done)
     const CovState cov0 = cov_state(h);
-    std::vector<std::function<int()>> head;
+    enum { PLAN_HEAD_FAC, PLAN_PROPAGATE, PLAN_AUGMENT, PLAN_GATHER };
+    struct { int kind; CovEdit e; } plan[3];   // (fused: the factor's launch behind the head; unfused: propagation, augmentation, lost features)
+    int n_plan = 0;
+    std::vector<int> lost_map;   // (the unfused removal's index map, staged when its launch goes out)
+    double* dPhi = h->d_covT + (size_t)46 * h->n_max; double* dQ = dPhi + 46 * 46;   // (the unfused propagation's Phi and Q, as orcvio_msckf_cov_propagate stages them)
+    const int aug_pose = h->res_n - (h->n_extra + d_lost);   // the new clone: in front of the feature states as they are BEFORE the removal
     // the fused form: ONE launch (k_frame_head) propagates and augments, pulls the whole arena and the in-state features' records out of
     // pinned memory and clears their dense rows; Phi, Q and the records are staged behind the tracks in the pinned arena
     const size_t slam_bytes = st->slam_features ? (size_t)st->slam_features->n_features * 160 + 9 * 64 : 0;
@@ -339,10 +328,10 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     FrameHeadArgs fa{};
     fa.pose_block = -1;
     if (fused && (st->Phi || st->augment || d_lost > 0)) {
-        const int nn = h->res_n, m = nn + (st->augment ? 6 : 0) - d_lost;   // (m: the state the first update sees)
-        fa.P = h->d_Pres; fa.n = nn; fa.out = h->d_Ptmp; fa.m = m; fa.leg = leg; fa.pose = st->augment ? nn - (h->n_extra + d_lost) : -1;
+        const CovEdit e = h->head(st->Phi != nullptr, st->augment != 0, d_lost);   // (e.m: the state the first update sees)
+        fa.P = e.P; fa.n = e.n; fa.out = e.Pout; fa.m = e.m; fa.leg = leg; fa.pose = st->augment ? aug_pose : -1;
         fa.lost = evs.lost;
-        fa.nb_cov = (m * m + 255) / 256;   // (the three regions enumerate every output element once)
+        fa.nb_cov = (e.m * e.m + 255) / 256;   // (the three regions enumerate every output element once)
         if (st->Phi) {
             char* hp = h->h_stage + off_aux;
             std::memcpy(hp, st->Phi, sizeof(double) * leg * leg);
@@ -350,92 +339,13 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             fa.Phi = reinterpret_cast<const double*>(h->h_stage_dev + off_aux);
             fa.Q = reinterpret_cast<const double*>(h->h_stage_dev + off_aux + al256(sizeof(double) * leg * leg));
         }
-        std::swap(h->d_Pres, h->d_Ptmp);
-        h->res_n = m;
-        if (st->Phi) h->fac_valid = false;
-        else if (h->fac_valid && h->fac_n == nn) {   // no propagation: the factor's rows are copied as orcvio_msckf_cov_augment copies them ...
-            const int pose = fa.pose, ldo = round_up(m + 1, 16), fk = h->fac_k, fld = h->fac_ld;
-            double* fs = h->d_Sres; double* fd = h->d_Stmp;
-            const LostMap lm = evs.lost;
-            head.push_back([=]() -> int {
-                if (lm.count > 0)   // ... and as orcvio_msckf_cov_remove_features deletes them, in the same gather
-                    hipLaunchKernelGGL(k_fac_head, dim3((fk * m + 255) / 256), dim3(256), 0, s, (const double*)fs, fld, fk, pose, lm, m, fd, ldo);
-                else hipLaunchKernelGGL(k_fac_augment, dim3((fk * m + 255) / 256), dim3(256), 0, s, (const double*)fs, fld, fk, nn, pose, fd, ldo);
-                HIPCHK(hipGetLastError());
-                return ORCVIO_OK;
-            });
-            fac_adopt(h, m, fk, ldo, st->augment ? 0 : h->fac_tail);
-        } else h->fac_valid = false;
+        if (e.fac) plan[n_plan++] = {PLAN_HEAD_FAC, e};   // no propagation: the factor's rows copied and deleted in a launch of their own
     }
-    if (!fused && st->Phi) {
-        const int nn = h->res_n;
-        double* src = h->d_Pres; double* dst = h->d_Ptmp;
-        double* dPhi = h->d_covT + (size_t)46 * h->n_max;
-        double* dQ = dPhi + 46 * 46;
-        const double* Phi = st->Phi; const double* Q = st->Q;
-        head.push_back([=]() -> int {
-            const AuxCopy cp[] = {{dPhi, Phi, sizeof(double) * (size_t)leg * leg}, {dQ, Q, sizeof(double) * (size_t)leg * leg}};
-            const int rc = aux_copies(h, s, cp, 2);
-            if (rc != ORCVIO_OK) return rc;
-            hipLaunchKernelGGL(k_cov_propagate_rows, dim3((leg * nn + 255) / 256), dim3(256), 0, s, (const double*)src, nn, (const double*)dPhi, leg, h->d_covT);
-            hipLaunchKernelGGL(k_cov_propagate_finish, dim3((nn * nn + 255) / 256), dim3(256), 0, s, (const double*)src, nn, (const double*)dPhi, (const double*)dQ, leg, (const double*)h->d_covT, dst);
-            HIPCHK(hipGetLastError());
-            return ORCVIO_OK;
-        });
-        std::swap(h->d_Pres, h->d_Ptmp);
-        h->fac_valid = false;
-    }
-    if (!fused && st->augment) {
-        const int nn = h->res_n, m = nn + 6, pose = nn - (h->n_extra + d_lost);   // (in front of the feature states as they are BEFORE the removal)
-        double* src = h->d_Pres; double* dst = h->d_Ptmp;
-        head.push_back([=]() -> int {
-            hipLaunchKernelGGL(k_cov_augment, dim3((m * m + 255) / 256), dim3(256), 0, s, (const double*)src, nn, pose, dst);
-            HIPCHK(hipGetLastError());
-            return ORCVIO_OK;
-        });
-        std::swap(h->d_Pres, h->d_Ptmp);
-        h->res_n = m;
-        if (h->fac_valid && h->fac_n == nn) {
-            const int ldo = round_up(m + 1, 16), fk = h->fac_k, fld = h->fac_ld;
-            double* fs = h->d_Sres; double* fd = h->d_Stmp;
-            head.push_back([=]() -> int {
-                hipLaunchKernelGGL(k_fac_augment, dim3((fk * m + 255) / 256), dim3(256), 0, s, (const double*)fs, fld, fk, nn, pose, fd, ldo);
-                HIPCHK(hipGetLastError());
-                return ORCVIO_OK;
-            });
-            fac_adopt(h, m, fk, ldo, 0);
-        } else h->fac_valid = false;
-    }
+    if (!fused && st->Phi) plan[n_plan++] = {PLAN_PROPAGATE, h->propagate()};
+    if (!fused && st->augment) plan[n_plan++] = {PLAN_AUGMENT, h->augment()};
     if (!fused && d_lost > 0) {   // the separate call's kernels (k_cov_remove / k_fac_remove) with its map
-        const int nn = h->res_n, m = nn - d_lost;
-        double* src = h->d_Pres; double* dst = h->d_Ptmp;
-        auto map = std::make_shared<std::vector<int>>();
-        for (int i = 0; i < m; ++i) {   // new index -> old index (ascending slots)
-            int o = i;
-            if (o >= evs.lost.fbase) {
-                int slot = (o - evs.lost.fbase) / evs.idp;
-                const int r = (o - evs.lost.fbase) % evs.idp;
-                for (int ls : evs.lost_slots) if (ls <= slot) ++slot;
-                o = evs.lost.fbase + evs.idp * slot + r;
-            }
-            map->push_back(o);
-        }
-        const bool fac = h->fac_valid && h->fac_n == nn;
-        const int ldo = round_up(m + 1, 16), fk = h->fac_k, fld = h->fac_ld;
-        double* fs = h->d_Sres; double* fd = h->d_Stmp;
-        head.push_back([=]() -> int {
-            const AuxCopy cp[] = {{h->d_covmap, map->data(), sizeof(int) * (size_t)m}};
-            const int rc = aux_copies(h, s, cp, 1);
-            if (rc != ORCVIO_OK) return rc;
-            hipLaunchKernelGGL(k_cov_remove, dim3((m * m + 255) / 256), dim3(256), 0, s, (const double*)src, nn, (const int*)h->d_covmap, m, dst);
-            if (fac) hipLaunchKernelGGL(k_fac_remove, dim3((fk * m + 255) / 256), dim3(256), 0, s, (const double*)fs, fld, fk, (const int*)h->d_covmap, m, fd, ldo);
-            HIPCHK(hipGetLastError());
-            return ORCVIO_OK;
-        });
-        if (fac) fac_adopt(h, m, fk, ldo, h->fac_tail);
-        else h->fac_valid = false;
-        std::swap(h->d_Pres, h->d_Ptmp);
-        h->res_n = m;
+        lost_map = lost_features_map(h->res_n, evs.lost.fbase, evs.idp, evs.lost_slots.data(), evs.lost.count);
+        plan[n_plan++] = {PLAN_GATHER, h->gather((int)lost_map.size())};
     }
     // ---- the first update's tracks: validated, the derived index arrays written (upload_finalize needs the prior's bookkeeping above)
     int rc = ORCVIO_OK;
@@ -462,7 +372,21 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
         rc = launch_frame_head(h, s, fa);
         if (rc != ORCVIO_OK) return rc;
     }
-    for (auto& f : head) { rc = f(); if (rc != ORCVIO_OK) return rc; }
+    for (int i = 0; i < n_plan && rc == ORCVIO_OK; ++i) {   // the launches of the edits planned above
+        const CovEdit& e = plan[i].e;
+        if (plan[i].kind == PLAN_HEAD_FAC) {   // the factor's rows as orcvio_msckf_cov_augment copies them and as orcvio_msckf_cov_remove_features deletes them, in one gather
+            const dim3 grid((e.fac_k * e.m + 255) / 256);
+            if (evs.lost.count > 0) hipLaunchKernelGGL(k_fac_head, grid, dim3(256), 0, s, e.S, e.ld_in, e.fac_k, fa.pose, evs.lost, e.m, e.Sout, e.ld_out);
+            else hipLaunchKernelGGL(k_fac_augment, grid, dim3(256), 0, s, e.S, e.ld_in, e.fac_k, e.n, fa.pose, e.Sout, e.ld_out);
+            HIPCHK(hipGetLastError());
+        } else if (plan[i].kind == PLAN_PROPAGATE) {
+            const AuxCopy cp[] = {{dPhi, st->Phi, sizeof(double) * (size_t)leg * leg}, {dQ, st->Q, sizeof(double) * (size_t)leg * leg}};
+            rc = aux_copies(h, s, cp, 2);
+            if (rc == ORCVIO_OK) rc = launch_cov_propagate(h, s, e, leg, dPhi, dQ);
+        } else if (plan[i].kind == PLAN_AUGMENT) rc = launch_cov_augment(h, s, e, aug_pose);
+        else rc = launch_cov_gather(h, s, e, lost_map);
+    }
+    if (rc != ORCVIO_OK) return rc;
     res->n_after = h->res_n;
     if (!fused) { rc = ingest_raw(h, s); if (rc != ORCVIO_OK) return rc; }
     tmark(1);

@@ -31,15 +31,11 @@ static int zupt_enqueue(orcvio_msckf_handle* h, const orcvio_msckf_zupt* z) {
     a.noise[0] = z->noise_v; a.noise[1] = z->noise_p; a.noise[2] = z->noise_q;
     a.n = n; a.b = z->leg_dim + 6 * z->n_clones; a.nui6 = 6 * h->n_nui;
     const int nt = (n + ZUPT_TILE - 1) / ZUPT_TILE;
-    hipLaunchKernelGGL(k_zupt_cov, dim3(nt, nt), dim3(256), 0, s, (const double*)h->d_Pres, a, h->d_Ptmp, zupt_dx(h), zupt_status(h));
+    const CovEdit e = h->zupt(h->n_nui == 0, ZUPT_KMAX);   // (nuisance states: the restored block breaks P = S S^T, no factor)
+    hipLaunchKernelGGL(k_zupt_cov, dim3(nt, nt), dim3(256), 0, s, e.P, a, e.Pout, zupt_dx(h), zupt_status(h));
+    if (e.fac) hipLaunchKernelGGL(k_zupt_fac, dim3((n + ZUPT_FAC_ROWS - 1) / ZUPT_FAC_ROWS), dim3(256), 0, s, e.S, e.ld_in, e.fac_k, a,
+                                  (const int*)zupt_status(h), e.Sout);
     HIPCHK(hipGetLastError());
-    if (h->fac_valid && h->fac_n == n && h->n_nui == 0 && h->fac_k <= ZUPT_KMAX) {
-        hipLaunchKernelGGL(k_zupt_fac, dim3((n + ZUPT_FAC_ROWS - 1) / ZUPT_FAC_ROWS), dim3(256), 0, s, (const double*)h->d_Sres, h->fac_ld, h->fac_k, a,
-                           (const int*)zupt_status(h), h->d_Stmp);
-        HIPCHK(hipGetLastError());
-        fac_adopt(h, n, h->fac_k, h->fac_ld, 0);   // (tail 0: the rows >= 15 are no longer zero in the trailing columns)
-    } else h->fac_valid = false;   // (nuisance states: the restored block breaks P = S S^T)
-    std::swap(h->d_Pres, h->d_Ptmp);
     return ORCVIO_OK;
 }
 
@@ -84,9 +80,9 @@ int32_t orcvio_msckf_cov_zupt_frame(orcvio_msckf_handle* h, const orcvio_msckf_z
     if (f->Phi) rc = orcvio_msckf_cov_propagate(h, z->leg_dim, f->Phi, f->Q);
     if (rc == ORCVIO_OK && f->augment) rc = orcvio_msckf_cov_augment(h);
     if (rc != ORCVIO_OK) return rc;
-    const int tail_before = h->fac_tail;
+    const CovState before = cov_state(h);
     rc = zupt_enqueue(h, z);
-    if (rc != ORCVIO_OK) return rc;   // (a launch that failed: nothing changed roles, propagation and augmentation stand)
+    if (rc != ORCVIO_OK) { cov_restore(h, before); return rc; }   // (a launch that failed: nothing changed roles, propagation and augmentation stand)
     if (f->remove_previous) {
         const int32_t prev = z->n_clones - 2;
         rc = orcvio_msckf_cov_remove_clones(h, z->leg_dim, &prev, 1);
@@ -101,7 +97,7 @@ int32_t orcvio_msckf_cov_zupt_frame(orcvio_msckf_handle* h, const orcvio_msckf_z
     *n_after = h->res_n;
     *applied = refused ? 0 : 1;
     if (refused) {   // the spare buffers took bit copies of the prior and of its factor, whose zero trailing columns are still zero
-        if (h->fac_valid) h->fac_tail = tail_before;
+        h->zupt_refused(before.fac_tail);
         g_last_error = "cov_zupt_frame: H P H^T + R not positive definite, or a non-finite covariance: the update was not applied";
         return ORCVIO_ERR_NOT_SPD;
     }

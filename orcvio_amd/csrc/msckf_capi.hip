@@ -30,6 +30,7 @@
 #include "object_lite.hpp"
 #include "io_ops.hpp"
 #include "frame_ops.hpp"
+#include "host/cov_book.hpp"
 #include <immintrin.h>
 #include <condition_variable>
 #include <memory>
@@ -71,7 +72,7 @@ struct ObjUse {   // a usable object track of the current object update
 };
 
 struct IpcComm;
-struct orcvio_msckf_handle {
+struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor and their bookkeeping: host/cov_book.hpp)
     int device = 0;
     int maxN = 0, maxF = 0, maxObs = 0;
     int n_max = 0, NAP_max = 0, NP_max = 0;
@@ -129,15 +130,13 @@ struct orcvio_msckf_handle {
     int ranks_seen = 0;                       // ranks whose block was present in the last sharded update looked at (orcvio_msckf_comm_details)
     int shard_status = 0;                     // sharded calls: this rank's own status travelling with its block (ORCVIO_ERR_PEER)
     hipStream_t last_stream = nullptr;   // stream of the last run_update / run_finish (download waits for it)
-    double *d_Pres = nullptr, *d_Ptmp = nullptr, *d_covT = nullptr;   // resident covariance, scratch, Phi*P rows
+    double* d_covT = nullptr;   // Phi*P rows of the propagation (d_Pres / d_Ptmp, the resident covariance and its spare buffer: CovBook)
     // Resident SQUARE-ROOT FACTOR of the resident covariance: P_res = S S^T with S (fac_n x fac_k), stored like the
     // Cholesky factor of the prior (d_RP): S(i,j) = d_Sres[j * fac_ld + i].  cov_commit keeps S+ = sigma Z^T of the update
     // that has just run (Z = L_M^-1 S^T is what the solve produces anyway), so the NEXT update of the same frame
     // (pruneImuStateBuffer, processObjects: src/orcvio.cpp:591-594, System.cpp:551-555) skips the Cholesky of its prior.
     // cov_augment / cov_remove_clones carry it along (rows copied / deleted); cov_set / cov_propagate invalidate it.
-    double *d_Sres = nullptr, *d_Stmp = nullptr;
-    int fac_n = 0, fac_k = 0, fac_ld = 0;
-    bool fac_valid = false;
+    // (d_Sres / d_Stmp, fac_n, fac_k, fac_ld, fac_tail, fac_valid: CovBook, with the rule of every edit)
     bool factor_opt = true;             // ORCVIO_OPT_RESIDENT_FACTOR
     int n_nui = 0;                      // ORCVIO_OPT_SCHMIDT_STATES: Schmidt nuisance states (6 columns each) at the END of the extra states
     bool obj_dof_rank = false;          // ORCVIO_OPT_OBJECT_DOF = 1: the object gate counts rows - rank(H_f) degrees of freedom (default: rows - columns, the reference's count)
@@ -160,7 +159,7 @@ struct orcvio_msckf_handle {
     // diag(M', s2 I_15) and only M' (kf - 15) is formed and factored.  `tail` = those trailing columns of the factor in use
     // (15, or 0: LDS-panel path, unfused solve, a resident factor that has been through an augmentation); fac_tail = the same
     // for the resident factor (kept by commit / remove_clones / clones_to_nuisance, dropped by augment).
-    int tail = 0, fac_tail = 0;
+    int tail = 0;
     // orcvio_msckf_io_update_frame: the object tracks' compression runs on a stream of its own beside the feature update's solve
     hipStream_t obj_stream = nullptr;
     hipEvent_t ev_obj = nullptr;
@@ -186,7 +185,6 @@ struct orcvio_msckf_handle {
     bool prior_forked = false;          // the Cholesky of the prior runs on the side stream (ev_side must be joined)
     int kf = 0;                         // columns of the prior's factor = dimension of M (n unless a resident factor is used)
     int* d_covmap = nullptr;
-    int res_n = 0;                      // dimension of the resident covariance (0 = none)
     bool pw_missing = false;            // uploaded without positions: triangulate_uploaded must run before the update
     int *d_tri_valid = nullptr, *d_tri_flags = nullptr, *d_tri_init = nullptr;
     double *d_tri_sol = nullptr, *d_tri_cost = nullptr;
@@ -354,35 +352,24 @@ struct UpdateCall {
     const unsigned* asm_wait = nullptr; unsigned asm_wait_val = 0;     // enqueue_update -> launch_solve_stage(ST_FORM_U): k_gemm_asmA_w
 };
 
-// ---- resident covariance / factor bookkeeping of the handle ---------------------------------------------------------------------
+// ---- resident covariance / factor bookkeeping of the handle (host/cov_book.hpp) ---------------------------------------------------
 // saved and restored around steps that are enqueued ahead of their outcome
-struct CovState { double *Pres, *Ptmp, *Sres, *Stmp; int res_n, fac_n, fac_k, fac_ld, fac_tail; bool fac_valid; };
-static inline CovState cov_state(const orcvio_msckf_handle* h) {
-    return CovState{h->d_Pres, h->d_Ptmp, h->d_Sres, h->d_Stmp, h->res_n, h->fac_n, h->fac_k, h->fac_ld, h->fac_tail, h->fac_valid};
+using CovState = CovBook;
+static inline CovState cov_state(const orcvio_msckf_handle* h) { return *h; }
+static inline void cov_restore(orcvio_msckf_handle* h, const CovState& c) { static_cast<CovBook&>(*h) = c; }
+// what the commit of the update enqueued last does to the resident factor
+static inline FacAfter update_fac_after(const orcvio_msckf_handle* h) {
+    if (h->last_update_thin) return FacAfter::drop;   // (the direct form of a thin stack leaves no square-root factor)
+    if (h->factor_opt && h->n_nui == 0) return FacAfter::adopt;   // S+ = sigma Z^T
+    return h->n_nui > 0 ? FacAfter::drop : FacAfter::leave;   // Schmidt: the nuisance block of P+ is the prior's, so P+ != s2 Z^T Z
 }
-static inline void cov_restore(orcvio_msckf_handle* h, const CovState& c) {
-    h->d_Pres = c.Pres; h->d_Ptmp = c.Ptmp; h->d_Sres = c.Sres; h->d_Stmp = c.Stmp;
-    h->res_n = c.res_n; h->fac_n = c.fac_n; h->fac_k = c.fac_k; h->fac_ld = c.fac_ld; h->fac_tail = c.fac_tail; h->fac_valid = c.fac_valid;
-}
-// the factor the last launch wrote into the spare buffer becomes the resident one: S is n x k with leading dimension ld, its last `tail`
-// columns zero in the active rows (the ONE place the two factor buffers change roles)
-static inline void fac_adopt(orcvio_msckf_handle* h, int n, int k, int ld, int tail) {
-    std::swap(h->d_Sres, h->d_Stmp);
-    h->fac_n = n; h->fac_k = k; h->fac_ld = ld; h->fac_tail = tail; h->fac_valid = true;
-}
-// ... the factor S+ = sigma Z^T of the update that has just been enqueued, and its covariance
-static inline void fac_adopt_update(orcvio_msckf_handle* h) {
-    fac_adopt(h, h->n, h->kf, h->ldz, h->tail);
-    h->res_n = h->n;
-}
+// the factor S+ = sigma Z^T of the update that has just been enqueued, and its covariance
+static inline void fac_adopt_update(orcvio_msckf_handle* h) { h->commit_update(h->n, h->kf, h->ldz, h->tail, false, FacAfter::adopt); }
 // the host-side bookkeeping of a commit that rides in the update's last launch (valid whether or not the device refuses the update:
 // a refused commit leaves the prior and a copy of its factor, io_ops.hpp k_epilogue)
 static inline void commit_bookkeeping(orcvio_msckf_handle* h) {
-    if (h->last_finpub_commit) { std::swap(h->d_Pres, h->d_Ptmp); h->last_finpub_commit = false; }   // (k_finish_pub wrote P+ into the spare buffer)
-    if (h->last_update_thin) h->fac_valid = false;   // (the direct form of a thin stack leaves no square-root factor)
-    else if (h->factor_opt && h->n_nui == 0) fac_adopt(h, h->n, h->kf, h->ldz, h->tail);
-    else if (h->n_nui > 0) h->fac_valid = false;   // Schmidt: the nuisance block of P+ is the prior's, so P+ != s2 Z^T Z
-    h->res_n = h->n;
+    h->commit_update(h->n, h->kf, h->ldz, h->tail, h->last_finpub_commit, update_fac_after(h));   // (k_finish_pub wrote P+ into the spare buffer)
+    h->last_finpub_commit = false;
 }
 
 template <typename T>
