@@ -1217,6 +1217,68 @@ typedef struct orcvio_msckf_frame_result_ex {
 int32_t orcvio_msckf_io_step_frame_ex(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* step, const orcvio_msckf_frame_events* events,
                                       orcvio_msckf_frame_result_ex* result);
 
+/* ---- IMU propagation from raw samples (batchImuProcessing -> processModel, src/orcvio.cpp:664-928, :3952-4367) -----------------------
+ * What the reference runs in front of every image: per IMU sample a state predictor, one of three forms of Phi, Q = Phi G Q_c G^T Phi^T dt
+ * and three products against P.  The call takes the raw samples.  Its HOST half (csrc/host/imu_model.hpp) selects the samples as
+ * :678-709 do (t <= state.time skipped; stop at the first t - time_bound > imu_img_time_th) and runs one predictor per selected sample
+ * (predictNewStateLARVIO or predictNewStateOrcVIO): *state and prev_meas are updated when the call returns, without a wait.  Its DEVICE
+ * half is one launch (k_imu_phi_q, one workgroup): the S pairs (Phi_k, Q_k) from the states the host half left, accumulated in order to
+ * Phi = Phi_S ... Phi_1 and Q (Q <- Phi_k Q Phi_k^T + Q_k), written where the propagation launches of orcvio_msckf_cov_propagate read
+ * them, which follow on the handle's stream: the resident factor is dropped as cov_propagate drops it.  The accumulated pair applied once
+ * equals the reference's per-sample application to rounding ("IMU propagation from raw samples").
+ *   cfg       leg_dim 22 only (calib_imu_instrinsic = 0: Tg = Ma = I, As = 0); use_larvio / use_left_perturbation / use_closed_form /
+ *             if_fej choose the predictor and the form of Phi as :750-773, :3960, :3997 do; Q_c_diag: the diagonal of
+ *             continuous_noise_cov (:429-438: gyro, acc, gyro bias, acc bias VARIANCES, three each)
+ *   state     in: imu_state (and the velocity / position of imu_state_FEJ_now, read under if_fej); out: the propagated state
+ *   prev_meas [6] m_gyro_old | m_acc_old (:703-704), in and out: carried from frame to frame by the caller
+ *   samples   [n_samples][7]: t | angular_velocity | linear_acceleration
+ *   info      wait (in): != 0 makes the call wait for the device once and report a refusal.  Out: n_used (skipped + processed: what the
+ *             reference erases from its buffer), n_propagated (S), dt = t_last - time_bound (imu_state.dt), mean_sforce (meanSForce;
+ *             zero when S = 0, where the reference divides by zero), applied (1; 0 after a refusal the call has seen, or S = 0)
+ *   Phi_out, Q_out   [22][22] or NULL; not NULL makes the call wait, as info->wait does
+ * S = 0 after selection: no launch, the covariance and its factor untouched, Phi_out = I, Q_out = 0.
+ * Refused on the device: a non-finite entry in Phi or Q -- the reference's right closed form (:4343, :4348) divides by |gyro|^2, so an
+ * exactly zero unbiased gyro sample gives NaN.  The kernel leaves a status word that the propagation launches behind it read: they
+ * copy P bit for bit.  A call that waits returns ORCVIO_ERR_NOT_SPD with applied = 0 (*state is propagated all the same: the mean does
+ * not depend on Phi); a call that does not wait cannot report it.  Either way the resident factor is dropped.
+ * Refused before anything is done (*state and prev_meas untouched): a null argument, leg_dim != 22, no resident covariance
+ * (ORCVIO_ERR_INVALID); more than 128 selected samples (ORCVIO_ERR_CAPACITY; info->n_used / n_propagated are filled). */
+typedef struct orcvio_msckf_imu_config {
+    int32_t leg_dim;                /* 22 */
+    int32_t use_larvio, use_left_perturbation, use_closed_form, if_fej;
+    double  gravity[3];             /* IMUState::gravity */
+    double  imu_img_time_th;        /* 1 / (2 imu_rate), :76 */
+    double  Q_c_diag[12];
+} orcvio_msckf_imu_config;
+typedef struct orcvio_msckf_imu_state {
+    double time;
+    double R_b2w[9], v[3], p[3];    /* imu_state.orientation (row-major), velocity, position */
+    double gyro_bias[3], acc_bias[3];
+    double v_fej[3], p_fej[3];      /* imu_state_FEJ_now.velocity / position */
+} orcvio_msckf_imu_state;
+typedef struct orcvio_msckf_imu_info {
+    int32_t wait;
+    int32_t n_used, n_propagated, applied;
+    double  dt, mean_sforce[3];
+} orcvio_msckf_imu_info;
+int32_t orcvio_msckf_cov_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, orcvio_msckf_imu_state* state,
+                                       double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
+                                       orcvio_msckf_imu_info* info, double* Phi_out, double* Q_out);
+/* The ARMED form (same inputs): the host half runs now -- *state, prev_meas and info are valid on return, info->applied = 0 -- and the
+ * next orcvio_msckf_io_step_frame / _io_step_frame_ex / _cov_zupt_frame on the handle is armed, in the manner of
+ * orcvio_msckf_io_triangulate: given Phi = Q = NULL, it enqueues k_imu_phi_q in front of its head launch (the propagation launches, for
+ * cov_zupt_frame) and hands them the device's Phi / Q instead of a staged copy -- the frame's one wait stays one wait, and the results
+ * are bit for bit those of the frame given Phi_out / Q_out of orcvio_msckf_cov_propagate_imu.  S = 0 after selection arms nothing.
+ * An armed handle given Phi != NULL: ORCVIO_ERR_INVALID, nothing done, the arming stands; so does it behind every other validation
+ * failure of the frame call.  orcvio_msckf_cov_propagate_imu and a second arming on an armed handle: ORCVIO_ERR_INVALID.
+ * A refused Phi / Q (non-finite) refuses the frame's propagation and BOTH updates (cov_zupt_frame: the zero-velocity update);
+ * augmentation, removals, anchor changes and marginalisation stand.  The frame call returns ORCVIO_ERR_NOT_SPD with status_first =
+ * status_prune = ORCVIO_ERR_NOT_SPD and stats[3] = 0 (cov_zupt_frame: *applied = 0).
+ * Not with a communicator on the handle (as io_step_frame), not together with orcvio_msckf_io_triangulate on the same frame, leg_dim 22. */
+int32_t orcvio_msckf_io_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, orcvio_msckf_imu_state* state,
+                                      double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
+                                      orcvio_msckf_imu_info* info);
+
 /* ---- Environment switches (read once per process; diagnostics and A/B measurements -- every one of them leaves the results unchanged) ----
  *   ORCVIO_COMM_TIMEOUT_S   bound of every wait another rank can strand, seconds (default 180)
  *   ORCVIO_IPC_WAIT_S       ipc transport: bound of the device-side wait for a peer's block, seconds (default 20, at most the above)

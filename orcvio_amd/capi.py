@@ -47,7 +47,7 @@ EXPORTS = [
     'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect', 'orcvio_msckf_io_triangulate',
     'orcvio_msckf_objects_refined', 'orcvio_msckf_counters', 'orcvio_msckf_comm_details', 'orcvio_msckf_profile_sharded',
     'orcvio_msckf_io_step_frame', 'orcvio_msckf_io_step_frame_ex', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
-    'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame',
+    'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame', 'orcvio_msckf_cov_propagate_imu', 'orcvio_msckf_io_propagate_imu',
 ]
 
 
@@ -174,6 +174,23 @@ class ZuptFrame(C.Structure):
     _fields_ = [('zupt', Zupt), ('Phi', _dp), ('Q', _dp), ('augment', C.c_int32), ('remove_previous', C.c_int32)]
 
 
+class ImuConfig(C.Structure):
+    """orcvio_msckf_imu_config (include/orcvio_msckf.h)."""
+    _fields_ = [('leg_dim', C.c_int32), ('use_larvio', C.c_int32), ('use_left_perturbation', C.c_int32), ('use_closed_form', C.c_int32),
+                ('if_fej', C.c_int32), ('gravity', C.c_double * 3), ('imu_img_time_th', C.c_double), ('Q_c_diag', C.c_double * 12)]
+
+
+class ImuState(C.Structure):
+    """orcvio_msckf_imu_state: imu_state and the velocity / position of imu_state_FEJ_now."""
+    _fields_ = [('time', C.c_double), ('R_b2w', C.c_double * 9), ('v', C.c_double * 3), ('p', C.c_double * 3), ('gyro_bias', C.c_double * 3),
+                ('acc_bias', C.c_double * 3), ('v_fej', C.c_double * 3), ('p_fej', C.c_double * 3)]
+
+
+class ImuInfo(C.Structure):
+    _fields_ = [('wait', C.c_int32), ('n_used', C.c_int32), ('n_propagated', C.c_int32), ('applied', C.c_int32), ('dt', C.c_double),
+                ('mean_sforce', C.c_double * 3)]
+
+
 class MsckfState(C.Structure):
     _fields_ = [('R_b2w_imu', C.c_double * 9), ('v', C.c_double * 3), ('p', C.c_double * 3), ('bg', C.c_double * 3),
                 ('ba', C.c_double * 3), ('R_b2c', C.c_double * 9), ('t_c_b', C.c_double * 3), ('td', C.c_double),
@@ -257,6 +274,10 @@ def _bind(lib):
                                                     C.POINTER(AnchorChange), C.c_int32, _dp, _dp]
     lib.orcvio_msckf_cov_zupt.argtypes = [C.c_void_p, C.POINTER(Zupt), _dp, _ip]
     lib.orcvio_msckf_cov_zupt_frame.argtypes = [C.c_void_p, C.POINTER(ZuptFrame), _dp, _ip, _ip]
+    lib.orcvio_msckf_cov_propagate_imu.argtypes = [C.c_void_p, C.POINTER(ImuConfig), C.POINTER(ImuState), _dp, _dp, C.c_int32, C.c_double,
+                                                   C.POINTER(ImuInfo), _dp, _dp]
+    lib.orcvio_msckf_io_propagate_imu.argtypes = [C.c_void_p, C.POINTER(ImuConfig), C.POINTER(ImuState), _dp, _dp, C.c_int32, C.c_double,
+                                                  C.POINTER(ImuInfo)]
     lib.orcvio_msckf_upload_nuisance_poses.argtypes = [C.c_void_p, C.c_void_p]
     lib.orcvio_msckf_update_object_tracks.argtypes = [C.c_void_p, C.POINTER(MsckfFlags), C.POINTER(ObjectEvalFlags), C.c_int32,
                                                       C.POINTER(ObjectTrackC), C.c_int32, _dp, C.POINTER(MsckfResult)]
@@ -1402,6 +1423,53 @@ class MsckfUpdater:
         Ph = np.ascontiguousarray(Phi, dtype=np.float64)
         Qc = np.ascontiguousarray(Q, dtype=np.float64)
         self._chk(self.lib.orcvio_msckf_cov_propagate(self.h, Ph.shape[0], _d(Ph), _d(Qc)), 'orcvio_msckf_cov_propagate')
+
+    @staticmethod
+    def imu_config(leg_dim=22, use_larvio=1, use_left=0, use_closed_form=1, if_fej=0, gravity=(0.0, 0.0, -9.81), imu_img_time_th=0.0025,
+                   Qc_diag=None):
+        c = ImuConfig(leg_dim, int(use_larvio), int(use_left), int(use_closed_form), int(if_fej))
+        c.gravity[:] = [float(x) for x in gravity]
+        c.imu_img_time_th = float(imu_img_time_th)
+        c.Q_c_diag[:] = [float(x) for x in (np.zeros(12) if Qc_diag is None else Qc_diag)]
+        return c
+
+    @staticmethod
+    def imu_state(time, R, v, p, bg, ba, v_fej=None, p_fej=None):
+        s = ImuState()
+        s.time = float(time)
+        s.R_b2w[:] = [float(x) for x in np.asarray(R).ravel()]
+        for name, val in (('v', v), ('p', p), ('gyro_bias', bg), ('acc_bias', ba), ('v_fej', v if v_fej is None else v_fej),
+                          ('p_fej', p if p_fej is None else p_fej)):
+            getattr(s, name)[:] = [float(x) for x in val]
+        return s
+
+    def cov_propagate_imu(self, cfg, state, prev_meas, samples, time_bound, wait=False, want_PhiQ=False, raise_on_refusal=True):
+        """orcvio_msckf_cov_propagate_imu: the IMU step from raw samples on the resident covariance.  cfg: ImuConfig; state: ImuState,
+        propagated in place; prev_meas [6] (m_gyro_old | m_acc_old), updated in place; samples [n][7] t | gyro | acc.  Returns
+        dict(status, n_used, n_propagated, dt, mean_sforce, applied, Phi, Q); Phi, Q [22][22] with want_PhiQ (the call then waits)."""
+        smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, 7)
+        assert isinstance(prev_meas, np.ndarray) and prev_meas.dtype == np.float64 and prev_meas.size == 6 and prev_meas.flags.c_contiguous
+        info = ImuInfo()
+        info.wait = 1 if wait else 0
+        Phi = np.zeros((22, 22)) if want_PhiQ else None
+        Q = np.zeros((22, 22)) if want_PhiQ else None
+        rc = self.lib.orcvio_msckf_cov_propagate_imu(self.h, C.byref(cfg), C.byref(state), _d(prev_meas), _d(smp) if smp.size else None,
+                                                     smp.shape[0], float(time_bound), C.byref(info), _d(Phi) if want_PhiQ else None,
+                                                     _d(Q) if want_PhiQ else None)
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_propagate_imu')
+        return dict(status=int(rc), n_used=int(info.n_used), n_propagated=int(info.n_propagated), dt=float(info.dt),
+                    mean_sforce=np.array(info.mean_sforce[:]), applied=int(info.applied), Phi=Phi, Q=Q)
+
+    def io_propagate_imu(self, cfg, state, prev_meas, samples, time_bound):
+        """orcvio_msckf_io_propagate_imu: the host half now (state, prev_meas updated in place), the next io_step_frame / io_step_frame_ex /
+        cov_zupt_frame on the handle -- given Phi = Q = None -- makes Phi and Q on the device in front of its head launch."""
+        smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, 7)
+        assert isinstance(prev_meas, np.ndarray) and prev_meas.dtype == np.float64 and prev_meas.size == 6 and prev_meas.flags.c_contiguous
+        info = ImuInfo()
+        self._chk(self.lib.orcvio_msckf_io_propagate_imu(self.h, C.byref(cfg), C.byref(state), _d(prev_meas), _d(smp) if smp.size else None,
+                                                         smp.shape[0], float(time_bound), C.byref(info)), 'orcvio_msckf_io_propagate_imu')
+        return dict(n_used=int(info.n_used), n_propagated=int(info.n_propagated), dt=float(info.dt), mean_sforce=np.array(info.mean_sforce[:]))
 
     def cov_augment(self):
         self._chk(self.lib.orcvio_msckf_cov_augment(self.h), 'orcvio_msckf_cov_augment')

@@ -107,9 +107,11 @@ int32_t orcvio_msckf_cov_set(orcvio_msckf_handle* h, int32_t n, const double* P)
 
 // ---- the launches of an edit, ONE per kernel family: what to read and write comes in the record the edit's bookkeeping left
 // (CovBook, host/cov_book.hpp); Phi and Q are device pointers, their staging stays with the caller
-static int launch_cov_propagate(orcvio_msckf_handle* h, hipStream_t s, const CovEdit& e, int leg, const double* dPhi, const double* dQ) {
+// refuse: a device word behind which Phi / Q are not to be applied (orcvio_msckf_cov_propagate_imu), or nullptr
+static int launch_cov_propagate(orcvio_msckf_handle* h, hipStream_t s, const CovEdit& e, int leg, const double* dPhi, const double* dQ,
+                                const int* refuse = nullptr) {
     hipLaunchKernelGGL(k_cov_propagate_rows, dim3((leg * e.n + 255) / 256), dim3(256), 0, s, e.P, e.n, dPhi, leg, h->d_covT);
-    hipLaunchKernelGGL(k_cov_propagate_finish, dim3((e.n * e.n + 255) / 256), dim3(256), 0, s, e.P, e.n, dPhi, dQ, leg, (const double*)h->d_covT, e.Pout);
+    hipLaunchKernelGGL(k_cov_propagate_finish, dim3((e.n * e.n + 255) / 256), dim3(256), 0, s, e.P, e.n, dPhi, dQ, leg, (const double*)h->d_covT, e.Pout, refuse);
     HIPCHK(hipGetLastError());
     return ORCVIO_OK;
 }

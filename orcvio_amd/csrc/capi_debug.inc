@@ -307,4 +307,43 @@ int32_t orcvio_msckf_debug_potrf_solve(orcvio_msckf_handle* h, const double* X, 
     return rc;
 }
 
+// k_imu_phi_q alone, by events on the handle's stream: the host half once, the records copied once, one warm-up launch, then `reps`
+// launches each between two events; ms_out [reps] (scripts/gpu_imu_propagate_timing.py takes the median).  The covariance is not touched.
+int32_t orcvio_msckf_debug_imu_kernel_ms(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, const orcvio_msckf_imu_state* state,
+                                         const double* prev_meas, const double* samples, int32_t n_samples, double time_bound, int32_t reps,
+                                         float* ms_out) {
+    if (!h || !cfg || !state || !prev_meas || !samples || !ms_out || reps < 1 || cfg->leg_dim != 22) return ORCVIO_ERR_INVALID;
+    ImuMeanState st;
+    double prev[6];
+    double* recs = h->imu_recs.data();
+    ImuBatchInfo bi{};
+    ImuFlags fl{};
+    { const int rh = imu_host_half(cfg, state, prev_meas, samples, n_samples, time_bound, &st, prev, recs, &bi, &fl, "debug_imu_kernel_ms"); if (rh != ORCVIO_OK) return rh; }
+    if (bi.n_propagated < 1) return ORCVIO_ERR_INVALID;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    double* dPhi = h->d_covT + (size_t)46 * h->n_max;
+    double* dQ = dPhi + 46 * 46;
+    int rc = imu_enqueue(h, s, cfg, fl, recs, bi.n_propagated, dPhi, dQ);   // (records staged, warm-up)
+    if (rc != ORCVIO_OK) return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t he = hipEventCreate(&e0);
+    if (he == hipSuccess) he = hipEventCreate(&e1);
+    ImuKernArgs a{};
+    a.recs = h->d_imu; a.Phi = dPhi; a.Q = dQ; a.status = imu_status(h); a.S = bi.n_propagated; a.flags = fl;
+    for (int i = 0; i < 3; ++i) a.grav[i] = cfg->gravity[i];
+    for (int i = 0; i < 12; ++i) a.qc[i] = cfg->Q_c_diag[i];
+    for (int r = 0; r < reps && he == hipSuccess; ++r) {   // (the first HIP error ends the loop; the events are destroyed on every path)
+        he = hipEventRecord(e0, s);
+        hipLaunchKernelGGL(k_imu_phi_q, dim3(1), dim3(64 * IMU_WAVES), imu_lds_bytes(a.S), s, a);
+        if (he == hipSuccess) he = hipEventRecord(e1, s);
+        if (he == hipSuccess) he = hipEventSynchronize(e1);
+        if (he == hipSuccess) he = hipEventElapsedTime(&ms_out[r], e0, e1);
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (he != hipSuccess) { g_last_error = std::string("debug_imu_kernel_ms: ") + hipGetErrorString(he); return ORCVIO_ERR_HIP; }
+    return ORCVIO_OK;
+}
+
 #endif  // ORCVIO_DEBUG_HOOKS

@@ -215,7 +215,7 @@ static void free_all(orcvio_msckf_handle* h) {
                     h->d_DinvP, h->d_U, h->d_M, h->d_RM, h->d_DinvM, h->d_Z, h->d_La, h->d_DinvA,
                     h->d_W, h->d_Y, h->d_KG, h->d_Gobj, h->d_RF, h->d_DinvF, h->d_Yobj, h->d_objH,
                     h->d_obj_gamma, h->d_obj_i, h->d_obj_accept, h->d_T3, h->d_Xobs, h->d_S,
-                    h->d_Pres, h->d_Ptmp, h->d_Sres, h->d_Stmp, h->d_covT, h->d_covmap, h->d_skip, h->d_tri_valid, h->d_tri_flags, h->d_tri_init, h->d_tri_sol, h->d_tri_cost, h->d_sync, h->d_la_rdy, h->d_U2, h->d_M2, h->d_RM2, h->d_DinvM2, h->d_Z2, h->d_outs2, h->d_chain_words, h->d_obj_done,
+                    h->d_Pres, h->d_Ptmp, h->d_Sres, h->d_Stmp, h->d_covT, h->d_covmap, h->d_imu, h->d_skip, h->d_tri_valid, h->d_tri_flags, h->d_tri_init, h->d_tri_sol, h->d_tri_cost, h->d_sync, h->d_la_rdy, h->d_U2, h->d_M2, h->d_RM2, h->d_DinvM2, h->d_Z2, h->d_outs2, h->d_chain_words, h->d_obj_done,
                     h->d_ekf_i, h->d_ekf_d, h->d_ekf_E, h->d_Gekf, h->d_ekf_gamma, h->d_ekf_accept, h->d_slam, h->d_dense, h->d_Rf, h->d_new, h->d_aug};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -225,6 +225,7 @@ static void free_all(orcvio_msckf_handle* h) {
     if (h->d_lm) (void)hipFree(h->d_lm);
     if (h->h_stage2) (void)hipHostFree(h->h_stage2);
     if (h->h_tri) (void)hipHostFree(h->h_tri);
+    if (h->h_imu_status) (void)hipHostFree(h->h_imu_status);
     if (h->d_tri_words) (void)hipFree(h->d_tri_words);
     if (h->d_in2) (void)hipFree(h->d_in2);
     if (h->d_step_words) (void)hipFree(h->d_step_words);
@@ -336,6 +337,15 @@ int32_t orcvio_msckf_create(int32_t device, int32_t max_clones, int32_t max_feat
         HIPCHK(hipMalloc(&h->d_Stmp, sizeof(double) * np2));
         HIPCHK(hipMalloc(&h->d_covT, sizeof(double) * (46 * (size_t)h->n_max + 2 * 46 * 46)));   // Phi P rows, then Phi and Q
         HIPCHK(hipMalloc(&h->d_covmap, sizeof(int) * h->n_max));
+        // orcvio_msckf_cov_propagate_imu: the per-sample records, then the status word of k_imu_phi_q; its dynamic LDS at 128 samples
+        // (105 KB) is beyond the 64 KB a kernel gets without asking.  Here, so that the call itself never allocates or synchronises
+        HIPCHK(hipMalloc(&h->d_imu, sizeof(double) * ((size_t)IMU_MAX_SAMPLES * IMU_REC + 8)));
+        HIPCHK(hipFuncSetAttribute((const void*)k_imu_phi_q, hipFuncAttributeMaxDynamicSharedMemorySize, (int)imu_lds_bytes(IMU_MAX_SAMPLES)));
+        h->imu_recs.resize((size_t)IMU_MAX_SAMPLES * IMU_REC);
+        HIPCHK(hipMemset(h->d_imu + (size_t)IMU_MAX_SAMPLES * IMU_REC, 0, 64));   // (the sixteen status words: the kernel writes [0] and [2] only)
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_imu_status), 64, hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->h_imu_status_dev), h->h_imu_status, 0));
+        std::memset(h->h_imu_status, 0, 64);
         HIPCHK(hipMalloc(&h->d_tri_valid, sizeof(int) * max_features));
         HIPCHK(hipMalloc(&h->d_tri_flags, sizeof(int) * max_features));
         HIPCHK(hipMalloc(&h->d_tri_init, sizeof(int) * max_features));

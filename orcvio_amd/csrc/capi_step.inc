@@ -126,6 +126,7 @@ struct StepSecond {   // what the second update of the frame needs besides the h
     const int* infoA;       // device: its status words
     int apply_dx;
     const StepEvents* ev;   // anchor changes between the pose step and the update (nullptr: none)
+    const int* also = nullptr;   // the armed IMU launch's status block: its refusal goes into the kept status words (PoseStepArgs.also)
 };
 
 // the second update's inputs into the (swapped-in) second arena and its launches; `wait` = run it the safe way (separate launches, the
@@ -148,7 +149,7 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
     }
     // window poses: the first update's, on the device (incremented by its dx or copied); the first update's status words are kept
     PoseStepArgs ps{b.posesA, h->d_poses, N, POSE_STRIDE, b.dxA, fl.leg_dim, b.apply_dx, (fl.use_larvio || fl.use_left_perturbation) ? 1 : 0,
-                    fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words};
+                    fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words, safe ? (const int*)nullptr : b.also};
     const bool events = b.ev && b.ev->k > 0;
     if (!h->step_fused || safe) {
         if (events) hipLaunchKernelGGL(k_event_step, dim3(1), dim3(128), 0, s, ps, b.ev->fs);
@@ -204,7 +205,7 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
 static int step_events_alone(orcvio_msckf_handle* h, hipStream_t s, const orcvio_msckf_flags& fl, int N, const StepSecond& b, bool safe, bool publish) {
     double* poses = reinterpret_cast<double*>(h->d_evt + EVT_D_POSES);
     PoseStepArgs ps{b.posesA, poses, N, POSE_STRIDE, b.dxA, fl.leg_dim, b.apply_dx, (fl.use_larvio || fl.use_left_perturbation) ? 1 : 0,
-                    fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words};
+                    fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words, safe ? (const int*)nullptr : b.also};
     hipLaunchKernelGGL(k_event_step, dim3(1), dim3(128), 0, s, ps, b.ev->fs);
     HIPCHK(hipGetLastError());
     return launch_change_anchors(h, s, *b.ev, poses, safe ? (const int*)nullptr : h->d_step_words, false, publish);
@@ -287,6 +288,12 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     const int leg = fl.leg_dim, N = h->N, n = h->n;
     if (st->leg_dim != leg) { g_last_error = std::string(who) + ": leg_dim differs from the flags of io_begin"; return ORCVIO_ERR_INVALID; }
     if ((st->Phi == nullptr) != (st->Q == nullptr)) { g_last_error = std::string(who) + ": Phi and Q come together"; return ORCVIO_ERR_INVALID; }
+    // armed by orcvio_msckf_io_propagate_imu: Phi and Q are made on the device (k_imu_phi_q) in front of the head launch
+    const bool armed = h->imu_armed;
+    if (armed && st->Phi) { g_last_error = std::string(who) + ": the handle is armed by orcvio_msckf_io_propagate_imu: Phi and Q must be NULL"; return ORCVIO_ERR_INVALID; }
+    if (armed && leg != 22) { g_last_error = std::string(who) + ": armed IMU propagation at leg_dim 22 only"; return ORCVIO_ERR_INVALID; }
+    if (armed && h->tri_armed) { g_last_error = std::string(who) + ": armed by orcvio_msckf_io_propagate_imu AND by orcvio_msckf_io_triangulate: one of the two per frame"; return ORCVIO_ERR_INVALID; }
+    const bool prop = st->Phi != nullptr || armed;
     if (st->n_remove < 0 || st->n_remove > 8 || (st->n_remove > 0 && !st->remove_clones)) { g_last_error = std::string(who) + ": remove_clones: at most eight"; return ORCVIO_ERR_INVALID; }
     for (int k = 0; k < st->n_remove; ++k)
         if (st->remove_clones[k] < 0 || st->remove_clones[k] >= N || (k > 0 && st->remove_clones[k] <= st->remove_clones[k - 1])) {
@@ -327,8 +334,8 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     const bool fused = h->step_fused && off_aux + 2 * al256(sizeof(double) * leg * leg) + slam_bytes <= h->in_cap;
     FrameHeadArgs fa{};
     fa.pose_block = -1;
-    if (fused && (st->Phi || st->augment || d_lost > 0)) {
-        const CovEdit e = h->head(st->Phi != nullptr, st->augment != 0, d_lost);   // (e.m: the state the first update sees)
+    if (fused && (prop || st->augment || d_lost > 0)) {
+        const CovEdit e = h->head(prop, st->augment != 0, d_lost);   // (e.m: the state the first update sees)
         fa.P = e.P; fa.n = e.n; fa.out = e.Pout; fa.m = e.m; fa.leg = leg; fa.pose = st->augment ? aug_pose : -1;
         fa.lost = evs.lost;
         fa.nb_cov = (e.m * e.m + 255) / 256;   // (the three regions enumerate every output element once)
@@ -339,9 +346,10 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             fa.Phi = reinterpret_cast<const double*>(h->h_stage_dev + off_aux);
             fa.Q = reinterpret_cast<const double*>(h->h_stage_dev + off_aux + al256(sizeof(double) * leg * leg));
         }
+        if (armed) { fa.Phi = dPhi; fa.Q = dQ; fa.refuse = imu_status(h); }   // (device memory: where k_imu_phi_q leaves them)
         if (e.fac) plan[n_plan++] = {PLAN_HEAD_FAC, e};   // no propagation: the factor's rows copied and deleted in a launch of their own
     }
-    if (!fused && st->Phi) plan[n_plan++] = {PLAN_PROPAGATE, h->propagate()};
+    if (!fused && prop) plan[n_plan++] = {PLAN_PROPAGATE, h->propagate()};
     if (!fused && st->augment) plan[n_plan++] = {PLAN_AUGMENT, h->augment()};
     if (!fused && d_lost > 0) {   // the separate call's kernels (k_cov_remove / k_fac_remove) with its map
         lost_map = lost_features_map(h->res_n, evs.lost.fbase, evs.idp, evs.lost_slots.data(), evs.lost.count);
@@ -354,6 +362,8 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     if (rc != ORCVIO_OK) { cov_restore(h, cov0); (void)arena_mark_read(h, s); return rc; }
     h->pw_missing = false;
     tmark(0);
+    if (armed) { rc = imu_consume(h, s); if (rc != ORCVIO_OK) return rc; }   // nothing can refuse the frame any more: the arming is taken
+    const int* imu_also = armed ? imu_status(h) : nullptr;
     if (fused) {
         fa.nseg = 1;
         fa.src[0] = h->h_stage_dev; fa.dst[0] = h->d_in; fa.bytes[0] = (unsigned)upload_bytes(h);
@@ -380,9 +390,11 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             else hipLaunchKernelGGL(k_fac_augment, grid, dim3(256), 0, s, e.S, e.ld_in, e.fac_k, e.n, fa.pose, e.Sout, e.ld_out);
             HIPCHK(hipGetLastError());
         } else if (plan[i].kind == PLAN_PROPAGATE) {
-            const AuxCopy cp[] = {{dPhi, st->Phi, sizeof(double) * (size_t)leg * leg}, {dQ, st->Q, sizeof(double) * (size_t)leg * leg}};
-            rc = aux_copies(h, s, cp, 2);
-            if (rc == ORCVIO_OK) rc = launch_cov_propagate(h, s, e, leg, dPhi, dQ);
+            if (!armed) {
+                const AuxCopy cp[] = {{dPhi, st->Phi, sizeof(double) * (size_t)leg * leg}, {dQ, st->Q, sizeof(double) * (size_t)leg * leg}};
+                rc = aux_copies(h, s, cp, 2);
+            }
+            if (rc == ORCVIO_OK) rc = launch_cov_propagate(h, s, e, leg, dPhi, dQ, imu_also);
         } else if (plan[i].kind == PLAN_AUGMENT) rc = launch_cov_augment(h, s, e, aug_pose);
         else rc = launch_cov_gather(h, s, e, lost_map);
     }
@@ -410,6 +422,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
         UpdateCall c;
         c.ekf_side = fused;           // (the in-state rows beside k_front: enqueue_update)
         c.already_ingested = fused;   // (k_frame_head has pulled the whole arena)
+        c.info_also = imu_also;       // (a refused Phi refuses this update's commit)
         tri_consume(h, c);            // (armed: k_triangulate behind the head, in front of the tracks' launch)
         tri_frame = c.tri; tri_frame_empty = h->tri_refuse_empty;
         rc = io_enqueue(h, s, false, true, c, true);
@@ -437,7 +450,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     const char* soB = nullptr;
     unsigned long long pubB = 0;
     if (evs.k > 0) { evs.fs.slam = h->d_slam; evs.fs.cap = h->ekf_cap; }   // (the records' buffers stand: slam_prepare above)
-    StepSecond sb{st->prune_tracks, posesA, dxA, infoA, first ? st->prune_apply_dx : 0, evs.k > 0 ? &evs : nullptr};
+    StepSecond sb{st->prune_tracks, posesA, dxA, infoA, first ? st->prune_apply_dx : 0, evs.k > 0 ? &evs : nullptr, imu_also};
     int rcB = ORCVIO_OK;
     unsigned long long pubE = 0;
     if (!second && evs.k > 0) {   // no update behind the changes: the anchor change is what the call waits for
@@ -462,6 +475,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     tmark(3);
     // ---- ONE wait: the flag word behind the last update
     rc = (pubB || pubE || pubA) ? io_wait(h, s, pubB ? pubB : (pubE ? pubE : pubA)) : ORCVIO_OK;
+    if (rc == ORCVIO_OK && armed && !(pubB || pubE || pubA)) HIPCHK(hipStreamSynchronize(s));   // (a frame without an update: the armed launch's status word is the one thing to wait for)
     tmark(4);
     if (timing && (++tcalls % 128) == 0) {
         fprintf(stderr, "io_step_frame (mean of 128, us after entry): checks + finalize %.1f | head launched %.1f | first update enqueued %.1f | second + removal enqueued %.1f | results %.1f\n",
@@ -496,6 +510,9 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     const int* infA = reinterpret_cast<const int*>(soA);
     const int* infB = soB ? reinterpret_cast<const int*>(soB) : nullptr;
     const bool lostA = first && infA[8] != 0, lostB = infB && infB[8] != 0 && !lostA;
+    // the armed launch found Phi or Q not finite: the head ran without propagation, both updates refused their commits
+    const bool imu_bad = armed && imu_refused(h);
+    const char* imu_msg = ": Phi or Q of the armed IMU propagation not finite: no propagation, no update";
     if (lostA || lostB) {
         // An in-launch hand-off was lost (another tenant of the device held compute units): that update's commit refused itself on the
         // device, and so did the second update's if the first was hit.  Drain, take the marginalisation back (it read the covariance, its
@@ -516,7 +533,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             if (rc == ORCVIO_OK) {
                 h->pw_missing = false;
                 if (tri_frame) { h->skip_active = true; h->tri_live = true; h->tri_refuse_empty = tri_frame_empty; }   // (the positions and d_skip of the lost attempt stand in HBM)
-                rc = io_run_forked(h, res->stats);
+                rc = imu_bad ? (int)ORCVIO_ERR_NOT_SPD : io_run_forked(h, res->stats);   // (a refused Phi: nothing to run again)
             }
             res->repaired++; h->cnt_step_repairs++;
             res->status_first = rc;
@@ -524,6 +541,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             if (second) step_arena_swap(h);
         } else {
             res->status_first = first ? feature_outcome_view(h, vA, soA, res->stats) : ORCVIO_OK;
+            if (imu_bad) res->status_first = ORCVIO_ERR_NOT_SPD;
             // the anchor changes went through behind the first update's commit and stand: the repeat of the second update does not
             // apply them again.  Its pose step reads the first update's dx, which the lost update has overwritten on the device: put back
             sb.ev = nullptr;
@@ -557,6 +575,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     }
     // ---- outcomes (the refusals of the device: M not positive definite, a non-finite result)
     res->status_first = first ? feature_outcome_view(h, vA, soA, res->stats) : ORCVIO_OK;
+    if (imu_bad) { res->status_first = ORCVIO_ERR_NOT_SPD; g_last_error = std::string(who) + imu_msg; }
     if (res->status_first != ORCVIO_OK) res->stats[3] = 0;
     const int sc_changes = changes_status();
     if (second) {

@@ -23,13 +23,13 @@ static inline int* zupt_status(orcvio_msckf_handle* h) { return reinterpret_cast
 
 // The launches: P+ and dx into the spare covariance buffer, S+ into the spare factor buffer; the buffers change roles on the host.
 // A refusal on the device leaves bit copies there, so what is enqueued behind this reads the prior.
-static int zupt_enqueue(orcvio_msckf_handle* h, const orcvio_msckf_zupt* z) {
+static int zupt_enqueue(orcvio_msckf_handle* h, const orcvio_msckf_zupt* z, const int* also = nullptr) {
     const int n = h->res_n;
     hipStream_t s = h->stream;
     ZuptArgs a;
     for (int k = 0; k < 9; ++k) a.r[k] = z->r[k];
     a.noise[0] = z->noise_v; a.noise[1] = z->noise_p; a.noise[2] = z->noise_q;
-    a.n = n; a.b = z->leg_dim + 6 * z->n_clones; a.nui6 = 6 * h->n_nui;
+    a.n = n; a.b = z->leg_dim + 6 * z->n_clones; a.nui6 = 6 * h->n_nui; a.also = also;
     const int nt = (n + ZUPT_TILE - 1) / ZUPT_TILE;
     const CovEdit e = h->zupt(h->n_nui == 0, ZUPT_KMAX);   // (nuisance states: the restored block breaks P = S S^T, no factor)
     hipLaunchKernelGGL(k_zupt_cov, dim3(nt, nt), dim3(256), 0, s, e.P, a, e.Pout, zupt_dx(h), zupt_status(h));
@@ -71,6 +71,9 @@ int32_t orcvio_msckf_cov_zupt_frame(orcvio_msckf_handle* h, const orcvio_msckf_z
     if (!h || !f || !dx || !applied || !n_after) { g_last_error = "cov_zupt_frame: null argument"; return ORCVIO_ERR_INVALID; }
     if ((f->Phi == nullptr) != (f->Q == nullptr)) { g_last_error = "cov_zupt_frame: Phi and Q come together"; return ORCVIO_ERR_INVALID; }
     const orcvio_msckf_zupt* z = &f->zupt;
+    const bool armed = h->imu_armed;   // orcvio_msckf_io_propagate_imu: Phi, Q come from k_imu_phi_q, in front of the propagation launches
+    if (armed && f->Phi) { g_last_error = "cov_zupt_frame: the handle is armed by orcvio_msckf_io_propagate_imu: Phi and Q must be NULL"; return ORCVIO_ERR_INVALID; }
+    if (armed && z->leg_dim != 22) { g_last_error = "cov_zupt_frame: armed IMU propagation at leg_dim 22 only"; return ORCVIO_ERR_INVALID; }
     const int n = h->res_n + (f->augment ? 6 : 0);   // what the update sees
     { const int rv = zupt_validate(h, z, n, "cov_zupt_frame"); if (rv != ORCVIO_OK) return rv; }
     // (with the dimensions above, cov_propagate, cov_augment and cov_remove_clones have nothing left to refuse)
@@ -78,10 +81,14 @@ int32_t orcvio_msckf_cov_zupt_frame(orcvio_msckf_handle* h, const orcvio_msckf_z
     HIPCHK(hipSetDevice(h->device));
     int rc = ORCVIO_OK;
     if (f->Phi) rc = orcvio_msckf_cov_propagate(h, z->leg_dim, f->Phi, f->Q);
+    if (armed) {   // a refused Phi (status word) leaves P as it is in the propagation and refuses the update; augmentation and marginalisation stand
+        rc = imu_consume(h, h->stream);
+        if (rc == ORCVIO_OK) rc = launch_cov_propagate(h, h->stream, h->propagate(), 22, imu_dphi(h), imu_dq(h), imu_status(h));
+    }
     if (rc == ORCVIO_OK && f->augment) rc = orcvio_msckf_cov_augment(h);
     if (rc != ORCVIO_OK) return rc;
     const CovState before = cov_state(h);
-    rc = zupt_enqueue(h, z);
+    rc = zupt_enqueue(h, z, armed ? imu_status(h) : nullptr);
     if (rc != ORCVIO_OK) { cov_restore(h, before); return rc; }   // (a launch that failed: nothing changed roles, propagation and augmentation stand)
     if (f->remove_previous) {
         const int32_t prev = z->n_clones - 2;
@@ -98,7 +105,8 @@ int32_t orcvio_msckf_cov_zupt_frame(orcvio_msckf_handle* h, const orcvio_msckf_z
     *applied = refused ? 0 : 1;
     if (refused) {   // the spare buffers took bit copies of the prior and of its factor, whose zero trailing columns are still zero
         h->zupt_refused(before.fac_tail);
-        g_last_error = "cov_zupt_frame: H P H^T + R not positive definite, or a non-finite covariance: the update was not applied";
+        g_last_error = armed && imu_refused(h) ? "cov_zupt_frame: Phi or Q of the armed IMU propagation not finite: no propagation, no update"
+                                               : "cov_zupt_frame: H P H^T + R not positive definite, or a non-finite covariance: the update was not applied";
         return ORCVIO_ERR_NOT_SPD;
     }
     return ORCVIO_OK;

@@ -24,11 +24,13 @@ __global__ __launch_bounds__(256) void k_cov_propagate_rows(const double* __rest
     T[idx] = s;
 }
 // out = P with  P_LL <- sym(T[:, :leg] Phi^T + Q),  P_LC <- T[:, leg:],  P_CL <- its transpose,  P_CC unchanged
+// refuse != nullptr and *refuse != 0 (k_imu_phi_q found Phi or Q not finite): out = P bit for bit
 __global__ __launch_bounds__(256) void k_cov_propagate_finish(const double* __restrict__ P, int n, const double* __restrict__ Phi,
                                                               const double* __restrict__ Q, int leg, const double* __restrict__ T,
-                                                              double* __restrict__ out) {
+                                                              double* __restrict__ out, const int* __restrict__ refuse) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= n * n) return;
+    if (refuse && *refuse) { out[idx] = P[idx]; return; }
     const int i = idx / n, j = idx - i * n;
     double v;
     if (i < leg && j < leg) {

@@ -57,7 +57,8 @@ __device__ __forceinline__ void dev_mat3_mul(const double* A, const double* B, d
 // loop (:4535-4565) never writes it -- dx[15:21] moves the IMU's extrinsic alone, which is not in the record.
 // Thread 0 also copies the status words info[0..15] of the update that has just run into `keep` (the second update's commit
 // refuses itself when the first was refused: EpilogueArgs.info_also).
-struct PoseStepArgs { const double* src; double* dst; int N, stride; const double* dx; int leg, apply, left, discard_large; const int* info; int* keep; };
+struct PoseStepArgs { const double* src; double* dst; int N, stride; const double* dx; int leg, apply, left, discard_large; const int* info; int* keep;
+                      const int* also = nullptr; };   // also: a status block whose refusal ([2]) the kept words take over (k_imu_phi_q's, the armed IMU frame)
 // does the increment take place: apply, unless discard_large_update discards dx (:4479-4494)
 __device__ __forceinline__ bool pose_step_applies(const double* __restrict__ dx, int apply, int discard_large) {
     bool app = apply != 0;
@@ -82,8 +83,10 @@ __device__ __forceinline__ void pose_step_record(const double* __restrict__ src,
     }
 }
 __device__ __forceinline__ void pose_step_body(const double* __restrict__ src, double* __restrict__ dst, int N, int stride, const double* __restrict__ dx,
-                                               int leg, int apply, int left, int discard_large, const int* __restrict__ info, int* __restrict__ keep, const int c) {
-    if (c < 16 && keep) keep[c] = info ? info[c] : 0;   // (info == nullptr: the frame had no first update)
+                                               int leg, int apply, int left, int discard_large, const int* __restrict__ info, int* __restrict__ keep, const int* __restrict__ also,
+                                               const int c) {
+    // (info == nullptr: the frame had no first update; also: a refused Phi refuses the second update as a refused first update does)
+    if (c < 16 && keep) keep[c] = (info ? info[c] : 0) | ((c == 2 && also && also[2] != 0) ? 1 : 0);
     if (c >= N) return;
     double r[28];
     pose_step_record(src, stride, dx, leg, pose_step_applies(dx, apply, discard_large), left, c, r);
@@ -141,13 +144,13 @@ __device__ __forceinline__ void feature_step_body(const FeatureStepArgs& f, cons
     if (q == 0) *f.status = any ? 1 : 0;
 }
 __global__ __launch_bounds__(64) void k_pose_step(PoseStepArgs p) {
-    pose_step_body(p.src, p.dst, p.N, p.stride, p.dx, p.leg, p.apply, p.left, p.discard_large, p.info, p.keep, threadIdx.x);
+    pose_step_body(p.src, p.dst, p.N, p.stride, p.dx, p.leg, p.apply, p.left, p.discard_large, p.info, p.keep, p.also, threadIdx.x);
 }
 // the two steps as a launch of their own (the unfused and the repair path, a frame without a second update): wavefront 0 the poses,
 // wavefront 1 the changed features
 __global__ __launch_bounds__(128) void k_event_step(PoseStepArgs p, FeatureStepArgs f) {
     const int t = threadIdx.x;
-    if (t < 64) pose_step_body(p.src, p.dst, p.N, p.stride, p.dx, p.leg, p.apply, p.left, p.discard_large, p.info, p.keep, t);
+    if (t < 64) pose_step_body(p.src, p.dst, p.N, p.stride, p.dx, p.leg, p.apply, p.left, p.discard_large, p.info, p.keep, p.also, t);
     else feature_step_body(f, p, t - 64);
 }
 
@@ -196,6 +199,8 @@ struct FrameHeadArgs {
     PoseStepArgs ps;
     FeatureStepArgs fs;         // ... and, in its second wavefront, the step of the features that change anchor (fs.k == 0: none)
     LostMap lost;               // covariance part: out (m x m) is what propagation + augmentation give WITHOUT the lost features' rows / columns
+    const int* refuse;          // optional (Phi, Q made on the device by k_imu_phi_q): refuse[2] != 0 -> they are not finite: the head runs as a frame
+                                // WITHOUT propagation (augmentation and the removals stand)
 };
 
 // The arithmetic of k_cov_propagate_rows / k_cov_propagate_finish / k_cov_augment (cov_ops.hpp), element by element in the same order --
@@ -216,7 +221,7 @@ __global__ __launch_bounds__(256) void k_frame_head(FrameHeadArgs a) {
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= a.nb_cov) {
         const int w = b - a.nb_cov;
-        if (w == a.pose_block && t < 64) pose_step_body(a.ps.src, a.ps.dst, a.ps.N, a.ps.stride, a.ps.dx, a.ps.leg, a.ps.apply, a.ps.left, a.ps.discard_large, a.ps.info, a.ps.keep, t);
+        if (w == a.pose_block && t < 64) pose_step_body(a.ps.src, a.ps.dst, a.ps.N, a.ps.stride, a.ps.dx, a.ps.leg, a.ps.apply, a.ps.left, a.ps.discard_large, a.ps.info, a.ps.keep, a.ps.also, t);
         if (w == a.pose_block && a.fs.k > 0 && t >= 64 && t < 128) feature_step_body(a.fs, a.ps, t - 64);
         int p0 = 0;   // pieces of the segments before this one
         for (int sgi = 0; sgi < a.nseg; ++sgi) {
@@ -246,11 +251,12 @@ __global__ __launch_bounds__(256) void k_frame_head(FrameHeadArgs a) {
     __shared__ double sT[LEG * LEG];
     const int n = a.n, m = a.m, pose = a.pose;
     constexpr int leg = LEG;
-    const int nL = a.Phi ? leg + (pose >= 0 ? 6 : 0) : 0, nC = m - nL;
+    const double* const Phi = (a.refuse && a.refuse[2] != 0) ? nullptr : a.Phi;
+    const int nL = Phi ? leg + (pose >= 0 ? 6 : 0) : 0, nC = m - nL;
     const int E1 = nL * nL, E2 = nL * nC, E3 = nC * nC;
     const int e0 = b * 256;
     if (e0 < E1 + E2) {   // (this workgroup has elements of regions 1 / 2)
-        for (int i = t; i < leg * leg; i += 256) sPhi[i] = a.Phi[i];
+        for (int i = t; i < leg * leg; i += 256) sPhi[i] = Phi[i];
         __syncthreads();
         if (e0 < E1) {
             for (int idx = t; idx < leg * leg; idx += 256) {

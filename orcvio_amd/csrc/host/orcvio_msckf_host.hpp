@@ -67,6 +67,11 @@ struct StateServer {
     // states, their 6 x 6 blocks BEHIND the feature states, in the order of nui_ids; SLAM features may stay anchored at them
     std::vector<StateIDType> nui_ids;
     IMUStateServer nui_imu_states;
+    // IMU propagation (processImu): imu_state_FEJ_now (velocity and position are read, under if_FEJ) and the previous IMU sample
+    // (OrcVIO::m_gyro_old / m_acc_old, :703-704).  imu_state_old and imu_state_FEJ_old live inside processModel only (:836, :893:
+    // overwritten before they are read): the per-sample records of the library's host half hold them.
+    IMUState imu_state_FEJ_now;
+    double m_gyro_old[3] = {0, 0, 0}, m_acc_old[3] = {0, 0, 0};
     int dim() const { return (int)std::lround(std::sqrt((double)state_cov.size())); }
 };
 
@@ -202,6 +207,19 @@ inline std::vector<double> zuptResidual(const StateServer& ss) {
     r[8] = aw * bz + az * bw + ax * by - ay * bx;
     return r;
 }
+
+// reference include/orcvio/orcvio.h ImuData: one buffered IMU message
+struct ImuData {
+    double timeStampToSec = 0;
+    double angular_velocity[3] = {0, 0, 0}, linear_acceleration[3] = {0, 0, 0};
+};
+struct ImuOutcome {
+    int status = ORCVIO_OK;
+    int n_used = 0, n_propagated = 0;
+    bool applied = false;
+    double dt = 0;                       // imu_state.dt: t_last - time_bound
+    double meanSForce[3] = {0, 0, 0};
+};
 
 struct UpdateOutcome {
     int status = ORCVIO_OK;
@@ -1042,6 +1060,44 @@ class MsckfBackend {
         }
         return incremented;
     }
+    // batchImuProcessing (src/orcvio.cpp:664-724) on the resident covariance: the buffered messages up to the image go through
+    // orcvio_msckf_cov_propagate_imu (mean on the host, Phi and Q on the device, the propagation behind them), imu_state, the FEJ copy
+    // and m_gyro_old / m_acc_old are updated, the used messages are erased from the buffer (:718-719).  wait: the call waits for the
+    // device and reports a refused Phi (ORCVIO_ERR_NOT_SPD: the covariance was not propagated; the mean was).
+    ImuOutcome processImu(StateServer& ss, const orcvio_msckf_imu_config& cfg, double time_bound, std::vector<ImuData>& imu_msg_buffer,
+                          bool wait = false) {
+        ImuOutcome out;
+        orcvio_msckf_imu_state st{};
+        const IMUState& im = ss.imu_state;
+        st.time = im.time;
+        std::memcpy(st.R_b2w, im.orientation, sizeof(st.R_b2w));
+        for (int k = 0; k < 3; ++k) {
+            st.v[k] = im.velocity[k]; st.p[k] = im.position[k]; st.gyro_bias[k] = im.gyro_bias[k]; st.acc_bias[k] = im.acc_bias[k];
+            st.v_fej[k] = ss.imu_state_FEJ_now.velocity[k]; st.p_fej[k] = ss.imu_state_FEJ_now.position[k];
+        }
+        double prev[6];
+        for (int k = 0; k < 3; ++k) { prev[k] = ss.m_gyro_old[k]; prev[3 + k] = ss.m_acc_old[k]; }
+        std::vector<double> samples(7 * imu_msg_buffer.size());
+        for (size_t i = 0; i < imu_msg_buffer.size(); ++i) {
+            samples[7 * i] = imu_msg_buffer[i].timeStampToSec;
+            for (int k = 0; k < 3; ++k) { samples[7 * i + 1 + k] = imu_msg_buffer[i].angular_velocity[k]; samples[7 * i + 4 + k] = imu_msg_buffer[i].linear_acceleration[k]; }
+        }
+        orcvio_msckf_imu_info info{};
+        info.wait = wait ? 1 : 0;
+        out.status = orcvio_msckf_cov_propagate_imu(h_, &cfg, &st, prev, samples.data(), (int32_t)imu_msg_buffer.size(), time_bound, &info, nullptr, nullptr);
+        out.n_used = info.n_used; out.n_propagated = info.n_propagated; out.applied = info.applied != 0; out.dt = info.dt;
+        for (int k = 0; k < 3; ++k) out.meanSForce[k] = info.mean_sforce[k];
+        if (out.status != ORCVIO_OK && out.status != ORCVIO_ERR_NOT_SPD) return out;   // (refused before anything was done: nothing changes)
+        IMUState& o = ss.imu_state;
+        o.time = st.time;
+        std::memcpy(o.orientation, st.R_b2w, sizeof(st.R_b2w));
+        for (int k = 0; k < 3; ++k) { o.velocity[k] = st.v[k]; o.position[k] = st.p[k]; }
+        if (info.n_propagated > 0) ss.imu_state_FEJ_now = o;   // (:894, :924; :820)
+        for (int k = 0; k < 3; ++k) { ss.m_gyro_old[k] = prev[k]; ss.m_acc_old[k] = prev[3 + k]; }
+        imu_msg_buffer.erase(imu_msg_buffer.begin(), imu_msg_buffer.begin() + info.n_used);
+        return out;
+    }
+
     // The whole update of a frame the zero-velocity check accepted: residual, orcvio_msckf_cov_zupt on the resident covariance (the
     // noises are VARIANCES; ORCVIO_OPT_EXTRA_STATES / _SCHMIDT_STATES declare what is behind the clones), the increments above.
     // The covariance is updated whether or not the increment discards a large dx, as the reference's is (:3389, :3431-3447).

@@ -22,6 +22,7 @@
 #include "triangulate_arm.hpp"
 #include "cov_ops.hpp"
 #include "zupt_ops.hpp"
+#include "imu_ops.hpp"
 #include "ekf_rows.hpp"
 #include "object_rows.hpp"
 #include "object_fused.hpp"
@@ -185,6 +186,15 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     bool prior_forked = false;          // the Cholesky of the prior runs on the side stream (ev_side must be joined)
     int kf = 0;                         // columns of the prior's factor = dimension of M (n unless a resident factor is used)
     int* d_covmap = nullptr;
+    double* d_imu = nullptr;            // orcvio_msckf_cov_propagate_imu: the per-sample records [128][IMU_REC], then the status word of k_imu_phi_q
+    std::vector<double> imu_recs;       // ... and their host copy, sized at create: the host half writes them, aux_copies stages them
+    // orcvio_msckf_io_propagate_imu: the next frame call on the handle enqueues k_imu_phi_q in front of its head launch (one-shot; the
+    // frame call consumes it).  The records wait in imu_recs.
+    bool imu_armed = false;
+    int imu_S = 0;
+    ImuFlags imu_fl{};
+    orcvio_msckf_imu_config imu_cfg{};
+    int *h_imu_status = nullptr, *h_imu_status_dev = nullptr;   // host-coherent word: the armed launch's status, read behind the frame's one wait
     bool pw_missing = false;            // uploaded without positions: triangulate_uploaded must run before the update
     int *d_tri_valid = nullptr, *d_tri_flags = nullptr, *d_tri_init = nullptr;
     double *d_tri_sol = nullptr, *d_tri_cost = nullptr;
@@ -397,6 +407,7 @@ const char* orcvio_msckf_last_error(void) { return g_last_error.c_str(); }
 #include "capi_comm.inc"   // the handle's RCCL communicator, bounded waits, the sharded updates
 #include "capi_cov.inc"   // per-kernel profile, the device-resident covariance and its square-root factor
 #include "capi_object_mapper.inc"   // the object mapper: the start and the Levenberg-Marquardt refinement of object tracks, with keypoints and bbox-only
+#include "capi_imu.inc"   // IMU propagation from raw samples: the host half (host/imu_model.hpp), k_imu_phi_q, the propagation behind it
 #include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: the 9-row update, the factor kept, the one-call stationary frame
 #include "capi_frame.inc"   // one frame in one call: feature update + object update, the objects' compression beside the features' solve
 #include "capi_step.inc"   // one FILTER frame in one call: propagate, augment, update, prune update, marginalise on the resident covariance

@@ -25,6 +25,7 @@ struct ZuptArgs {
     double r[9];
     double noise[3];   // variances of r_v, r_p, r_q
     int n, b, nui6;    // state dimension, leg + 6 N, 6 x nuisance states (the trailing block P+ keeps)
+    const int* also = nullptr;   // optional: a status block whose refusal ([2] != 0: k_imu_phi_q's Phi not finite) refuses this update too
 };
 
 // state index of the l-th of the 15 rows H touches: 3..5, then b-12 .. b-1
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256) void k_zupt_cov(const double* __restrict__ P, 
         if (bad) sBad = 1;
     }
     __syncthreads();
-    const bool refused = sBad != 0;
+    const bool refused = sBad != 0 || (a.also && a.also[2] != 0);
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *status = refused ? 1 : 0;
     if (!refused && tid < 2 * ZUPT_TILE) {   // V = C^-1 Y at the tile's columns (tid < 32) and rows (tid >= 32): ONE code path for both
         const int w = tid / ZUPT_TILE, t = tid - w * ZUPT_TILE;
