@@ -1898,8 +1898,10 @@ def debug_factor(upd: MsckfUpdater):
     return out.T.copy()
 
 
-def debug_potrf(upd: MsckfUpdater, X, tol_rel=0.0, force_lds_path=False):
-    """Test helper: Cholesky factor (lower), block inverses and pivot info of a host matrix."""
+def debug_potrf(upd: MsckfUpdater, X, tol_rel=0.0, force_lds_path=False, rev=False):
+    """Test helper: Cholesky factor (lower), block inverses and pivot info of a host matrix.  rev: the matrix is factored reversed, as
+    the update factors its prior (X'(i, j) = X(n-1-i, n-1-j)); L is then the factor L' of X' as stored, and S(i, c) = L'(n-1-i, c)
+    has S S^T = X."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     n = X.shape[0]
     L = np.zeros((n, n))
@@ -1907,8 +1909,8 @@ def debug_potrf(upd: MsckfUpdater, X, tol_rel=0.0, force_lds_path=False):
     Dinv = np.zeros((nb, 16, 16))
     info = np.zeros(2, dtype=np.int32)
     lib = upd.lib
-    lib.orcvio_msckf_debug_potrf.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _ip]
-    rc = lib.orcvio_msckf_debug_potrf(upd.h, _d(X), n, float(tol_rel), int(force_lds_path), _d(L), _d(Dinv), _i(info))
+    lib.orcvio_msckf_debug_potrf.argtypes = [C.c_void_p, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _ip, C.c_int32]
+    rc = lib.orcvio_msckf_debug_potrf(upd.h, _d(X), n, float(tol_rel), int(force_lds_path), _d(L), _d(Dinv), _i(info), int(bool(rev)))
     if rc != 0:
         raise MsckfError(rc, 'debug_potrf')
     return L, Dinv, info
@@ -1928,22 +1930,42 @@ def debug_trsm(upd: MsckfUpdater, X, B):
     return Z
 
 
-def debug_potrf_solve(upd: MsckfUpdater, X, B, la=0, stamps=False, reps=0):
-    """Test helper / diagnostic: L = chol(X) and Z = L^-1 B in ONE launch -- k_potrf_solve (la = 0) or k_potrf_solve_la
-    (la = 2, 3: the trailing update spread over far workgroups).  Returns dict(L, Z, info[dropped, non-positive, lost], stamps, us)."""
+def debug_potrf_solve(upd: MsckfUpdater, X, B, la=0, stamps=False, reps=0, bx=None, tail=0, tail_scale=0.0, product_strides=False):
+    """Test helper / diagnostic: L = chol(X) and Z = L^-1 [B | bx] in ONE launch -- k_potrf_solve (la = 0) or k_potrf_solve_la
+    (la = 2, 3: the trailing update spread over far workgroups) -- in the argument forms of the update's own call: X is n x n, B is
+    (n + tail) x nc1; bx (n values) is one more column behind B; the `tail` rows of B behind the first n come back as tail_scale * B
+    (zero in bx's column); product_strides lays B out on the device as the update finds the prior's factor (row stride = the leading
+    dimension, columns in reverse order through a column stride of -1, the base at the last column).
+    Returns dict(L, Z [n + tail, nc1 + (bx is not None)], info[dropped, non-positive, lost], stamps, us, guard_row, guard_col: the row and
+    the column of the NaN-filled scratch just outside Z as the launch left them, outside: entries of the whole scratch outside Z that
+    are no longer NaN)."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     B = np.ascontiguousarray(B, dtype=np.float64)
-    n, nrhs = B.shape
+    n = X.shape[0]
+    tail = int(tail)
+    if X.shape != (n, n) or B.ndim != 2 or B.shape[0] != n + tail:
+        raise ValueError('debug_potrf_solve: X is n x n and B is (n + tail) x nc1')
+    nrhs = B.shape[1]
+    if bx is not None:
+        bx = np.ascontiguousarray(bx, dtype=np.float64).ravel()
+        if bx.size != n:
+            raise ValueError('debug_potrf_solve: bx has n values')
+    ncols = nrhs + (bx is not None)
     L = np.zeros((n, n))
-    Z = np.zeros((n, nrhs))
+    Zg = np.zeros((n + tail + 1, ncols + 1))
     info = np.zeros(3, dtype=np.int32)
+    outside = C.c_int32(-1)
     st = np.zeros(512, dtype=np.uint64)
     us = C.c_double(0.0)
     lib = upd.lib
     lib.orcvio_msckf_debug_potrf_solve.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _dp, C.c_void_p, C.c_void_p,
-                                                   C.c_int32, C.POINTER(C.c_double)]
-    rc = lib.orcvio_msckf_debug_potrf_solve(upd.h, _d(X), n, _d(B), nrhs, int(la), _d(L), _d(Z), info.ctypes.data,
-                                            st.ctypes.data if stamps else None, int(reps), C.byref(us))
+                                                   C.c_int32, C.POINTER(C.c_double), _dp, C.c_int32, C.c_double, C.c_int32,
+                                                   C.POINTER(C.c_int32)]
+    rc = lib.orcvio_msckf_debug_potrf_solve(upd.h, _d(X), n, _d(B), nrhs, int(la), _d(L), _d(Zg), info.ctypes.data,
+                                            st.ctypes.data if stamps else None, int(reps), C.byref(us),
+                                            _d(bx) if bx is not None else None, tail, float(tail_scale), int(bool(product_strides)),
+                                            C.byref(outside))
     if rc != 0:
         raise MsckfError(rc, 'debug_potrf_solve')
-    return dict(L=L, Z=Z, info=info, stamps=st.astype(np.int64) if stamps else None, us=us.value)
+    return dict(L=L, Z=np.ascontiguousarray(Zg[:n + tail, :ncols]), info=info, stamps=st.astype(np.int64) if stamps else None, us=us.value,
+                guard_row=Zg[n + tail, :].copy(), guard_col=Zg[:, ncols].copy(), outside=int(outside.value))

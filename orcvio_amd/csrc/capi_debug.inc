@@ -98,10 +98,12 @@ int32_t orcvio_msckf_debug_occupy(orcvio_msckf_handle* h, int32_t n_cus, double 
 }
 
 // Test hook: factor an arbitrary symmetric n x n host matrix with the same kernels the update uses.
-// Out: L (n x n lower, row-major, host), Dinv ([nb][16][16]), info[2] (dropped / negative pivots).
+// rev: factor the reversed matrix X'(i, j) = X(n-1-i, n-1-j), as the update factors its prior (register path only).
+// Out: L (n x n lower, row-major, host; with rev the factor L' of X' as stored), Dinv ([nb][16][16]), info[2] (dropped / negative pivots).
 int32_t orcvio_msckf_debug_potrf(orcvio_msckf_handle* h, const double* X, int32_t n, double tol_rel, int32_t force_lds_path,
-                                 double* L_out, double* Dinv_out, int32_t* info_out) {
+                                 double* L_out, double* Dinv_out, int32_t* info_out, int32_t rev) {
     if (!h || !X || n < 1 || n > h->n_max) return ORCVIO_ERR_INVALID;
+    if (rev && (force_lds_path || (n + 15) / 16 > 14)) return ORCVIO_ERR_INVALID;   // (only k_potrf_reg reads its input reversed)
     HIPCHK(hipSetDevice(h->device));
     const int saveNP = h->NP;
     const bool save_path = h->reg_path;
@@ -111,7 +113,7 @@ int32_t orcvio_msckf_debug_potrf(orcvio_msckf_handle* h, const double* X, int32_
     HIPCHK(hipMemcpy(h->d_M, X, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(h->d_info, 0, sizeof(int) * 8));
     HIPCHK(hipMemset(h->d_RM, 0, sizeof(double) * (size_t)h->NP_max * h->NP_max));   // lower tiles: zero for any layout
-    int rc = launch_potrf(h, h->stream, h->d_M, n, n, tol_rel, h->d_RM, h->d_DinvM, h->d_info);
+    int rc = launch_potrf(h, h->stream, h->d_M, n, n, tol_rel, h->d_RM, h->d_DinvM, h->d_info, rev ? 1 : 0);
     if (rc == ORCVIO_OK) {
         HIPCHK(hipStreamSynchronize(h->stream));
         std::vector<double> buf((size_t)NP * NP);
@@ -238,19 +240,45 @@ int32_t orcvio_msckf_debug_feature_ablate(orcvio_msckf_handle* h, int32_t ablate
     return ORCVIO_OK;
 }
 
-// Test hook / diagnostic: chol(X) and Z = L^-1 B in ONE launch, through k_potrf_solve (la = 0) or k_potrf_solve_la (la = 2, 3), on an
-// arbitrary SPD host matrix X (n x n) and right-hand sides B (n x nrhs, row-major).  L_out n x n (lower), Z_out n x nrhs,
-// info_out[3] (dropped pivots, non-positive pivots, lost hand-offs), stamps (optional, 512 words: potrf_lookahead.hpp), us_out
-// (optional: average launch time over `reps` launches, each behind the two small clears it needs).
+// Test hook / diagnostic: chol(X) and Z = L^-1 [B | bx] in ONE launch, through k_potrf_solve (la = 0) or k_potrf_solve_la (la = 2, 3), on an
+// arbitrary SPD host matrix X (n x n) and right-hand sides B ((n + tail) x nrhs, row-major), in the argument forms of the update's own
+// call (launch_solve_stage, ST_POTRF_M):
+//   bx (optional, n values): the extra column behind B, stride 1 (the update's g);
+//   tail, tail_scale: `tail` more rows of B behind the n that take part in the factorisation; their rows of Z are tail_scale * B, the
+//     extra column's are zero;
+//   product_strides: B lies on the device as the update finds the prior's factor -- rows of stride ld (= NP_max), the columns stored in
+//     reverse (column stride -1), the base pointer at the last column.  0: rows of stride nrhs, column stride 1.
+// The padding of M, the right-hand-side scratch around B and bx, and all of Z are filled with NaN before the launch.
+// L_out n x n (lower); Z_out (n + tail + 1) x (ncols + 1), ncols = nrhs + (bx != NULL): Z, then one guard row and one guard column of the
+// scratch as the launch left them (NaN = untouched; NaN too where the scratch ends with Z); outside_out (optional): how many entries of the
+// whole Z scratch outside Z's extent are no longer NaN; info_out[3] (dropped pivots, non-positive pivots, lost hand-offs), stamps
+// (optional, 512 words: potrf_lookahead.hpp), us_out (optional: average launch time over `reps` launches, each behind the two small clears
+// it needs).
 int32_t orcvio_msckf_debug_potrf_solve(orcvio_msckf_handle* h, const double* X, int32_t n, const double* B, int32_t nrhs, int32_t la,
-                                       double* L_out, double* Z_out, int32_t* info_out, unsigned long long* stamps, int32_t reps, double* us_out) {
+                                       double* L_out, double* Z_out, int32_t* info_out, unsigned long long* stamps, int32_t reps, double* us_out,
+                                       const double* bx, int32_t tail, double tail_scale, int32_t product_strides, int32_t* outside_out) {
     if (!h || !X || !B || n < 1 || n > h->n_max || n > 224 || nrhs < 1 || nrhs > h->NP_max || (la != 0 && la != 2 && la != 3)) return ORCVIO_ERR_INVALID;
+    const int ncols = nrhs + (bx ? 1 : 0), nrows = n + tail;
+    // B and bx share the right-hand-side scratch (NP_max x NP_max): B in its first rows, bx in its last row
+    if (tail < 0 || nrows > h->NP_max - 1 || ncols > h->NP_max) return ORCVIO_ERR_INVALID;
     HIPCHK(hipSetDevice(h->device));
     const int NP = round_up(n, 16), ldz = h->NP_max;
+    const size_t np2 = (size_t)h->NP_max * h->NP_max;
+    const long ldb = product_strides ? (long)h->NP_max : (long)nrhs;
     HIPCHK(hipMemset(h->d_M, 0xff, sizeof(double) * (size_t)NP * NP));   // (NaN in the padding: the kernels must mask it)
     HIPCHK(hipMemcpy2D(h->d_M, sizeof(double) * NP, X, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_U, B, sizeof(double) * (size_t)n * nrhs, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(h->d_RM, 0, sizeof(double) * (size_t)h->NP_max * h->NP_max));
+    double* d_bx = h->d_U + (size_t)(h->NP_max - 1) * h->NP_max;
+    {
+        std::vector<double> stage(np2, __builtin_nan(""));
+        for (int i = 0; i < nrows; ++i)
+            for (int c = 0; c < nrhs; ++c) stage[(size_t)i * ldb + (product_strides ? nrhs - 1 - c : c)] = B[(size_t)i * nrhs + c];
+        if (bx) std::memcpy(stage.data() + (size_t)(h->NP_max - 1) * h->NP_max, bx, sizeof(double) * n);
+        HIPCHK(hipMemcpy(h->d_U, stage.data(), sizeof(double) * np2, hipMemcpyHostToDevice));
+    }
+    const double* dB = product_strides ? h->d_U + (nrhs - 1) : h->d_U;
+    const long sBc = product_strides ? -1L : 1L;
+    HIPCHK(hipMemset(h->d_Z, 0xff, sizeof(double) * np2));
+    HIPCHK(hipMemset(h->d_RM, 0, sizeof(double) * np2));
     HIPCHK(hipMemset(h->d_info, 0, sizeof(int) * 16));
     unsigned long long* d_st = nullptr;
     if (stamps) { HIPCHK(hipMalloc(&d_st, sizeof(unsigned long long) * 512)); HIPCHK(hipMemset(d_st, 0, sizeof(unsigned long long) * 512)); }
@@ -259,9 +287,9 @@ int32_t orcvio_msckf_debug_potrf_solve(orcvio_msckf_handle* h, const double* X, 
         HIPCHK(hipMemsetAsync(h->d_flag, 0, sizeof(int), s));
         HIPCHK(hipMemsetAsync(h->d_la_rdy, 0, 64, s));
         if (la) return launch_potrf_solve_la(h, s, la, h->d_M, NP, n, h->d_RM, NP, h->d_DinvM, h->d_info + 2, h->d_flag, h->d_la_rdy, h->d_info + 8,
-                                             h->d_U, (long)nrhs, 1L, nrhs, nullptr, 0L, h->d_Z, ldz, 0, 0.0, st);
-        return launch_potrf_solve_slots(s, h->d_M, NP, n, h->d_RM, NP, h->d_DinvM, h->d_info + 2, h->d_flag, h->d_info + 8, h->d_U, (long)nrhs, 1L, nrhs, nullptr, 0L,
-                                        h->d_Z, ldz, 0, 0.0);
+                                             dB, ldb, sBc, nrhs, bx ? d_bx : nullptr, bx ? 1L : 0L, h->d_Z, ldz, tail, tail_scale, st);
+        return launch_potrf_solve_slots(s, h->d_M, NP, n, h->d_RM, NP, h->d_DinvM, h->d_info + 2, h->d_flag, h->d_info + 8, dB, ldb, sBc, nrhs,
+                                        bx ? d_bx : nullptr, bx ? 1L : 0L, h->d_Z, ldz, tail, tail_scale);
     };
     int rc = once(d_st);
     if (rc == ORCVIO_OK && reps > 0 && us_out) {
@@ -286,11 +314,20 @@ int32_t orcvio_msckf_debug_potrf_solve(orcvio_msckf_handle* h, const double* X, 
         if (L_out)
             for (int i = 0; i < n; ++i)
                 for (int j = 0; j < n; ++j) L_out[(size_t)i * n + j] = buf[(size_t)j * NP + i];   // L = R^T
-        if (Z_out) {
-            std::vector<double> zb((size_t)n * ldz);
-            HIPCHK(hipMemcpy(zb.data(), h->d_Z, sizeof(double) * zb.size(), hipMemcpyDeviceToHost));
-            for (int i = 0; i < n; ++i)
-                for (int c = 0; c < nrhs; ++c) Z_out[(size_t)i * nrhs + c] = zb[(size_t)i * ldz + c];
+        if (Z_out || outside_out) {
+            std::vector<double> zb(np2);
+            HIPCHK(hipMemcpy(zb.data(), h->d_Z, sizeof(double) * np2, hipMemcpyDeviceToHost));
+            if (Z_out)
+                for (int i = 0; i <= nrows; ++i)
+                    for (int c = 0; c <= ncols; ++c)
+                        Z_out[(size_t)i * (ncols + 1) + c] = (i < h->NP_max && c < ldz) ? zb[(size_t)i * ldz + c] : __builtin_nan("");
+            if (outside_out) {
+                int outside = 0;
+                for (int i = 0; i < h->NP_max; ++i)
+                    for (int c = 0; c < ldz; ++c)
+                        if (!(i < nrows && c < ncols) && zb[(size_t)i * ldz + c] == zb[(size_t)i * ldz + c]) ++outside;
+                *outside_out = outside;
+            }
         }
         if (info_out) {
             int inf[16];
@@ -303,7 +340,9 @@ int32_t orcvio_msckf_debug_potrf_solve(orcvio_msckf_handle* h, const double* X, 
     HIPCHK(hipMemset(h->d_info, 0, sizeof(int) * 16));
     HIPCHK(hipMemset(h->d_flag, 0, sizeof(int)));
     HIPCHK(hipMemset(h->d_la_rdy, 0, 64));
-    HIPCHK(hipMemset(h->d_RM, 0, sizeof(double) * (size_t)h->NP_max * h->NP_max));   // lower tiles: zero for any layout
+    HIPCHK(hipMemset(h->d_RM, 0, sizeof(double) * np2));   // lower tiles: zero for any layout
+    HIPCHK(hipMemset(h->d_U, 0, sizeof(double) * np2));    // (no NaN left behind in the handle's scratch)
+    HIPCHK(hipMemset(h->d_Z, 0, sizeof(double) * np2));
     return rc;
 }
 
