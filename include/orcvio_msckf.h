@@ -1111,7 +1111,8 @@ int32_t orcvio_msckf_cov_change_anchors(orcvio_msckf_handle* h, const orcvio_msc
                                         const orcvio_msckf_anchor_change* changes, int32_t count, double* new_param, double* new_inv_depth);
 
 /* ---- Zero-velocity frames on the resident covariance (measurementUpdate_ZUPT_vpq, src/orcvio.cpp:3326-3454) --------------------------
- * On a frame the zero-velocity check accepts (checkZUPTFeat / checkZUPTIMU, :3081-3320: images and IMU samples, the caller's), the
+ * On a frame the zero-velocity check accepts (checkZUPTFeat, :3081-3126: pixel distances, the caller's; checkZUPTIMU, :3129-3323: IMU
+ * samples against the covariance, the caller's or orcvio_msckf_cov_zupt_check_imu / _cov_zupt_frame_checked below), the
  * reference runs a 9-row update on the current velocity and on the pose difference of the two newest clones instead of the MSCKF
  * updates, and marginalises the previous clone (:2641-2645).  The Jacobian's sparsity is fixed (:3329-3334), so nothing of size 9 x n
  * is passed: the call takes the residual and the three variances.
@@ -1265,7 +1266,7 @@ int32_t orcvio_msckf_cov_propagate_imu(orcvio_msckf_handle* h, const orcvio_msck
                                        double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
                                        orcvio_msckf_imu_info* info, double* Phi_out, double* Q_out);
 /* The ARMED form (same inputs): the host half runs now -- *state, prev_meas and info are valid on return, info->applied = 0 -- and the
- * next orcvio_msckf_io_step_frame / _io_step_frame_ex / _cov_zupt_frame on the handle is armed, in the manner of
+ * next orcvio_msckf_io_step_frame / _io_step_frame_ex / _cov_zupt_frame / _cov_zupt_frame_checked on the handle is armed, in the manner of
  * orcvio_msckf_io_triangulate: given Phi = Q = NULL, it enqueues k_imu_phi_q in front of its head launch (the propagation launches, for
  * cov_zupt_frame) and hands them the device's Phi / Q instead of a staged copy -- the frame's one wait stays one wait, and the results
  * are bit for bit those of the frame given Phi_out / Q_out of orcvio_msckf_cov_propagate_imu.  S = 0 after selection arms nothing.
@@ -1278,6 +1279,80 @@ int32_t orcvio_msckf_cov_propagate_imu(orcvio_msckf_handle* h, const orcvio_msck
 int32_t orcvio_msckf_io_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, orcvio_msckf_imu_state* state,
                                       double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
                                       orcvio_msckf_imu_info* info);
+
+/* ---- Zero-velocity DETECTION from IMU samples on the resident covariance (checkZUPTIMU, src/orcvio.cpp:3129-3323) ----------------------
+ * The test the configurations with if_use_feature_zupt_flag = 0 run on every image, between stateAugmentation and removeLostFeatures:
+ * over the S samples of the frame (imu_recent_zupt: the samples the IMU call's host half selected) it stacks m = S - 1 blocks of six
+ * rows on the nine states (theta, b_g, b_a) -- gyro rows [0 I 0] with a ZERO residual (:3194) and noise sigma_w2 / dt_i,
+ * accelerometer rows [J_i 0 R] with r_i = -R a_i - g, a_i = m_acc_i - b_a, J_i = skew(R a_i) (left perturbation) or R skew(a_i), noise
+ * sigma_a2 / dt_i, dt_i = t_i+1 - t_i -- and compares chi^2 = r^T (H P_m H^T + R)^-1 r with the quantile of 6 m degrees of freedom.
+ * P_m is the 9 x 9 marginal of the covariance AS PROPAGATION LEFT IT (rows and columns 0..2, 9..14) plus
+ * diag(dt_sum sigma_wb I, dt_sum sigma_ab I) on its bias block (sigma_wb, sigma_ab unsquared, as :3228-3229 write it).
+ * The device does not form the 6 m x 6 m matrix (762 x 762 at 128 samples): H has nine columns and R is diagonal, so
+ *   A = H^T R^-1 H,  b = H^T R^-1 r,  c = r^T R^-1 r;   P_m = L L^T,  M = I + L^T A L = C C^T,  chi^2 = c - |C^-1 L^T b|^2
+ * is the same number ("Zero-velocity detection": the measured distance to the dense form).  One launch
+ * (k_zupt_check, one workgroup), which reads 81 entries of P -- both triangles, averaged -- and writes nothing of P or its factor.
+ *   chk       the reference's constants (orcvio_msckf_zupt_check_default fills them) and use_left_perturbation
+ *   verdict   evaluated (0: fewer than two samples, :3134, or refused), accept (do_zupt), dof = 6 (S - 1), chi2, chi2_check =
+ *             orcvio_msckf_chi2_quantile(dof, chi2_prob) (the reference's table below 500 rows and its boost quantile above are this
+ *             function), speed = |v|;  accept = evaluated && !(chi2 > chi2_multiplier chi2_check) && !(speed > max_velocity).
+ *             The speed test is host arithmetic; chi2 is evaluated and reported whatever it says.
+ *             status: ORCVIO_OK, or ORCVIO_ERR_NOT_SPD behind a refusal on the device (then evaluated = 0).
+ *   cov_zupt_check_imu            tests the resident covariance as it stands: R_b2w [9] row-major, v, acc_bias, gravity [3], samples
+ *                                 [n_samples][7] (t | gyro | acc) the SELECTED ones.  One launch, one wait; n_samples < 2: no launch,
+ *                                 evaluated = 0, ORCVIO_OK.  P, its factor and the factor's validity are untouched.
+ *   cov_propagate_imu_checked     orcvio_msckf_cov_propagate_imu (same arguments, same host half and launches) with k_zupt_check behind the
+ *                                 propagation launches, on the propagated P, the propagated state and the samples the host half selected;
+ *                                 the call always waits, once.  P is bit for bit what the unchecked call leaves, the verdict bit for bit
+ *                                 that of cov_zupt_check_imu behind it.  A refused Phi / Q: evaluated = 0, ORCVIO_ERR_NOT_SPD, as the unchecked
+ *                                 call; one selected sample: propagated, evaluated = 0.  A moving frame on these configurations is this
+ *                                 call followed by orcvio_msckf_io_step_frame with Phi = NULL: two waits, no cov_get, no dense solve.
+ *   cov_zupt_frame_checked        the stationary frame on a handle ARMED by orcvio_msckf_io_propagate_imu (frame->Phi = Q = NULL,
+ *                                 zupt.leg_dim 22): the launches of cov_zupt_frame with k_zupt_check behind the augmentation; the update
+ *                                 reads the check's status block, which carries the armed propagation's refusal on.  The calling thread waits
+ *                                 ONCE.  Accepted: dx, P, the factor and *n_after bit for bit those of io_propagate_imu + cov_zupt_frame --
+ *                                 but the previous clone (remove_previous) is marginalised BEHIND the wait and only when the update was
+ *                                 applied (enqueued, no second wait), where cov_zupt_frame enqueues it in front of the wait.  Rejected by
+ *                                 the check: ORCVIO_OK, *applied = 0, dx = 0, verdict.accept = 0; propagation and augmentation stand,
+ *                                 nothing is marginalised, P is what cov_propagate_imu + cov_augment leave, the factor kept or dropped by
+ *                                 cov_zupt_frame's rule for a refused update; the caller goes on with orcvio_msckf_io_step_frame
+ *                                 (Phi = NULL, augment = 0).  A parked platform spends one wait per frame.  Refused on the device (the check
+ *                                 or the update): ORCVIO_ERR_NOT_SPD, *applied = 0, nothing marginalised.  One selected sample: no check, no
+ *                                 update (*applied = 0, evaluated = 0), propagation and augmentation stand.  An unarmed handle:
+ *                                 ORCVIO_ERR_INVALID, nothing done.
+ * Refused on the device (evaluated = 0, status ORCVIO_ERR_NOT_SPD): a non-finite entry among the marginal's 81 entries, P_m or M not
+ * positive definite, the status word of an IMU propagation in front already set.  The rest of P is NOT examined.
+ * Refused before anything is enqueued (ORCVIO_ERR_INVALID, nothing done, an arming stands): a null argument, leg_dim != 22, no resident
+ * covariance, a communicator on the handle, non-finite samples, state or constants, a variance, sigma_wb / sigma_ab, chi2_multiplier or
+ * max_velocity <= 0, chi2_prob outside (0, 1), and a sample interval dt_i <= 0.  THE LAST DIVERGES FROM THE REFERENCE, which divides by
+ * dt_i: a zero gives NaN, NaN > threshold is false, and checkZUPTIMU ACCEPTS the frame.  More than 128 samples: ORCVIO_ERR_CAPACITY.
+ * Not in this call: the check inside orcvio_msckf_io_step_frame / _io_step_frame_ex (it would have to choose between two frame kinds
+ * and two sets of clones to marginalise in front of the frame's wait); checkZUPTFeat, a sort of pixel distances the front end owns. */
+typedef struct orcvio_msckf_zupt_check {
+    double sigma_w2, sigma_a2;      /* :3140-3142, variances                         */
+    double sigma_wb, sigma_ab;      /* :3144-3146, used unsquared as :3228-3229 do    */
+    double chi2_prob;               /* chi_square_threshold_zupt, 0.95               */
+    double chi2_multiplier;         /* 1                                             */
+    double max_velocity;            /* 0.25                                          */
+    int32_t use_left_perturbation;
+} orcvio_msckf_zupt_check;
+typedef struct orcvio_msckf_zupt_verdict {
+    int32_t evaluated;   /* 0: fewer than two samples (:3134), or refused             */
+    int32_t accept;      /* do_zupt                                                   */
+    int32_t dof;         /* 6 (S - 1)                                                 */
+    int32_t status;      /* ORCVIO_OK, or ORCVIO_ERR_NOT_SPD behind a device refusal  */
+    double chi2, chi2_check, speed;
+} orcvio_msckf_zupt_verdict;
+void orcvio_msckf_zupt_check_default(orcvio_msckf_zupt_check* chk);
+int32_t orcvio_msckf_cov_zupt_check_imu(orcvio_msckf_handle* h, const orcvio_msckf_zupt_check* chk, const double* R_b2w, const double* v,
+                                        const double* acc_bias, const double* gravity, const double* samples, int32_t n_samples,
+                                        orcvio_msckf_zupt_verdict* verdict);
+int32_t orcvio_msckf_cov_propagate_imu_checked(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, orcvio_msckf_imu_state* state,
+                                               double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
+                                               orcvio_msckf_imu_info* info, double* Phi_out, double* Q_out,
+                                               const orcvio_msckf_zupt_check* chk, orcvio_msckf_zupt_verdict* verdict);
+int32_t orcvio_msckf_cov_zupt_frame_checked(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame* frame, const orcvio_msckf_zupt_check* chk,
+                                            double* dx, int32_t* applied, int32_t* n_after, orcvio_msckf_zupt_verdict* verdict);
 
 /* ---- Environment switches (read once per process; diagnostics and A/B measurements -- every one of them leaves the results unchanged) ----
  *   ORCVIO_COMM_TIMEOUT_S   bound of every wait another rank can strand, seconds (default 180)

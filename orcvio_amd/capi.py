@@ -48,6 +48,8 @@ EXPORTS = [
     'orcvio_msckf_objects_refined', 'orcvio_msckf_counters', 'orcvio_msckf_comm_details', 'orcvio_msckf_profile_sharded',
     'orcvio_msckf_io_step_frame', 'orcvio_msckf_io_step_frame_ex', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
     'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame', 'orcvio_msckf_cov_propagate_imu', 'orcvio_msckf_io_propagate_imu',
+    'orcvio_msckf_zupt_check_default', 'orcvio_msckf_cov_zupt_check_imu', 'orcvio_msckf_cov_propagate_imu_checked',
+    'orcvio_msckf_cov_zupt_frame_checked',
 ]
 
 
@@ -191,6 +193,18 @@ class ImuInfo(C.Structure):
                 ('mean_sforce', C.c_double * 3)]
 
 
+class ZuptCheck(C.Structure):
+    """orcvio_msckf_zupt_check: the constants of checkZUPTIMU (include/orcvio_msckf.h)."""
+    _fields_ = [('sigma_w2', C.c_double), ('sigma_a2', C.c_double), ('sigma_wb', C.c_double), ('sigma_ab', C.c_double),
+                ('chi2_prob', C.c_double), ('chi2_multiplier', C.c_double), ('max_velocity', C.c_double), ('use_left_perturbation', C.c_int32)]
+
+
+class ZuptVerdict(C.Structure):
+    """orcvio_msckf_zupt_verdict (include/orcvio_msckf.h)."""
+    _fields_ = [('evaluated', C.c_int32), ('accept', C.c_int32), ('dof', C.c_int32), ('status', C.c_int32), ('chi2', C.c_double),
+                ('chi2_check', C.c_double), ('speed', C.c_double)]
+
+
 class MsckfState(C.Structure):
     _fields_ = [('R_b2w_imu', C.c_double * 9), ('v', C.c_double * 3), ('p', C.c_double * 3), ('bg', C.c_double * 3),
                 ('ba', C.c_double * 3), ('R_b2c', C.c_double * 9), ('t_c_b', C.c_double * 3), ('td', C.c_double),
@@ -278,6 +292,12 @@ def _bind(lib):
                                                    C.POINTER(ImuInfo), _dp, _dp]
     lib.orcvio_msckf_io_propagate_imu.argtypes = [C.c_void_p, C.POINTER(ImuConfig), C.POINTER(ImuState), _dp, _dp, C.c_int32, C.c_double,
                                                   C.POINTER(ImuInfo)]
+    lib.orcvio_msckf_zupt_check_default.argtypes = [C.POINTER(ZuptCheck)]
+    lib.orcvio_msckf_zupt_check_default.restype = None
+    lib.orcvio_msckf_cov_zupt_check_imu.argtypes = [C.c_void_p, C.POINTER(ZuptCheck), _dp, _dp, _dp, _dp, _dp, C.c_int32, C.POINTER(ZuptVerdict)]
+    lib.orcvio_msckf_cov_propagate_imu_checked.argtypes = [C.c_void_p, C.POINTER(ImuConfig), C.POINTER(ImuState), _dp, _dp, C.c_int32, C.c_double,
+                                                           C.POINTER(ImuInfo), _dp, _dp, C.POINTER(ZuptCheck), C.POINTER(ZuptVerdict)]
+    lib.orcvio_msckf_cov_zupt_frame_checked.argtypes = [C.c_void_p, C.POINTER(ZuptFrame), C.POINTER(ZuptCheck), _dp, _ip, _ip, C.POINTER(ZuptVerdict)]
     lib.orcvio_msckf_upload_nuisance_poses.argtypes = [C.c_void_p, C.c_void_p]
     lib.orcvio_msckf_update_object_tracks.argtypes = [C.c_void_p, C.POINTER(MsckfFlags), C.POINTER(ObjectEvalFlags), C.c_int32,
                                                       C.POINTER(ObjectTrackC), C.c_int32, _dp, C.POINTER(MsckfResult)]
@@ -1552,6 +1572,68 @@ class MsckfUpdater:
         if rc != 0 and (raise_on_refusal or rc != 6):
             raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame')
         return dict(dx=dx[:nu], applied=int(applied.value), n_after=int(n_after.value), rc=rc)
+
+    @staticmethod
+    def zupt_check(use_left=0, **over):
+        """orcvio_msckf_zupt_check with the reference's constants (orcvio_msckf_zupt_check_default); keywords override fields."""
+        c = ZuptCheck()
+        load().orcvio_msckf_zupt_check_default(C.byref(c))
+        c.use_left_perturbation = int(use_left)
+        for k, v in over.items():
+            setattr(c, k, v)
+        return c
+
+    @staticmethod
+    def _verdict(v, rc):
+        return dict(rc=int(rc), evaluated=int(v.evaluated), accept=int(v.accept), dof=int(v.dof), status=int(v.status), chi2=float(v.chi2),
+                    chi2_check=float(v.chi2_check), speed=float(v.speed))
+
+    def cov_zupt_check_imu(self, chk, R_b2w, v, acc_bias, gravity, samples, raise_on_refusal=True):
+        """orcvio_msckf_cov_zupt_check_imu: checkZUPTIMU on the resident covariance as it stands.  samples [S][7] (t | gyro | acc): the
+        selected ones.  Returns dict(rc, evaluated, accept, dof, status, chi2, chi2_check, speed)."""
+        smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, 7)
+        arr = [np.ascontiguousarray(x, dtype=np.float64).reshape(k) for x, k in ((R_b2w, 9), (v, 3), (acc_bias, 3), (gravity, 3))]
+        out = ZuptVerdict()
+        rc = self.lib.orcvio_msckf_cov_zupt_check_imu(self.h, C.byref(chk), _d(arr[0]), _d(arr[1]), _d(arr[2]), _d(arr[3]),
+                                                      _d(smp) if smp.size else None, smp.shape[0], C.byref(out))
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_check_imu')
+        return self._verdict(out, rc)
+
+    def cov_propagate_imu_checked(self, cfg, state, prev_meas, samples, time_bound, chk, want_PhiQ=False, raise_on_refusal=True):
+        """orcvio_msckf_cov_propagate_imu_checked: cov_propagate_imu with the zero-velocity check on the propagated covariance behind it,
+        one wait.  Returns (the dict of cov_propagate_imu, the dict of cov_zupt_check_imu)."""
+        smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, 7)
+        assert isinstance(prev_meas, np.ndarray) and prev_meas.dtype == np.float64 and prev_meas.size == 6 and prev_meas.flags.c_contiguous
+        info = ImuInfo()
+        info.wait = 1
+        Phi = np.zeros((22, 22)) if want_PhiQ else None
+        Q = np.zeros((22, 22)) if want_PhiQ else None
+        out = ZuptVerdict()
+        rc = self.lib.orcvio_msckf_cov_propagate_imu_checked(self.h, C.byref(cfg), C.byref(state), _d(prev_meas), _d(smp) if smp.size else None,
+                                                             smp.shape[0], float(time_bound), C.byref(info), _d(Phi) if want_PhiQ else None,
+                                                             _d(Q) if want_PhiQ else None, C.byref(chk), C.byref(out))
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_propagate_imu_checked')
+        return (dict(status=int(rc), n_used=int(info.n_used), n_propagated=int(info.n_propagated), dt=float(info.dt),
+                     mean_sforce=np.array(info.mean_sforce[:]), applied=int(info.applied), Phi=Phi, Q=Q), self._verdict(out, rc))
+
+    def cov_zupt_frame_checked(self, chk, leg_dim, n_clones, r, noises, augment=True, remove_previous=True, raise_on_refusal=True):
+        """orcvio_msckf_cov_zupt_frame_checked: the stationary frame on a handle armed by io_propagate_imu, the zero-velocity check in
+        front of its update, one wait.  Returns (dict(dx, applied, n_after, rc), the dict of cov_zupt_check_imu)."""
+        f = ZuptFrame()
+        f.zupt = self._zupt_struct(leg_dim, n_clones, r, noises)
+        f.augment, f.remove_previous = int(bool(augment)), int(bool(remove_previous))
+        n = C.c_int32(0)
+        self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), None), 'orcvio_msckf_cov_get')
+        nu = n.value + (6 if augment else 0)
+        dx = np.zeros(max(nu, 1))
+        applied, n_after = C.c_int32(-1), C.c_int32(-1)
+        out = ZuptVerdict()
+        rc = self.lib.orcvio_msckf_cov_zupt_frame_checked(self.h, C.byref(f), C.byref(chk), _d(dx), C.byref(applied), C.byref(n_after), C.byref(out))
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame_checked')
+        return dict(dx=dx[:nu], applied=int(applied.value), n_after=int(n_after.value), rc=rc), self._verdict(out, rc)
 
     def set_object_dof_rank(self, on: bool):
         """ORCVIO_OPT_OBJECT_DOF: 1 = the object gate counts rows - rank(H_f) degrees of freedom (default rows - columns)."""

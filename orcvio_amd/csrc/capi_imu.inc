@@ -63,20 +63,46 @@ static int imu_consume(orcvio_msckf_handle* h, hipStream_t s) {
 }
 static inline bool imu_refused(const orcvio_msckf_handle* h) { return *reinterpret_cast<const volatile int*>(h->h_imu_status) != 0; }
 
-int32_t orcvio_msckf_cov_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, orcvio_msckf_imu_state* state,
-                                       double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
-                                       orcvio_msckf_imu_info* info, double* Phi_out, double* Q_out) {
-    if (!h || !cfg || !state || !prev_meas || !info || n_samples < 0 || (n_samples > 0 && !samples)) { g_last_error = "cov_propagate_imu: null argument"; return ORCVIO_ERR_INVALID; }
-    if (cfg->leg_dim != 22) { g_last_error = "cov_propagate_imu: leg_dim must be 22 (the IMU intrinsics' 24 states have no device form)"; return ORCVIO_ERR_INVALID; }
-    if (h->res_n < 22) { g_last_error = "cov_propagate_imu: no resident covariance"; return ORCVIO_ERR_INVALID; }
-    if ((Phi_out == nullptr) != (Q_out == nullptr)) { g_last_error = "cov_propagate_imu: Phi_out and Q_out come together"; return ORCVIO_ERR_INVALID; }
-    if (h->imu_armed) { g_last_error = "cov_propagate_imu: the handle is armed by orcvio_msckf_io_propagate_imu (its records wait for the frame call)"; return ORCVIO_ERR_INVALID; }
+// The samples the host half selected (:678-709), in order: they ARE imu_recent_zupt (:676-690), what the zero-velocity check reads.
+// t0: state.time before the host half; sel [S][7].
+static void imu_selected(const double* samples, int n, double t0, int S, double* sel) {
+    double cur = t0;
+    int s = 0;
+    for (int k = 0; k < n && s < S; ++k) {
+        if (samples[k * 7] <= cur) continue;
+        for (int i = 0; i < 7; ++i) sel[(size_t)s * 7 + i] = samples[k * 7 + i];
+        cur = samples[k * 7];
+        ++s;
+    }
+}
+
+// the zero-velocity check behind the propagation (capi_zupt_check.inc, which follows in the translation unit)
+static int zchk_prepare(const orcvio_msckf_zupt_check* c, const double* R, const double* v, const double* ba, const double* g,
+                        const double* samples, int S, const char* who, ZuptCheckJob* j);
+static int zchk_enqueue(orcvio_msckf_handle* h, hipStream_t s, const ZuptCheckJob& j, const int* also);
+static int zchk_verdict(const ZuptCheckJob& j, const double* out, int st, const char* who, orcvio_msckf_zupt_verdict* v);
+static inline double* zchk_out(orcvio_msckf_handle* h);
+static inline int* zchk_status(orcvio_msckf_handle* h);
+
+// orcvio_msckf_cov_propagate_imu (chk = NULL) and orcvio_msckf_cov_propagate_imu_checked: the same host half and launches, the checked
+// form with k_zupt_check behind the propagation launches and ONE wait for both
+static int imu_propagate_call(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, orcvio_msckf_imu_state* state,
+                              double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
+                              orcvio_msckf_imu_info* info, double* Phi_out, double* Q_out,
+                              const orcvio_msckf_zupt_check* chk, orcvio_msckf_zupt_verdict* verdict, const char* who) {
+    const std::string w(who);
+    if (!h || !cfg || !state || !prev_meas || !info || n_samples < 0 || (n_samples > 0 && !samples)) { g_last_error = w + ": null argument"; return ORCVIO_ERR_INVALID; }
+    if (cfg->leg_dim != 22) { g_last_error = w + ": leg_dim must be 22 (the IMU intrinsics' 24 states have no device form)"; return ORCVIO_ERR_INVALID; }
+    if (h->res_n < 22) { g_last_error = w + ": no resident covariance"; return ORCVIO_ERR_INVALID; }
+    if ((Phi_out == nullptr) != (Q_out == nullptr)) { g_last_error = w + ": Phi_out and Q_out come together"; return ORCVIO_ERR_INVALID; }
+    if (h->imu_armed) { g_last_error = w + ": the handle is armed by orcvio_msckf_io_propagate_imu (its records wait for the frame call)"; return ORCVIO_ERR_INVALID; }
     ImuMeanState st;
     double prev[6];
     double* recs = h->imu_recs.data();
     ImuBatchInfo bi{};
     ImuFlags fl{};
-    const int rh = imu_host_half(cfg, state, prev_meas, samples, n_samples, time_bound, &st, prev, recs, &bi, &fl, "cov_propagate_imu");
+    const double t0 = state->time;
+    const int rh = imu_host_half(cfg, state, prev_meas, samples, n_samples, time_bound, &st, prev, recs, &bi, &fl, who);
     info->n_used = bi.n_used; info->n_propagated = bi.n_propagated; info->dt = bi.dt; info->applied = 0;
     for (int i = 0; i < 3; ++i) info->mean_sforce[i] = bi.mean_sforce[i];
     if (rh != ORCVIO_OK) return rh;
@@ -87,6 +113,12 @@ int32_t orcvio_msckf_cov_propagate_imu(orcvio_msckf_handle* h, const orcvio_msck
             for (int i = 0; i < 22 * 22; ++i) { Phi_out[i] = (i / 22 == i % 22) ? 1.0 : 0.0; Q_out[i] = 0.0; }
         return ORCVIO_OK;
     }
+    const bool check = chk && S >= 2;   // (one selected sample: :3134, nothing to test with)
+    if (check) {   // the check's own validation, with *state and prev_meas still untouched: the PROPAGATED state, the selected samples
+        imu_selected(samples, n_samples, t0, S, h->imu_sel.data());
+        const int rc = zchk_prepare(chk, st.R, st.v, st.ba, cfg->gravity, h->imu_sel.data(), S, who, &h->zchk_job);
+        if (rc != ORCVIO_OK) return rc;
+    }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     double* dPhi = imu_dphi(h);
@@ -96,16 +128,27 @@ int32_t orcvio_msckf_cov_propagate_imu(orcvio_msckf_handle* h, const orcvio_msck
     imu_state_out(st, state);
     for (int i = 0; i < 6; ++i) prev_meas[i] = prev[i];
     info->applied = 1;
-    if (!info->wait && !Phi_out) return ORCVIO_OK;
+    if (check) { const int rc = zchk_enqueue(h, s, h->zchk_job, imu_status(h)); if (rc != ORCVIO_OK) return rc; }
+    if (!chk && !info->wait && !Phi_out) return ORCVIO_OK;
     int refused = 0;
-    const FetchCopy fc[] = {{Phi_out, dPhi, sizeof(double) * 22 * 22}, {Q_out, dQ, sizeof(double) * 22 * 22}, {&refused, imu_status(h), sizeof(int)}};
-    { const int rc = fetch_copies(h, s, fc, 3); if (rc != ORCVIO_OK) return rc; }
+    double out[4] = {0, 0, 0, 0};
+    int zst[4] = {0, 0, 0, 0};
+    const FetchCopy fc[] = {{Phi_out, dPhi, sizeof(double) * 22 * 22}, {Q_out, dQ, sizeof(double) * 22 * 22}, {&refused, imu_status(h), sizeof(int)},
+                            {out, zchk_out(h), sizeof(out)}, {zst, zchk_status(h), sizeof(zst)}};
+    { const int rc = fetch_copies(h, s, fc, check ? 5 : 3); if (rc != ORCVIO_OK) return rc; }
+    if (check) (void)zchk_verdict(h->zchk_job, out, zst[2], who, verdict);   // (behind a refused Phi: evaluated = 0, ORCVIO_ERR_NOT_SPD)
     if (refused) {
         info->applied = 0;
-        g_last_error = "cov_propagate_imu: Phi or Q not finite (the right closed form with a zero gyro sample): the covariance was not propagated";
+        g_last_error = w + ": Phi or Q not finite (the right closed form with a zero gyro sample): the covariance was not propagated";
         return ORCVIO_ERR_NOT_SPD;
     }
-    return ORCVIO_OK;
+    return check ? verdict->status : ORCVIO_OK;
+}
+
+int32_t orcvio_msckf_cov_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, orcvio_msckf_imu_state* state,
+                                       double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
+                                       orcvio_msckf_imu_info* info, double* Phi_out, double* Q_out) {
+    return imu_propagate_call(h, cfg, state, prev_meas, samples, n_samples, time_bound, info, Phi_out, Q_out, nullptr, nullptr, "cov_propagate_imu");
 }
 
 // Arms the next orcvio_msckf_io_step_frame / _io_step_frame_ex / _cov_zupt_frame on the handle, in the manner of
@@ -122,6 +165,7 @@ int32_t orcvio_msckf_io_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf
     double prev[6];
     ImuBatchInfo bi{};
     ImuFlags fl{};
+    const double t0 = state->time;
     const int rh = imu_host_half(cfg, state, prev_meas, samples, n_samples, time_bound, &st, prev, h->imu_recs.data(), &bi, &fl, "io_propagate_imu");
     info->n_used = bi.n_used; info->n_propagated = bi.n_propagated; info->dt = bi.dt; info->applied = 0;   // (applied: nothing is, yet)
     for (int i = 0; i < 3; ++i) info->mean_sforce[i] = bi.mean_sforce[i];
@@ -130,5 +174,8 @@ int32_t orcvio_msckf_io_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf
     if (bi.n_propagated == 0) return ORCVIO_OK;   // nothing selected: nothing armed, the frame call runs without propagation
     for (int i = 0; i < 6; ++i) prev_meas[i] = prev[i];
     h->imu_armed = true; h->imu_S = bi.n_propagated; h->imu_fl = fl; h->imu_cfg = *cfg;
+    // what orcvio_msckf_cov_zupt_frame_checked tests: the selected samples and the propagated state
+    imu_selected(samples, n_samples, t0, bi.n_propagated, h->imu_sel.data());
+    h->imu_after = st;
     return ORCVIO_OK;
 }

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../../include/orcvio_msckf.h"
+#include "zupt_check_model.hpp"
 
 namespace orcvio_amd {
 
@@ -212,6 +213,13 @@ inline std::vector<double> zuptResidual(const StateServer& ss) {
 struct ImuData {
     double timeStampToSec = 0;
     double angular_velocity[3] = {0, 0, 0}, linear_acceleration[3] = {0, 0, 0};
+};
+// checkZUPTIMU's outcome (MsckfBackend::checkZuptImu): orcvio_msckf_zupt_verdict with the call's status beside it
+struct ZuptCheckOutcome {
+    int status = ORCVIO_OK;        // ORCVIO_OK also when the check rejects; ORCVIO_ERR_NOT_SPD: refused (not evaluated)
+    bool evaluated = false, do_zupt = false;
+    int dof = 0;
+    double chi2 = 0, chi2_check = 0, speed = 0;
 };
 struct ImuOutcome {
     int status = ORCVIO_OK;
@@ -1095,6 +1103,53 @@ class MsckfBackend {
         if (info.n_propagated > 0) ss.imu_state_FEJ_now = o;   // (:894, :924; :820)
         for (int k = 0; k < 3; ++k) { ss.m_gyro_old[k] = prev[k]; ss.m_acc_old[k] = prev[3 + k]; }
         imu_msg_buffer.erase(imu_msg_buffer.begin(), imu_msg_buffer.begin() + info.n_used);
+        return out;
+    }
+
+    // checkZUPTIMU (src/orcvio.cpp:3129-3323) without its side effects (the reference deletes the in-state features and runs the
+    // update when it accepts: the caller's, zuptUpdate below).  imu_recent_zupt: the messages the IMU step selected (:676-690).  With
+    // the covariance resident: orcvio_msckf_cov_zupt_check_imu, one launch on the marginal in HBM.  Without: the SAME arithmetic on
+    // ss.state_cov (zupt_check_model.hpp, the header the kernel is built from), the 56 sums in row order -- equal to the device's to
+    // rounding, not bit for bit.  Neither forms the 6 (S - 1) x 6 (S - 1) matrix.  Validation and refusals as the library call's.
+    ZuptCheckOutcome checkZuptImu(const StateServer& ss, const orcvio_msckf_zupt_check& chk, const double gravity[3],
+                                  const std::vector<ImuData>& imu_recent_zupt) {
+        ZuptCheckOutcome out;
+        const int S = (int)imu_recent_zupt.size();
+        std::vector<double> samples(7 * (size_t)S);
+        for (int i = 0; i < S; ++i) {
+            samples[7 * (size_t)i] = imu_recent_zupt[i].timeStampToSec;
+            for (int k = 0; k < 3; ++k) { samples[7 * (size_t)i + 1 + k] = imu_recent_zupt[i].angular_velocity[k]; samples[7 * (size_t)i + 4 + k] = imu_recent_zupt[i].linear_acceleration[k]; }
+        }
+        const IMUState& im = ss.imu_state;
+        if (resident_covariance) {
+            orcvio_msckf_zupt_verdict v{};
+            out.status = orcvio_msckf_cov_zupt_check_imu(h_, &chk, im.orientation, im.velocity, im.acc_bias, gravity, samples.data(), S, &v);
+            out.evaluated = v.evaluated != 0; out.do_zupt = v.accept != 0; out.dof = v.dof; out.chi2 = v.chi2; out.chi2_check = v.chi2_check; out.speed = v.speed;
+            return out;
+        }
+        // ---- the fall-back on the host's own covariance
+        auto finite = [](const double* x, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
+        const double pos[6] = {chk.sigma_w2, chk.sigma_a2, chk.sigma_wb, chk.sigma_ab, chk.max_velocity, chk.chi2_multiplier};
+        for (double x : pos)
+            if (!std::isfinite(x) || !(x > 0.0)) { out.status = ORCVIO_ERR_INVALID; return out; }
+        if (!(chk.chi2_prob > 0.0) || !(chk.chi2_prob < 1.0) || flags.leg_dim != 22 || ss.dim() < 22) { out.status = ORCVIO_ERR_INVALID; return out; }
+        if (S < 2) return out;   // (:3134)
+        if (S > ZCHK_MAX_SAMPLES) { out.status = ORCVIO_ERR_CAPACITY; return out; }
+        if (!finite(samples.data(), samples.size()) || !finite(im.orientation, 9) || !finite(im.velocity, 3) || !finite(im.acc_bias, 3) || !finite(gravity, 3)) {
+            out.status = ORCVIO_ERR_INVALID; return out;
+        }
+        std::vector<double> rows((size_t)(S - 1) * ZCHK_ROW);
+        if (zupt_check_pack(samples.data(), S, rows.data()) != 0) { out.status = ORCVIO_ERR_INVALID; return out; }   // dt <= 0: the reference would accept on a NaN
+        const ZuptCheckConsts k{chk.sigma_w2, chk.sigma_a2, chk.sigma_wb, chk.sigma_ab, chk.use_left_perturbation ? 1 : 0};
+        out.dof = 6 * (S - 1);
+        out.chi2_check = orcvio_msckf_chi2_quantile(out.dof, chk.chi2_prob);
+        out.speed = std::sqrt(im.velocity[0] * im.velocity[0] + im.velocity[1] * im.velocity[1] + im.velocity[2] * im.velocity[2]);
+        double res[3];
+        if (zupt_check_host(ss.state_cov.data(), ss.dim(), rows.data(), S - 1, im.orientation, im.acc_bias, gravity, k, res) != ZCHK_OK) {
+            out.status = ORCVIO_ERR_NOT_SPD; return out;
+        }
+        out.evaluated = true; out.chi2 = res[0];
+        out.do_zupt = !(out.chi2 > chk.chi2_multiplier * out.chi2_check) && !(out.speed > chk.max_velocity);
         return out;
     }
 

@@ -23,6 +23,7 @@
 #include "cov_ops.hpp"
 #include "zupt_ops.hpp"
 #include "imu_ops.hpp"
+#include "zupt_check_ops.hpp"
 #include "ekf_rows.hpp"
 #include "object_rows.hpp"
 #include "object_fused.hpp"
@@ -194,6 +195,10 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     int imu_S = 0;
     ImuFlags imu_fl{};
     orcvio_msckf_imu_config imu_cfg{};
+    std::vector<double> imu_sel;        // the samples the host half selected [128][7] (imu_recent_zupt): what a checked call tests
+    ImuMeanState imu_after{};           // ... and the state it propagated to (armed form: kept for orcvio_msckf_cov_zupt_frame_checked)
+    double* d_zchk = nullptr;           // k_zupt_check: the packed rows [128][4], its four result doubles (eight reserved), sixteen status words
+    ZuptCheckJob zchk_job{};            // the check validated in front of a checked propagation's launches
     int *h_imu_status = nullptr, *h_imu_status_dev = nullptr;   // host-coherent word: the armed launch's status, read behind the frame's one wait
     bool pw_missing = false;            // uploaded without positions: triangulate_uploaded must run before the update
     int *d_tri_valid = nullptr, *d_tri_flags = nullptr, *d_tri_init = nullptr;
@@ -409,6 +414,7 @@ const char* orcvio_msckf_last_error(void) { return g_last_error.c_str(); }
 #include "capi_object_mapper.inc"   // the object mapper: the start and the Levenberg-Marquardt refinement of object tracks, with keypoints and bbox-only
 #include "capi_imu.inc"   // IMU propagation from raw samples: the host half (host/imu_model.hpp), k_imu_phi_q, the propagation behind it
 #include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: the 9-row update, the factor kept, the one-call stationary frame
+#include "capi_zupt_check.inc"   // zero-velocity detection from IMU samples: k_zupt_check stand-alone, behind the IMU propagation, inside the stationary frame
 #include "capi_frame.inc"   // one frame in one call: feature update + object update, the objects' compression beside the features' solve
 #include "capi_step.inc"   // one FILTER frame in one call: propagate, augment, update, prune update, marginalise on the resident covariance
 #include "capi_state.inc"   // triangulation, incrementState_IMUCam (host arithmetic)
