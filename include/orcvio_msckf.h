@@ -1245,7 +1245,7 @@ int32_t orcvio_msckf_io_step_frame_ex(orcvio_msckf_handle* h, const orcvio_msckf
  * Refused before anything is done (*state and prev_meas untouched): a null argument, leg_dim != 22, no resident covariance
  * (ORCVIO_ERR_INVALID); more than 128 selected samples (ORCVIO_ERR_CAPACITY; info->n_used / n_propagated are filled). */
 typedef struct orcvio_msckf_imu_config {
-    int32_t leg_dim;                /* 22 */
+    int32_t leg_dim;                /* 22; 46 for orcvio_msckf_cov_propagate_imu_calib */
     int32_t use_larvio, use_left_perturbation, use_closed_form, if_fej;
     double  gravity[3];             /* IMUState::gravity */
     double  imu_img_time_th;        /* 1 / (2 imu_rate), :76 */
@@ -1279,6 +1279,32 @@ int32_t orcvio_msckf_cov_propagate_imu(orcvio_msckf_handle* h, const orcvio_msck
 int32_t orcvio_msckf_io_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, orcvio_msckf_imu_state* state,
                                       double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
                                       orcvio_msckf_imu_info* info);
+
+/* ---- IMU propagation with intrinsic calibration: leg_dim 46 (calib_imu_instrinsic = 1) ------------------------------------------------
+ * orcvio_msckf_cov_propagate_imu with the 24 IMU intrinsics in the state (error-state columns 22 .. 45, T1 T2 T3 A1 A2 A3 M1 M2, three
+ * each: the order of orcvio_msckf_state.imu_intrinsics).  Semantics, info, S = 0, S > 128, the refusal of a non-finite Phi and "waits
+ * only if asked" are that call's, word for word; what differs:
+ *   measurement  updateImuMx (:4373-4418) makes Tg, As, Ma from intr; f = m_acc - b_a, acc = Ma f, w = m_gyro - As acc - b_g,
+ *                gyro = Tg w (:733-746), and the same from prev_meas -- BOTH halves of prev_meas are read.  The predictors get gyro, acc.
+ *   Phi          the left / LARVIO closed form carries Tg, Tg As, Ma in its bias blocks, a (theta, b_a) block, and 24 blocks
+ *                Phi[0:9, 22:46] (:4016-4305).  The Euler forms and the right closed form write no intrinsic block, as the reference
+ *                writes them (:3952-3978, :4308-4367): their Phi is the 15 x 15 of leg_dim 22 inside an identity.
+ *   device       one launch, k_imu_phi_q46: rows 15 .. 45 of every Phi_k are identity rows and Q lives in the leading 15 x 15, so only
+ *                Phi[0:15, 22:46] is accumulated beside the 22 recursion ("IMU propagation at leg_dim 46").
+ *   Phi_out, Q_out   [46][46] or NULL.  S = 0: Phi_out = I, Q_out = 0.
+ * A frame at 46 is this call without a wait followed by orcvio_msckf_io_step_frame with Phi = NULL, or Phi_out / Q_out handed to the frame.
+ * Refused before anything is done (ORCVIO_ERR_INVALID, *state and prev_meas untouched): a null argument (intr included), leg_dim != 46
+ * (orcvio_msckf_cov_propagate_imu serves 22), a non-finite intrinsic, a resident covariance of fewer than 46 states, an armed handle.
+ * NOT at 46: the armed form (orcvio_msckf_io_propagate_imu; arming was measured slower than handing Phi, Q to the frame, and the frame
+ * head reads a 22-wide pair on that path), the zero-velocity check (checkZUPTIMU reads Ma, As, Tg too, :3184-3188: the _checked
+ * calls stay at 22), and any "corrected" mode of what the reference writes. */
+typedef struct orcvio_msckf_imu_intrinsics {
+    double x[24];   /* T1 T2 T3 A1 A2 A3 M1 M2, as orcvio_msckf_state.imu_intrinsics */
+} orcvio_msckf_imu_intrinsics;
+int32_t orcvio_msckf_cov_propagate_imu_calib(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg,
+                                             const orcvio_msckf_imu_intrinsics* intr, orcvio_msckf_imu_state* state, double* prev_meas,
+                                             const double* samples, int32_t n_samples, double time_bound, orcvio_msckf_imu_info* info,
+                                             double* Phi_out, double* Q_out);   /* [46][46] or NULL */
 
 /* ---- Zero-velocity DETECTION from IMU samples on the resident covariance (checkZUPTIMU, src/orcvio.cpp:3129-3323) ----------------------
  * The test the configurations with if_use_feature_zupt_flag = 0 run on every image, between stateAugmentation and removeLostFeatures:

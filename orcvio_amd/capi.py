@@ -49,7 +49,7 @@ EXPORTS = [
     'orcvio_msckf_io_step_frame', 'orcvio_msckf_io_step_frame_ex', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
     'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame', 'orcvio_msckf_cov_propagate_imu', 'orcvio_msckf_io_propagate_imu',
     'orcvio_msckf_zupt_check_default', 'orcvio_msckf_cov_zupt_check_imu', 'orcvio_msckf_cov_propagate_imu_checked',
-    'orcvio_msckf_cov_zupt_frame_checked',
+    'orcvio_msckf_cov_zupt_frame_checked', 'orcvio_msckf_cov_propagate_imu_calib',
 ]
 
 
@@ -193,6 +193,11 @@ class ImuInfo(C.Structure):
                 ('mean_sforce', C.c_double * 3)]
 
 
+class ImuIntrinsics(C.Structure):
+    """orcvio_msckf_imu_intrinsics: T1 T2 T3 A1 A2 A3 M1 M2, as orcvio_msckf_state.imu_intrinsics."""
+    _fields_ = [('x', C.c_double * 24)]
+
+
 class ZuptCheck(C.Structure):
     """orcvio_msckf_zupt_check: the constants of checkZUPTIMU (include/orcvio_msckf.h)."""
     _fields_ = [('sigma_w2', C.c_double), ('sigma_a2', C.c_double), ('sigma_wb', C.c_double), ('sigma_ab', C.c_double),
@@ -292,6 +297,8 @@ def _bind(lib):
                                                    C.POINTER(ImuInfo), _dp, _dp]
     lib.orcvio_msckf_io_propagate_imu.argtypes = [C.c_void_p, C.POINTER(ImuConfig), C.POINTER(ImuState), _dp, _dp, C.c_int32, C.c_double,
                                                   C.POINTER(ImuInfo)]
+    lib.orcvio_msckf_cov_propagate_imu_calib.argtypes = [C.c_void_p, C.POINTER(ImuConfig), C.POINTER(ImuIntrinsics), C.POINTER(ImuState), _dp, _dp,
+                                                         C.c_int32, C.c_double, C.POINTER(ImuInfo), _dp, _dp]
     lib.orcvio_msckf_zupt_check_default.argtypes = [C.POINTER(ZuptCheck)]
     lib.orcvio_msckf_zupt_check_default.restype = None
     lib.orcvio_msckf_cov_zupt_check_imu.argtypes = [C.c_void_p, C.POINTER(ZuptCheck), _dp, _dp, _dp, _dp, _dp, C.c_int32, C.POINTER(ZuptVerdict)]
@@ -1478,6 +1485,32 @@ class MsckfUpdater:
                                                      _d(Q) if want_PhiQ else None)
         if rc != 0 and (raise_on_refusal or rc != 6):
             raise MsckfError(rc, 'orcvio_msckf_cov_propagate_imu')
+        return dict(status=int(rc), n_used=int(info.n_used), n_propagated=int(info.n_propagated), dt=float(info.dt),
+                    mean_sforce=np.array(info.mean_sforce[:]), applied=int(info.applied), Phi=Phi, Q=Q)
+
+    @staticmethod
+    def imu_intrinsics(x=None):
+        """ImuIntrinsics from 24 values (T1 T2 T3 A1 A2 A3 M1 M2); None: T2 = M2 = 1, the rest 0 (Tg = Ma = I, As = 0)."""
+        s = ImuIntrinsics()
+        vals = [0, 0, 0, 1, 1, 1] + [0] * 15 + [1, 1, 1] if x is None else np.asarray(x, dtype=np.float64).ravel()
+        assert len(vals) == 24
+        s.x[:] = [float(v) for v in vals]
+        return s
+
+    def cov_propagate_imu_calib(self, cfg, intr, state, prev_meas, samples, time_bound, wait=False, want_PhiQ=False, raise_on_refusal=True):
+        """orcvio_msckf_cov_propagate_imu_calib: cov_propagate_imu at leg_dim 46, the 24 IMU intrinsics (ImuIntrinsics) in the state.
+        Returns the dict of cov_propagate_imu; Phi, Q [46][46] with want_PhiQ (the call then waits)."""
+        smp = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, 7)
+        assert isinstance(prev_meas, np.ndarray) and prev_meas.dtype == np.float64 and prev_meas.size == 6 and prev_meas.flags.c_contiguous
+        info = ImuInfo()
+        info.wait = 1 if wait else 0
+        Phi = np.zeros((46, 46)) if want_PhiQ else None
+        Q = np.zeros((46, 46)) if want_PhiQ else None
+        rc = self.lib.orcvio_msckf_cov_propagate_imu_calib(self.h, C.byref(cfg), C.byref(intr), C.byref(state), _d(prev_meas),
+                                                           _d(smp) if smp.size else None, smp.shape[0], float(time_bound), C.byref(info),
+                                                           _d(Phi) if want_PhiQ else None, _d(Q) if want_PhiQ else None)
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_propagate_imu_calib')
         return dict(status=int(rc), n_used=int(info.n_used), n_propagated=int(info.n_propagated), dt=float(info.dt),
                     mean_sforce=np.array(info.mean_sforce[:]), applied=int(info.applied), Phi=Phi, Q=Q)
 

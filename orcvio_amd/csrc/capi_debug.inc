@@ -385,4 +385,41 @@ int32_t orcvio_msckf_debug_imu_kernel_ms(orcvio_msckf_handle* h, const orcvio_ms
     return ORCVIO_OK;
 }
 
+// k_imu_phi_q46 alone, in the same manner (scripts/gpu_imu_calib_timing.py).  The covariance is not touched.
+int32_t orcvio_msckf_debug_imu_kernel46_ms(orcvio_msckf_handle* h, const orcvio_msckf_imu_config* cfg, const orcvio_msckf_imu_intrinsics* intr,
+                                           const orcvio_msckf_imu_state* state, const double* prev_meas, const double* samples,
+                                           int32_t n_samples, double time_bound, int32_t reps, float* ms_out) {
+    if (!h || !cfg || !intr || !state || !prev_meas || !samples || !ms_out || reps < 1 || cfg->leg_dim != 46) return ORCVIO_ERR_INVALID;
+    ImuIntrinsicMx mx;
+    imu_intrinsic_mx(intr->x, &mx);
+    ImuMeanState st;
+    double prev[6];
+    double* recs = h->imu_recs46.data();
+    ImuBatchInfo bi{};
+    ImuFlags fl{};
+    { const int rh = imu_host_half46(cfg, mx, state, prev_meas, samples, n_samples, time_bound, &st, prev, recs, &bi, &fl, "debug_imu_kernel46_ms"); if (rh != ORCVIO_OK) return rh; }
+    if (bi.n_propagated < 1) return ORCVIO_ERR_INVALID;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    double* dPhi = imu_dphi(h);
+    double* dQ = imu_dq(h);
+    int rc = imu_enqueue46(h, s, cfg, fl, mx, recs, bi.n_propagated, dPhi, dQ);   // (records staged, warm-up)
+    if (rc != ORCVIO_OK) return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t he = hipEventCreate(&e0);
+    if (he == hipSuccess) he = hipEventCreate(&e1);
+    const ImuKernArgs46 a = imu_args46(h, cfg, fl, mx, bi.n_propagated, dPhi, dQ);
+    for (int r = 0; r < reps && he == hipSuccess; ++r) {
+        he = hipEventRecord(e0, s);
+        hipLaunchKernelGGL(k_imu_phi_q46, dim3(1), dim3(64 * IMU_WAVES), imu46_lds_bytes(), s, a);
+        if (he == hipSuccess) he = hipEventRecord(e1, s);
+        if (he == hipSuccess) he = hipEventSynchronize(e1);
+        if (he == hipSuccess) he = hipEventElapsedTime(&ms_out[r], e0, e1);
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (he != hipSuccess) { g_last_error = std::string("debug_imu_kernel46_ms: ") + hipGetErrorString(he); return ORCVIO_ERR_HIP; }
+    return ORCVIO_OK;
+}
+
 #endif  // ORCVIO_DEBUG_HOOKS

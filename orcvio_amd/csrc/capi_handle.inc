@@ -215,7 +215,7 @@ static void free_all(orcvio_msckf_handle* h) {
                     h->d_DinvP, h->d_U, h->d_M, h->d_RM, h->d_DinvM, h->d_Z, h->d_La, h->d_DinvA,
                     h->d_W, h->d_Y, h->d_KG, h->d_Gobj, h->d_RF, h->d_DinvF, h->d_Yobj, h->d_objH,
                     h->d_obj_gamma, h->d_obj_i, h->d_obj_accept, h->d_T3, h->d_Xobs, h->d_S,
-                    h->d_Pres, h->d_Ptmp, h->d_Sres, h->d_Stmp, h->d_covT, h->d_covmap, h->d_imu, h->d_zchk, h->d_skip, h->d_tri_valid, h->d_tri_flags, h->d_tri_init, h->d_tri_sol, h->d_tri_cost, h->d_sync, h->d_la_rdy, h->d_U2, h->d_M2, h->d_RM2, h->d_DinvM2, h->d_Z2, h->d_outs2, h->d_chain_words, h->d_obj_done,
+                    h->d_Pres, h->d_Ptmp, h->d_Sres, h->d_Stmp, h->d_covT, h->d_covmap, h->d_imu, h->d_imu46, h->d_zchk, h->d_skip, h->d_tri_valid, h->d_tri_flags, h->d_tri_init, h->d_tri_sol, h->d_tri_cost, h->d_sync, h->d_la_rdy, h->d_U2, h->d_M2, h->d_RM2, h->d_DinvM2, h->d_Z2, h->d_outs2, h->d_chain_words, h->d_obj_done,
                     h->d_ekf_i, h->d_ekf_d, h->d_ekf_E, h->d_Gekf, h->d_ekf_gamma, h->d_ekf_accept, h->d_slam, h->d_dense, h->d_Rf, h->d_new, h->d_aug};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -347,6 +347,10 @@ int32_t orcvio_msckf_create(int32_t device, int32_t max_clones, int32_t max_feat
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->h_imu_status_dev), h->h_imu_status, 0));
         std::memset(h->h_imu_status, 0, 64);
         h->imu_sel.resize((size_t)IMU_MAX_SAMPLES * 7);
+        // orcvio_msckf_cov_propagate_imu_calib: the wider records of leg_dim 46 and k_imu_phi_q46's dynamic LDS (a round's compact forms, 83 KB)
+        HIPCHK(hipMalloc(&h->d_imu46, sizeof(double) * (size_t)IMU_MAX_SAMPLES * IMU_REC46));
+        HIPCHK(hipFuncSetAttribute((const void*)k_imu_phi_q46, hipFuncAttributeMaxDynamicSharedMemorySize, (int)imu46_lds_bytes()));
+        h->imu_recs46.resize((size_t)IMU_MAX_SAMPLES * IMU_REC46);
         HIPCHK(hipMalloc(&h->d_zchk, sizeof(double) * ((size_t)ZCHK_MAX_SAMPLES * ZCHK_ROW + 16)));   // k_zupt_check: rows, results, status words
         HIPCHK(hipMemset(h->d_zchk, 0, sizeof(double) * ((size_t)ZCHK_MAX_SAMPLES * ZCHK_ROW + 16)));
         HIPCHK(hipMalloc(&h->d_tri_valid, sizeof(int) * max_features));

@@ -92,7 +92,7 @@ static int imu_propagate_call(orcvio_msckf_handle* h, const orcvio_msckf_imu_con
                               const orcvio_msckf_zupt_check* chk, orcvio_msckf_zupt_verdict* verdict, const char* who) {
     const std::string w(who);
     if (!h || !cfg || !state || !prev_meas || !info || n_samples < 0 || (n_samples > 0 && !samples)) { g_last_error = w + ": null argument"; return ORCVIO_ERR_INVALID; }
-    if (cfg->leg_dim != 22) { g_last_error = w + ": leg_dim must be 22 (the IMU intrinsics' 24 states have no device form)"; return ORCVIO_ERR_INVALID; }
+    if (cfg->leg_dim != 22) { g_last_error = w + ": leg_dim must be 22 (this call has no intrinsics to read: orcvio_msckf_cov_propagate_imu_calib serves 46, without the check)"; return ORCVIO_ERR_INVALID; }
     if (h->res_n < 22) { g_last_error = w + ": no resident covariance"; return ORCVIO_ERR_INVALID; }
     if ((Phi_out == nullptr) != (Q_out == nullptr)) { g_last_error = w + ": Phi_out and Q_out come together"; return ORCVIO_ERR_INVALID; }
     if (h->imu_armed) { g_last_error = w + ": the handle is armed by orcvio_msckf_io_propagate_imu (its records wait for the frame call)"; return ORCVIO_ERR_INVALID; }
@@ -157,7 +157,7 @@ int32_t orcvio_msckf_io_propagate_imu(orcvio_msckf_handle* h, const orcvio_msckf
                                       double* prev_meas, const double* samples, int32_t n_samples, double time_bound,
                                       orcvio_msckf_imu_info* info) {
     if (!h || !cfg || !state || !prev_meas || !info || n_samples < 0 || (n_samples > 0 && !samples)) { g_last_error = "io_propagate_imu: null argument"; return ORCVIO_ERR_INVALID; }
-    if (cfg->leg_dim != 22) { g_last_error = "io_propagate_imu: leg_dim must be 22 (the IMU intrinsics' 24 states have no device form)"; return ORCVIO_ERR_INVALID; }
+    if (cfg->leg_dim != 22) { g_last_error = "io_propagate_imu: leg_dim must be 22 (the armed form has no 46: orcvio_msckf_cov_propagate_imu_calib in front of the frame call)"; return ORCVIO_ERR_INVALID; }
     if (h->res_n < 22) { g_last_error = "io_propagate_imu: no resident covariance"; return ORCVIO_ERR_INVALID; }
     if (h->comm || h->ipc) { g_last_error = "io_propagate_imu: not with a communicator on the handle"; return ORCVIO_ERR_INVALID; }
     if (h->imu_armed) { g_last_error = "io_propagate_imu: the handle is armed already"; return ORCVIO_ERR_INVALID; }

@@ -1,7 +1,7 @@
 // imu_model.hpp -- the reference's IMU step (batchImuProcessing -> processModel, src/orcvio.cpp:664-823) at leg_dim = 22, in plain
 // C++ that compiles for the host and for the device (the guard pattern of msckf_math.hpp, no Eigen).  With calib_imu_instrinsic = 0
 // (every shipped YAML) Tg = Ma = I and As = 0: gyro = m_gyro - b_g, acc = m_acc - b_a, and the calib_imu block of calPhiClosedForm
-// does not exist.  leg_dim = 46 is refused by the callers.
+// does not exist.  leg_dim = 46 (calib_imu_instrinsic = 1) has functions of its own at the end of this header: imu_*46.
 //
 //   imu_propagate_mean   sample selection (:678-709) + one predictor per selected sample: predictNewStateLARVIO (:825-897) or
 //                        predictNewStateOrcVIO (:899-928).  HOST: 3-vectors and 3 x 3 matrices.  Leaves one RECORD per sample --
@@ -537,6 +537,316 @@ inline void imu_accumulate_host(const double* recs, int S, ImuFlags f, const dou
             const bool in = i < IMU_DIM && j < IMU_DIM;
             Phi[i * IMU_LEG + j] = in ? A[i * IMU_DIM + j] : (i == j ? 1.0 : 0.0);
             Q[i * IMU_LEG + j] = in ? 0.5 * (B[i * IMU_DIM + j] + B[j * IMU_DIM + i]) : 0.0;
+        }
+}
+
+// =====================================================================================================================================
+// leg_dim = 46 (calib_imu_instrinsic = 1): the 24 IMU intrinsics T1 T2 T3 A1 A2 A3 M1 M2 (three each) are error-state columns 22 .. 45.
+//   imu_intrinsic_matrices  updateImuMx (:4373-4418): Tg, As from the triples, Ma lower triangular (M1 strict lower part, M2 diagonal)
+//   imu_measurement46       :733-746: f = m_acc - b_a, acc = Ma f, w = m_gyro - As acc - b_g, gyro = Tg w (the predictors get gyro, acc)
+//   imu_propagate_mean46    imu_propagate_mean on the corrected gyro, acc; records of IMU_REC46 doubles: today's 40 (gyro, acc and
+//                           gyro_old are the corrected ones) and f, w, f_old, w_old, acc_old behind them
+//   imu_phi46_lead          the leading 15 x 15: the left / LARVIO closed form with Tg, TA = Tg As, Ma (:4016-4037; a tenth block,
+//                           (theta, b_a), is no longer zero); the Euler forms and the right closed form are imu_phi's (they write no
+//                           intrinsic block and read no intrinsic matrix, :3952-3978, :4308-4367: as written)
+//   imu_phi46_triple        one of the eight 9 x 3 column groups Phi_k[0:9, 22 + 3 j : 25 + 3 j] of the left / LARVIO closed form (:4039-4305)
+//   imu_accumulate_host46   Phi, Q [46][46] on the host.  Rows 15 .. 45 of every Phi_k are identity rows and G has nothing below row 15:
+//                           Q lives in the leading 15 x 15 (today's recursion) and Phi = [[A, B], [0, I]], A <- A_k A, B <- A_k B + B_k
+//                           with B [15][24] (its columns 22 .. 45 of Phi), B_k non-zero in rows 0 .. 8 only.
+// Not at 46: the armed form (orcvio_msckf_io_propagate_imu) and the zero-velocity check (checkZUPTIMU reads Ma, As, Tg too, :3184-3188).
+enum { IMU_LEG46 = 46, IMU_NI = 24, IMU_TRIPLES = 8 };
+enum { IMU_REC_F = 40, IMU_REC_W = 43, IMU_REC_F_OLD = 46, IMU_REC_W_OLD = 49, IMU_REC_ACC_OLD = 52, IMU_REC46 = 55 };
+// a sample's compact form at 46: ten 3 x 3 blocks | N_k (24) | B_k [9][24]
+enum { IMU_PHI_BLOCKS46 = 10, IMU_COMPACT46_N00 = 90, IMU_COMPACT46_ND = 108, IMU_COMPACT46_B = 114, IMU_COMPACT46 = 330 };
+
+struct ImuIntrinsicMx { double Tg[9], As[9], Ma[9], TA[9]; };   // TA = Tg As (:4000)
+
+ORC_IMU_HD void imu_intrinsic_matrices(const double* x, double* Tg, double* As, double* Ma) {
+    const double *T1 = x, *T2 = x + 3, *T3 = x + 6, *A1 = x + 9, *A2 = x + 12, *A3 = x + 15, *M1 = x + 18, *M2 = x + 21;
+    Tg[0] = T2[0]; Tg[1] = T3[0]; Tg[2] = T3[1];
+    Tg[3] = T1[0]; Tg[4] = T2[1]; Tg[5] = T3[2];
+    Tg[6] = T1[1]; Tg[7] = T1[2]; Tg[8] = T2[2];
+    As[0] = A2[0]; As[1] = A3[0]; As[2] = A3[1];
+    As[3] = A1[0]; As[4] = A2[1]; As[5] = A3[2];
+    As[6] = A1[1]; As[7] = A1[2]; As[8] = A2[2];
+    Ma[0] = M2[0]; Ma[1] = 0.0;   Ma[2] = 0.0;
+    Ma[3] = M1[0]; Ma[4] = M2[1]; Ma[5] = 0.0;
+    Ma[6] = M1[1]; Ma[7] = M1[2]; Ma[8] = M2[2];
+}
+ORC_IMU_HD void imu_intrinsic_mx(const double* x, ImuIntrinsicMx* m) {
+    imu_intrinsic_matrices(x, m->Tg, m->As, m->Ma);
+    m3_mul(m->Tg, m->As, m->TA);
+}
+ORC_IMU_HD void imu_measurement46(const double* m_gyro, const double* m_acc, const double* bg, const double* ba, const ImuIntrinsicMx& m,
+                                  double* f, double* w, double* acc, double* gyro) {
+    double t[3];
+    for (int i = 0; i < 3; ++i) f[i] = m_acc[i] - ba[i];
+    m3_mulv(m.Ma, f, acc);
+    m3_mulv(m.As, acc, t);
+    for (int i = 0; i < 3; ++i) w[i] = m_gyro[i] - t[i] - bg[i];
+    m3_mulv(m.Tg, w, gyro);
+}
+
+// the ten blocks: imu_block's nine, and (theta, b_a) as the tenth
+ORC_IMU_HD int imu_block46(int bi, int bj) { return (bi == 0 && bj == 4) ? 9 : imu_block(bi, bj); }
+struct ImuCompactSink46 {
+    double* c;
+    ORC_IMU_HD void init() {
+        for (int i = 0; i < 9 * IMU_PHI_BLOCKS46; ++i) c[i] = 0.0;
+        c[0] = c[4] = c[8] = 1.0;
+    }
+    ORC_IMU_HD void put(int r, int cc, const double* B, double s) {
+        const int b = imu_block46(r / 3, cc / 3);
+        for (int i = 0; i < 9; ++i) c[b * 9 + i] = s * B[i];
+    }
+};
+
+template <class Sink>
+ORC_IMU_HD void imu_phi46_lead(const double* rec, ImuFlags f, const double* grav, const ImuIntrinsicMx& mx, Sink& out) {
+    if (!((f.use_larvio || f.use_closed_form) && (f.use_larvio || f.use_left))) {   // Euler forms, right closed form: today's blocks
+        imu_phi(rec, f, grav, out);
+        return;
+    }
+    out.init();
+    const double dt = rec[IMU_REC_DT];
+    const double *gyro = rec + IMU_REC_GYRO, *go = rec + IMU_REC_GYRO_OLD, *C = rec + IMU_REC_R_OLD;
+    const double *vk = rec + IMU_REC_VK, *pk = rec + IMU_REC_PK, *vk1 = rec + IMU_REC_VK1, *pk1 = rec + IMU_REC_PK1;
+    double I3[9], cr[3], aa[3], Ah[9], M[9], T[9], U[9], V[9], S[9], X[9], Y[9], w[3];
+    m3_eye(I3, 1.0);
+    v3_cross(go, gyro, cr);
+    for (int i = 0; i < 3; ++i) aa[i] = dt * (go[i] + gyro[i]) / 2 + dt * dt * cr[i] / 12;
+    m3_skew(aa, Ah);
+    // B1 = -0.5 C (2 I + Ah) dt;  Phi_q_bg = B1 Tg;  Phi_q_ba = -B1 TA Ma
+    for (int i = 0; i < 9; ++i) M[i] = 2 * I3[i] + Ah[i];
+    m3_mul(C, M, T);
+    for (int i = 0; i < 9; ++i) T[i] = -0.5 * T[i] * dt;
+    m3_mul(T, mx.Tg, X);
+    out.put(0, 9, X, 1.0);
+    m3_mul(T, mx.TA, X);
+    m3_mul(X, mx.Ma, Y);
+    out.put(0, 12, Y, -1.0);
+    // Phi_v_q
+    for (int i = 0; i < 3; ++i) w[i] = vk1[i] - vk[i] - grav[i] * dt;
+    m3_skew(w, S);
+    out.put(3, 0, S, -1.0);
+    // Phi_v_bg (as written: no Tg)
+    for (int i = 0; i < 3; ++i) w[i] = -pk1[i] + pk[i] + vk1[i] * dt - 0.5 * grav[i] * dt * dt;
+    m3_skew(w, S);
+    m3_mul(S, C, U);
+    for (int i = 0; i < 3; ++i) w[i] = -0.5 * pk1[i] + 0.5 * pk[i] + 0.5 * vk1[i] * dt - grav[i] * dt * dt / 6;
+    m3_skew(w, S);
+    m3_mul(S, C, M);
+    m3_mul(M, Ah, S);
+    for (int i = 0; i < 9; ++i) U[i] = U[i] + S[i];
+    out.put(3, 9, U, 1.0);
+    // Phi_v_ba = B1 Ma - Phi_v_bg TA Ma
+    m3_mul(T, mx.Ma, X);
+    m3_mul(U, mx.TA, M);
+    m3_mul(M, mx.Ma, Y);
+    for (int i = 0; i < 9; ++i) X[i] = X[i] - Y[i];
+    out.put(3, 12, X, 1.0);
+    // Phi_p_q, Phi_p_v
+    for (int i = 0; i < 3; ++i) w[i] = pk1[i] - pk[i] - vk[i] * dt - 0.5 * grav[i] * dt * dt;
+    m3_skew(w, S);
+    out.put(6, 0, S, -1.0);
+    out.put(6, 3, I3, dt);
+    // Phi_p_bg
+    m3_skew(grav, S);
+    m3_mul(S, C, V);
+    for (int i = 0; i < 3; ++i) w[i] = pk1[i] - pk[i] - grav[i] * dt * dt / 6;
+    m3_skew(w, S);
+    m3_mul(S, C, M);
+    m3_mul(M, Ah, S);
+    for (int i = 0; i < 9; ++i) V[i] = -dt * dt * dt * V[i] / 6 + dt * S[i] / 4;
+    out.put(6, 9, V, 1.0);
+    // Phi_p_ba = -C (3 I + Ah) dt^2 / 6 Ma - Phi_p_bg TA Ma
+    for (int i = 0; i < 9; ++i) M[i] = 3 * I3[i] + Ah[i];
+    m3_mul(C, M, T);
+    for (int i = 0; i < 9; ++i) T[i] = -T[i] * dt * dt / 6;
+    m3_mul(T, mx.Ma, X);
+    m3_mul(V, mx.TA, M);
+    m3_mul(M, mx.Ma, Y);
+    for (int i = 0; i < 9; ++i) X[i] = X[i] - Y[i];
+    out.put(6, 12, X, 1.0);
+}
+
+// whether the form writes intrinsic blocks at all: the left / LARVIO closed form only
+ORC_IMU_HD bool imu_has_intrinsic_blocks(ImuFlags f) { return (f.use_larvio || f.use_closed_form) && (f.use_larvio || f.use_left); }
+
+// WL / WD / WU of :4042-4137 (kind 0, 1, 2) from a 3-vector
+ORC_IMU_HD void imu_pattern(int kind, const double* x, double* M) {
+    for (int i = 0; i < 9; ++i) M[i] = 0.0;
+    if (kind == 0) { M[3] = x[0]; M[7] = x[0]; M[8] = x[1]; }
+    else if (kind == 1) { M[0] = x[0]; M[4] = x[1]; M[8] = x[2]; }
+    else { M[0] = x[1]; M[1] = x[2]; M[5] = x[2]; }
+}
+// Column group j (0 .. 7: T1 T2 T3 A1 A2 A3 M1 M2) of the left / LARVIO closed form, out [9][3]: rows theta, v, p.  The three families
+// differ in the vector the pattern is made from (w, acc, f: old, mid, new), the factor in front of it (I, Tg, TA), the sign, and -- the M
+// family only -- a direct term in the velocity rows (:4235-4241).
+ORC_IMU_HD void imu_phi46_triple(const double* rec, const ImuIntrinsicMx& mx, int j, double* out) {
+    const double dt = rec[IMU_REC_DT];
+    const double *gyro = rec + IMU_REC_GYRO, *go = rec + IMU_REC_GYRO_OLD, *acc = rec + IMU_REC_ACC, *acco = rec + IMU_REC_ACC_OLD;
+    const double* C = rec + IMU_REC_R_OLD;
+    const int grp = j < 3 ? 0 : (j < 6 ? 1 : 2), kind = j < 6 ? j % 3 : j - 6;
+    double cr[3], aa[3], Ah[9], Rm[9], Rp[9], I3[9];
+    m3_eye(I3, 1.0);
+    v3_cross(go, gyro, cr);
+    for (int i = 0; i < 3; ++i) aa[i] = dt * (go[i] + gyro[i]) / 2 + dt * dt * cr[i] / 12;
+    m3_skew(aa, Ah);
+    for (int i = 0; i < 9; ++i) { Rm[i] = I3[i] + 0.5 * Ah[i]; Rp[i] = I3[i] + Ah[i]; }
+    const double* so = rec + (grp == 0 ? (int)IMU_REC_W_OLD : (grp == 1 ? (int)IMU_REC_ACC_OLD : (int)IMU_REC_F_OLD));
+    const double* sn = rec + (grp == 0 ? (int)IMU_REC_W : (grp == 1 ? (int)IMU_REC_ACC : (int)IMU_REC_F));
+    double sm[3];
+    if (grp == 0) {
+        v3_cross(so, sn, cr);
+        for (int i = 0; i < 3; ++i) sm[i] = (so[i] + sn[i]) / 2 + dt * cr[i] / 12;
+    } else {
+        for (int i = 0; i < 3; ++i) sm[i] = (sn[i] + so[i]) / 2;
+    }
+    double X1[9], Xh[9], Xp[9], k1[9], k2[9], k4[9], T[9], Rq[9];
+    imu_pattern(kind, so, X1);
+    imu_pattern(kind, sm, Xh);
+    imu_pattern(kind, sn, Xp);
+    if (grp == 0) {
+        for (int i = 0; i < 9; ++i) k1[i] = X1[i];
+        m3_mul(Rm, Xh, k2);
+        m3_mul(Rp, Xp, k4);
+    } else {
+        const double* L = grp == 1 ? mx.Tg : mx.TA;
+        m3_mul(L, X1, k1);
+        m3_mul(Rm, L, T);
+        m3_mul(T, Xh, k2);
+        m3_mul(Rp, L, T);
+        m3_mul(T, Xp, k4);
+    }
+    for (int i = 0; i < 9; ++i) Rq[i] = dt * (k1[i] + 4 * k2[i] + k4[i]) / 6;
+    const double sq = grp == 0 ? 1.0 : -1.0, sv = grp == 0 ? -1.0 : 1.0;
+    m3_mul(C, Rq, T);
+    for (int i = 0; i < 9; ++i) out[i] = sq * T[i];
+    // velocity rows
+    double am[3], y[3], Sm[9], Sp[9], kv1[9], kv2[9], kv3[9], kv4[9], E[9], fR[9];
+    for (int i = 0; i < 3; ++i) am[i] = (acc[i] + acco[i]) / 2;
+    m3_mulv(Rm, am, y);
+    m3_skew(y, Sm);
+    m3_mulv(Rp, acc, y);
+    m3_skew(y, Sp);
+    for (int i = 0; i < 9; ++i) Sm[i] = Sm[i] * dt;
+    m3_mul(Sm, k1, kv2);
+    m3_mul(Sm, k2, kv3);
+    m3_mul(Sp, Rq, kv4);
+    for (int i = 0; i < 9; ++i) { kv1[i] = 0.0; kv2[i] = kv2[i] / 2; kv3[i] = kv3[i] / 2; }
+    if (grp == 2) {
+        for (int i = 0; i < 9; ++i) kv1[i] = X1[i];
+        m3_mul(Rm, Xh, E);
+        for (int i = 0; i < 9; ++i) { kv2[i] = E[i] + kv2[i]; kv3[i] = E[i] + kv3[i]; }
+        m3_mul(Rp, Xp, E);
+        for (int i = 0; i < 9; ++i) kv4[i] = E[i] + kv4[i];
+    }
+    for (int i = 0; i < 9; ++i) fR[i] = dt * (kv1[i] + 2 * kv2[i] + 2 * kv3[i] + kv4[i]) / 6;
+    m3_mul(C, fR, T);
+    for (int i = 0; i < 9; ++i) out[9 + i] = sv * T[i];
+    // position rows: kp1 = 0, kp2 = dt kv1 / 2, kp3 = dt kv2 / 2, kp4 = fR
+    for (int i = 0; i < 9; ++i) E[i] = 2 * (dt * kv1[i] / 2) + 2 * (dt * kv2[i] / 2) + fR[i];
+    m3_mul(C, E, T);
+    for (int i = 0; i < 9; ++i) out[18 + i] = sv * (T[i] * dt) / 6;
+}
+
+// imu_propagate_mean at 46: the same selection and predictors, on the measurement of :733-746.  recs [<= cap][IMU_REC46].
+inline bool imu_propagate_mean46(const ImuModelConfig& c, const ImuIntrinsicMx& mx, ImuMeanState* st, double* prev_meas, const double* samples,
+                                 int n, double time_bound, double* recs, int cap, ImuBatchInfo* info) {
+    int used = 0, count = 0;
+    double dt_img = 0.0, cur = st->time;
+    for (int k = 0; k < n; ++k) {
+        const double t = samples[k * 7];
+        if (t <= cur) { ++used; continue; }
+        if (t - time_bound > c.imu_img_time_th) break;
+        ++count; ++used;
+        dt_img = t - time_bound;
+        cur = t;
+    }
+    info->n_used = used; info->n_propagated = count; info->dt = dt_img;
+    info->mean_sforce[0] = info->mean_sforce[1] = info->mean_sforce[2] = 0.0;
+    if (count > cap) return false;
+    double sum[3] = {0, 0, 0};
+    int s = 0;
+    for (int k = 0; k < n && s < count; ++k) {
+        const double* row = samples + k * 7;
+        const double t = row[0];
+        if (t <= st->time) continue;
+        double* rec = recs + (size_t)s * IMU_REC46;
+        const double dt = t - st->time;
+        rec[IMU_REC_DT] = dt;
+        imu_measurement46(row + 1, row + 4, st->bg, st->ba, mx, rec + IMU_REC_F, rec + IMU_REC_W, rec + IMU_REC_ACC, rec + IMU_REC_GYRO);
+        imu_measurement46(prev_meas, prev_meas + 3, st->bg, st->ba, mx, rec + IMU_REC_F_OLD, rec + IMU_REC_W_OLD, rec + IMU_REC_ACC_OLD, rec + IMU_REC_GYRO_OLD);
+        for (int i = 0; i < 3; ++i) {
+            rec[IMU_REC_VK + i] = c.flags.if_fej ? st->v_fej[i] : st->v[i];
+            rec[IMU_REC_PK + i] = c.flags.if_fej ? st->p_fej[i] : st->p[i];
+        }
+        for (int i = 0; i < 9; ++i) rec[IMU_REC_R_OLD + i] = st->R[i];
+        if (!c.flags.use_larvio) imu_predict_orcvio(dt, rec + IMU_REC_GYRO, rec + IMU_REC_ACC, c.gravity, st->R, st->v, st->p);
+        else imu_predict_larvio(dt, rec + IMU_REC_GYRO, rec + IMU_REC_ACC, c.gravity, st->R, st->v, st->p);
+        for (int i = 0; i < 3; ++i) { st->v_fej[i] = st->v[i]; st->p_fej[i] = st->p[i]; }
+        for (int i = 0; i < 9; ++i) rec[IMU_REC_R_NEW + i] = st->R[i];
+        for (int i = 0; i < 3; ++i) { rec[IMU_REC_VK1 + i] = st->v[i]; rec[IMU_REC_PK1 + i] = st->p[i]; }
+        st->time = t;
+        for (int i = 0; i < 6; ++i) prev_meas[i] = row[1 + i];
+        for (int i = 0; i < 3; ++i) sum[i] += row[4 + i];
+        ++s;
+    }
+    if (count > 0)
+        for (int i = 0; i < 3; ++i) info->mean_sforce[i] = sum[i] / count;
+    return true;
+}
+
+// The ordered product on the host at 46.  Phi, Q [46][46] out.
+inline void imu_accumulate_host46(const double* recs, int S, ImuFlags f, const double* grav, const double* qc, const ImuIntrinsicMx& mx,
+                                  double* Phi, double* Q) {
+    double A[IMU_DIM * IMU_DIM], B[IMU_DIM * IMU_DIM], P[IMU_DIM * IMU_DIM], T[IMU_DIM * IMU_DIM], U[IMU_DIM * IMU_DIM];
+    double Bi[IMU_DIM * IMU_NI], Bt[IMU_DIM * IMU_NI], Bk[9 * IMU_NI];
+    for (int i = 0; i < IMU_DIM * IMU_DIM; ++i) { A[i] = (i / IMU_DIM == i % IMU_DIM) ? 1.0 : 0.0; B[i] = 0.0; }
+    for (int i = 0; i < IMU_DIM * IMU_NI; ++i) Bi[i] = 0.0;
+    const bool intr = imu_has_intrinsic_blocks(f);
+    for (int k = 0; k < S; ++k) {
+        const double* rec = recs + (size_t)k * IMU_REC46;
+        ImuDenseSink sink{P, IMU_DIM};
+        imu_phi46_lead(rec, f, grav, mx, sink);
+        double nc[24];
+        imu_noise(rec, f, qc, nc);
+        for (int i = 0; i < 9 * IMU_NI; ++i) Bk[i] = 0.0;
+        if (intr)
+            for (int j = 0; j < IMU_TRIPLES; ++j) {
+                double g[27];
+                imu_phi46_triple(rec, mx, j, g);
+                for (int r = 0; r < 9; ++r)
+                    for (int c = 0; c < 3; ++c) Bk[r * IMU_NI + 3 * j + c] = g[r * 3 + c];
+            }
+        for (int i = 0; i < IMU_DIM; ++i)
+            for (int j = 0; j < IMU_DIM; ++j) U[i * IMU_DIM + j] = B[i * IMU_DIM + j] + imu_noise_at(nc, i, j);
+        imu_mul15(P, U, T);                                 // T = Phi_k (Q + N_k)
+        for (int i = 0; i < IMU_DIM; ++i)
+            for (int j = 0; j < IMU_DIM; ++j) {
+                double s = 0.0;
+                for (int l = 0; l < IMU_DIM; ++l) s += T[i * IMU_DIM + l] * P[j * IMU_DIM + l];
+                B[i * IMU_DIM + j] = s;
+            }
+        for (int i = 0; i < IMU_DIM; ++i)                   // B <- A_k B + B_k
+            for (int j = 0; j < IMU_NI; ++j) {
+                double s = 0.0;
+                for (int l = 0; l < IMU_DIM; ++l) s += P[i * IMU_DIM + l] * Bi[l * IMU_NI + j];
+                Bt[i * IMU_NI + j] = i < 9 ? s + Bk[i * IMU_NI + j] : s;
+            }
+        for (int i = 0; i < IMU_DIM * IMU_NI; ++i) Bi[i] = Bt[i];
+        imu_mul15(P, A, T);
+        for (int i = 0; i < IMU_DIM * IMU_DIM; ++i) A[i] = T[i];
+    }
+    for (int i = 0; i < IMU_LEG46; ++i)
+        for (int j = 0; j < IMU_LEG46; ++j) {
+            const bool in = i < IMU_DIM && j < IMU_DIM;
+            double p = i == j ? 1.0 : 0.0;
+            if (in) p = A[i * IMU_DIM + j];
+            else if (i < IMU_DIM && j >= IMU_LEG) p = Bi[i * IMU_NI + j - IMU_LEG];
+            Phi[i * IMU_LEG46 + j] = p;
+            Q[i * IMU_LEG46 + j] = in ? 0.5 * (B[i * IMU_DIM + j] + B[j * IMU_DIM + i]) : 0.0;
         }
 }
 

@@ -1092,7 +1092,13 @@ class MsckfBackend {
         }
         orcvio_msckf_imu_info info{};
         info.wait = wait ? 1 : 0;
-        out.status = orcvio_msckf_cov_propagate_imu(h_, &cfg, &st, prev, samples.data(), (int32_t)imu_msg_buffer.size(), time_bound, &info, nullptr, nullptr);
+        if (cfg.leg_dim == 46) {   // calib_imu_instrinsic: the 24 intrinsics of the state enter the measurement and Phi
+            orcvio_msckf_imu_intrinsics intr;
+            std::memcpy(intr.x, ss.imu_intrinsics, sizeof(intr.x));
+            out.status = orcvio_msckf_cov_propagate_imu_calib(h_, &cfg, &intr, &st, prev, samples.data(), (int32_t)imu_msg_buffer.size(), time_bound, &info, nullptr, nullptr);
+        } else {
+            out.status = orcvio_msckf_cov_propagate_imu(h_, &cfg, &st, prev, samples.data(), (int32_t)imu_msg_buffer.size(), time_bound, &info, nullptr, nullptr);
+        }
         out.n_used = info.n_used; out.n_propagated = info.n_propagated; out.applied = info.applied != 0; out.dt = info.dt;
         for (int k = 0; k < 3; ++k) out.meanSForce[k] = info.mean_sforce[k];
         if (out.status != ORCVIO_OK && out.status != ORCVIO_ERR_NOT_SPD) return out;   // (refused before anything was done: nothing changes)

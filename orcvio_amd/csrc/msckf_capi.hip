@@ -189,6 +189,8 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     int* d_covmap = nullptr;
     double* d_imu = nullptr;            // orcvio_msckf_cov_propagate_imu: the per-sample records [128][IMU_REC], then the status word of k_imu_phi_q
     std::vector<double> imu_recs;       // ... and their host copy, sized at create: the host half writes them, aux_copies stages them
+    double* d_imu46 = nullptr;          // orcvio_msckf_cov_propagate_imu_calib: the records at leg_dim 46 [128][IMU_REC46] (the status word is d_imu's)
+    std::vector<double> imu_recs46;     // ... and their host copy
     // orcvio_msckf_io_propagate_imu: the next frame call on the handle enqueues k_imu_phi_q in front of its head launch (one-shot; the
     // frame call consumes it).  The records wait in imu_recs.
     bool imu_armed = false;
@@ -413,6 +415,7 @@ const char* orcvio_msckf_last_error(void) { return g_last_error.c_str(); }
 #include "capi_cov.inc"   // per-kernel profile, the device-resident covariance and its square-root factor
 #include "capi_object_mapper.inc"   // the object mapper: the start and the Levenberg-Marquardt refinement of object tracks, with keypoints and bbox-only
 #include "capi_imu.inc"   // IMU propagation from raw samples: the host half (host/imu_model.hpp), k_imu_phi_q, the propagation behind it
+#include "capi_imu_calib.inc"   // ... at leg_dim 46 (IMU intrinsics in the state): the imu_*46 host half, k_imu_phi_q46
 #include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: the 9-row update, the factor kept, the one-call stationary frame
 #include "capi_zupt_check.inc"   // zero-velocity detection from IMU samples: k_zupt_check stand-alone, behind the IMU propagation, inside the stationary frame
 #include "capi_frame.inc"   // one frame in one call: feature update + object update, the objects' compression beside the features' solve
