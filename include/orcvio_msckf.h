@@ -1022,9 +1022,9 @@ int32_t orcvio_msckf_triangulate_uploaded(orcvio_msckf_handle* h, const orcvio_t
  * p_w echoed, NaN in inv_param and cost.
  * ORCVIO_ERR_INVALID, nothing armed and *out untouched: no open arena, a pending orcvio_msckf_io_submit, a mode outside
  * 0..2, a NULL or non-finite config (or negative iteration counts), an object update in the arena, a communicator on
- * the handle.  The prune update of the frame calls still takes its positions from the caller
+ * the handle.  The prune update of the frame calls is armed by orcvio_msckf_io_triangulate_prune below
  * (initializePosition_AssignAnchor, :2782-2791, uses observations the prune tracks do not list). */
-enum { ORCVIO_TRI_KEEP = 0, ORCVIO_TRI_ALL = 1, ORCVIO_TRI_ALL_BUT_LAST = 2 };
+enum { ORCVIO_TRI_KEEP = 0, ORCVIO_TRI_ALL = 1, ORCVIO_TRI_ALL_BUT_LAST = 2, ORCVIO_TRI_ALL_MOTION_BUT_LAST = 3 };
 typedef struct orcvio_msckf_io_tri {
     const int32_t* valid;     /* [F] 1: the track has a position (given or triangulated) and took part in the update */
     const int32_t* flags;     /* [F] ORCVIO_TRI_NO_MOTION / _NEG_DEPTH / _BIG_PROJ bits                              */
@@ -1034,6 +1034,35 @@ typedef struct orcvio_msckf_io_tri {
 } orcvio_msckf_io_tri;
 int32_t orcvio_msckf_io_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg,
                                     const int32_t* mode /* [F] or NULL */, orcvio_msckf_io_tri* out);
+
+/* The same for the SECOND (prune) update of orcvio_msckf_io_step_frame / _io_step_frame_ex: what pruneImuStateBuffer does to a tracked
+ * feature that is not initialised yet (src/orcvio.cpp:2776-2793) -- checkMotion(imu_states_augment, if_tracked), then
+ * initializePosition_AssignAnchor over EVERY observation in the window, on the poses as the frame's first update has left them
+ * (prune_apply_dx: incremented on the device by the first update's dx).  Call it between orcvio_msckf_io_begin and the frame call; it
+ * holds for ONE frame, a new orcvio_msckf_io_begin drops it.  The launch goes behind the pose step and the pull of the second
+ * update's tracks, in front of the first kernel of the prune update that reads a position.
+ *   tri_tracks  track j of step->prune_tracks gets track j of tri_tracks: ALL its observations in the window (ascending clone,
+ *               window indices, obs_z), the current image's included; p_w and obs_zvel are not read.  The list is COPIED into pinned
+ *               staging of the handle by this call: the caller's memory need not outlive it.
+ *   mode[j]     as above, and ORCVIO_TRI_ALL_MOTION_BUT_LAST (this call only): every listed observation in the triangulation, the
+ *               motion check on the first and the SECOND-TO-LAST (feature.hpp:358-359, :451-500); of two listed observations the
+ *               second-to-last is the first: no motion, ORCVIO_TRI_NO_MOTION, as in the reference.  mode == NULL: every track that
+ *               mode.  ORCVIO_TRI_KEEP takes prune_tracks->p_w[j] (a feature that is initialised, :2782); the p_w of every other
+ *               track is never read and may be NaN.
+ * out: a SECOND pinned block of the handle (the first update's own arming keeps its block: both armings in one frame are allowed, and so
+ * is this one beside orcvio_msckf_io_propagate_imu), filled when the frame's one wait returns and whatever becomes of the update (the
+ * reference initialises the feature before it gates it).  inv_param is in the LAST listed camera's frame: id_anchor, invParam, invDepth
+ * and obs_anchor follow from it.  A failing track takes no part in the prune update (prune_accept = 0, prune_gamma = NaN, no rows);
+ * without a single valid track the prune update is refused on the device -- prune_stats[3] = 0, status_prune = ORCVIO_OK, P and its
+ * factor bit for bit as the first update left them (used_IDs.size() != 0, :2804).
+ * ORCVIO_ERR_INVALID, nothing armed and *out untouched: no open arena, a pending orcvio_msckf_io_submit, a NULL or non-finite config, a
+ * mode outside 0..3, an index outside the window, clones not ascending within a track, a communicator on the handle.  A track longer
+ * than ORCVIO_MAX_TRACK: ORCVIO_ERR_TRACK_TOO_LONG; more tracks or observations than the handle holds: ORCVIO_ERR_CAPACITY.
+ * In the frame call (ORCVIO_ERR_INVALID, nothing done, the arming stands): armed but prune_tracks == NULL, tri_tracks->n_features !=
+ * prune_tracks->n_features, a prune observation whose clone does not occur in its track's list. */
+int32_t orcvio_msckf_io_triangulate_prune(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg,
+                                          const orcvio_msckf_tracks* tri_tracks, const int32_t* mode /* [F2] or NULL */,
+                                          orcvio_msckf_io_tri* out);
 
 /* ---- Device-resident covariance ------------------------------------------
  * The three places besides the update where the reference touches state_cov, on a copy of P that stays in HBM, so that

@@ -44,7 +44,7 @@ EXPORTS = [
     'orcvio_msckf_comm_unique_id', 'orcvio_msckf_comm_init', 'orcvio_msckf_comm_destroy', 'orcvio_msckf_comm_info',
     'orcvio_msckf_run_update_sharded', 'orcvio_msckf_update_features_sharded', 'orcvio_msckf_update_object_tracks_sharded',
     'orcvio_msckf_comm_barrier', 'orcvio_msckf_comm_allreduce_max', 'orcvio_msckf_io_begin', 'orcvio_msckf_io_update',
-    'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect', 'orcvio_msckf_io_triangulate',
+    'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect', 'orcvio_msckf_io_triangulate', 'orcvio_msckf_io_triangulate_prune',
     'orcvio_msckf_objects_refined', 'orcvio_msckf_counters', 'orcvio_msckf_comm_details', 'orcvio_msckf_profile_sharded',
     'orcvio_msckf_io_step_frame', 'orcvio_msckf_io_step_frame_ex', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
     'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame', 'orcvio_msckf_cov_propagate_imu', 'orcvio_msckf_io_propagate_imu',
@@ -324,6 +324,7 @@ def _bind(lib):
     lib.orcvio_msckf_io_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip]
     lib.orcvio_msckf_io_submit.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.orcvio_msckf_io_triangulate.argtypes = [C.c_void_p, C.POINTER(TriangulationConfig), _ip, C.POINTER(MsckfIoTri)]
+    lib.orcvio_msckf_io_triangulate_prune.argtypes = [C.c_void_p, C.POINTER(TriangulationConfig), C.POINTER(MsckfTracks), _ip, C.POINTER(MsckfIoTri)]
     lib.orcvio_msckf_io_collect.argtypes = [C.c_void_p, _ip]
     lib.orcvio_msckf_io_step_frame.argtypes = [C.c_void_p, C.POINTER(FrameStep), C.POINTER(FrameResult)]
     lib.orcvio_msckf_io_step_frame_ex.argtypes = [C.c_void_p, C.POINTER(FrameStep), C.POINTER(FrameEvents), C.POINTER(FrameResultEx)]
@@ -800,6 +801,26 @@ class MsckfUpdater:
         out = MsckfIoTri()
         self._chk(self.lib.orcvio_msckf_io_triangulate(self.h, None if c is None else C.byref(c), _i(md), C.byref(out)), 'orcvio_msckf_io_triangulate')
         F = self.F
+        view = lambda ptr, shape: np.ctypeslib.as_array(ptr, shape=shape)
+        return dict(valid=view(out.valid, (max(F, 1),))[:F], flags=view(out.flags, (max(F, 1),))[:F], p_w=view(out.p_w, (max(F, 1), 3))[:F],
+                    solution=view(out.inv_param, (max(F, 1), 3))[:F], cost=view(out.cost, (max(F, 1),))[:F])
+
+    def io_triangulate_prune(self, tri_win, cfg=None, mode=None):
+        """orcvio_msckf_io_triangulate_prune: arms the SECOND (prune) update of the next io_step_frame / io_step_frame_ex on the open
+        arena.  tri_win: a synth.Window (or anything with F, obs_ptr, obs_clone, obs_z) listing EVERY observation of the prune tracks in
+        the window, track j for track j of the prune set; tri_win=False passes NULL.  mode: None (every track TRI_ALL_MOTION_BUT_LAST) or
+        [F2].  Returns numpy VIEWS of the handle's second pinned block (valid, flags, p_w, solution, cost), filled when the frame returns."""
+        c = None if cfg is False else self._tri_config(cfg)
+        md = None if mode is None else np.ascontiguousarray(mode, dtype=np.int32)
+        out = MsckfIoTri()
+        F, tr = 0, None
+        if tri_win is not False:
+            F = int(tri_win.F)
+            arrs = [np.ascontiguousarray(tri_win.obs_ptr, dtype=np.int32), np.ascontiguousarray(tri_win.obs_clone, dtype=np.int32),
+                    np.ascontiguousarray(tri_win.obs_z, dtype=np.float64)]
+            tr = MsckfTracks(F, None, _i(arrs[0]), _i(arrs[1]), _d(arrs[2]), None)
+        self._chk(self.lib.orcvio_msckf_io_triangulate_prune(self.h, None if c is None else C.byref(c), None if tr is None else C.byref(tr), _i(md),
+                                                             C.byref(out)), 'orcvio_msckf_io_triangulate_prune')
         view = lambda ptr, shape: np.ctypeslib.as_array(ptr, shape=shape)
         return dict(valid=view(out.valid, (max(F, 1),))[:F], flags=view(out.flags, (max(F, 1),))[:F], p_w=view(out.p_w, (max(F, 1), 3))[:F],
                     solution=view(out.inv_param, (max(F, 1), 3))[:F], cost=view(out.cost, (max(F, 1),))[:F])
@@ -1359,7 +1380,8 @@ class MsckfUpdater:
         return P
 
     def io_step_frame_ex(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
-                         n_feature_states=0, lost=(), changes=(), R_b2c=None, t_c_b=None, literal_3d=0, raise_on_refusal=True, triangulate=None):
+                         n_feature_states=0, lost=(), changes=(), R_b2c=None, t_c_b=None, literal_3d=0, raise_on_refusal=True, triangulate=None,
+                         triangulate_prune=None):
         """orcvio_msckf_io_step_frame_ex: io_step_frame plus the frame's feature events.  `win` and set_extra_states are those AFTER the
         removals; lost: slots in feature_states before the call (ascending), n_feature_states their count before the removals;
         changes: objects with slot (after the removals), old, new, p_w, p_fej; R_b2c / t_c_b: the IMU's current extrinsics.
@@ -1377,21 +1399,27 @@ class MsckfUpdater:
         ev = FrameEvents(int(idp_dim), int(literal_3d), int(n_feature_states), _i(ls) if len(ls) else None, len(ls), arr if k else None, k,
                          _d(Rb), _d(tb))
         return self.io_step_frame(win, Phi, Q, augment, slam, idp_dim, prune, prune_apply_dx, remove, raise_on_refusal, _events=(ev, k, (ls, arr, Rb, tb)),
-                                  triangulate=triangulate)
+                                  triangulate=triangulate, triangulate_prune=triangulate_prune)
 
     def io_step_frame(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
-                      raise_on_refusal=True, _events=None, triangulate=None):
+                      raise_on_refusal=True, _events=None, triangulate=None, triangulate_prune=None):
         """orcvio_msckf_io_step_frame: ONE filter frame on the resident covariance -- propagation, augmentation, the update on `win`'s
         tracks (+ the in-state features `slam`), the prune update on `prune`'s tracks (a synth.Window sharing win's poses), the
         marginalisation of `remove`.  Returns dict(dx, gamma, accept, stats, prune_dx, prune_gamma, prune_accept, prune_stats, n_after,
         status_first, status_prune, repaired) with copies of the results.  triangulate: None, True or dict(cfg=, mode=) -- the first
-        update triangulates its tracks on the device (io_triangulate); the dict then has tri = copies of valid, flags, p_w, solution, cost."""
+        update triangulates its tracks on the device (io_triangulate); the dict then has tri = copies of valid, flags, p_w, solution, cost.
+        triangulate_prune: None, or a pair (window listing EVERY observation of the prune tracks, modes or None) [a third entry: the
+        config] -- the prune update triangulates its tracks on the device between the two updates (io_triangulate_prune); the dict then
+        has prune_tri with the keys of tri."""
         io = self.io_begin(win.flags, win.N, win.F, int(win.obs_ptr[-1]), with_P=2)
         self.io_fill(io, win, with_P=False)
         tri = None
         if triangulate:
             targ = triangulate if isinstance(triangulate, dict) else {}
             tri = self.io_triangulate(targ.get('cfg'), targ.get('mode'))
+        tri2 = None
+        if triangulate_prune is not None:
+            tri2 = self.io_triangulate_prune(triangulate_prune[0], triangulate_prune[2] if len(triangulate_prune) > 2 else None, triangulate_prune[1])
         keep = []
         st = FrameStep()
         st.leg_dim = int(win.flags.leg_dim)
@@ -1440,6 +1468,8 @@ class MsckfUpdater:
                          status_changes=int(rex.status_changes))
         if tri is not None:
             extra['tri'] = {k: v.copy() for k, v in tri.items()}
+        if tri2 is not None:
+            extra['prune_tri'] = {k: v.copy() for k, v in tri2.items()}
         return dict(**extra, rc=rc, dx=arr(res.dx, n, np.float64), gamma=arr(res.gamma, win.F, np.float64), accept=arr(res.accept, win.F, np.int32),
                     stats=np.array(res.stats[:], dtype=np.int32), prune_dx=arr(res.prune_dx, n, np.float64),
                     prune_gamma=arr(res.prune_gamma, F2, np.float64), prune_accept=arr(res.prune_accept, F2, np.int32),

@@ -150,7 +150,7 @@ int32_t orcvio_msckf_download(orcvio_msckf_handle* h, orcvio_msckf_result* res) 
 // memory, [the commit of P+ and its square-root factor], then the flag).  No copy-engine transfer, no stream
 // synchronisation: the calling thread spins on the flag.
 static int launch_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg, bool have_init, bool mark_skip, hipStream_t s,
-                              bool io, bool with_mode);   // (capi_state.inc)
+                              bool io, bool with_mode, bool prune, int* raise);   // (capi_state.inc)
 // An update armed by orcvio_msckf_io_triangulate: from here on it runs as behind orcvio_msckf_triangulate_uploaded (d_skip is read by
 // every form of the front end).  Called behind upload_finalize, which resets both words; the arming is consumed.
 static inline void tri_consume(orcvio_msckf_handle* h, UpdateCall& c) {
@@ -162,6 +162,15 @@ static inline void tri_consume(orcvio_msckf_handle* h, UpdateCall& c) {
     // refuses the frame's second (info_also: P and its factor stay, bit for bit) -- and is no error: stats[3] = 0
     h->tri_refuse_empty = h->F > 0 && h->ekf_F == 0 && h->dense_rows == 0 && h->new_F == 0 && !c.info_also;
     if (h->tri_refuse_empty) c.info_also = h->d_tri_words;
+}
+// The frame's second update armed by orcvio_msckf_io_triangulate_prune (behind upload_finalize on the swapped-in second arena; the frame
+// call has taken the arming).  The prune update has nothing but its tracks, so it always refuses itself without a valid one -- and its
+// commit already reads the frame's kept status words (info_also): the launch RAISES word [2] of those instead of taking info_also over,
+// so that both refusals reach the commit (io_enqueue).  The repair path keeps no words: it reads the launch's own block (io_run_forked).
+static inline void tri_consume_prune(orcvio_msckf_handle* h, UpdateCall& c) {
+    c.tri = true; c.tri_prune = true;
+    h->skip_active = true; h->tri_live = true; h->tri_live_prune = true;
+    h->tri_refuse_empty = h->F > 0;
 }
 static unsigned long long io_signature(const orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool commit, const UpdateCall& c, bool finpub = false) {
     unsigned long long sig = launch_signature(h, s, h->h_stage_dev, (long)(0x100 | (want_P ? 1 : 0) | (commit ? 2 : 0) | (finpub ? 4 : 0)), c);
@@ -176,6 +185,7 @@ static unsigned long long io_signature(const orcvio_msckf_handle* h, hipStream_t
         mix((unsigned long long)t.outer_loop_max_iteration); mix((unsigned long long)t.inner_loop_max_iteration);
         mix(h->tri_with_mode); mix((unsigned long long)(size_t)h->h_tri_dev); mix((unsigned long long)(size_t)c.info_also);
     }
+    mix(c.tri_prune);
     return sig;
 }
 
@@ -202,7 +212,9 @@ static int io_enqueue(orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool c
     // (the repeat of an armed update -- tri_live without c.tri -- pulls no more either: the positions in HBM are the device's own)
     if (!c.already_ingested) rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, h->io_poses);
     // the armed update's triangulation: ONE launch behind the pull of the arena, in front of the first kernel that reads p_w or d_skip
-    if (rc == ORCVIO_OK && c.tri) rc = launch_triangulate(h, &h->tri_cfg, false, true, s, true, h->tri_with_mode);
+    if (rc == ORCVIO_OK && c.tri && !c.tri_prune) rc = launch_triangulate(h, &h->tri_cfg, false, true, s, true, h->tri_with_mode, false, nullptr);
+    // ... the prune update's, out of its own list: behind the pose step and the pull, with the frame's kept status words to raise
+    if (rc == ORCVIO_OK && c.tri_prune) rc = launch_triangulate(h, &h->tri2_cfg, false, true, s, true, true, true, c.retry_forked ? nullptr : h->d_step_words + 2);
     if (rc == ORCVIO_OK) rc = enqueue_update(h, s, c);
     if (rc != ORCVIO_OK || c.fin_pub) return rc;
     // ONE launch behind the update: the results to host-coherent memory, the commit (refused on the device if the update is),
@@ -321,7 +333,7 @@ static int io_run(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* sta
 static int io_run_forked(orcvio_msckf_handle* h, int32_t* stats) {
     UpdateCall c;
     c.retry_forked = true;
-    if (h->tri_live && h->tri_refuse_empty) c.info_also = h->d_tri_words;   // (the word of the attempt that triangulated stands)
+    if (h->tri_live && h->tri_refuse_empty) c.info_also = h->tri_live_prune ? h->d_tri2_words : h->d_tri_words;   // (the word of the attempt that triangulated stands)
     return io_run(h, false, true, stats, c);
 }
 static int io_finish(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats) {

@@ -11,11 +11,24 @@ void orcvio_msckf_triangulation_config_default(orcvio_triangulation_config* c) {
 
 // io: the launch inside an armed in-place update (orcvio_msckf_io_triangulate) -- the modes out of the handle's pinned block (with_mode),
 // the results published into it
+// prune: the launch of the frame's second update (orcvio_msckf_io_triangulate_prune) -- the CSR is the staged list in HBM, the modes and
+// the results the second block's, p_w / d_skip the (swapped-in) second arena's; raise: word [2] of the kept status words
 static int launch_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg, bool have_init, bool mark_skip, hipStream_t s,
-                              bool io, bool with_mode) {
+                              bool io, bool with_mode, bool prune, int* raise) {
     if (h->F == 0) return ORCVIO_OK;
     TriArgs a{};
-    if (io) {
+    if (prune) {
+        const TriBlock b = tri_block_layout(h->maxF);
+        const TriList l = tri_list_layout(h->tri2_F, h->tri2_nobs);
+        char* d = h->h_tri2_dev;
+        a.mode = reinterpret_cast<const int*>(d + b.mode);
+        a.pub_valid = reinterpret_cast<int*>(d + b.valid); a.pub_flags = reinterpret_cast<int*>(d + b.flags);
+        a.pub_cost = reinterpret_cast<double*>(d + b.cost); a.pub_pw = reinterpret_cast<double*>(d + b.p_w);
+        a.pub_sol = reinterpret_cast<double*>(d + b.inv_param);
+        a.words = h->d_tri2_words; a.raise = raise;
+        a.obs_ptr = reinterpret_cast<const int*>(h->d_tri2_list + l.obs_ptr); a.obs_clone = reinterpret_cast<const int*>(h->d_tri2_list + l.obs_clone);
+        a.obs_z = reinterpret_cast<const double*>(h->d_tri2_list + l.obs_z);
+    } else if (io) {
         const TriBlock b = tri_block_layout(h->maxF);
         char* d = h->h_tri_dev;
         a.mode = with_mode ? reinterpret_cast<const int*>(d + b.mode) : nullptr;
@@ -24,7 +37,8 @@ static int launch_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation
         a.pub_sol = reinterpret_cast<double*>(d + b.inv_param);
         a.words = h->d_tri_words;
     }
-    a.poses = h->d_poses; a.obs_ptr = h->d_obs_ptr; a.obs_clone = h->d_obs_clone; a.obs_z = h->d_obs_z;
+    a.poses = h->d_poses;
+    if (!prune) { a.obs_ptr = h->d_obs_ptr; a.obs_clone = h->d_obs_clone; a.obs_z = h->d_obs_z; }
     a.is_init = have_init ? h->d_tri_init : nullptr;
     a.p_w = h->d_pw; a.valid = h->d_tri_valid; a.flags = h->d_tri_flags; a.solution = h->d_tri_sol; a.cost = h->d_tri_cost;
     a.skip = mark_skip ? h->d_skip : nullptr;
@@ -48,7 +62,7 @@ int32_t orcvio_msckf_triangulate_uploaded(orcvio_msckf_handle* h, const orcvio_t
         const AuxCopy cp[] = {{h->d_tri_init, is_initialized, sizeof(int) * (size_t)h->F}};   // (the caller's memory: through the bounce buffer)
         { const int rc = aux_copies(h, s, cp, 1); if (rc != ORCVIO_OK) return rc; }
     }
-    int rc = launch_triangulate(h, cfg, is_initialized != nullptr, true, s, false, false);
+    int rc = launch_triangulate(h, cfg, is_initialized != nullptr, true, s, false, false, false, nullptr);
     if (rc != ORCVIO_OK) return rc;
     h->skip_active = true;
     h->pw_missing = false;
@@ -89,6 +103,45 @@ int32_t orcvio_msckf_io_triangulate(orcvio_msckf_handle* h, const orcvio_triangu
     return ORCVIO_OK;
 }
 
+// Arms the SECOND update of the next frame call (capi_step.inc): nothing is enqueued here.  The list and the modes are copied into the
+// handle's second pinned block (tri_prune_arm_stage), the config is kept by value.
+int32_t orcvio_msckf_io_triangulate_prune(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg, const orcvio_msckf_tracks* tri_tracks,
+                                          const int32_t* mode, orcvio_msckf_io_tri* out) {
+    const char* who = "orcvio_msckf_io_triangulate_prune: ";
+    if (!h || !out) { g_last_error = std::string(who) + "null argument"; return ORCVIO_ERR_INVALID; }
+    if (!h->io_open) { g_last_error = std::string(who) + "call orcvio_msckf_io_begin first"; return ORCVIO_ERR_INVALID; }
+    if (h->io_submitted) { g_last_error = std::string(who) + "an update submitted with orcvio_msckf_io_submit has not been collected"; return ORCVIO_ERR_INVALID; }
+    if (h->objects_mode) { g_last_error = std::string(who) + "the arena holds an object update"; return ORCVIO_ERR_INVALID; }
+    if (h->comm || h->ipc) { g_last_error = std::string(who) + "not with a communicator on the handle"; return ORCVIO_ERR_INVALID; }
+    const TriPruneBlock b = tri_prune_layout(h->maxF, h->maxObs);
+    if (!h->h_tri2) {
+        if (!tri_config_ok(cfg)) { g_last_error = std::string(who) + "a NULL or non-finite config (iteration counts must not be negative)"; return ORCVIO_ERR_INVALID; }
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipMalloc(&h->d_tri2_list, b.bytes - b.list));
+        HIPCHK(hipMemset(h->d_tri2_list, 0, b.bytes - b.list));
+        HIPCHK(hipMalloc(&h->d_tri2_words, 64));
+        HIPCHK(hipMemset(h->d_tri2_words, 0, 64));
+        HIPCHK(hipMalloc(&h->d_skip2, sizeof(int) * (size_t)(h->maxF > 0 ? h->maxF : 1)));
+        HIPCHK(hipMemset(h->d_skip2, 0, sizeof(int) * (size_t)(h->maxF > 0 ? h->maxF : 1)));
+        HIPCHK(hipHostMalloc(&h->h_tri2, b.bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->h_tri2_dev), h->h_tri2, 0));
+        std::memset(h->h_tri2, 0, b.bytes);
+    }
+    // (every reader and writer of the block on the device belongs to a frame whose wait has returned)
+    const char* why = "";
+    const int rc = tri_prune_arm_stage(cfg, tri_tracks, mode, h->N, h->maxF, h->maxObs, h->h_tri2, &why);
+    if (rc != ORCVIO_OK) { g_last_error = std::string(who) + why; return rc; }
+    h->tri2_cfg = *cfg;
+    h->tri2_F = tri_tracks->n_features; h->tri2_nobs = tri_tracks->obs_ptr[tri_tracks->n_features];
+    h->tri2_armed = true;
+    out->valid = reinterpret_cast<const int32_t*>(h->h_tri2 + b.res.valid);
+    out->flags = reinterpret_cast<const int32_t*>(h->h_tri2 + b.res.flags);
+    out->cost = reinterpret_cast<const double*>(h->h_tri2 + b.res.cost);
+    out->p_w = reinterpret_cast<const double*>(h->h_tri2 + b.res.p_w);
+    out->inv_param = reinterpret_cast<const double*>(h->h_tri2 + b.res.inv_param);
+    return ORCVIO_OK;
+}
+
 int32_t orcvio_msckf_triangulate(orcvio_msckf_handle* h, const orcvio_triangulation_config* cfg, const orcvio_msckf_window* w,
                                  const orcvio_msckf_tracks* tr, const int32_t* is_initialized, orcvio_triangulation_result* res) {
     if (!h || !cfg || !w || !tr || !res || !w->R_b2w || !w->t_b_w || !w->R_b2c || !w->t_c_b || !tr->obs_ptr) {
@@ -115,7 +168,7 @@ int32_t orcvio_msckf_triangulate(orcvio_msckf_handle* h, const orcvio_triangulat
     hipStream_t s = h->stream;
     // this call owns the track buffers: whatever was uploaded for an update is gone
     h->uploaded = false; h->ran = false; h->skip_active = false; h->objects_mode = false; h->io_open = false;
-    h->tri_armed = false; h->tri_live = false; h->tri_refuse_empty = false;
+    h->tri_armed = false; h->tri2_armed = false; h->tri_live = false; h->tri_refuse_empty = false; h->tri_live_prune = false;
     h->N = N; h->F = F; h->nobs = nobs;
     HIPCHK(hipStreamSynchronize(s));
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }
@@ -139,7 +192,7 @@ int32_t orcvio_msckf_triangulate(orcvio_msckf_handle* h, const orcvio_triangulat
         const int rc = aux_copies(h, s, cp, (int)(sizeof(cp) / sizeof(cp[0])));
         if (rc != ORCVIO_OK) return rc;
     }
-    int rc = launch_triangulate(h, cfg, is_initialized != nullptr, false, s, false, false);
+    int rc = launch_triangulate(h, cfg, is_initialized != nullptr, false, s, false, false, false, nullptr);
     if (rc != ORCVIO_OK) return rc;
     if (F > 0) {
         // results: into ONE pinned block by asynchronous copies, one synchronisation, then into the caller's arrays

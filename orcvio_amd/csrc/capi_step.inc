@@ -26,6 +26,7 @@ static void step_arena_swap(orcvio_msckf_handle* h) {
     std::swap(h->d_in, h->d_in2);
     std::swap(h->h_stage, h->h_stage2);
     std::swap(h->h_stage_dev, h->h_stage2_dev);
+    if (h->d_skip2) std::swap(h->d_skip, h->d_skip2);   // (an armed first update's dropped tracks stay where its repeat looks for them)
     h->arena_swapped = !h->arena_swapped;
 }
 
@@ -127,7 +128,11 @@ struct StepSecond {   // what the second update of the frame needs besides the h
     int apply_dx;
     const StepEvents* ev;   // anchor changes between the pose step and the update (nullptr: none)
     const int* also = nullptr;   // the armed IMU launch's status block: its refusal goes into the kept status words (PoseStepArgs.also)
+    bool tri = false;            // armed by orcvio_msckf_io_triangulate_prune: k_triangulate on the staged list in front of the update
 };
+// the staged list of the armed prune update: where it stands in pinned memory, and its bytes
+static inline size_t tri2_list_bytes(const orcvio_msckf_handle* h) { return tri_list_layout(h->tri2_F, h->tri2_nobs).bytes; }
+static inline const char* tri2_list_src(const orcvio_msckf_handle* h) { return h->h_tri2_dev + tri_prune_layout(h->maxF, h->maxObs).list; }
 
 // the second update's inputs into the (swapped-in) second arena and its launches; `wait` = run it the safe way (separate launches, the
 // forked front end, the outcome checked and the commit made by the host) -- the repair path
@@ -157,6 +162,7 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
         HIPCHK(hipGetLastError());
         // everything the caller's tracks hold, behind the poses
         rc = launch_ingest(h, s, h->h_stage_dev + h->io_optr, h->d_in + h->io_optr, upload_bytes(h) - h->io_optr);
+        if (rc == ORCVIO_OK && b.tri) rc = launch_ingest(h, s, tri2_list_src(h), h->d_tri2_list, tri2_list_bytes(h));   // (the separate launches' form of the head's segment)
         if (rc != ORCVIO_OK) return rc;
     }
     if (rc == ORCVIO_OK) rc = upload_finalize(h, who);
@@ -169,6 +175,13 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
             HIPCHK(hipStreamSynchronize(s));
             if (*evt_status_host(h) != 0) { g_last_error = std::string(who) + ": a changed feature's position is not finite: no anchor change, no prune update"; return ORCVIO_ERR_NOT_SPD; }
         }
+        if (b.tri) {   // triangulated again: a lost FIRST update left the poses of the attempt without its dx (same poses, same bits otherwise)
+            UpdateCall ct;
+            ct.retry_forked = true;
+            tri_consume_prune(h, ct);
+            rc = launch_triangulate(h, &h->tri2_cfg, false, true, s, true, true, true, nullptr);
+            if (rc != ORCVIO_OK) return rc;
+        }
         return io_run_forked(h, stats);
     }
     h->last_stream = s;
@@ -179,6 +192,7 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
         fa.nseg = 2;
         fa.src[0] = h->h_stage_dev; fa.dst[0] = h->d_in; fa.bytes[0] = (unsigned)h->io_poses;
         fa.src[1] = h->h_stage_dev + h->io_optr; fa.dst[1] = h->d_in + h->io_optr; fa.bytes[1] = (unsigned)(upload_bytes(h) - h->io_optr);
+        if (b.tri) { fa.nseg = 3; fa.src[2] = tri2_list_src(h); fa.dst[2] = h->d_tri2_list; fa.bytes[2] = (unsigned)tri2_list_bytes(h); }   // (the armed prune update's list rides along)
         rc = launch_frame_head(h, s, fa);
         if (rc != ORCVIO_OK) return rc;
     }
@@ -189,6 +203,7 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
     UpdateCall c;
     c.already_ingested = h->step_fused;   // (k_frame_head has pulled the whole arena)
     c.info_also = h->d_step_words;        // (a refused first update refuses this update's commit as well)
+    if (b.tri) tri_consume_prune(h, c);   // (k_triangulate behind the pull and the anchor change, in front of the tracks' launch: io_enqueue)
     rc = io_enqueue(h, s, false, true, c, true);
     h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h, false);
     if (rc != ORCVIO_OK) return rc;
@@ -300,6 +315,15 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             g_last_error = std::string(who) + ": remove_clones must be ascending window indices"; return ORCVIO_ERR_INVALID;
         }
     if (st->prune_tracks) { const int rv = step_validate_tracks(h, st->prune_tracks, N, fl.estimate_td != 0, who); if (rv != ORCVIO_OK) return rv; }
+    // armed by orcvio_msckf_io_triangulate_prune: the second update's positions are made on the device between the two updates
+    const bool tri2 = h->tri2_armed;
+    if (tri2) {
+        auto bad = [&](const char* what) { g_last_error = std::string(who) + ": armed by orcvio_msckf_io_triangulate_prune: " + what; return ORCVIO_ERR_INVALID; };
+        if (!st->prune_tracks) return bad("the frame has no prune_tracks");
+        if (st->prune_tracks->n_features != h->tri2_F) return bad("tri_tracks and prune_tracks differ in their number of tracks");
+        if (!tri_prune_covers(h->h_tri2, h->maxF, h->maxObs, h->tri2_F, st->prune_tracks->obs_ptr, st->prune_tracks->obs_clone))
+            return bad("a prune observation's clone does not occur in its track's list");
+    }
     HIPCHK(hipSetDevice(h->device));
     StepEvents evs;
     { const int rv = step_validate_events(h, st, ev, h->F > 0 || (st->slam_features && st->slam_features->n_features > 0), evs, who); if (rv != ORCVIO_OK) return rv; }
@@ -363,6 +387,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     h->pw_missing = false;
     tmark(0);
     if (armed) { rc = imu_consume(h, s); if (rc != ORCVIO_OK) return rc; }   // nothing can refuse the frame any more: the arming is taken
+    h->tri2_armed = false;   // (... and so is the prune update's)
     const int* imu_also = armed ? imu_status(h) : nullptr;
     if (fused) {
         fa.nseg = 1;
@@ -450,7 +475,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     const char* soB = nullptr;
     unsigned long long pubB = 0;
     if (evs.k > 0) { evs.fs.slam = h->d_slam; evs.fs.cap = h->ekf_cap; }   // (the records' buffers stand: slam_prepare above)
-    StepSecond sb{st->prune_tracks, posesA, dxA, infoA, first ? st->prune_apply_dx : 0, evs.k > 0 ? &evs : nullptr, imu_also};
+    StepSecond sb{st->prune_tracks, posesA, dxA, infoA, first ? st->prune_apply_dx : 0, evs.k > 0 ? &evs : nullptr, imu_also, tri2};
     int rcB = ORCVIO_OK;
     unsigned long long pubE = 0;
     if (!second && evs.k > 0) {   // no update behind the changes: the anchor change is what the call waits for

@@ -26,6 +26,7 @@ static int upload_begin(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags,
     if (!with_P && h->res_n != n && !(pending_aug && n <= h->res_n + 6)) { g_last_error = std::string(who) + ": P == NULL but the resident covariance does not match the window"; return ORCVIO_ERR_INVALID; }
     h->uploaded = false; h->ran = false; h->io_open = false;
     h->tri_armed = false;          // (an arming of orcvio_msckf_io_triangulate belongs to the arena it was made on)
+    h->tri2_armed = false;         // (... and so does one of orcvio_msckf_io_triangulate_prune: the frame call has taken it by now)
     h->last_update_thin = false;   // (set again by the update itself if it takes the direct form of a thin stack)
     h->flags = *flags;
     h->N = N; h->F = F; h->nobs = nobs;
@@ -170,7 +171,7 @@ static int upload_finalize(orcvio_msckf_handle* h, const char* who) {
     h->chunks = t3rows > 0 ? (t3rows + rpc - 1) / rpc : 1;
     h->uploaded = true;
     h->ran = false;
-    h->skip_active = false; h->tri_live = false; h->tri_refuse_empty = false;
+    h->skip_active = false; h->tri_live = false; h->tri_refuse_empty = false; h->tri_live_prune = false;
     h->objects_mode = false;   // (a staged object update may have left it set)
     return ORCVIO_OK;
 }

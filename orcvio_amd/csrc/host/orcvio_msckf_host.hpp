@@ -932,6 +932,122 @@ class MsckfBackend {
         return out;
     }
 
+    // ---- pruneImuStateBuffer's positions inside the one-call frame (orcvio_msckf_io_triangulate_prune) ------------------------------
+    // The features pruneImuStateBuffer uses when the clones rm_imu_state_ids leave (src/orcvio.cpp:2647-2793): tracked now (an
+    // observation of curr_id), not in the state, seen in at least two of the clones that leave -- in map_server order -- as the two
+    // lists of the armed frame: tri_* every observation in the window (what initializePosition_AssignAnchor triangulates from,
+    // feature.hpp:451-500), prune_* those of the clones that leave (the Jacobian rows, :2810-2845).  mode: ORCVIO_TRI_KEEP where
+    // is_initialized (its position stands, :2782), else ORCVIO_TRI_ALL_MOTION_BUT_LAST.  anchor: the last listed clone.
+    struct PruneTriLists {
+        std::vector<FeatureIDType> ids;
+        std::vector<int32_t> mode;
+        std::vector<StateIDType> anchor;
+        std::vector<int32_t> remove_idx;   // window indices of the clones that leave, ascending
+        std::vector<double> p_w, tri_z, prune_z, prune_zvel;
+        std::vector<int32_t> tri_ptr, tri_clone, prune_ptr, prune_clone;
+        orcvio_msckf_tracks tri_tracks() const { return {(int32_t)ids.size(), nullptr, tri_ptr.data(), tri_clone.data(), tri_z.data(), nullptr}; }
+        orcvio_msckf_tracks prune_tracks() const { return {(int32_t)ids.size(), p_w.data(), prune_ptr.data(), prune_clone.data(), prune_z.data(), prune_zvel.data()}; }
+    };
+    static PruneTriLists buildPruneTriLists(const StateServer& ss, const MapServer& map_server, const std::vector<StateIDType>& rm_imu_state_ids,
+                                            StateIDType curr_id) {
+        PruneTriLists l;
+        l.tri_ptr.assign(1, 0); l.prune_ptr.assign(1, 0);
+        std::map<StateIDType, int> index_of;
+        int N = 0;
+        for (const auto& kv : ss.imu_states_augment) index_of[kv.first] = N++;
+        for (StateIDType sid : rm_imu_state_ids)
+            if (index_of.count(sid)) l.remove_idx.push_back(index_of.at(sid));
+        std::sort(l.remove_idx.begin(), l.remove_idx.end());
+        for (const auto& item : map_server) {
+            const Feature& f = item.second;
+            int involved = 0;
+            for (StateIDType sid : rm_imu_state_ids) involved += f.observations.count(sid) ? 1 : 0;
+            if (f.in_state || involved < 2 || !f.observations.count(curr_id)) continue;
+            l.ids.push_back(f.id);
+            l.mode.push_back(f.is_initialized ? ORCVIO_TRI_KEEP : ORCVIO_TRI_ALL_MOTION_BUT_LAST);
+            l.p_w.insert(l.p_w.end(), f.position, f.position + 3);
+            StateIDType last = -1;
+            for (const auto& ob : f.observations) {
+                auto it = index_of.find(ob.first);
+                if (it == index_of.end()) continue;   // (a clone that left the window: feature.hpp:465-466)
+                l.tri_clone.push_back(it->second);
+                l.tri_z.push_back(ob.second.x); l.tri_z.push_back(ob.second.y);
+                last = ob.first;
+                if (std::find(rm_imu_state_ids.begin(), rm_imu_state_ids.end(), ob.first) == rm_imu_state_ids.end()) continue;
+                l.prune_clone.push_back(it->second);
+                l.prune_z.push_back(ob.second.x); l.prune_z.push_back(ob.second.y);
+                auto v = f.observations_vel.find(ob.first);
+                l.prune_zvel.push_back(v == f.observations_vel.end() ? 0.0 : v->second.x);
+                l.prune_zvel.push_back(v == f.observations_vel.end() ? 0.0 : v->second.y);
+            }
+            l.anchor.push_back(last);
+            l.tri_ptr.push_back((int32_t)l.tri_clone.size());
+            l.prune_ptr.push_back((int32_t)l.prune_clone.size());
+        }
+        return l;
+    }
+    // What initializePosition_AssignAnchor leaves in the Feature (feature.hpp:485-497), from the armed frame's second block; the
+    // features that failed are returned (the reference `continue`s past them: they stay in the map, uninitialised).
+    static std::vector<FeatureIDType> writeBackPruneTriangulation(MapServer& map_server, const PruneTriLists& l, const orcvio_msckf_io_tri& tri) {
+        std::vector<FeatureIDType> failed;
+        for (size_t k = 0; k < l.ids.size(); ++k) {
+            if (l.mode[k] == ORCVIO_TRI_KEEP) continue;
+            Feature& f = map_server.at(l.ids[k]);
+            f.failed_by_neg_dpth = (tri.flags[k] & ORCVIO_TRI_NEG_DEPTH) != 0;
+            f.failed_by_big_proj = (tri.flags[k] & ORCVIO_TRI_BIG_PROJ) != 0;
+            if (!tri.valid[k]) { failed.push_back(l.ids[k]); continue; }
+            if (!f.is_initialized) std::memcpy(f.position_FEJ, f.position, sizeof(f.position));
+            f.is_initialized = true;
+            std::memcpy(f.position, tri.p_w + 3 * k, sizeof(f.position));
+            std::memcpy(f.invParam, tri.inv_param + 3 * k, sizeof(f.invParam));
+            f.id_anchor = l.anchor[k];
+            f.invDepth = tri.inv_param[3 * k + 2];   // 1 / final_position(2) = rho
+            f.obs_anchor[0] = tri.inv_param[3 * k]; f.obs_anchor[1] = tri.inv_param[3 * k + 1]; f.obs_anchor[2] = 1.0;   // final_position(0..1) * invDepth = (alpha, beta)
+        }
+        return failed;
+    }
+    // The frame call site: removeLostFeatures' update on lost_ids at their positions, pruneImuStateBuffer's update on the features
+    // buildPruneTriLists selects -- their positions made on the device between the two updates, on the poses the first leaves
+    // (prune_apply_dx) -- and the marginalisation of rm_imu_state_ids, in ONE orcvio_msckf_io_step_frame on the resident covariance
+    // (covarianceToDevice first).  The containers are written back; the state is incremented by both updates' dx as the reference
+    // does.  lists / result: what was armed and what came back (pointers into the handle, valid until its next frame).
+    UpdateOutcome stepFramePruneArmed(StateServer& ss, MapServer& map_server, const std::vector<FeatureIDType>& lost_ids,
+                                      const std::vector<StateIDType>& rm_imu_state_ids, StateIDType curr_id, PruneTriLists* lists = nullptr,
+                                      orcvio_msckf_frame_result* result = nullptr, orcvio_msckf_io_tri* tri_out = nullptr) {
+        UpdateOutcome out;
+        if (!resident_covariance) { out.status = ORCVIO_ERR_INVALID; return out; }
+        const PruneTriLists l = buildPruneTriLists(ss, map_server, rm_imu_state_ids, curr_id);
+        orcvio_msckf_io io{};
+        orcvio_msckf_io_tri tri{};
+        int nn = 0;
+        out.status = fillArena(ss, map_server, lost_ids, {}, false, &io, &nn);
+        const orcvio_msckf_tracks tt = l.tri_tracks(), pt = l.prune_tracks();
+        if (out.status == ORCVIO_OK && !l.ids.empty()) out.status = orcvio_msckf_io_triangulate_prune(h_, &optimization_config, &tt, l.mode.data(), &tri);
+        if (out.status != ORCVIO_OK) return out;
+        orcvio_msckf_frame_step st{};
+        st.leg_dim = flags.leg_dim;
+        st.prune_tracks = l.ids.empty() ? nullptr : &pt;
+        st.prune_apply_dx = 1;
+        st.remove_clones = l.remove_idx.data(); st.n_remove = (int32_t)l.remove_idx.size();
+        orcvio_msckf_frame_result res{};
+        out.status = orcvio_msckf_io_step_frame(h_, &st, &res);
+        if (lists) *lists = l;
+        if (result) *result = res;
+        if (tri_out) *tri_out = tri;
+        if (out.status != ORCVIO_OK) return out;
+        if (!l.ids.empty()) writeBackPruneTriangulation(map_server, l, tri);
+        out.accepted.assign(res.accept, res.accept + lost_ids.size());
+        out.gamma.assign(res.gamma, res.gamma + lost_ids.size());
+        out.delta_x.assign(res.dx, res.dx + nn);
+        out.updated = res.stats[3] != 0 || res.prune_stats[3] != 0;
+        if (res.stats[3] != 0) out.state_incremented = incrementState_IMUCam(ss, out.delta_x);
+        if (res.prune_stats[3] != 0) {
+            const std::vector<double> dx2(res.prune_dx, res.prune_dx + nn);
+            out.state_incremented = incrementState_IMUCam(ss, dx2) || out.state_incremented;
+        }
+        return out;
+    }
+
     // ---- objects --------------------------------------------------------------------------------
     // OrcVIO::constructObjectResidualJacobians (src/orcvio.cpp:2017-2151) in compact form: returns false if
     // no frame of the object is in the window.  jacobian_wrt_sensor_state: rows x 6 row-major, ordered

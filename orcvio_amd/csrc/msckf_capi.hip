@@ -213,6 +213,16 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     bool tri_refuse_empty = false;      // the current armed update has nothing but its tracks: without a valid one it leaves P and its factor alone
     bool tri_live = false;              // the positions of the current upload were made on the device by an armed update: a repeat of that update
                                         // (a lost hand-off) keeps them and d_skip -- it pulls the derived index arrays only and does not triangulate again
+    // orcvio_msckf_io_triangulate_prune: the SECOND update of the next frame call triangulates its tracks, from an observation list of its
+    // own (one-shot: the frame consumes it, an orcvio_msckf_io_begin drops it); all of it on first use
+    char *h_tri2 = nullptr, *h_tri2_dev = nullptr;   // pinned second block: modes and results as h_tri, the staged list behind them (tri_prune_layout)
+    char* d_tri2_list = nullptr;        // the list in HBM (tri_list_layout of the armed counts), pulled by the second update's head
+    int* d_tri2_words = nullptr;        // [16] status block of that launch (TriArgs.words)
+    int* d_skip2 = nullptr;             // [maxF] the second arena's d_skip (swapped with it: step_arena_swap)
+    bool tri2_armed = false;
+    int tri2_F = 0, tri2_nobs = 0;      // tracks and observations of the staged list
+    orcvio_triangulation_config tri2_cfg{};
+    bool tri_live_prune = false;        // tri_live, and the launch was the prune update's: the repeat's refusal word is d_tri2_words
     int* d_flag = nullptr;              // step counter of that launch (inside the d_info allocation, own 128-byte line)
     // device buffers
     double *d_poses = nullptr, *d_pw = nullptr, *d_obs_z = nullptr, *d_obs_zvel = nullptr, *d_P = nullptr;
@@ -357,6 +367,7 @@ struct UpdateCall {
     bool ekf_side = false;              // the step call's first update: the in-state rows beside k_front, on the side stream
     bool already_ingested = false;      // k_frame_head has pulled the arena of this update (io_enqueue skips its ingest launch)
     bool tri = false;                   // armed by orcvio_msckf_io_triangulate: k_triangulate behind the pull of the arena (io_enqueue; h->tri_cfg, h->tri_with_mode)
+    bool tri_prune = false;             // ... by orcvio_msckf_io_triangulate_prune: the frame's second update (h->tri2_cfg, the staged list, the second block)
     unsigned* mark_M_word = nullptr;    // ST_FORM_M / ST_POTRF_M store mark_M_val there once M is formed, and put the pointer back to null: the caller
     unsigned mark_M_val = 0u;           //  sees from its record whether the mark went out
     const unsigned* join_wait = nullptr;   // the ST_FORM_U product polls this counter (the frame call's object half) ...

@@ -30,7 +30,9 @@ struct TriArgs {
     double* solution;         // [F][3] (alpha, beta, rho) in the last camera's frame
     double* cost;             // [F]
     int* skip;                // [F] or nullptr: 1 where the track must not enter the update
-    const int* mode;          // [F] or nullptr (every track 1): 0 keep p_w[j] as it is, 1 all listed observations, 2 all but the last
+    const int* mode;          // [F] or nullptr (every track 1): 0 keep p_w[j] as it is, 1 all listed observations, 2 all but the last,
+                              //  3 all listed observations with the motion check on the first and the SECOND-TO-LAST (pruneImuStateBuffer's
+                              //  checkMotion(.., if_tracked) in front of initializePosition_AssignAnchor, feature.hpp:358-359, :451-500)
     int* pub_valid;           // not nullptr: host-coherent copies of the five results ([F], [F], [F], [F][3], [F][3]), stored by the
     int* pub_flags;           //  lane that stores the results, with a system-scope fence behind them
     double* pub_cost;
@@ -39,6 +41,8 @@ struct TriArgs {
     int* words;               // not nullptr: [2] <- 1 when NO track of the launch is valid, else 0 (read as a status block by the update's
                               //  finish: an update without a single track leaves P and its factor alone, as removeLostFeatures returns
                               //  before any arithmetic, src/orcvio.cpp:2440-2446); [4] valid tracks, [5] arrivals: zero between launches
+    int* raise;               // not nullptr (with words): <- 1 when NO track of the launch is valid, left alone otherwise -- word [2] of a status
+                              //  block that holds another refusal already (the frame's kept status words, read by the prune update's commit)
     double translation_threshold, huber_epsilon, estimation_precision, initial_damping, cost_threshold, init_final_dist_threshold;
     int outer_max, inner_max;
     int F;
@@ -80,6 +84,7 @@ __device__ __forceinline__ void tri_arrive(const TriArgs& p, int valid) {
     if (old == p.F - 1) {
         const int nv = __hip_atomic_load(p.words + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         p.words[2] = nv == 0 ? 1 : 0;
+        if (nv == 0 && p.raise) *p.raise = 1;
         __hip_atomic_store(p.words + 4, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(p.words + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -139,15 +144,19 @@ __global__ __launch_bounds__(64) void k_triangulate(TriArgs p) {
     for (int a = 0; a < 3; ++a) tl[a] = __shfl(tc[a], M - 1);
     const double zl0 = __shfl(z[0], M - 1), zl1 = __shfl(z[1], M - 1);
 
-    // ---- checkMotion (feature.hpp:354-397): first and last listed observation ------------------------
+    // ---- checkMotion (feature.hpp:354-397): first and last listed observation; mode 3: first and second-to-last (of two listed
+    // observations that is the first itself: the translation is exactly zero, the track has no motion -- as the reference, :359)
     if (!init) {
+        double tm[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) tm[a] = __shfl(tc[a], M - (md == 3 ? 2 : 1));
         double mo = 0.0;
         if (t == 0) {
             const double nz = 1.0 / sqrt(z[0] * z[0] + z[1] * z[1] + 1.0);
             const double d0 = z[0] * nz, d1 = z[1] * nz, d2 = nz;
             double d[3], tr[3];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) { d[a] = R[3 * a] * d0 + R[3 * a + 1] * d1 + R[3 * a + 2] * d2; tr[a] = tl[a] - tc[a]; }
+            for (int a = 0; a < 3; ++a) { d[a] = R[3 * a] * d0 + R[3 * a + 1] * d1 + R[3 * a + 2] * d2; tr[a] = tm[a] - tc[a]; }
             const double par = tr[0] * d[0] + tr[1] * d[1] + tr[2] * d[2];
             const double o0 = tr[0] - par * d[0], o1 = tr[1] - par * d[1], o2 = tr[2] - par * d[2];
             mo = sqrt(o0 * o0 + o1 * o1 + o2 * o2);
