@@ -1064,6 +1064,52 @@ int32_t orcvio_msckf_io_triangulate_prune(orcvio_msckf_handle* h, const orcvio_t
                                           const orcvio_msckf_tracks* tri_tracks, const int32_t* mode /* [F2] or NULL */,
                                           orcvio_msckf_io_tri* out);
 
+/* The choice of the two clones that leave, CHECKED inside orcvio_msckf_io_step_frame / _io_step_frame_ex.  The reference chooses them
+ * (findRedundantImuStates, src/orcvio.cpp:2582-2626) in pruneImuStateBuffer, i.e. on position_cam / orientation_cam as
+ * removeLostFeatures' update has just rewritten them (incrementState_IMUCam, :4535-4565).  A one-call frame is issued before that
+ * update's dx exists, so its remove_clones -- and the prune_tracks that follow from them -- are a PREDICTION made on the poses from
+ * before the update; near rotation_threshold / translation_threshold the prediction can differ from the reference's choice.  This call
+ * arms the next frame call (between orcvio_msckf_io_begin and the frame call; it holds for ONE frame, a new orcvio_msckf_io_begin drops
+ * it; allowed beside orcvio_msckf_io_propagate_imu and beside both triangulation armings): one small launch between the frame's two
+ * updates evaluates the reference's loop on the poses the first update leaves and compares the result with remove_clones.
+ *   window of N clones, key = N-4.  Iteration 1 compares clone N-3 with the key; taken (angle < rotation_threshold && distance <
+ *   translation_threshold && tracking_ok): N-3 leaves, next N-2; not taken: the oldest clone leaves and the compared clone moves back by
+ *   two, to N-5 (:2615-2618, as written).  Iteration 2 likewise.  Results, ascending: {N-3, N-2}, {0, N-3}, {0, N-5}, {0, 1}.
+ *   distance = |position_cam(c) - position_cam(key)|; angle = the rotation angle of orientation_cam(c)^T orientation_cam(key) as Eigen
+ *   3.3's AngleAxisd(Matrix3d) gives it (quaternion of the matrix, 2 atan2(|vec|, |w|)).
+ *   dx applied (a committed first update, prune_apply_dx != 0, not discarded by discard_large_update): orientation_cam = R_b2w+
+ *   R_imu_cam0+^T, position_cam = t_b_w+ + R_b2w+ t_cam0_imu+, the body pose as the frame's pose step leaves it, the extrinsic the one
+ *   given HERE incremented by dx[15:21] (the IMU state's, not the clone's frozen one).  dx not applied (no first update, a refused one,
+ *   a discarded dx, prune_apply_dx = 0): the reference's containers are untouched -- cam_poses are read as they are.
+ * The choices AGREE: the frame is the unarmed frame bit for bit, except that its marginalisation is enqueued behind the frame's one wait
+ * (and not waited for).  They DIFFER: the frame's second half -- anchor changes, prune update, marginalisation -- is held back on the
+ * device: P and its factor stay bit for bit as the first update left them, status_prune = ORCVIO_OK, prune_stats[3] = 0,
+ * status_changes = ORCVIO_OK with no new parameters to read, n_after is the dimension BEFORE the marginalisation, the frame call
+ * returns ORCVIO_OK (a disagreement is not an error), and `chosen` names the clones to run that half again with (a frame call without
+ * propagation, augmentation and first update that carries prune_tracks, the events' changes and remove_clones).
+ * Divergence: N >= 6 is required.  At N = 5 clone N-5 IS the oldest and the reference's own loop can name clone 0 twice.
+ * ORCVIO_ERR_INVALID, nothing armed: no open arena, a pending orcvio_msckf_io_submit, a communicator on the handle, N < 6, a NULL
+ * cam_poses, a non-finite entry, a threshold <= 0.  In the armed frame call (ORCVIO_ERR_INVALID, nothing done, the arming stands):
+ * n_remove != 2, remove_clones not one of the four sets above, prune_tracks == NULL (the launch rides in front of the prune update). */
+typedef struct orcvio_msckf_clone_choice_config {
+    double rotation_threshold, translation_threshold;
+    int32_t tracking_ok;      /* tracking_rate > tracking_rate_threshold, evaluated by the caller                                    */
+    double R_imu_cam0[9];     /* the IMU state's extrinsic at the time of the call (row-major) ...                                  */
+    double t_cam0_imu[3];
+    const double* cam_poses;  /* [N][12] orientation_cam 9 (row-major) | position_cam 3, as the containers hold them before the
+                                 frame's first update; COPIED by this call                                                          */
+} orcvio_msckf_clone_choice_config;
+typedef struct orcvio_msckf_clone_choice {   /* pinned block of the handle, filled when the frame's wait returns                       */
+    int32_t evaluated;        /* 1: this frame's launch has stored the block                                                          */
+    int32_t agree;            /* chosen == the frame's remove_clones                                                                  */
+    int32_t chosen[2];        /* ascending window indices                                                                             */
+    int32_t compared[2];      /* the clone compared with the key in iteration 1, 2                                                    */
+    int32_t taken[2];         /* ... and whether it was taken                                                                         */
+    double angle[2], distance[2];
+} orcvio_msckf_clone_choice;
+int32_t orcvio_msckf_io_choose_clones(orcvio_msckf_handle* h, const orcvio_msckf_clone_choice_config* cfg,
+                                      const orcvio_msckf_clone_choice** out);
+
 /* ---- Device-resident covariance ------------------------------------------
  * The three places besides the update where the reference touches state_cov, on a copy of P that stays in HBM, so that
  * P does not cross PCIe every frame.  n = leg_dim + 6 * (clones in the window); no EKF-SLAM / nuisance states.

@@ -44,7 +44,7 @@ EXPORTS = [
     'orcvio_msckf_comm_unique_id', 'orcvio_msckf_comm_init', 'orcvio_msckf_comm_destroy', 'orcvio_msckf_comm_info',
     'orcvio_msckf_run_update_sharded', 'orcvio_msckf_update_features_sharded', 'orcvio_msckf_update_object_tracks_sharded',
     'orcvio_msckf_comm_barrier', 'orcvio_msckf_comm_allreduce_max', 'orcvio_msckf_io_begin', 'orcvio_msckf_io_update',
-    'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect', 'orcvio_msckf_io_triangulate', 'orcvio_msckf_io_triangulate_prune',
+    'orcvio_msckf_augment_state_ref_ldlt', 'orcvio_msckf_io_update_frame', 'orcvio_msckf_io_stage_object_tracks', 'orcvio_msckf_io_submit', 'orcvio_msckf_io_collect', 'orcvio_msckf_io_triangulate', 'orcvio_msckf_io_triangulate_prune', 'orcvio_msckf_io_choose_clones',
     'orcvio_msckf_objects_refined', 'orcvio_msckf_counters', 'orcvio_msckf_comm_details', 'orcvio_msckf_profile_sharded',
     'orcvio_msckf_io_step_frame', 'orcvio_msckf_io_step_frame_ex', 'orcvio_msckf_cov_remove_features', 'orcvio_msckf_cov_change_anchors',
     'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame', 'orcvio_msckf_cov_propagate_imu', 'orcvio_msckf_io_propagate_imu',
@@ -163,6 +163,18 @@ class MsckfIoTri(C.Structure):
 
 
 TRI_KEEP, TRI_ALL, TRI_ALL_BUT_LAST = 0, 1, 2
+
+
+class CloneChoiceConfig(C.Structure):
+    """orcvio_msckf_clone_choice_config (include/orcvio_msckf.h)."""
+    _fields_ = [('rotation_threshold', C.c_double), ('translation_threshold', C.c_double), ('tracking_ok', C.c_int32),
+                ('R_imu_cam0', C.c_double * 9), ('t_cam0_imu', C.c_double * 3), ('cam_poses', C.POINTER(C.c_double))]
+
+
+class CloneChoice(C.Structure):
+    """orcvio_msckf_clone_choice: the pinned result block of the handle."""
+    _fields_ = [('evaluated', C.c_int32), ('agree', C.c_int32), ('chosen', C.c_int32 * 2), ('compared', C.c_int32 * 2), ('taken', C.c_int32 * 2),
+                ('angle', C.c_double * 2), ('distance', C.c_double * 2)]
 
 
 class Zupt(C.Structure):
@@ -325,6 +337,7 @@ def _bind(lib):
     lib.orcvio_msckf_io_submit.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.orcvio_msckf_io_triangulate.argtypes = [C.c_void_p, C.POINTER(TriangulationConfig), _ip, C.POINTER(MsckfIoTri)]
     lib.orcvio_msckf_io_triangulate_prune.argtypes = [C.c_void_p, C.POINTER(TriangulationConfig), C.POINTER(MsckfTracks), _ip, C.POINTER(MsckfIoTri)]
+    lib.orcvio_msckf_io_choose_clones.argtypes = [C.c_void_p, C.POINTER(CloneChoiceConfig), C.POINTER(C.POINTER(CloneChoice))]
     lib.orcvio_msckf_io_collect.argtypes = [C.c_void_p, _ip]
     lib.orcvio_msckf_io_step_frame.argtypes = [C.c_void_p, C.POINTER(FrameStep), C.POINTER(FrameResult)]
     lib.orcvio_msckf_io_step_frame_ex.argtypes = [C.c_void_p, C.POINTER(FrameStep), C.POINTER(FrameEvents), C.POINTER(FrameResultEx)]
@@ -824,6 +837,28 @@ class MsckfUpdater:
         view = lambda ptr, shape: np.ctypeslib.as_array(ptr, shape=shape)
         return dict(valid=view(out.valid, (max(F, 1),))[:F], flags=view(out.flags, (max(F, 1),))[:F], p_w=view(out.p_w, (max(F, 1), 3))[:F],
                     solution=view(out.inv_param, (max(F, 1), 3))[:F], cost=view(out.cost, (max(F, 1),))[:F])
+
+    def io_choose_clones(self, cam_poses, rotation_threshold, translation_threshold, tracking_ok=1, R_imu_cam0=None, t_cam0_imu=None):
+        """orcvio_msckf_io_choose_clones: arms the next io_step_frame / io_step_frame_ex on the open arena -- the frame's remove_clones are
+        checked on the device against findRedundantImuStates on the poses the first update leaves.  cam_poses [N][12] (orientation_cam
+        row-major | position_cam) as they stand before the frame, or False for NULL; R_imu_cam0 / t_cam0_imu the IMU state's extrinsic.
+        Returns the handle's pinned CloneChoice block (a ctypes structure, filled when the frame returns; choice_dict() copies it)."""
+        cfg = CloneChoiceConfig()
+        cfg.rotation_threshold, cfg.translation_threshold, cfg.tracking_ok = float(rotation_threshold), float(translation_threshold), int(tracking_ok)
+        cfg.R_imu_cam0[:] = [float(x) for x in np.asarray(np.eye(3) if R_imu_cam0 is None else R_imu_cam0, dtype=np.float64).ravel()]
+        cfg.t_cam0_imu[:] = [float(x) for x in np.asarray(np.zeros(3) if t_cam0_imu is None else t_cam0_imu, dtype=np.float64).ravel()]
+        cp = None
+        if cam_poses is not False:
+            cp = np.ascontiguousarray(cam_poses, dtype=np.float64)
+            cfg.cam_poses = _d(cp)
+        out = C.POINTER(CloneChoice)()
+        self._chk(self.lib.orcvio_msckf_io_choose_clones(self.h, C.byref(cfg), C.byref(out)), 'orcvio_msckf_io_choose_clones')
+        return out.contents
+
+    @staticmethod
+    def choice_dict(blk):
+        return dict(evaluated=int(blk.evaluated), agree=int(blk.agree), chosen=[int(x) for x in blk.chosen], compared=[int(x) for x in blk.compared],
+                    taken=[int(x) for x in blk.taken], angle=np.array(blk.angle[:], dtype=np.float64), distance=np.array(blk.distance[:], dtype=np.float64))
 
     def io_submit(self, want_P=True, commit=False):
         """orcvio_msckf_io_submit: the update on what stands in the arena is launched; io_collect() waits for it."""
@@ -1381,7 +1416,7 @@ class MsckfUpdater:
 
     def io_step_frame_ex(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
                          n_feature_states=0, lost=(), changes=(), R_b2c=None, t_c_b=None, literal_3d=0, raise_on_refusal=True, triangulate=None,
-                         triangulate_prune=None):
+                         triangulate_prune=None, choose_clones=None):
         """orcvio_msckf_io_step_frame_ex: io_step_frame plus the frame's feature events.  `win` and set_extra_states are those AFTER the
         removals; lost: slots in feature_states before the call (ascending), n_feature_states their count before the removals;
         changes: objects with slot (after the removals), old, new, p_w, p_fej; R_b2c / t_c_b: the IMU's current extrinsics.
@@ -1399,10 +1434,10 @@ class MsckfUpdater:
         ev = FrameEvents(int(idp_dim), int(literal_3d), int(n_feature_states), _i(ls) if len(ls) else None, len(ls), arr if k else None, k,
                          _d(Rb), _d(tb))
         return self.io_step_frame(win, Phi, Q, augment, slam, idp_dim, prune, prune_apply_dx, remove, raise_on_refusal, _events=(ev, k, (ls, arr, Rb, tb)),
-                                  triangulate=triangulate, triangulate_prune=triangulate_prune)
+                                  triangulate=triangulate, triangulate_prune=triangulate_prune, choose_clones=choose_clones)
 
     def io_step_frame(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
-                      raise_on_refusal=True, _events=None, triangulate=None, triangulate_prune=None):
+                      raise_on_refusal=True, _events=None, triangulate=None, triangulate_prune=None, choose_clones=None):
         """orcvio_msckf_io_step_frame: ONE filter frame on the resident covariance -- propagation, augmentation, the update on `win`'s
         tracks (+ the in-state features `slam`), the prune update on `prune`'s tracks (a synth.Window sharing win's poses), the
         marginalisation of `remove`.  Returns dict(dx, gamma, accept, stats, prune_dx, prune_gamma, prune_accept, prune_stats, n_after,
@@ -1410,7 +1445,8 @@ class MsckfUpdater:
         update triangulates its tracks on the device (io_triangulate); the dict then has tri = copies of valid, flags, p_w, solution, cost.
         triangulate_prune: None, or a pair (window listing EVERY observation of the prune tracks, modes or None) [a third entry: the
         config] -- the prune update triangulates its tracks on the device between the two updates (io_triangulate_prune); the dict then
-        has prune_tri with the keys of tri."""
+        has prune_tri with the keys of tri.  choose_clones: None, or the keyword arguments of io_choose_clones -- `remove` is then the
+        caller's prediction, checked on the device between the two updates; the dict has choice (choice_dict)."""
         io = self.io_begin(win.flags, win.N, win.F, int(win.obs_ptr[-1]), with_P=2)
         self.io_fill(io, win, with_P=False)
         tri = None
@@ -1420,6 +1456,7 @@ class MsckfUpdater:
         tri2 = None
         if triangulate_prune is not None:
             tri2 = self.io_triangulate_prune(triangulate_prune[0], triangulate_prune[2] if len(triangulate_prune) > 2 else None, triangulate_prune[1])
+        choice = None if choose_clones is None else self.io_choose_clones(**choose_clones)
         keep = []
         st = FrameStep()
         st.leg_dim = int(win.flags.leg_dim)
@@ -1470,6 +1507,8 @@ class MsckfUpdater:
             extra['tri'] = {k: v.copy() for k, v in tri.items()}
         if tri2 is not None:
             extra['prune_tri'] = {k: v.copy() for k, v in tri2.items()}
+        if choice is not None:
+            extra['choice'] = self.choice_dict(choice)
         return dict(**extra, rc=rc, dx=arr(res.dx, n, np.float64), gamma=arr(res.gamma, win.F, np.float64), accept=arr(res.accept, win.F, np.int32),
                     stats=np.array(res.stats[:], dtype=np.int32), prune_dx=arr(res.prune_dx, n, np.float64),
                     prune_gamma=arr(res.prune_gamma, F2, np.float64), prune_accept=arr(res.prune_accept, F2, np.int32),

@@ -228,6 +228,7 @@ static void free_all(orcvio_msckf_handle* h) {
     if (h->h_imu_status) (void)hipHostFree(h->h_imu_status);
     if (h->d_tri_words) (void)hipFree(h->d_tri_words);
     if (h->h_tri2) (void)hipHostFree(h->h_tri2);
+    if (h->h_cc) (void)hipHostFree(h->h_cc);
     for (void* q : {(void*)h->d_tri2_list, (void*)h->d_tri2_words, (void*)h->d_skip2}) if (q) (void)hipFree(q);
     if (h->d_in2) (void)hipFree(h->d_in2);
     if (h->d_step_words) (void)hipFree(h->d_step_words);

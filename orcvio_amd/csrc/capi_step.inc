@@ -129,6 +129,7 @@ struct StepSecond {   // what the second update of the frame needs besides the h
     const StepEvents* ev;   // anchor changes between the pose step and the update (nullptr: none)
     const int* also = nullptr;   // the armed IMU launch's status block: its refusal goes into the kept status words (PoseStepArgs.also)
     bool tri = false;            // armed by orcvio_msckf_io_triangulate_prune: k_triangulate on the staged list in front of the update
+    const StepChoice* cc = nullptr;   // armed by orcvio_msckf_io_choose_clones: k_clone_choice directly behind the pose step
 };
 // the staged list of the armed prune update: where it stands in pinned memory, and its bytes
 static inline size_t tri2_list_bytes(const orcvio_msckf_handle* h) { return tri_list_layout(h->tri2_F, h->tri2_nobs).bytes; }
@@ -169,6 +170,16 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
     if (rc != ORCVIO_OK) return rc;
     h->pw_missing = false;
     if (safe) {
+        if (b.cc) {   // the same launch, the same bits; the host reads the verdict itself: on a disagreement nothing of the second half runs
+            // (no status words: the host has run the first update again or read its outcome, and comes here only behind a committed one)
+            rc = launch_clone_choice(h, s, fl, N, *b.cc, h->d_poses, b.dxA, b.apply_dx, nullptr, false);
+            if (rc == ORCVIO_OK) rc = clone_choice_collect(h, s);
+            if (rc != ORCVIO_OK) return rc;
+            if (!cc_block(h)->agree) {
+                std::memset(h->h_stage + h->in_cap, 0, h->outs_small);   // (prune_dx = 0, no status words)
+                return ORCVIO_OK;
+            }
+        }
         if (events) {   // the repair path waits anyway: the changed features' status is read before the update goes out
             rc = launch_change_anchors(h, s, *b.ev, h->d_poses, nullptr, false, false);
             if (rc != ORCVIO_OK) return rc;
@@ -194,6 +205,10 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
         fa.src[1] = h->h_stage_dev + h->io_optr; fa.dst[1] = h->d_in + h->io_optr; fa.bytes[1] = (unsigned)(upload_bytes(h) - h->io_optr);
         if (b.tri) { fa.nseg = 3; fa.src[2] = tri2_list_src(h); fa.dst[2] = h->d_tri2_list; fa.bytes[2] = (unsigned)tri2_list_bytes(h); }   // (the armed prune update's list rides along)
         rc = launch_frame_head(h, s, fa);
+        if (rc != ORCVIO_OK) return rc;
+    }
+    if (b.cc) {   // behind the pose step, in front of everything of the second half that writes the covariance
+        rc = launch_clone_choice(h, s, fl, N, *b.cc, h->d_poses, b.dxA, b.apply_dx, h->d_step_words, true);
         if (rc != ORCVIO_OK) return rc;
     }
     if (events) {   // enqueued, not waited for: between the first update's commit and this update
@@ -324,6 +339,14 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
         if (!tri_prune_covers(h->h_tri2, h->maxF, h->maxObs, h->tri2_F, st->prune_tracks->obs_ptr, st->prune_tracks->obs_clone))
             return bad("a prune observation's clone does not occur in its track's list");
     }
+    // armed by orcvio_msckf_io_choose_clones: remove_clones is the caller's PREDICTION, checked on the device between the two updates
+    const bool cc = h->cc_armed;
+    if (cc) {
+        auto bad = [&](const char* what) { g_last_error = std::string(who) + ": armed by orcvio_msckf_io_choose_clones: " + what; return ORCVIO_ERR_INVALID; };
+        if (st->n_remove != 2) return bad("n_remove must be 2");
+        if (!clone_choice_possible(N, st->remove_clones[0], st->remove_clones[1])) return bad("remove_clones is not one of {N-3, N-2}, {0, N-3}, {0, N-5}, {0, 1}");
+        if (!st->prune_tracks) return bad("the frame has no prune_tracks (the check rides in front of the prune update: pass a track set)");
+    }
     HIPCHK(hipSetDevice(h->device));
     StepEvents evs;
     { const int rv = step_validate_events(h, st, ev, h->F > 0 || (st->slam_features && st->slam_features->n_features > 0), evs, who); if (rv != ORCVIO_OK) return rv; }
@@ -388,6 +411,12 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     tmark(0);
     if (armed) { rc = imu_consume(h, s); if (rc != ORCVIO_OK) return rc; }   // nothing can refuse the frame any more: the arming is taken
     h->tri2_armed = false;   // (... and so is the prune update's)
+    h->cc_armed = false;     // (... and the check of the clones that leave)
+    StepChoice choice{};
+    if (cc) {
+        choice.pred[0] = st->remove_clones[0]; choice.pred[1] = st->remove_clones[1];
+        std::memset(cc_block(h), 0, sizeof(orcvio_msckf_clone_choice));   // (evaluated = 0 until this frame's launch has stored its block)
+    }
     const int* imu_also = armed ? imu_status(h) : nullptr;
     if (fused) {
         fa.nseg = 1;
@@ -476,12 +505,17 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     unsigned long long pubB = 0;
     if (evs.k > 0) { evs.fs.slam = h->d_slam; evs.fs.cap = h->ekf_cap; }   // (the records' buffers stand: slam_prepare above)
     StepSecond sb{st->prune_tracks, posesA, dxA, infoA, first ? st->prune_apply_dx : 0, evs.k > 0 ? &evs : nullptr, imu_also, tri2};
+    if (cc) {
+        if (evs.k > 0) choice.raise_evt = evs.fs.status;   // (a disagreement refuses the anchor change through the feature step's word)
+        sb.cc = &choice;
+    }
     int rcB = ORCVIO_OK;
     unsigned long long pubE = 0;
     if (!second && evs.k > 0) {   // no update behind the changes: the anchor change is what the call waits for
         rcB = step_events_alone(h, s, fl, N, sb, false, true);
         if (rcB == ORCVIO_OK) pubE = ++h->pub_enqueued;
     }
+    const CovState cov_before_second = cov_state(h);
     if (second) {
         step_arena_swap(h);
         rcB = step_second_update(h, fl, N, sb, false, nullptr, who);
@@ -496,7 +530,8 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     // ---- marginalisation, enqueued behind the updates
     const CovState cov_before_remove = cov_state(h);
     int rcR = ORCVIO_OK;
-    if (rcB == ORCVIO_OK && st->n_remove > 0) rcR = step_remove(h, leg, st->remove_clones, st->n_remove);
+    // (an armed choice: the marginalisation goes out behind the wait, once the device's verdict is known, and is not waited for)
+    if (rcB == ORCVIO_OK && st->n_remove > 0 && !cc) rcR = step_remove(h, leg, st->remove_clones, st->n_remove);
     tmark(3);
     // ---- ONE wait: the flag word behind the last update
     rc = (pubB || pubE || pubA) ? io_wait(h, s, pubB ? pubB : (pubE ? pubE : pubA)) : ORCVIO_OK;
@@ -514,12 +549,26 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
         return code;
     };
     if (rc != ORCVIO_OK) { h->ran = false; return leave(rc); }
+    // the choice's verdict: held = the second half was (or is to be) held back -- no anchor change, no prune update, no marginalisation
+    bool held = cc && rcB != ORCVIO_OK;
+    if (cc && rcB == ORCVIO_OK) {
+        rc = clone_choice_collect(h, s);
+        if (rc != ORCVIO_OK) { h->ran = false; return leave(rc); }
+        held = cc_block(h)->evaluated != 0 && cc_block(h)->agree == 0;
+        // held back, and the prune update took the direct form of a thin stack: that form writes no factor and its commit's bookkeeping
+        // drops the resident one -- but the commit refused itself, the first update's factor stands untouched where it was
+        if (held && h->last_update_thin && cov_before_second.fac_follows()) {
+            h->d_Sres = cov_before_second.d_Sres; h->d_Stmp = cov_before_second.d_Stmp;
+            h->fac_n = cov_before_second.fac_n; h->fac_k = cov_before_second.fac_k; h->fac_ld = cov_before_second.fac_ld;
+            h->fac_tail = cov_before_second.fac_tail; h->fac_valid = true;
+        }
+    }
     if (rex && evs.k > 0) {
         rex->new_param = reinterpret_cast<const double*>(h->h_evt + EVT_H_PAR);
         rex->new_inv_depth = rex->new_param + 3 * ANCHOR_MAX_K;
     }
     auto changes_status = [&]() {   // the word the anchor change left: a changed feature's position was not finite
-        const int sc = evs.k > 0 && *evt_status_host(h) != 0 ? ORCVIO_ERR_NOT_SPD : ORCVIO_OK;
+        const int sc = evs.k > 0 && *evt_status_host(h) != 0 && !held ? ORCVIO_ERR_NOT_SPD : ORCVIO_OK;   // (held: the word was raised by the choice)
         if (rex) rex->status_changes = sc;
         if (sc != ORCVIO_OK) g_last_error = std::string(who) + ": a changed feature's position is not finite (an incremented inverse depth of zero): no anchor change, no prune update";
         return sc;
@@ -572,8 +621,14 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             sb.ev = nullptr;
             if (first) HIPCHK(hipMemcpyAsync(const_cast<double*>(dxA), soA + vA.oo_dx, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
         }
+        if (cc && res->status_first != ORCVIO_OK) {   // no second update will carry the choice: on the caller's records as they are (dx not applied)
+            rc = launch_clone_choice(h, s, fl, N, choice, nullptr, dxA, 0, nullptr, false);
+            if (rc == ORCVIO_OK) rc = clone_choice_collect(h, s);
+            if (rc != ORCVIO_OK) return leave(rc);
+            held = cc_block(h)->agree == 0;
+        }
         // (lostA: the anchor change refused itself on the first update's kept status word; it runs behind the repeat, once)
-        if (sb.ev && (!second || res->status_first != ORCVIO_OK)) {   // no second update to carry them: the changes are bookkeeping and stand
+        if (sb.ev && !held && (!second || res->status_first != ORCVIO_OK)) {   // no second update to carry them: the changes are bookkeeping and stand
             rc = step_events_alone(h, s, fl, N, sb, true, false);
             if (rc != ORCVIO_OK) return leave(rc);
             HIPCHK(hipStreamSynchronize(s));
@@ -587,13 +642,14 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
                 res->repaired++; h->cnt_step_repairs++;
                 res->status_prune = rcB;
                 if (rcB != ORCVIO_OK && rcB != ORCVIO_ERR_NOT_SPD) return leave(rcB);
+                if (cc) held = cc_block(h)->agree == 0;   // (held: step_second_update ran nothing behind the choice)
                 soB = h->h_stage + h->in_cap;
                 res->prune_dx = reinterpret_cast<const double*>(soB + h->oo_dx);
                 res->prune_gamma = reinterpret_cast<const double*>(soB + h->oo_gamma);
                 res->prune_accept = reinterpret_cast<const int32_t*>(soB + h->oo_accept);
             }
         }
-        if (st->n_remove > 0) { rcR = step_remove(h, leg, st->remove_clones, st->n_remove); if (rcR != ORCVIO_OK) return leave(rcR); }
+        if (st->n_remove > 0 && !held) { rcR = step_remove(h, leg, st->remove_clones, st->n_remove); if (rcR != ORCVIO_OK) return leave(rcR); }
         h->cnt_step_frames++;
         const int sc = changes_status();
         return leave(res->status_first != ORCVIO_OK ? res->status_first : (res->status_prune != ORCVIO_OK ? res->status_prune : sc));
@@ -607,6 +663,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
         if (rcB != ORCVIO_OK) res->status_prune = rcB;
         else if (res->status_first != ORCVIO_OK) { res->status_prune = res->status_first; res->prune_stats[3] = 0; }   // (refused with the first: info_also)
         else if (sc_changes != ORCVIO_OK) { res->status_prune = sc_changes; res->prune_stats[3] = 0; }   // (refused with the changes: the kept status word)
+        else if (held) { (void)feature_outcome_view(h, vB, soB, res->prune_stats); res->status_prune = ORCVIO_OK; res->prune_stats[3] = 0; }   // (held back: not an error)
         else {
             res->status_prune = feature_outcome_view(h, vB, soB, res->prune_stats);
             if (res->status_prune != ORCVIO_OK) res->prune_stats[3] = 0;
@@ -614,6 +671,7 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
     }
     h->ran = false;   // (both commits are part of the call: nothing is left for orcvio_msckf_cov_commit)
     h->cnt_step_frames++;
+    if (cc && !held && rcB == ORCVIO_OK && st->n_remove > 0) rcR = step_remove(h, leg, st->remove_clones, st->n_remove);   // (enqueued behind the wait, not waited for)
     if (rcR != ORCVIO_OK) return leave(rcR);
     if (!second && rcB != ORCVIO_OK) return leave(rcB);
     return leave(res->status_first != ORCVIO_OK ? res->status_first : (res->status_prune != ORCVIO_OK ? res->status_prune : sc_changes));

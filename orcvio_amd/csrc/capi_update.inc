@@ -27,6 +27,7 @@ static int upload_begin(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags,
     h->uploaded = false; h->ran = false; h->io_open = false;
     h->tri_armed = false;          // (an arming of orcvio_msckf_io_triangulate belongs to the arena it was made on)
     h->tri2_armed = false;         // (... and so does one of orcvio_msckf_io_triangulate_prune: the frame call has taken it by now)
+    h->cc_armed = false;           // (... and one of orcvio_msckf_io_choose_clones)
     h->last_update_thin = false;   // (set again by the update itself if it takes the direct form of a thin stack)
     h->flags = *flags;
     h->N = N; h->F = F; h->nobs = nobs;

@@ -22,6 +22,7 @@
 
 #include "../../../include/orcvio_msckf.h"
 #include "zupt_check_model.hpp"
+#include "clone_choice_model.hpp"
 
 namespace orcvio_amd {
 
@@ -1045,6 +1046,119 @@ class MsckfBackend {
             const std::vector<double> dx2(res.prune_dx, res.prune_dx + nn);
             out.state_incremented = incrementState_IMUCam(ss, dx2) || out.state_incremented;
         }
+        return out;
+    }
+
+    // ---- the choice of the clones that leave (orcvio_msckf_io_choose_clones) ---------------------------------------------------------
+    // OrcVIO::findRedundantImuStates (src/orcvio.cpp:2582-2626) on the containers as they stand -- position_cam / orientation_cam as
+    // the last incrementState_IMUCam left them -- from host/clone_choice_model.hpp, the arithmetic k_clone_choice runs.  Returns the
+    // state ids ascending; empty for a window of fewer than six clones (the reference's loop can name the oldest clone twice there).
+    struct CloneChoiceThresholds {
+        double rotation_threshold = 0.2618, translation_threshold = 0.4, tracking_rate_threshold = 0.5;   // config/euroc.yaml
+    };
+    static std::vector<double> cameraRecords(const StateServer& ss) {
+        std::vector<double> cam;
+        for (const auto& kv : ss.imu_states_augment) {
+            cam.insert(cam.end(), kv.second.orientation_cam, kv.second.orientation_cam + 9);
+            cam.insert(cam.end(), kv.second.position_cam, kv.second.position_cam + 3);
+        }
+        return cam;
+    }
+    static std::vector<StateIDType> findRedundantImuStates(const StateServer& ss, double tracking_rate, const CloneChoiceThresholds& t,
+                                                           CloneChoice* detail = nullptr) {
+        const int N = (int)ss.imu_states_augment.size();
+        if (N < CLONE_CHOICE_MIN_N) return {};
+        const std::vector<double> cam = cameraRecords(ss);
+        CloneChoice o{};
+        clone_choice_on_records(N, cam.data(), t.rotation_threshold, t.translation_threshold, tracking_rate > t.tracking_rate_threshold ? 1 : 0, nullptr, &o);
+        if (detail) *detail = o;
+        return stateIdsOf(ss, o.chosen);
+    }
+    static std::vector<StateIDType> stateIdsOf(const StateServer& ss, const int32_t idx[2]) {
+        std::vector<StateIDType> ids;
+        int i = 0;
+        for (const auto& kv : ss.imu_states_augment) { if (i == idx[0] || i == idx[1]) ids.push_back(kv.first); ++i; }
+        return ids;
+    }
+    // The frame call site with the choice checked on the device: the clones are PREDICTED on the containers as they stand (before the
+    // frame's first update), the frame is armed with that prediction (orcvio_msckf_io_choose_clones) and, as stepFramePruneArmed, with
+    // the prune triangulation; the state increments are applied.  When the device -- which evaluates the choice on the poses the first
+    // update leaves, where the reference does -- chooses other clones, the frame's second half was held back: the lists are built again
+    // for the device's choice on the incremented containers and that half runs as a second frame without propagation, augmentation
+    // and first update.  path: 1 the prediction held (one frame), 2 it did not (the second half re-issued), 0 the prediction named no
+    // prune feature (nothing to arm the check on: the first half as a frame, the choice on the host, the second half as a frame).
+    struct FrameChosenReport {
+        int path = 0;
+        std::vector<StateIDType> predicted, chosen;
+        orcvio_msckf_clone_choice choice{};
+    };
+    UpdateOutcome stepFrameChosen(StateServer& ss, MapServer& map_server, const std::vector<FeatureIDType>& lost_ids, double tracking_rate,
+                                  const CloneChoiceThresholds& thr, StateIDType curr_id, FrameChosenReport* report = nullptr) {
+        UpdateOutcome out;
+        FrameChosenReport rep;
+        if (!resident_covariance) { out.status = ORCVIO_ERR_INVALID; return out; }
+        rep.predicted = findRedundantImuStates(ss, tracking_rate, thr);
+        if (rep.predicted.empty()) { out.status = ORCVIO_ERR_INVALID; return out; }
+        const PruneTriLists l = buildPruneTriLists(ss, map_server, rep.predicted, curr_id);
+        auto second_half = [&](const std::vector<StateIDType>& rm) {   // on the containers as they stand: no first update, no dx to apply
+            const UpdateOutcome o2 = stepFramePruneArmed(ss, map_server, {}, rm, curr_id);
+            out.status = o2.status;
+            out.updated = out.updated || o2.updated;
+            out.state_incremented = out.state_incremented || o2.state_incremented;
+        };
+        if (l.ids.empty()) {   // the exact two-frame route
+            out = stepFramePruneArmed(ss, map_server, lost_ids, {}, curr_id);
+            if (out.status != ORCVIO_OK) return out;
+            rep.chosen = findRedundantImuStates(ss, tracking_rate, thr);
+            second_half(rep.chosen);
+            if (report) *report = rep;
+            return out;
+        }
+        orcvio_msckf_io io{};
+        orcvio_msckf_io_tri tri{};
+        int nn = 0;
+        out.status = fillArena(ss, map_server, lost_ids, {}, false, &io, &nn);
+        if (out.status != ORCVIO_OK) return out;
+        const std::vector<double> cam = cameraRecords(ss);
+        orcvio_msckf_clone_choice_config cfg{};
+        cfg.rotation_threshold = thr.rotation_threshold; cfg.translation_threshold = thr.translation_threshold;
+        cfg.tracking_ok = tracking_rate > thr.tracking_rate_threshold ? 1 : 0;
+        std::memcpy(cfg.R_imu_cam0, ss.imu_state.R_imu_cam0, sizeof(cfg.R_imu_cam0));
+        std::memcpy(cfg.t_cam0_imu, ss.imu_state.t_cam0_imu, sizeof(cfg.t_cam0_imu));
+        cfg.cam_poses = cam.data();
+        const orcvio_msckf_clone_choice* choice = nullptr;
+        out.status = orcvio_msckf_io_choose_clones(h_, &cfg, &choice);
+        const orcvio_msckf_tracks tt = l.tri_tracks(), pt = l.prune_tracks();
+        if (out.status == ORCVIO_OK) out.status = orcvio_msckf_io_triangulate_prune(h_, &optimization_config, &tt, l.mode.data(), &tri);
+        if (out.status != ORCVIO_OK) return out;
+        orcvio_msckf_frame_step st{};
+        st.leg_dim = flags.leg_dim;
+        st.prune_tracks = &pt;
+        st.prune_apply_dx = 1;
+        st.remove_clones = l.remove_idx.data(); st.n_remove = (int32_t)l.remove_idx.size();
+        orcvio_msckf_frame_result res{};
+        out.status = orcvio_msckf_io_step_frame(h_, &st, &res);
+        if (out.status != ORCVIO_OK) return out;
+        rep.choice = *choice;
+        rep.chosen = stateIdsOf(ss, choice->chosen);
+        out.accepted.assign(res.accept, res.accept + lost_ids.size());
+        out.gamma.assign(res.gamma, res.gamma + lost_ids.size());
+        out.delta_x.assign(res.dx, res.dx + nn);
+        out.updated = res.stats[3] != 0;
+        if (res.stats[3] != 0) out.state_incremented = incrementState_IMUCam(ss, out.delta_x);
+        if (choice->agree) {
+            rep.path = 1;
+            writeBackPruneTriangulation(map_server, l, tri);
+            if (res.prune_stats[3] != 0) {
+                const std::vector<double> dx2(res.prune_dx, res.prune_dx + nn);
+                out.state_incremented = incrementState_IMUCam(ss, dx2) || out.state_incremented;
+                out.updated = true;
+            }
+        } else {   // (the held frame's triangulation block belongs to features the reference would not have initialised: not written back)
+            rep.path = 2;
+            second_half(rep.chosen);
+        }
+        if (report) *report = rep;
         return out;
     }
 

@@ -32,6 +32,7 @@
 #include "object_lite.hpp"
 #include "io_ops.hpp"
 #include "frame_ops.hpp"
+#include "clone_choice_ops.hpp"
 #include "host/cov_book.hpp"
 #include <immintrin.h>
 #include <condition_variable>
@@ -223,6 +224,12 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     int tri2_F = 0, tri2_nobs = 0;      // tracks and observations of the staged list
     orcvio_triangulation_config tri2_cfg{};
     bool tri_live_prune = false;        // tri_live, and the launch was the prune update's: the repeat's refusal word is d_tri2_words
+    // orcvio_msckf_io_choose_clones: the next frame call checks the caller's remove_clones against findRedundantImuStates on the poses its
+    // first update leaves (k_clone_choice between the two updates; one-shot as the armings above); allocated on first use
+    char *h_cc = nullptr, *h_cc_dev = nullptr;   // pinned: the result block | its sequence word (CCH_SEQ_OFFSET) | the staged configuration (CCH_CFG_BYTES0)
+    bool cc_armed = false;
+    int cc_tracking_ok = 0;
+    unsigned long long cc_seq = 0;      // launches of k_clone_choice so far: the value the next one stores behind its block
     int* d_flag = nullptr;              // step counter of that launch (inside the d_info allocation, own 128-byte line)
     // device buffers
     double *d_poses = nullptr, *d_pw = nullptr, *d_obs_z = nullptr, *d_obs_zvel = nullptr, *d_P = nullptr;
@@ -430,6 +437,7 @@ const char* orcvio_msckf_last_error(void) { return g_last_error.c_str(); }
 #include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: the 9-row update, the factor kept, the one-call stationary frame
 #include "capi_zupt_check.inc"   // zero-velocity detection from IMU samples: k_zupt_check stand-alone, behind the IMU propagation, inside the stationary frame
 #include "capi_frame.inc"   // one frame in one call: feature update + object update, the objects' compression beside the features' solve
+#include "capi_clone_choice.inc"   // the check of the clones that leave inside the one-call frame: arming, k_clone_choice's launch, its result
 #include "capi_step.inc"   // one FILTER frame in one call: propagate, augment, update, prune update, marginalise on the resident covariance
 #include "capi_state.inc"   // triangulation, incrementState_IMUCam (host arithmetic)
 #include "capi_debug.inc"   // diagnostics build only: test hooks and ablation timers
