@@ -12,7 +12,14 @@
  *   - plain C, caller-owned buffers, no exceptions, int status codes;
  *   - all floating point is FP64, ids / indices are int32;
  *   - matrices handed over by the host are dense.  P is symmetric so row- and
- *     column-major coincide; every other matrix states its layout;
+ *     column-major coincide; every other matrix states its layout.  P MUST be
+ *     symmetric: of each pair P[i][j], P[j][i] outside the diagonal 16 x 16 tiles
+ *     (floor(i/16) != floor(j/16)) the update may read either one.  The in-place form
+ *     (orcvio_msckf_io.P) and the copying calls that pull P into device memory
+ *     themselves (orcvio_msckf_update_features, the object updates' P) read the UPPER
+ *     one (floor(j/16) > floor(i/16)) and never touch the other: only the rows'
+ *     suffixes from their diagonal tile on cross the link, the device mirrors them
+ *     (orcvio_msckf_counters [10]).  The diagonal tiles are read whole;
  *   - error-state order is the reference's (src/orcvio.cpp:202-225,4497-4533):
  *       theta(0:3) v(3:6) p(6:9) bg(9:12) ba(12:15) theta_ext(15:18) t_ext(18:21)
  *       td(21) [IMU intrinsics 22:46 if leg_dim==46] | clone i: theta,p at leg_dim+6i
@@ -370,7 +377,8 @@ int32_t orcvio_msckf_download_ekf(orcvio_msckf_handle* h, double* gamma, int32_t
  * OrcVIO::pruneImuStateBuffer (:2803-2851): featureJacobian_msckf ->
  * nullspace_project_inplace_svd -> gatingTestFeature -> stack -> QR compression ->
  * measurementUpdate_{hybrid(pure MSCKF case),msckf}.  Host buffers in, host buffers out;
- * P is n x n with n = leg_dim + 6*n_clones. */
+ * P is n x n with n = leg_dim + 6*n_clones, symmetric: outside the diagonal 16 x 16 tiles only the upper
+ * entries are read (Conventions; n odd: all of them). */
 int32_t orcvio_msckf_update_features(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags,
                                      const orcvio_msckf_window* window,
                                      const orcvio_msckf_tracks* tracks, const double* P,
@@ -404,7 +412,8 @@ typedef struct orcvio_msckf_io {
     int32_t* obs_clone;
     double* obs_z;
     double* obs_zvel;
-    double* P;
+    double* P;            /* n x n, symmetric; of the entries outside the diagonal 16 x 16 tiles the update reads the upper ones only
+                             (floor(j/16) > floor(i/16)): the lower ones need not be written (Conventions; n odd: all are read) */
     const double* dx;
     const double* gamma;
     const int32_t* accept;
@@ -752,8 +761,10 @@ int32_t orcvio_msckf_objects_download(orcvio_msckf_handle* h, orcvio_msckf_resul
  *       ORCVIO_OPT_OBJECT_REFINE = 0, ORCVIO_OPT_REF_STACK_HF, ORCVIO_OPT_OBJECT_QR = 0)
  *   [6] frames (orcvio_msckf_io_update_frame) whose object solve ran chained to the feature update's factor (ORCVIO_FRAME_CHAIN)
  *   [7] frame calls that found their object tracks staged ahead (orcvio_msckf_io_stage_object_tracks)
- *   [8] filter frames through orcvio_msckf_io_step_frame   [9] updates of such frames run again after a lost in-launch hand-off */
-#define ORCVIO_COUNTERS 10
+ *   [8] filter frames through orcvio_msckf_io_step_frame   [9] updates of such frames run again after a lost in-launch hand-off
+ *   [10] pulls of a host P into device memory that moved its upper tile-trapezoid only and mirrored it on the device (n even; an odd
+ *        n, possible with extra states, takes the linear pull of the whole matrix and is not counted) */
+#define ORCVIO_COUNTERS 11
 int32_t orcvio_msckf_counters(orcvio_msckf_handle* h, int64_t* counters, int32_t count);
 
 /* Objects of the last downloaded object update (any entry point) whose projection against H_f went through the explicit basis

@@ -9,7 +9,8 @@
 //        11 {fac_valid, fac_n, fac_k, res_n} -> int32[4], 12 the resident factor [fac_k][fac_n],
 //        13 the dense rows [dense_rows][NAP] (caller-projected rows, then the rows of the entering features: zero U part, V part),
 //        14 {dense_rows, NAP} -> int32[2],
-//        15 did the last object update take the one-launch compression (k_obj_fused)? -> int32
+//        15 did the last object update take the one-launch compression (k_obj_fused)? -> int32,
+//        16 the n x n prior of the last update as it stands in device memory (h->d_P: a host P as its pull left it)
 int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst, int64_t max_bytes) {
     if (!h || !dst) return ORCVIO_ERR_INVALID;
     HIPCHK(hipSetDevice(h->device));
@@ -65,6 +66,7 @@ int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst
             *reinterpret_cast<int32_t*>(dst) = h->obj_last_fused ? 1 : 0;
             return ORCVIO_OK;
         }
+        case 16: src = h->d_P; bytes = (size_t)h->n * h->n * sizeof(double); break;   // the prior as the pull left it in device memory
         case 7: {
             int32_t dims[8] = {h->n, h->NA, h->NAP, h->NP, h->m_tot, h->Mmax, h->ldz, h->reg_path ? 1 : 0};
             if ((size_t)max_bytes < sizeof(dims)) return ORCVIO_ERR_INVALID;

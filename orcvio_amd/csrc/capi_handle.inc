@@ -207,6 +207,34 @@ static int launch_ingest(orcvio_msckf_handle* h, hipStream_t s, const void* src_
     HIPCHK(hipGetLastError());
     return ORCVIO_OK;
 }
+// Every inbound P: [lin_off, io_P) of the arena (the caller-written arrays in front of P; lin_off = io_P: P alone) and the n x n prior
+// at io_P behind it -> HBM in ONE launch.  n even (ingest_sym_ok): only the upper tile-trapezoid of P crosses the link and the device
+// mirrors it (k_ingest_sym; counted in orcvio_msckf_counters [10]).  n odd: rows are only 8-byte aligned -- the call takes the linear
+// pull of the whole range, as before.
+static int launch_ingest_P(orcvio_msckf_handle* h, hipStream_t s, size_t lin_off, int n) {
+    const size_t P_bytes = sizeof(double) * (size_t)n * n;
+    if (!ingest_sym_ok(n)) return launch_ingest(h, s, h->h_stage_dev + lin_off, h->d_in + lin_off, h->io_P - lin_off + P_bytes);
+    const size_t lin16 = (h->io_P - lin_off) / 16;   // (the parts of the arena are 256-byte aligned: whole units, none straddles into P)
+    const size_t lanes = lin16 + ingest_sym_lanes(n);
+    int grid = (int)((lanes + 255) / 256);   // one round of loads covers everything, as k_ingest's grid does
+    if (grid > 4 * h->n_cus) grid = 4 * h->n_cus;
+    hipLaunchKernelGGL(k_ingest_sym, dim3(grid), dim3(256), 0, s, reinterpret_cast<const u32x4*>(h->h_stage_dev + lin_off),
+                       reinterpret_cast<u32x4*>(h->d_in + lin_off), lin16, reinterpret_cast<const double*>(h->h_stage_dev + h->io_P),
+                       reinterpret_cast<double*>(h->d_in + h->io_P), n);
+    HIPCHK(hipGetLastError());
+    h->cnt_sym_pulls++;
+    return ORCVIO_OK;
+}
+// the copying calls' half of it: the caller's P -> the arena.  upper_only: the arena is read by launch_ingest_P alone, so only what
+// that pull fetches is copied (the same predicate, the same row segments); otherwise (the staged upload's copy of the whole arena) all of it
+static void stage_prior(orcvio_msckf_handle* h, const double* P, int n, bool upper_only) {
+    double* dst = reinterpret_cast<double*>(h->h_stage + h->io_P);
+    if (!upper_only || !ingest_sym_ok(n)) { std::memcpy(dst, P, sizeof(double) * (size_t)n * n); return; }
+    for (int i = 0; i < n; ++i) {
+        const size_t o = (size_t)i * n + ingest_sym_seg_start(i);
+        std::memcpy(dst + o, P + o, sizeof(double) * (size_t)ingest_sym_seg_len(n, i));
+    }
+}
 // ---- create / destroy ---------------------------------------------------------------------
 static void free_all(orcvio_msckf_handle* h) {
     (void)hipDeviceSynchronize();   // (asynchronous copies out of the pinned buffers, a commit's tail: nothing of this handle is in flight any more)

@@ -221,8 +221,9 @@ static int objects_pipeline(orcvio_msckf_handle* h, hipStream_t s, double* dst, 
     return ORCVIO_OK;
 }
 
-// Prior of an object update: the caller's P staged through pinned memory (one asynchronous copy; the caller's buffer is
-// free when the call returns), or the resident covariance in place (no copy at all).
+// Prior of an object update: the caller's P staged through pinned memory and pulled from there by one launch (launch_ingest_P: of an
+// even n only the upper tiles are staged and travel; the caller's buffer is free when the call returns), or the resident covariance in
+// place (no copy at all).
 static int objects_prior(orcvio_msckf_handle* h, hipStream_t s, const double* P, const char* who) {
     const int n = h->n;
     if (!P && h->res_n != n) { g_last_error = std::string(who) + ": P == NULL but the resident covariance does not match the window"; return ORCVIO_ERR_INVALID; }
@@ -236,8 +237,8 @@ static int objects_prior(orcvio_msckf_handle* h, hipStream_t s, const double* P,
     layout_inputs(h, h->N, 0, 0, false, P != nullptr, n);
     layout_outputs(h, n, 1);
     if (P) {
-        std::memcpy(h->h_stage + h->io_P, P, sizeof(double) * (size_t)n * n);
-        const int ri = launch_ingest(h, s, h->h_stage_dev + h->io_P, h->d_P, sizeof(double) * (size_t)n * n);
+        stage_prior(h, P, n, true);   // (what the pull below fetches: the upper tile-trapezoid when n is even)
+        const int ri = launch_ingest_P(h, s, h->io_P, n);
         if (ri != ORCVIO_OK) return ri;
         { const int rm = arena_mark_read(h, s); if (rm != ORCVIO_OK) return rm; }
     }
@@ -1046,7 +1047,7 @@ int32_t orcvio_msckf_counters(orcvio_msckf_handle* h, int64_t* counters, int32_t
     if (!h || !counters || count < 1) { g_last_error = "counters: null argument"; return ORCVIO_ERR_INVALID; }
     const int64_t v[ORCVIO_COUNTERS] = {h->front_fallbacks, h->cnt_graph_captures, h->cnt_graph_replays, h->cnt_plain_runs,
                                         h->front_blocked_by_comm ? 1 : 0, h->obj_last_fused ? 1 : 0, h->cnt_chained, (int64_t)h->cnt_prestaged,
-                                        h->cnt_step_frames, h->cnt_step_repairs};
+                                        h->cnt_step_frames, h->cnt_step_repairs, h->cnt_sym_pulls};
     for (int i = 0; i < count && i < ORCVIO_COUNTERS; ++i) counters[i] = v[i];
     for (int i = ORCVIO_COUNTERS; i < count; ++i) counters[i] = 0;
     return ORCVIO_OK;

@@ -57,7 +57,9 @@ static inline size_t upload_bytes(const orcvio_msckf_handle* h) {
 // The caller-written part of the arena (poses, tracks, P: everything behind the derived index arrays) pulled into HBM by a launch
 // of its own, issued BEFORE the host validates the index arrays and derives the per-clone lists (upload_finalize, ~8 us at
 // config 2): the transfer runs under that host work, and the launch graph of the update only has the derived arrays left to fetch.
+// With a prior from the host the same launch brings P in as its upper tile-trapezoid and mirrors it on the device (launch_ingest_P).
 static int ingest_raw(orcvio_msckf_handle* h, hipStream_t s) {
+    if (h->io_with_P) return launch_ingest_P(h, s, h->io_poses, h->n);
     return launch_ingest(h, s, h->h_stage_dev + h->io_poses, h->d_in + h->io_poses, upload_bytes(h) - h->io_poses);
 }
 
@@ -177,11 +179,12 @@ static int upload_finalize(orcvio_msckf_handle* h, const char* who) {
     return ORCVIO_OK;
 }
 
-// the caller's arrays -> the arena (orcvio_msckf_upload and the copying one-shot calls)
-static void stage_inputs(orcvio_msckf_handle* h, const orcvio_msckf_window* w, const orcvio_msckf_tracks* tr, const double* P) {
+// the caller's arrays -> the arena (orcvio_msckf_upload and the copying one-shot calls); P_upper_only: the arena goes to the device through
+// ingest_raw, which fetches the upper tile-trapezoid of P only (stage_prior)
+static void stage_inputs(orcvio_msckf_handle* h, const orcvio_msckf_window* w, const orcvio_msckf_tracks* tr, const double* P, bool P_upper_only) {
     const int N = h->N, F = h->F, nobs = h->nobs;
     char* st = h->h_stage;
-    if (P) std::memcpy(st + h->io_P, P, sizeof(double) * (size_t)h->n * h->n);
+    if (P) stage_prior(h, P, h->n, P_upper_only);
     double* poses = reinterpret_cast<double*>(st + h->io_poses);
     const double* tfej = w->t_fej ? w->t_fej : w->t_b_w;
     for (int i = 0; i < N; ++i) {
@@ -219,7 +222,7 @@ static int upload_to_arena(orcvio_msckf_handle* h, const orcvio_msckf_flags* fla
     if (F > 0 && nobs > 0 && (!tr->obs_clone || !tr->obs_z)) { g_last_error = std::string(who) + ": null track arrays"; return ORCVIO_ERR_INVALID; }
     int rc = upload_begin(h, flags, N, F, nobs, P != nullptr, tr->obs_zvel != nullptr, who);
     if (rc != ORCVIO_OK) return rc;
-    stage_inputs(h, w, tr, P);
+    stage_inputs(h, w, tr, P, early_ingest);
     if (early_ingest) { rc = ingest_raw(h, h->stream); if (rc != ORCVIO_OK) return rc; }   // (io path: what was just staged travels under the finalize)
     rc = upload_finalize(h, who);
     if (rc != ORCVIO_OK) return rc;

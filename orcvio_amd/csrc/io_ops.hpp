@@ -4,6 +4,7 @@
 // src/orcvio.cpp:2497-2560, :2803-2851).  HBM-/PCIe-bound byte movers: 16 bytes per lane, coalesced.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "host/ingest_sym_map.hpp"
 
 namespace orcvio_amd {
 
@@ -18,6 +19,31 @@ __global__ __launch_bounds__(256) void k_ingest(const u32x4* __restrict__ src, u
     if (zero && blockIdx.x == 0 && threadIdx.x < 32 && (zero_mask >> threadIdx.x & 1u)) zero[threadIdx.x] = 0;
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride) dst[i] = __builtin_nontemporal_load(src + i);
+}
+
+// k_ingest of the caller-written part of the arena when a symmetric prior P stands at its end (host/ingest_sym_map.hpp): the linear
+// part [src, src + 16 lin16) as k_ingest moves it, and of P only the upper tile-trapezoid -- row i's suffix from its diagonal 16 x 16
+// tile on -- stored where it was fetched from and, right of the diagonal tile, mirrored to (j, i).  Every element of the n x n image is
+// written exactly once, so for a symmetric P the image is bit for bit the linear pull's.  n even (ingest_sym_ok: the launcher's
+// business).  Loads: one 16-byte non-temporal request per lane, consecutive lanes along the row; the mirror's two 8-byte stores go down a
+// column (HBM, merged in L2).
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(256) void k_ingest_sym(const u32x4* __restrict__ src, u32x4* __restrict__ dst, size_t lin16,
+                                                    const double* __restrict__ Psrc, double* __restrict__ Pdst, int n) {
+    const size_t total = lin16 + ingest_sym_lanes(n);
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += stride) {
+        if (idx < lin16) { dst[idx] = __builtin_nontemporal_load(src + idx); continue; }
+        int i, j;
+        if (!ingest_sym_unit(n, (unsigned)(idx - lin16), &i, &j)) continue;   // (the row's prefix: nothing travels)
+        const size_t o = (size_t)i * n + j;
+        const f64x2 v = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(Psrc + o));
+        *reinterpret_cast<f64x2*>(Pdst + o) = v;
+        if (ingest_sym_mirrored(i, j)) {
+            Pdst[(size_t)j * n + i] = v.x;
+            Pdst[(size_t)(j + 1) * n + i] = v.y;
+        }
+    }
 }
 
 // The epilogue of a zero-copy update, ONE launch behind k_finish_sqrt:

@@ -274,6 +274,7 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     unsigned* d_chain_words = nullptr;  // [0] feature half: M formed, [1] feature half: committed (cumulative values); [32] step counter, [48..63] block-row words of the second solve, [64] its finish workgroups' counter (LaFin)
     unsigned chain_seq = 0u;
     long long cnt_chained = 0;          // frames whose object solve ran chained (orcvio_msckf_counters [6])
+    long long cnt_sym_pulls = 0;        // pulls of a host P that took the upper-trapezoid form (launch_ingest_P; orcvio_msckf_counters [10])
     bool frame_chain = true;            // ORCVIO_FRAME_CHAIN (read at create, default 1): orcvio_msckf_io_update_frame runs the object solve chained (capi_frame.inc)
     bool blk2_opt = true;               // ORCVIO_BLK2 (read at create): windows of 15 .. 26 block steps factor by 2 x 2 blocks out of the register kernels
     bool la_attr = false;               // the dynamic-LDS opt-in of k_potrf_solve_la is set for this handle's device
