@@ -397,9 +397,12 @@ int32_t orcvio_msckf_update_features(orcvio_msckf_handle* h, const orcvio_msckf_
  *              P [n][n] (NULL when with_P == 0).  Outputs, valid after io_update returns ORCVIO_OK and until the next call on
  *              the handle that takes tracks: dx [n], gamma [F], accept [F], P_out [n][n] (written only with want_P).
  *   io_update  validates what stands in the arena (the index arrays, as orcvio_msckf_upload does), and runs the update: ONE
- *              launch of a captured graph whose first kernel pulls the arena into HBM and whose last kernel pushes the results
+ *              launch of a captured graph that pulls the arena into HBM and whose last kernel pushes the results
  *              into the (host-coherent) output block and raises a flag word there; the calling thread spins on that word -- no
- *              copy-engine transfer, no stream synchronisation.  commit != 0: orcvio_msckf_cov_commit is part of the same launch
+ *              copy-engine transfer, no stream synchronisation.  The arena is read until that launch has ENDED, not by its first
+ *              kernel alone: the index lists the library derives from the caller's arrays stay in the arena and the tracks' kernel
+ *              reads them there (orcvio_msckf_counters [11]), so the arena is the caller's to write again when io_update (or
+ *              io_collect) has returned, not before.  commit != 0: orcvio_msckf_cov_commit is part of the same launch
  *              (P+ and its square-root factor become resident; refused on the device if the update is).  stats as in
  *              orcvio_msckf_result.  The same arena may be updated again (next frame, same sizes) without a new io_begin.
  * Status codes as orcvio_msckf_update_features; ORCVIO_ERR_TIMEOUT if the results were never published. */
@@ -763,8 +766,12 @@ int32_t orcvio_msckf_objects_download(orcvio_msckf_handle* h, orcvio_msckf_resul
  *   [7] frame calls that found their object tracks staged ahead (orcvio_msckf_io_stage_object_tracks)
  *   [8] filter frames through orcvio_msckf_io_step_frame   [9] updates of such frames run again after a lost in-launch hand-off
  *   [10] pulls of a host P into device memory that moved its upper tile-trapezoid only and mirrored it on the device (n even; an odd
- *        n, possible with extra states, takes the linear pull of the whole matrix and is not counted) */
-#define ORCVIO_COUNTERS 11
+ *        n, possible with extra states, takes the linear pull of the whole matrix and is not counted)
+ *   [11] in-place updates (orcvio_msckf_io_update / _io_submit, the copying orcvio_msckf_update_features) whose fused front end read the
+ *        host-derived index lists (per-clone rows and positions) in the pinned arena itself instead of pulling them into device memory
+ *        first: every such update but a materialised-stack one, the direct form of a thin stack, one armed by
+ *        orcvio_msckf_io_triangulate, and one that takes the forked front end */
+#define ORCVIO_COUNTERS 12
 int32_t orcvio_msckf_counters(orcvio_msckf_handle* h, int64_t* counters, int32_t count);
 
 /* Objects of the last downloaded object update (any entry point) whose projection against H_f went through the explicit basis

@@ -628,13 +628,14 @@ class MsckfUpdater:
     def counters(self):
         """Cumulative counters of the handle: front_fallbacks (fused front end re-run on the forked path because another tenant of the
         device held compute units), launch sequences captured / replayed from a graph / run as plain launches, ..., sym_pulls (pulls of a host P that moved its upper
-        tiles only and mirrored them on the device: every even n)."""
-        v = (C.c_int64 * 11)()
+        tiles only and mirrored them on the device: every even n), lists_in_place (in-place updates whose front end read the host-derived
+        index lists in the pinned arena itself, without the launch that pulls them into device memory)."""
+        v = (C.c_int64 * 12)()
         self.lib.orcvio_msckf_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
-        self._chk(self.lib.orcvio_msckf_counters(self.h, v, 11), 'orcvio_msckf_counters')
+        self._chk(self.lib.orcvio_msckf_counters(self.h, v, 12), 'orcvio_msckf_counters')
         return dict(front_fallbacks=int(v[0]), graph_captures=int(v[1]), graph_replays=int(v[2]), plain_runs=int(v[3]),
                     front_blocked_by_comm=int(v[4]), obj_fused=int(v[5]), chained_frames=int(v[6]), prestaged_frames=int(v[7]),
-                    step_frames=int(v[8]), step_repairs=int(v[9]), sym_pulls=int(v[10]))
+                    step_frames=int(v[8]), step_repairs=int(v[9]), sym_pulls=int(v[10]), lists_in_place=int(v[11]))
 
     def comm_info(self):
         r, w = C.c_int32(0), C.c_int32(0)

@@ -235,6 +235,7 @@ int32_t orcvio_msckf_run_update_sharded(orcvio_msckf_handle* h, void* stream) {
     if (ev) HIPCHK(hipEventRecord(ev[0], s));
     int rc = run_local_impl(h, s, mine);
     if (rc != ORCVIO_OK) return rc;
+    { const int rl = lists_refresh(h, s); if (rl != ORCVIO_OK) return rl; }   // (d_row_ptr; the tracks' launch has been through it already)
     hipLaunchKernelGGL(k_shard_meta, dim3(1), dim3(64), 0, s, mine + ne, h->shard_status, 0, h->F > 0 ? (const int*)h->d_accept : (const int*)nullptr,
                        (const int*)h->d_row_ptr, h->F, q, h->comm_rank);
     HIPCHK(hipGetLastError());

@@ -210,7 +210,10 @@ static int io_enqueue(orcvio_msckf_handle* h, hipStream_t s, bool want_P, bool c
     // inputs: the derived index arrays at the head of the arena (the caller-written part behind them went ahead: ingest_raw)
     int rc = ORCVIO_OK;
     // (the repeat of an armed update -- tri_live without c.tri -- pulls no more either: the positions in HBM are the device's own)
-    if (!c.already_ingested) rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, h->io_poses);
+    // (... and none where k_front reads the lists in the arena itself: lists_in_place_active -- the HBM copy is then an earlier upload's)
+    const bool in_place = lists_in_place_active(h, c);
+    if (!c.already_ingested && !in_place) rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, h->io_poses);
+    if (!in_place) h->lists_stale = false;   // (the whole head has travelled: this node, or k_frame_head)
     // the armed update's triangulation: ONE launch behind the pull of the arena, in front of the first kernel that reads p_w or d_skip
     if (rc == ORCVIO_OK && c.tri && !c.tri_prune) rc = launch_triangulate(h, &h->tri_cfg, false, true, s, true, h->tri_with_mode, false, nullptr);
     // ... the prune update's, out of its own list: behind the pose step and the pull, with the frame's kept status words to raise
@@ -302,15 +305,21 @@ static int io_launch(orcvio_msckf_handle* h, bool want_P, bool commit, UpdateCal
     h->last_stream = s;
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }
     const bool finpub = finpub_active(h, c) && !want_P;
+    c.io_single = true; c.fin_pub = finpub;   // (what io_enqueue is going to find: the predicate below is a function of the handle and this record)
+    const bool in_place = lists_in_place_active(h, c);
     int rc = run_with_graph(h, h->g_io, io_signature(h, s, want_P, commit, c, finpub), s, [&](bool) { return io_enqueue(h, s, want_P, commit, c, true); });
     h->A_deferred = front_defers_assembly(h, c.retry_forked);   // (a replayed graph does not pass through enqueue_update)
+    h->lists_stale = in_place;   // (... nor through io_enqueue: the launch has either pulled the three lists into HBM or read them in the arena)
+    if (in_place && rc == ORCVIO_OK) h->cnt_lists_in_place++;
     h->last_finpub_commit = commit && finpub;   // (... nor through io_enqueue)
     h->last_update_thin = finpub && thin_possible(h, c);
     if (h->last_update_thin) h->A_deferred = false;
     if (rc != ORCVIO_OK) return rc;
     h->pub_enqueued++;   // (one k_epilogue per launch, captured or not)
     h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false;
-    return arena_mark_read(h, s);   // (the arena's last reader is the ingest node at the head of that launch)
+    // (the event stands behind the WHOLE launch: its ingest node at the head reads the arena, and so does k_front where it reads the
+    //  derived lists in place -- its clone_ptr entries as late as the Gram items behind its device-wide barrier)
+    return arena_mark_read(h, s);
 }
 // ... second half: the results are in the pinned output block when this returns
 static int io_finish(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats);

@@ -1047,7 +1047,7 @@ int32_t orcvio_msckf_counters(orcvio_msckf_handle* h, int64_t* counters, int32_t
     if (!h || !counters || count < 1) { g_last_error = "counters: null argument"; return ORCVIO_ERR_INVALID; }
     const int64_t v[ORCVIO_COUNTERS] = {h->front_fallbacks, h->cnt_graph_captures, h->cnt_graph_replays, h->cnt_plain_runs,
                                         h->front_blocked_by_comm ? 1 : 0, h->obj_last_fused ? 1 : 0, h->cnt_chained, (int64_t)h->cnt_prestaged,
-                                        h->cnt_step_frames, h->cnt_step_repairs, h->cnt_sym_pulls};
+                                        h->cnt_step_frames, h->cnt_step_repairs, h->cnt_sym_pulls, h->cnt_lists_in_place};
     for (int i = 0; i < count && i < ORCVIO_COUNTERS; ++i) counters[i] = v[i];
     for (int i = ORCVIO_COUNTERS; i < count; ++i) counters[i] = 0;
     return ORCVIO_OK;

@@ -113,7 +113,7 @@ static int upload_finalize(orcvio_msckf_handle* h, const char* who) {
         unsigned bad = 0;
         std::vector<unsigned char>& is_run = h->track_is_run;
         is_run.resize(F > 0 ? F : 1);
-        const int o_first = F > 0 ? obs_ptr[0] : 0;   // (observations in front of obs_ptr[0] are carried along unused, but checked and placed)
+        const int o_first = F > 0 ? obs_ptr[0] : 0;   // (observations in front of obs_ptr[0] are carried along unused)
         for (int j = 0; j < F; ++j) {
             const int o0 = obs_ptr[j], M = obs_ptr[j + 1] - o0;
             const int* oc = obs_clone + o0;
@@ -133,17 +133,15 @@ static int upload_finalize(orcvio_msckf_handle* h, const char* who) {
                 }
             }
         }
-        for (int o = 0; o < o_first; ++o) {
-            const unsigned c = (unsigned)obs_clone[o];
-            bad |= (c >= (unsigned)N);
-            cnt[(c < (unsigned)N ? c : 0u) + 1]++;
-        }
+        // (... checked, NOT counted: no track writes their rows of Xobs, and a clone's Gram item sums every row of the clone's range --
+        //  counted, they brought whatever an earlier update had left at their positions into S)
+        for (int o = 0; o < o_first; ++o) bad |= ((unsigned)obs_clone[o] >= (unsigned)N);
         if (bad) { g_last_error = std::string(who) + ": obs_clone out of range"; return ORCVIO_ERR_INVALID; }
         for (int i = 0; i < N; ++i) cnt[i + 1] += cnt[i];
         int* clone_obs = reinterpret_cast<int*>(st + h->io_cobs);
         int fill[ORCVIO_MAX_CLONES + 2];
         std::memcpy(fill, cnt, sizeof(int) * (N + 1));
-        for (int o = 0; o < o_first; ++o) clone_obs[o] = fill[obs_clone[o]]++;
+        for (int o = 0; o < o_first; ++o) clone_obs[o] = 0;   // (never read: no track owns them)
         for (int j = 0; j < F; ++j) {
             const int o0 = obs_ptr[j], M = obs_ptr[j + 1] - o0;
             if (M <= 0) continue;
@@ -237,16 +235,43 @@ int32_t orcvio_msckf_upload(orcvio_msckf_handle* h, const orcvio_msckf_flags* fl
     // ONE asynchronous copy (no synchronisation: the staging buffer is rewritten only by the next upload, which the caller
     // issues after the download / sync of this update; the kernels are ordered behind the copy on the same stream)
     HIPCHK(hipMemcpyAsync(h->d_in, h->h_stage, upload_bytes(h), hipMemcpyHostToDevice, h->stream));
+    h->lists_stale = false;   // (the derived lists travel with the rest)
     return arena_mark_read(h, h->stream);
 }
 
 // ---- launches --------------------------------------------------------------------------------
-static FeatArgs feature_args(const orcvio_msckf_handle* h) {
+// The three lists upload_finalize derives on the host (row_ptr, clone_ptr, clone_obs) stand at the head of the pinned arena.  The plain
+// in-place update (io_launch) does not pull them into HBM: k_front reads clone_obs and clone_ptr where the host wrote them -- 120 bytes
+// per track and 8 per clone item, each loaded once and well ahead of its use (msckf_kernels.hpp, feature_body) -- and never reads
+// row_ptr (materialised stack only).  ONE predicate decides it for the enqueue, the launch signature and the host's flag; everything
+// else (the forked front end, the repeat of a lost hand-off, the frame calls, the thin form, armed updates, staged and sharded
+// updates, object updates) keeps the pull and its HBM pointers.
+static inline bool thin_possible(const orcvio_msckf_handle* h, const UpdateCall& c);
+static bool front_fused_active(const orcvio_msckf_handle* h, bool retry_forked);
+static inline bool lists_in_place_active(const orcvio_msckf_handle* h, const UpdateCall& c) {
+    return c.io_single && !c.already_ingested && front_fused_active(h, c.retry_forked) && !h->materialize && !(c.fin_pub && thin_possible(h, c)) &&
+           !c.tri && !c.tri_prune && !h->objects_mode;
+}
+// After such an update the HBM image of the lists is an earlier upload's (h->lists_stale; cleared wherever the whole head travels).  The
+// launches that read d_clone_obs / d_clone_ptr / d_row_ptr call this first: the pull the update left out, on their stream -- the repeat
+// of a lost hand-off inside the same call, a staged run_update behind an in-place update.  The arena holds the lists of the last
+// upload_finalize until the next one.
+static int lists_refresh(orcvio_msckf_handle* h, hipStream_t s) {
+    if (!h->lists_stale) return ORCVIO_OK;
+    h->lists_stale = false;
+    const int rc = launch_ingest(h, s, h->h_stage_dev, h->d_in, h->io_poses);
+    // (one more reader of the arena, never a node of a captured graph: launch_signature gives such a sequence no signature)
+    return rc == ORCVIO_OK ? arena_mark_read(h, s) : rc;
+}
+
+static FeatArgs feature_args(const orcvio_msckf_handle* h, bool lists_in_place = false) {
     FeatArgs a;
     a.poses = h->d_poses; a.p_w = h->d_pw; a.obs_ptr = h->d_obs_ptr; a.obs_clone = h->d_obs_clone;
-    a.obs_z = h->d_obs_z; a.obs_zvel = h->d_obs_zvel; a.P = h->d_P; a.row_ptr = h->d_row_ptr; a.chi2 = h->d_chi2;
+    a.obs_z = h->d_obs_z; a.obs_zvel = h->d_obs_zvel; a.P = h->d_P; a.chi2 = h->d_chi2;
+    a.row_ptr = h->d_row_ptr;   // (read with Hs only -- never by an update that reads its lists in place, whose HBM copy is stale)
+    a.obs_pos = lists_in_place ? reinterpret_cast<const int*>(h->h_stage_dev + h->io_cobs) : h->d_clone_obs;
     a.skip = h->skip_active ? h->d_skip : nullptr;
-    a.Hs = h->materialize ? h->d_Hs : nullptr; a.T3 = h->d_T3; a.Xobs = h->d_Xobs; a.obs_pos = h->d_clone_obs; a.gamma = h->d_gamma; a.accept = h->d_accept; a.Rf = h->d_Rf;
+    a.Hs = h->materialize ? h->d_Hs : nullptr; a.T3 = h->d_T3; a.Xobs = h->d_Xobs; a.gamma = h->d_gamma; a.accept = h->d_accept; a.Rf = h->d_Rf;
     a.sigma2 = h->flags.noise_feature * h->flags.noise_feature;
     a.n = h->n; a.leg = h->flags.leg_dim; a.N = h->N; a.NA = h->NA; a.NAP = h->NAP; a.Mmax = h->Mmax; a.F = h->F;
     a.use_larvio = h->flags.use_larvio; a.use_left = h->flags.use_left_perturbation; a.if_fej = h->flags.if_fej;
@@ -257,6 +282,7 @@ static FeatArgs feature_args(const orcvio_msckf_handle* h) {
 
 static int launch_feature(orcvio_msckf_handle* h, hipStream_t s) {
     if (h->F == 0) return ORCVIO_OK;
+    { const int rl = lists_refresh(h, s); if (rl != ORCVIO_OK) return rl; }
     const FeatArgs a = feature_args(h);
     const size_t lds = feat_lds_bytes(h->Mmax, h->NAP, h->N);
     const int npass = (h->NAP + 63) / 64;
@@ -308,7 +334,9 @@ static bool front_defers_assembly(const orcvio_msckf_handle* h, bool retry_forke
 // compress_dst != nullptr: the compression (Grams + assembly of A into compress_dst) runs inside the same launch;
 // grams_only: ... without the assembly (the caller's next kernel is k_gemm_asmA)
 static int launch_front(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c, double* compress_dst, bool grams_only = false) {
-    const FeatArgs a = feature_args(h);
+    const bool in_place = lists_in_place_active(h, c);
+    if (!in_place) { const int rl = lists_refresh(h, s); if (rl != ORCVIO_OK) return rl; }
+    const FeatArgs a = feature_args(h, in_place);
     const double eps = 2.220446049250313e-16;
     const int nfar = front_far_workgroups(h);
     FrontPotrfArgs q{h->d_P, h->n, h->n, 8.0 * eps, h->d_RP, h->NP, h->d_DinvP, h->d_info, h->use_factor ? 1 : 0, rev_prior_active(h) ? 1 : 0,
@@ -323,7 +351,7 @@ static int launch_front(orcvio_msckf_handle* h, hipStream_t s, UpdateCall& c, do
     g.chunks = front_row_chunks(h);
     h->front_chunks = g.chunks;
     g.rows_per_chunk = round_up((t3rows + g.chunks - 1) / g.chunks, 4);
-    g.Gpart = h->d_Gpart; g.S = h->d_S; g.clone_rows = h->d_clone_ptr; g.counter = h->d_sync; g.lost = h->d_info + 8;
+    g.Gpart = h->d_Gpart; g.S = h->d_S; g.clone_rows = in_place ? reinterpret_cast<const int*>(h->h_stage_dev + h->io_cptr) : h->d_clone_ptr; g.counter = h->d_sync; g.lost = h->d_info + 8;
     g.A_dst = compress_dst; g.cb0 = h->flags.leg_dim - 15; g.plus = extra_gram(h); g.spin_limit = h->front_spin_limit;
     g.started = c.front_mark; g.started_val = c.front_mark_val;
     if (g.enabled && g.chunks > h->gram_chunks_cap) { g_last_error = "launch_front: too many row chunks"; return ORCVIO_ERR_CAPACITY; }
@@ -371,6 +399,7 @@ static int launch_gram(orcvio_msckf_handle* h, hipStream_t s) {
         HIPCHK(hipMemsetAsync(h->d_Gpart, 0, sizeof(double) * (size_t)h->NAP * h->NAP, s));
         return ORCVIO_OK;
     }
+    { const int rl = lists_refresh(h, s); if (rl != ORCVIO_OK) return rl; }
     // grid.y < chunks: T3 tiles; grid.y == chunks: one workgroup per clone for the sparse rows
     dim3 grid(ntiles > h->N ? ntiles : h->N, h->chunks + 1), block(1024);
     hipLaunchKernelGGL(k_gram_pair, grid, block, 0, s, h->d_T3, 3 * h->F, h->NAP, h->rows_per_chunk, h->chunks, h->d_Gpart, h->d_Xobs,
@@ -786,6 +815,11 @@ static unsigned long long launch_signature(const orcvio_msckf_handle* h, hipStre
     mix(h->use_factor ? (unsigned long long)(size_t)h->d_Sres : 0ull);
     mix(h->tail); mix(rev_prior_active(h));
     mix((unsigned long long)(size_t)s); mix((unsigned long long)(size_t)p0); mix((unsigned long long)extra);
+    // k_front's list pointers are captured: the arena's (lists_in_place_active) or the HBM copy's.  A sequence that has to pull a stale
+    // HBM copy first (lists_refresh) gets NO signature -- plain launches, once: that pull is not part of the sequence's graph
+    const bool in_place = lists_in_place_active(h, c);
+    mix(in_place);
+    if (!in_place && h->lists_stale) return 0ull;
     return sig;
 }
 

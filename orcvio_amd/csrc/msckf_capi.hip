@@ -275,6 +275,8 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     unsigned chain_seq = 0u;
     long long cnt_chained = 0;          // frames whose object solve ran chained (orcvio_msckf_counters [6])
     long long cnt_sym_pulls = 0;        // pulls of a host P that took the upper-trapezoid form (launch_ingest_P; orcvio_msckf_counters [10])
+    long long cnt_lists_in_place = 0;   // updates whose k_front read row_ptr / clone_ptr / clone_obs in the pinned arena (lists_in_place_active; orcvio_msckf_counters [11])
+    bool lists_stale = false;           // ... and the HBM image of those three lists belongs to an earlier upload since: whoever reads it pulls it first (lists_refresh)
     bool frame_chain = true;            // ORCVIO_FRAME_CHAIN (read at create, default 1): orcvio_msckf_io_update_frame runs the object solve chained (capi_frame.inc)
     bool blk2_opt = true;               // ORCVIO_BLK2 (read at create): windows of 15 .. 26 block steps factor by 2 x 2 blocks out of the register kernels
     bool la_attr = false;               // the dynamic-LDS opt-in of k_potrf_solve_la is set for this handle's device
@@ -374,6 +376,7 @@ struct UpdateCall {
     bool fin_frame = false;             // the chained frame call is enqueueing its feature half (finish_fused_active)
     bool ekf_side = false;              // the step call's first update: the in-state rows beside k_front, on the side stream
     bool already_ingested = false;      // k_frame_head has pulled the arena of this update (io_enqueue skips its ingest launch)
+    bool io_single = false;             // io_launch's: ONE update on the arena, whose host-derived lists stay as they are until the launch has ended (lists_in_place_active)
     bool tri = false;                   // armed by orcvio_msckf_io_triangulate: k_triangulate behind the pull of the arena (io_enqueue; h->tri_cfg, h->tri_with_mode)
     bool tri_prune = false;             // ... by orcvio_msckf_io_triangulate_prune: the frame's second update (h->tri2_cfg, the staged list, the second block)
     unsigned* mark_M_word = nullptr;    // ST_FORM_M / ST_POTRF_M store mark_M_val there once M is formed, and put the pointer back to null: the caller

@@ -276,8 +276,14 @@ __host__ __device__ inline size_t feat_lds_bytes(int Mmax, int NAP, int N) {
     const int R2 = 2 * Mmax;
     size_t dbl = (size_t)R2 * 7 + (size_t)R2 * 6 + R2 + (size_t)R2 * 4 + 64 * 4 + 16 + 4 + 8 * (size_t)NAP + 272 + 272 +
                  (size_t)R2 * feat_lde(Mmax);
-    size_t bytes = dbl * 8 + (size_t)(N + Mmax + 4 + 2 * Mmax) * 4;   // (... | sC2O N | sOC Mmax | sFlag 4 | sDone Mmax | sLim Mmax)
+    size_t bytes = dbl * 8 + (size_t)(N + Mmax + 4 + 3 * Mmax + 2) * 4;   // (... | sC2O N | sOC Mmax | sFlag 4 | sDone Mmax | sLim Mmax | sPos Mmax | sPre 2)
     return (bytes + 15) & ~(size_t)15;
+}
+// sPos of a team's LDS block ([Mmax] obs_pos of the track's observations; the two ints behind it, sPre, are k_front's: feature_body's `pre`)
+__host__ __device__ inline size_t feat_lds_pos_offset(int Mmax, int NAP, int N) {
+    const int R2 = 2 * Mmax;
+    const size_t dbl = (size_t)R2 * 7 + (size_t)R2 * 6 + R2 + (size_t)R2 * 4 + 64 * 4 + 16 + 4 + 8 * (size_t)NAP + 272 + 272 + (size_t)R2 * feat_lde(Mmax);
+    return dbl * 8 + (size_t)(N + Mmax + 4 + 2 * Mmax) * 4;
 }
 
 // One workgroup of four wavefronts per feature track.
@@ -300,16 +306,28 @@ __host__ __device__ inline size_t feat_lds_bytes(int Mmax, int NAP, int N) {
 // feature_body: track j on the 256 threads `tid` = 0..255 of one four-wavefront team with its own LDS block; the
 // team is a whole workgroup (k_feature) or half of one (k_front).  Its three workgroup barriers are unconditional for a
 // live track, so two teams of one workgroup stay in step.
+// obs_pos may stand in pinned HOST memory (the in-place update reads the host's list where the host wrote it): every entry is loaded
+// ONCE, by wave 0 at the one point where that wavefront has no other global load to wait for (behind the Jacobians' inputs, in front of
+// the QR and the gate, which run out of LDS and registers -- the return counter is in order: a slow load in flight would hold up every
+// later wait of the wavefront), and goes through the team's LDS (sPos).  pre (k_front only, else nullptr): two more ints fetched by
+// two idle lanes of that same load into sPre behind sPos -- the caller reads them behind the body's last barrier.
 template <int NPASS, bool PAD_BARRIERS = false>
-__device__ __forceinline__ void feature_body(const FeatArgs& p, const int j, const int tid, double* __restrict__ smem) {
+__device__ __forceinline__ void feature_body(const FeatArgs& p, const int j, const int tid, double* __restrict__ smem, const int* __restrict__ pre = nullptr) {
     constexpr int NPD = (NPASS + 2) / 3;   // passes of the 192 threads of waves 1..3 over the NAP columns
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), t = tid & 63;
     const int lo = p.obs_ptr[j];
     const int M = p.obs_ptr[j + 1] - lo;
+    int* sPos = reinterpret_cast<int*>(reinterpret_cast<char*>(smem) + feat_lds_pos_offset(p.Mmax, p.NAP, p.N));   // [Mmax]
+    int* sPre = sPos + p.Mmax;                                                                                     // [2]
     if (M < 2 || (p.skip && p.skip[j])) {   // whole workgroup
         if (tid == 0) { p.gamma[j] = NAN; p.accept[j] = 0; }
+        if (pre && tid < 2) sPre[tid] = pre[tid];
         for (int e = tid; e < 3 * p.NAP; e += 256) st_pub<PAD_BARRIERS>(&p.T3[(size_t)3 * j * p.NAP + e], 0.0);
-        for (int e = tid; e < 32 * M; e += 256) st_pub<PAD_BARRIERS>(&p.Xobs[(size_t)32 * p.obs_pos[lo + (e >> 5)] + (e & 31)], 0.0);
+        const int pos_t = t < M ? p.obs_pos[lo + t] : 0;   // (once per observation and wavefront: M <= ORCVIO_MAX_TRACK = 32 lanes)
+        for (int e0 = 64 * wave; e0 < 32 * M; e0 += 256) {   // (wave-uniform trips: every lane takes part in the shuffle)
+            const int e = e0 + t, pos = __shfl(pos_t, e >> 5);
+            if (e < 32 * M) st_pub<PAD_BARRIERS>(&p.Xobs[(size_t)32 * pos + (e & 31)], 0.0);
+        }
         if (p.Hs) {   // a track dropped by the triangulation still owns rows of the materialised stack: zero them
             const size_t r0 = (size_t)p.row_ptr[j], r1 = (size_t)p.row_ptr[j + 1];
             for (size_t e = r0 * p.NAP + tid; e < r1 * p.NAP; e += 256) p.Hs[e] = 0.0;
@@ -343,7 +361,7 @@ __device__ __forceinline__ void feature_body(const FeatArgs& p, const int j, con
     int* sLim = sDone + p.Mmax;                   // [Mmax] columns of P that observation l needs: [0, sLim[l]) (upper triangle of E only)
 
     for (int i = tid; i < p.N; i += 256) sC2O[i] = -1;
-    for (int i = tid; i < p.Mmax; i += 256) sDone[i] = 0;
+    for (int i = tid; i < p.Mmax; i += 256) { sDone[i] = 0; sPos[i] = 0; }   // (sPos: an in-range position whatever happens)
     if (tid == 0) { sFlag[1] = 0; sFlag[2] = 0; }
     __syncthreads();
 
@@ -386,6 +404,13 @@ __device__ __forceinline__ void feature_body(const FeatArgs& p, const int j, con
     __syncthreads();   // the Jacobians are all phase E needs: waves 1..3 start on it while wave 0 does the QR
 
     if (wave == 0) {
+        // obs_pos of observation t (and the caller's two ints on lanes 62, 63: M <= 32), issued here: nothing this wavefront waits
+        // for until the gate's end is a global load, so the latency of a read from host memory passes under the QR
+        int pos_t = 0;
+        {
+            const int* src = t < M ? p.obs_pos + lo + t : ((pre && t >= 62) ? pre + (t - 62) : nullptr);
+            if (src) pos_t = *src;
+        }
         // ---- C: Householder QR of H_f (2M x 3), LAPACK dgeqr2 convention ------------------
         const int g0 = 2 * t, g1 = 2 * t + 1;
         double v0[3], v1[3], beta[3], rdiag[3];
@@ -448,8 +473,10 @@ __device__ __forceinline__ void feature_body(const FeatArgs& p, const int j, con
 #pragma unroll
             for (int q = 0; q < 4; ++q) sB[t * 4 + q] = b4[q];
         }
+        if (t < M) sPos[t] = pos_t;
+        else if (pre && t >= 62) sPre[t - 62] = pos_t;
         wave_sync();
-        if (t == 0) __hip_atomic_store(&sFlag[2], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);   // sV, sQ, sB are final (phase D reads them)
+        if (t == 0) __hip_atomic_store(&sFlag[2], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);   // sV, sQ, sB, sPos are final (phase D and the outputs of waves 1..3 read them)
     }
 
     // ---- E: E = J P_aa J^T (waves 1..3; wave 0 factors the block columns of E + s2 I as they complete, phase G).
@@ -790,7 +817,7 @@ __device__ __forceinline__ void feature_body(const FeatArgs& p, const int j, con
             const int row = e >> 4, c = e & 15;
             double v = 0.0;
             if (live && c < 14) v = (c < 7) ? sJe[row * 7 + c] : ((c < 13) ? sJx[row * 6 + (c - 7)] : sR[row]);
-            st_pub<PAD_BARRIERS>(&p.Xobs[(size_t)32 * p.obs_pos[lo + (row >> 1)] + 16 * (row & 1) + c], v);
+            st_pub<PAD_BARRIERS>(&p.Xobs[(size_t)32 * sPos[row >> 1] + 16 * (row & 1) + c], v);
         }
     };
     if (outputs && wave > 0) { write_t3(true); write_xobs(true); }
@@ -2241,13 +2268,24 @@ __global__ __launch_bounds__(512) void k_front(FeatArgs p, FrontPotrfArgs q, int
     const int team = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
     const int j = 2 * ((int)blockIdx.x - 1 - q.nfar) + team;
     const int local = threadIdx.x & 255;
+    const int nfb = (int)gridDim.x - 1 - q.nfar, me = (int)blockIdx.x - 1 - q.nfar;
+    // The two clone_rows entries of this workgroup's FIRST Gram item, if that is a clone item, are fetched ahead of the device-wide
+    // barrier (they may stand in host memory): by team 0's track at its quiet point (feature_body's pre), or right here by a
+    // workgroup without tracks, which has nothing else to wait for.
+    const int first_clone = g.enabled ? me - (p.NAP >> 4) * ((p.NAP >> 4) + 1) / 2 * g.chunks : -1;
+    const int* pre = (first_clone >= 0 && first_clone < p.N) ? g.clone_rows + first_clone : nullptr;
+    int pre0 = 0, pre1 = 0;
     if (j < p.F) {
-        feature_body<NPASS, true>(p, j, team ? ((local + 128) & 255) : local, smem + (size_t)team * team_doubles);
-    } else {   // (an odd track count: the last workgroup has one team)
+        feature_body<NPASS, true>(p, j, team ? ((local + 128) & 255) : local, smem + (size_t)team * team_doubles, team ? nullptr : pre);
+    } else {   // (an odd track count: the last workgroup has one team; more workgroups than track pairs: neither)
+        if (pre && 2 * me >= p.F) { pre0 = pre[0]; pre1 = pre[1]; }
         __syncthreads(); __syncthreads(); __syncthreads();
     }
     if (!g.enabled) return;
-    const int nfb = (int)gridDim.x - 1 - q.nfar, me = (int)blockIdx.x - 1 - q.nfar;
+    if (pre && 2 * me < p.F) {   // (team 0 has left them in its LDS block, in front of the body's last barrier)
+        const int* sPre = reinterpret_cast<const int*>(reinterpret_cast<const char*>(smem) + feat_lds_pos_offset(p.Mmax, p.NAP, p.N)) + p.Mmax;
+        pre0 = sPre[0]; pre1 = sPre[1];
+    }
     unsigned long long* stamp = reinterpret_cast<unsigned long long*>(g.counter) + 8;   // diagnostic (bytes 64..): 100 MHz clock
 #define FRONT_STAMP(i) do { if (me == 0 && threadIdx.x == 0) stamp[i] = wall_clock64(); } while (0)
     FRONT_STAMP(1);
@@ -2268,7 +2306,9 @@ __global__ __launch_bounds__(512) void k_front(FeatArgs p, FrontPotrfArgs q, int
             gramw_body<8, 20, true, true>(smem, p.T3, p.NAP, r0, r1 > r0 ? r1 : r0, bi, bj, g.Gpart + (size_t)ch * p.NAP * p.NAP, p.NAP);
         } else {
             const int c = it - ntiles * g.chunks;
-            gramw_body<8, 20, true>(smem, p.Xobs, 16, g.clone_rows[c], g.clone_rows[c + 1], 0, 0, g.S + (size_t)c * 256, 16);
+            // (the first item's two entries came in ahead of the barrier; a further round -- fewer workgroups than items -- loads directly)
+            const int cr0 = it == me ? pre0 : g.clone_rows[c], cr1 = it == me ? pre1 : g.clone_rows[c + 1];
+            gramw_body<8, 20, true>(smem, p.Xobs, 16, cr0, cr1, 0, 0, g.S + (size_t)c * 256, 16);
         }
         __syncthreads();   // the reduction buffer is reused by the next item
     }
