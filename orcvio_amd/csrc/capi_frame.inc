@@ -142,7 +142,7 @@ static int frame_chain_finish(orcvio_msckf_handle* h, const ChainGeom& g, int do
     h->pub_pending = true;
     h->pub_enqueued++;
     h->commit_update(n, kf, ldz, g.tail, false, FacAfter::adopt);
-    h->ran = true; h->last_update_objects = true; h->last_run_kind = 2; h->last_sharded = false;
+    mark_update_enqueued(h, 2);
     h->last_stream = sb;
     h->cnt_chained++;
     return ORCVIO_OK;
@@ -195,10 +195,9 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     if (res_f->P_out || res_f->K || res_f->G || res_f->H_thin || res_f->r_thin) { g_last_error = std::string(who) + ": the feature half returns dx, gamma, accept and stats (P+ stays resident)"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     static const bool overlap = [] { const char* e = getenv("ORCVIO_FRAME_OVERLAP"); return !e || atoi(e) != 0; }();   // 0: the two calls in sequence
-    static const bool timing = dbg_getenv("ORCVIO_TIMING") != nullptr;   // diagnostics: host wall time of the parts of this call, microseconds after its start
-    const auto tf0 = std::chrono::steady_clock::now();
-    double tfs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto tmark = [&](int i) { if (timing) tfs[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tf0).count(); };
+    PhaseTimer timer;   // diagnostics (ORCVIO_TIMING): host wall time of the parts of THIS call, microseconds after its start
+    PhaseTimer::Run tm = PhaseTimer::begin(&timer);
+    auto tmark = [&](int i) { tm.mark(i); };
     int rc = ingest_raw(h, h->stream);   // what the caller wrote travels while the host checks it
     if (rc == ORCVIO_OK) rc = upload_finalize(h, who);
     if (rc != ORCVIO_OK) { (void)arena_mark_read(h, h->stream); return rc; }   // (the early pull may still be reading the arena)
@@ -318,7 +317,7 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     }
     h->pub_enqueued++;
     const unsigned long long feat_pub = h->pub_enqueued;   // (the feature half's publication: what io_wait below waits for)
-    h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false;
+    mark_update_enqueued(h, 0);
     // (No event behind the arena's last reader here -- the ingest kernels at the head of the feature half: a hipEventRecord costs ~5 us of
     //  stream time, and it would stand between the feature half's epilogue and the object solve.  This call does not return before the
     //  feature half has published -- behind its ingest -- or, on the failure paths below, before the streams are drained: the arena is
@@ -407,8 +406,8 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     }
     rc = orcvio_msckf_objects_download(h, res_o);
     tmark(5);
-    if (timing) fprintf(stderr, "io_update_frame: ingest + checks %.1f | feature half + compression%s enqueued %.1f | object bookkeeping %.1f | object solve enqueued %.1f | feature results %.1f | object results %.1f us\n",
-                        tfs[0], chain ? " + chained solve" : "", tfs[1], tfs[2], tfs[3], tfs[4], tfs[5]);
+    if (timer.due(1)) fprintf(stderr, "io_update_frame: ingest + checks %.1f | feature half + compression%s enqueued %.1f | object bookkeeping %.1f | object solve enqueued %.1f | feature results %.1f | object results %.1f us\n",
+                              timer.mean(0, 1), chain ? " + chained solve" : "", timer.mean(1, 1), timer.mean(2, 1), timer.mean(3, 1), timer.mean(4, 1), timer.mean(5, 1));
     h->out_shift = 0;
     h->objects_mode = false;
     if (chain) {   // (the chained object solve ran on the objects' stream, with status words of its own)

@@ -605,7 +605,7 @@ static int run_update_impl(orcvio_msckf_handle* h, void* stream, UpdateCall& c) 
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }   // (a copy of the previous results nobody fetched)
     int rc = run_with_graph(h, h->g_update, launch_signature(h, s, nullptr, 0, c), s, [&](bool) { return enqueue_update(h, s, c); });
     h->A_deferred = front_defers_assembly(h, c.retry_forked);   // (a replayed graph does not pass through enqueue_update)
-    if (rc == ORCVIO_OK) { h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false; }
+    if (rc == ORCVIO_OK) mark_update_enqueued(h, 0);
     return rc;
 }
 int32_t orcvio_msckf_run_update(orcvio_msckf_handle* h, void* stream) {

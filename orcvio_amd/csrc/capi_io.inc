@@ -316,7 +316,7 @@ static int io_launch(orcvio_msckf_handle* h, bool want_P, bool commit, UpdateCal
     if (h->last_update_thin) h->A_deferred = false;
     if (rc != ORCVIO_OK) return rc;
     h->pub_enqueued++;   // (one k_epilogue per launch, captured or not)
-    h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false;
+    mark_update_enqueued(h, 0);
     // (the event stands behind the WHOLE launch: its ingest node at the head reads the arena, and so does k_front where it reads the
     //  derived lists in place -- its clone_ptr entries as late as the Gram items behind its device-wide barrier)
     return arena_mark_read(h, s);
@@ -324,17 +324,16 @@ static int io_launch(orcvio_msckf_handle* h, bool want_P, bool commit, UpdateCal
 // ... second half: the results are in the pinned output block when this returns
 static int io_finish(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats);
 static int io_run(orcvio_msckf_handle* h, bool want_P, bool commit, int32_t* stats, UpdateCall& c) {
-    static const bool timing = dbg_getenv("ORCVIO_TIMING") != nullptr;
-    const auto tl0 = std::chrono::steady_clock::now();
+    static PhaseTimer timer;   // diagnostics (ORCVIO_TIMING): the means of 64 calls
+    PhaseTimer::Run tm = PhaseTimer::begin(&timer);
     int rc = io_launch(h, want_P, commit, c);
     if (rc != ORCVIO_OK) return rc;
-    const auto tl1 = std::chrono::steady_clock::now();
+    tm.mark(0);
     rc = io_finish(h, want_P, commit, stats);
-    if (timing) {
-        static int calls = 0;
-        if ((++calls % 64) == 0)
-            fprintf(stderr, "io_run: launch %.1f us, wait + outcome %.1f us\n", std::chrono::duration<double, std::micro>(tl1 - tl0).count(),
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl1).count());
+    tm.mark(1);
+    if (timer.due(64)) {
+        fprintf(stderr, "io_run: launch %.1f us, wait + outcome %.1f us\n", timer.mean(0, 64), timer.mean(1, 64) - timer.mean(0, 64));
+        timer.reset();
     }
     return rc;
 }
@@ -406,18 +405,17 @@ int32_t orcvio_msckf_io_begin(orcvio_msckf_handle* h, const orcvio_msckf_flags* 
 int32_t orcvio_msckf_io_update(orcvio_msckf_handle* h, int32_t want_P, int32_t commit, int32_t* stats) {
     if (!h || !h->io_open) { g_last_error = "io_update: call orcvio_msckf_io_begin first"; return ORCVIO_ERR_INVALID; }
     if (h->io_submitted) { g_last_error = "io_update: an update submitted with orcvio_msckf_io_submit has not been collected"; return ORCVIO_ERR_INVALID; }
-    static const bool timing = dbg_getenv("ORCVIO_TIMING") != nullptr;
-    const auto tf0 = std::chrono::steady_clock::now();
+    static PhaseTimer timer;   // diagnostics (ORCVIO_TIMING): the means of 64 calls
+    PhaseTimer::Run tm = PhaseTimer::begin(&timer);
     HIPCHK(hipSetDevice(h->device));
     int rc = ingest_raw(h, h->stream);   // what the caller wrote travels while the host checks it
     if (rc != ORCVIO_OK) return rc;
-    const auto tf1 = std::chrono::steady_clock::now();
+    tm.mark(0);
     rc = upload_finalize(h, "orcvio_msckf_io_update");
-    if (timing) {
-        static int calls = 0;
-        if ((++calls % 64) == 0)
-            fprintf(stderr, "io_update: set device %.1f us, finalize %.1f us\n", std::chrono::duration<double, std::micro>(tf1 - tf0).count(),
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tf1).count());
+    tm.mark(1);
+    if (timer.due(64)) {
+        fprintf(stderr, "io_update: set device %.1f us, finalize %.1f us\n", timer.mean(0, 64), timer.mean(1, 64) - timer.mean(0, 64));
+        timer.reset();
     }
     if (rc != ORCVIO_OK) {   // (the arena keeps its layout: the caller may repair its arrays and call again -- once the early pull
                              //  of what it wrote, still in flight, has read the arena: the next writer waits for this event, ADVICE r3)

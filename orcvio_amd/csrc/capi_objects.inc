@@ -938,7 +938,7 @@ static int objects_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, i
     prof_mark(h, s, "k_gemm(U)+k_gemm(M)+k_potrf_solve(M)");
     rc = launch_solve_stage(h, s, ST_FINISH, c);
     prof_mark(h, s, "k_finish_sqrt (gate inside)");
-    if (rc == ORCVIO_OK) { h->ran = true; h->last_update_objects = true; h->last_run_kind = 2; h->last_sharded = meta0 != nullptr; }
+    if (rc == ORCVIO_OK) mark_update_enqueued(h, 2, meta0 != nullptr);
     return rc;
 }
 

@@ -168,7 +168,8 @@ int32_t orcvio_msckf_triangulate(orcvio_msckf_handle* h, const orcvio_triangulat
     hipStream_t s = h->stream;
     // this call owns the track buffers: whatever was uploaded for an update is gone
     h->uploaded = false; h->ran = false; h->skip_active = false; h->objects_mode = false; h->io_open = false;
-    h->tri_armed = false; h->tri2_armed = false; h->tri_live = false; h->tri_refuse_empty = false; h->tri_live_prune = false;
+    drop_one_shot_armings(h);
+    h->tri_live = false; h->tri_refuse_empty = false; h->tri_live_prune = false;
     h->N = N; h->F = F; h->nobs = nobs;
     HIPCHK(hipStreamSynchronize(s));
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }

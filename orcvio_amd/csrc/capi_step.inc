@@ -121,12 +121,12 @@ static int launch_change_anchors(orcvio_msckf_handle* h, hipStream_t s, const St
 }
 
 struct StepSecond {   // what the second update of the frame needs besides the handle
-    const orcvio_msckf_tracks* tr;
-    const double* posesA;   // device: the first update's window poses
-    const double* dxA;      // device: its dx
-    const int* infoA;       // device: its status words
-    int apply_dx;
-    const StepEvents* ev;   // anchor changes between the pose step and the update (nullptr: none)
+    const orcvio_msckf_tracks* tr = nullptr;
+    const double* posesA = nullptr;   // device: the first update's window poses
+    const double* dxA = nullptr;      // device: its dx
+    const int* infoA = nullptr;       // device: its status words
+    int apply_dx = 0;
+    const StepEvents* ev = nullptr;   // anchor changes between the pose step and the update (nullptr: none)
     const int* also = nullptr;   // the armed IMU launch's status block: its refusal goes into the kept status words (PoseStepArgs.also)
     bool tri = false;            // armed by orcvio_msckf_io_triangulate_prune: k_triangulate on the staged list in front of the update
     const StepChoice* cc = nullptr;   // armed by orcvio_msckf_io_choose_clones: k_clone_choice directly behind the pose step
@@ -135,9 +135,29 @@ struct StepSecond {   // what the second update of the frame needs besides the h
 static inline size_t tri2_list_bytes(const orcvio_msckf_handle* h) { return tri_list_layout(h->tri2_F, h->tri2_nobs).bytes; }
 static inline const char* tri2_list_src(const orcvio_msckf_handle* h) { return h->h_tri2_dev + tri_prune_layout(h->maxF, h->maxObs).list; }
 
-// the second update's inputs into the (swapped-in) second arena and its launches; `wait` = run it the safe way (separate launches, the
-// forked front end, the outcome checked and the commit made by the host) -- the repair path
-static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& fl, int N, const StepSecond& b, bool safe, int32_t* stats, const char* who) {
+// window poses behind the first update: its own, on the device (incremented by its dx or copied) into `out`; the first update's status
+// words are kept -- not on the repair path (safe): the host has run the first update again or read its outcome
+static inline PoseStepArgs step_pose_args(const orcvio_msckf_handle* h, const orcvio_msckf_flags& fl, int N, const StepSecond& b, double* out, bool safe) {
+    return PoseStepArgs{b.posesA, out, N, POSE_STRIDE, b.dxA, fl.leg_dim, b.apply_dx, (fl.use_larvio || fl.use_left_perturbation) ? 1 : 0,
+                        fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words, safe ? (const int*)nullptr : b.also};
+}
+
+// An update of the frame has been enqueued (rc: what io_enqueue returned): the launch counters, the marks and the commit's bookkeeping,
+// which rides in the update's last launch.  Returns the publication to wait for; 0: the enqueue failed, nothing counted.
+static unsigned long long frame_update_enqueued(orcvio_msckf_handle* h, int rc) {
+    h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h, false);
+    if (rc != ORCVIO_OK) return 0;
+    h->cnt_plain_runs++;
+    h->pub_enqueued++;
+    mark_update_enqueued(h, 0);
+    commit_bookkeeping(h);
+    return h->pub_enqueued;
+}
+
+// The second update, the part both of its forms share: its inputs into the (swapped-in) second arena, the pose-step arguments, the
+// validation.  separate (ORCVIO_STEP_FUSED=0, the repair path): the pose step and the pulls go out as launches of their own, in front
+// of the host's validation -- they travel while it runs; the fused head pulls the derived index arrays too and goes out behind it.
+static int step_second_stage(orcvio_msckf_handle* h, const orcvio_msckf_flags& fl, int N, const StepSecond& b, bool safe, PoseStepArgs& ps, const char* who) {
     hipStream_t s = h->stream;
     const orcvio_msckf_tracks* tr = b.tr;
     const int F2 = tr->n_features, nobs2 = F2 > 0 ? tr->obs_ptr[F2] : 0;
@@ -153,12 +173,9 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
             if (h->io_zvel != h->io_z) std::memcpy(st + h->io_zvel, tr->obs_zvel, sizeof(double) * 2 * nobs2);
         }
     }
-    // window poses: the first update's, on the device (incremented by its dx or copied); the first update's status words are kept
-    PoseStepArgs ps{b.posesA, h->d_poses, N, POSE_STRIDE, b.dxA, fl.leg_dim, b.apply_dx, (fl.use_larvio || fl.use_left_perturbation) ? 1 : 0,
-                    fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words, safe ? (const int*)nullptr : b.also};
-    const bool events = b.ev && b.ev->k > 0;
+    ps = step_pose_args(h, fl, N, b, h->d_poses, safe);
     if (!h->step_fused || safe) {
-        if (events) hipLaunchKernelGGL(k_event_step, dim3(1), dim3(128), 0, s, ps, b.ev->fs);
+        if (b.ev && b.ev->k > 0) hipLaunchKernelGGL(k_event_step, dim3(1), dim3(128), 0, s, ps, b.ev->fs);
         else hipLaunchKernelGGL(k_pose_step, dim3(1), dim3(64), 0, s, ps);
         HIPCHK(hipGetLastError());
         // everything the caller's tracks hold, behind the poses
@@ -166,35 +183,19 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
         if (rc == ORCVIO_OK && b.tri) rc = launch_ingest(h, s, tri2_list_src(h), h->d_tri2_list, tri2_list_bytes(h));   // (the separate launches' form of the head's segment)
         if (rc != ORCVIO_OK) return rc;
     }
-    if (rc == ORCVIO_OK) rc = upload_finalize(h, who);
+    rc = upload_finalize(h, who);
     if (rc != ORCVIO_OK) return rc;
     h->pw_missing = false;
-    if (safe) {
-        if (b.cc) {   // the same launch, the same bits; the host reads the verdict itself: on a disagreement nothing of the second half runs
-            // (no status words: the host has run the first update again or read its outcome, and comes here only behind a committed one)
-            rc = launch_clone_choice(h, s, fl, N, *b.cc, h->d_poses, b.dxA, b.apply_dx, nullptr, false);
-            if (rc == ORCVIO_OK) rc = clone_choice_collect(h, s);
-            if (rc != ORCVIO_OK) return rc;
-            if (!cc_block(h)->agree) {
-                std::memset(h->h_stage + h->in_cap, 0, h->outs_small);   // (prune_dx = 0, no status words)
-                return ORCVIO_OK;
-            }
-        }
-        if (events) {   // the repair path waits anyway: the changed features' status is read before the update goes out
-            rc = launch_change_anchors(h, s, *b.ev, h->d_poses, nullptr, false, false);
-            if (rc != ORCVIO_OK) return rc;
-            HIPCHK(hipStreamSynchronize(s));
-            if (*evt_status_host(h) != 0) { g_last_error = std::string(who) + ": a changed feature's position is not finite: no anchor change, no prune update"; return ORCVIO_ERR_NOT_SPD; }
-        }
-        if (b.tri) {   // triangulated again: a lost FIRST update left the poses of the attempt without its dx (same poses, same bits otherwise)
-            UpdateCall ct;
-            ct.retry_forked = true;
-            tri_consume_prune(h, ct);
-            rc = launch_triangulate(h, &h->tri2_cfg, false, true, s, true, true, true, nullptr);
-            if (rc != ORCVIO_OK) return rc;
-        }
-        return io_run_forked(h, stats);
-    }
+    return ORCVIO_OK;
+}
+
+// ... enqueued behind the first update, nothing waited for (the one-pass form).  *pub: the publication to wait for.
+static int step_second_enqueue(orcvio_msckf_handle* h, const orcvio_msckf_flags& fl, int N, const StepSecond& b, unsigned long long* pub, const char* who) {
+    hipStream_t s = h->stream;
+    PoseStepArgs ps;
+    int rc = step_second_stage(h, fl, N, b, false, ps, who);
+    if (rc != ORCVIO_OK) return rc;
+    const bool events = b.ev && b.ev->k > 0;
     h->last_stream = s;
     if (h->step_fused) {   // ONE launch in front of the update: the pose step and the pull of the tracks + derived index arrays
         FrameHeadArgs fa{};
@@ -220,13 +221,40 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
     c.info_also = h->d_step_words;        // (a refused first update refuses this update's commit as well)
     if (b.tri) tri_consume_prune(h, c);   // (k_triangulate behind the pull and the anchor change, in front of the tracks' launch: io_enqueue)
     rc = io_enqueue(h, s, false, true, c, true);
-    h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h, false);
+    *pub = frame_update_enqueued(h, rc);
+    return rc;
+}
+
+// ... run the safe way on the repair path: separate launches, the forked front end, the outcome checked and the commit made by the host
+static int step_second_safe(orcvio_msckf_handle* h, const orcvio_msckf_flags& fl, int N, const StepSecond& b, int32_t* stats, const char* who) {
+    hipStream_t s = h->stream;
+    PoseStepArgs ps;
+    int rc = step_second_stage(h, fl, N, b, true, ps, who);
     if (rc != ORCVIO_OK) return rc;
-    h->cnt_plain_runs++;
-    h->pub_enqueued++;
-    h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false;
-    commit_bookkeeping(h);
-    return ORCVIO_OK;
+    if (b.cc) {   // the same launch, the same bits; the host reads the verdict itself: on a disagreement nothing of the second half runs
+        // (no status words: the host has run the first update again or read its outcome, and comes here only behind a committed one)
+        rc = launch_clone_choice(h, s, fl, N, *b.cc, h->d_poses, b.dxA, b.apply_dx, nullptr, false);
+        if (rc == ORCVIO_OK) rc = clone_choice_collect(h, s);
+        if (rc != ORCVIO_OK) return rc;
+        if (!cc_block(h)->agree) {
+            std::memset(h->h_stage + h->in_cap, 0, h->outs_small);   // (prune_dx = 0, no status words)
+            return ORCVIO_OK;
+        }
+    }
+    if (b.ev && b.ev->k > 0) {   // the repair path waits anyway: the changed features' status is read before the update goes out
+        rc = launch_change_anchors(h, s, *b.ev, h->d_poses, nullptr, false, false);
+        if (rc != ORCVIO_OK) return rc;
+        HIPCHK(hipStreamSynchronize(s));
+        if (*evt_status_host(h) != 0) { g_last_error = std::string(who) + ": a changed feature's position is not finite: no anchor change, no prune update"; return ORCVIO_ERR_NOT_SPD; }
+    }
+    if (b.tri) {   // triangulated again: a lost FIRST update left the poses of the attempt without its dx (same poses, same bits otherwise)
+        UpdateCall ct;
+        ct.retry_forked = true;
+        tri_consume_prune(h, ct);
+        rc = launch_triangulate(h, &h->tri2_cfg, false, true, s, true, true, true, nullptr);
+        if (rc != ORCVIO_OK) return rc;
+    }
+    return io_run_forked(h, stats);
 }
 
 // A frame without a second update that carries anchor changes: the pose step into the events' own pose records, the feature step and
@@ -234,8 +262,7 @@ static int step_second_update(orcvio_msckf_handle* h, const orcvio_msckf_flags& 
 // raises the flag.  safe: the repair path (no kept status words: the first update has been run again and checked by the host).
 static int step_events_alone(orcvio_msckf_handle* h, hipStream_t s, const orcvio_msckf_flags& fl, int N, const StepSecond& b, bool safe, bool publish) {
     double* poses = reinterpret_cast<double*>(h->d_evt + EVT_D_POSES);
-    PoseStepArgs ps{b.posesA, poses, N, POSE_STRIDE, b.dxA, fl.leg_dim, b.apply_dx, (fl.use_larvio || fl.use_left_perturbation) ? 1 : 0,
-                    fl.discard_large_update, b.infoA, safe ? (int*)nullptr : h->d_step_words, safe ? (const int*)nullptr : b.also};
+    const PoseStepArgs ps = step_pose_args(h, fl, N, b, poses, safe);
     hipLaunchKernelGGL(k_event_step, dim3(1), dim3(128), 0, s, ps, b.ev->fs);
     HIPCHK(hipGetLastError());
     return launch_change_anchors(h, s, *b.ev, poses, safe ? (const int*)nullptr : h->d_step_words, false, publish);
@@ -307,32 +334,94 @@ static int step_validate_events(orcvio_msckf_handle* h, const orcvio_msckf_frame
     return ORCVIO_OK;   // (fs.slam / fs.cap: once the records' device buffers stand, slam_prepare)
 }
 
-// One implementation behind both calls: ev == nullptr (or empty) is orcvio_msckf_io_step_frame.
-static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* st, const orcvio_msckf_frame_events* ev, orcvio_msckf_frame_result* res,
-                           orcvio_msckf_frame_result_ex* rex, const char* who) {
-    if (!h || !st || !res) { g_last_error = std::string(who) + ": null argument"; return ORCVIO_ERR_INVALID; }
+// ---- one frame: its record, its phases, its one exit ---------------------------------------------------------------------------------
+// What ONE call of step_frame_impl knows, on that call's stack and passed by reference through the phases below (as UpdateCall is for
+// one update).  Nothing of it is state of the filter or kept in the handle: it dies with the call.
+enum { PLAN_HEAD_FAC, PLAN_PROPAGATE, PLAN_AUGMENT, PLAN_GATHER };
+struct FrameRun {
+    // ---- the arguments
+    const orcvio_msckf_frame_step* st = nullptr;
+    const orcvio_msckf_frame_events* ev = nullptr;
+    orcvio_msckf_frame_result* res = nullptr;
+    orcvio_msckf_frame_result_ex* rex = nullptr;
+    const char* who = "";
+    // ---- set by the checks (frame_check)
+    orcvio_msckf_flags fl{};
+    int leg = 0, N = 0, n = 0;
+    bool imu = false, tri2 = false, cc = false;   // the armings found on the handle (io_propagate_imu, io_triangulate_prune, io_choose_clones): taken in frame_head
+    bool prop = false;                            // the frame propagates (Phi / Q given, or made on the device by the armed launch)
+    StepEvents evs;
+    int d_lost = 0;                               // states that leave in front of the first update
+    // ---- left by frame_head
+    bool begun = false;                           // nothing can refuse the frame any more: the armings are taken, launches go out (frame_leave)
+    bool fused = false;
+    FrameHeadArgs fa{};
+    struct { int kind; CovEdit e; } plan[3];      // (fused: the factor's launch behind the head; unfused: propagation, augmentation, lost features)
+    int n_plan = 0;
+    std::vector<int> lost_map;                    // (the unfused removal's index map, staged when its launch goes out)
+    int aug_pose = 0;                             // the new clone: in front of the feature states as they are BEFORE the removal
+    StepChoice choice{};
+    const int* imu_also = nullptr;                // the armed IMU launch's status block (a refused Phi refuses both updates' commits)
+    CovState cov0, cov_before_second, cov_before_remove;   // the covariance's bookkeeping at entry, behind the first update, behind the second
+    // ---- left by frame_first: what the first update's outcome needs on the host once the handle's fields belong to the second
+    bool first = false;
+    FeatureView vA{};
+    const char* soA = nullptr;
+    const double *posesA = nullptr, *dxA = nullptr;
+    const int* infoA = nullptr;
+    int FA = 0, nobsA = 0;
+    bool tri_frame = false, tri_frame_empty = false;   // the first update triangulates its own tracks (orcvio_msckf_io_triangulate)
+    // ---- left by frame_second_half
+    bool second = false;
+    StepSecond sb;
+    FeatureView vB{};
+    const char* soB = nullptr;
+    unsigned long long pubA = 0, pubB = 0, pubE = 0;   // the publications of the first update, the second, the anchor change alone
+    int rcB = ORCVIO_OK, rcR = ORCVIO_OK;              // what enqueueing the second half / the marginalisation returned
+    // ---- left by frame_results
+    bool held = false;            // the choice's verdict: the second half was (or is to be) held back -- no anchor change, no prune update, no marginalisation
+    bool lostA = false, lostB = false, imu_bad = false;
+    PhaseTimer::Run tm;           // ORCVIO_TIMING
+};
+
+// The one exit behind frame_check.  A frame that was refused before it began leaves nothing to put back (frame_head has restored the
+// covariance's bookkeeping itself; the arena stays open: the caller may repair its arrays and call again).
+static int frame_leave(orcvio_msckf_handle* h, FrameRun& f, int code) {
+    if (!f.begun) return code;
+    if (h->arena_swapped) step_arena_swap(h);
+    h->io_open = false;
+    f.res->n_after = h->res_n;
+    return code;
+}
+
+// Every refusal that precedes the first change of filter state: covariance, factor, armings and arena stay as they were.
+static int frame_check(orcvio_msckf_handle* h, FrameRun& f) {
+    const orcvio_msckf_frame_step* st = f.st;
+    const char* who = f.who;
+    if (!h || !st || !f.res) { g_last_error = std::string(who) + ": null argument"; return ORCVIO_ERR_INVALID; }
     if (h->io_submitted) { g_last_error = std::string(who) + ": an update submitted with orcvio_msckf_io_submit has not been collected"; return ORCVIO_ERR_INVALID; }
     if (!h->io_open || h->io_with_P) { g_last_error = std::string(who) + ": call orcvio_msckf_io_begin with with_P = 2 (or 0) first: the frame runs on the resident covariance"; return ORCVIO_ERR_INVALID; }
     if (h->comm || h->ipc) { g_last_error = std::string(who) + ": not with a communicator on the handle (the sharded calls are the multi-GPU form)"; return ORCVIO_ERR_INVALID; }
-    const orcvio_msckf_flags fl = h->flags;
-    const int leg = fl.leg_dim, N = h->N, n = h->n;
+    f.fl = h->flags;
+    f.leg = f.fl.leg_dim; f.N = h->N; f.n = h->n;
+    const int leg = f.leg, N = f.N;
     if (st->leg_dim != leg) { g_last_error = std::string(who) + ": leg_dim differs from the flags of io_begin"; return ORCVIO_ERR_INVALID; }
     if ((st->Phi == nullptr) != (st->Q == nullptr)) { g_last_error = std::string(who) + ": Phi and Q come together"; return ORCVIO_ERR_INVALID; }
     // armed by orcvio_msckf_io_propagate_imu: Phi and Q are made on the device (k_imu_phi_q) in front of the head launch
-    const bool armed = h->imu_armed;
-    if (armed && st->Phi) { g_last_error = std::string(who) + ": the handle is armed by orcvio_msckf_io_propagate_imu: Phi and Q must be NULL"; return ORCVIO_ERR_INVALID; }
-    if (armed && leg != 22) { g_last_error = std::string(who) + ": armed IMU propagation at leg_dim 22 only"; return ORCVIO_ERR_INVALID; }
-    if (armed && h->tri_armed) { g_last_error = std::string(who) + ": armed by orcvio_msckf_io_propagate_imu AND by orcvio_msckf_io_triangulate: one of the two per frame"; return ORCVIO_ERR_INVALID; }
-    const bool prop = st->Phi != nullptr || armed;
+    f.imu = h->imu_armed;
+    if (f.imu && st->Phi) { g_last_error = std::string(who) + ": the handle is armed by orcvio_msckf_io_propagate_imu: Phi and Q must be NULL"; return ORCVIO_ERR_INVALID; }
+    if (f.imu && leg != 22) { g_last_error = std::string(who) + ": armed IMU propagation at leg_dim 22 only"; return ORCVIO_ERR_INVALID; }
+    if (f.imu && h->tri_armed) { g_last_error = std::string(who) + ": armed by orcvio_msckf_io_propagate_imu AND by orcvio_msckf_io_triangulate: one of the two per frame"; return ORCVIO_ERR_INVALID; }
+    f.prop = st->Phi != nullptr || f.imu;
     if (st->n_remove < 0 || st->n_remove > 8 || (st->n_remove > 0 && !st->remove_clones)) { g_last_error = std::string(who) + ": remove_clones: at most eight"; return ORCVIO_ERR_INVALID; }
     for (int k = 0; k < st->n_remove; ++k)
         if (st->remove_clones[k] < 0 || st->remove_clones[k] >= N || (k > 0 && st->remove_clones[k] <= st->remove_clones[k - 1])) {
             g_last_error = std::string(who) + ": remove_clones must be ascending window indices"; return ORCVIO_ERR_INVALID;
         }
-    if (st->prune_tracks) { const int rv = step_validate_tracks(h, st->prune_tracks, N, fl.estimate_td != 0, who); if (rv != ORCVIO_OK) return rv; }
+    if (st->prune_tracks) { const int rv = step_validate_tracks(h, st->prune_tracks, N, f.fl.estimate_td != 0, who); if (rv != ORCVIO_OK) return rv; }
     // armed by orcvio_msckf_io_triangulate_prune: the second update's positions are made on the device between the two updates
-    const bool tri2 = h->tri2_armed;
-    if (tri2) {
+    f.tri2 = h->tri2_armed;
+    if (f.tri2) {
         auto bad = [&](const char* what) { g_last_error = std::string(who) + ": armed by orcvio_msckf_io_triangulate_prune: " + what; return ORCVIO_ERR_INVALID; };
         if (!st->prune_tracks) return bad("the frame has no prune_tracks");
         if (st->prune_tracks->n_features != h->tri2_F) return bad("tri_tracks and prune_tracks differ in their number of tracks");
@@ -340,51 +429,49 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             return bad("a prune observation's clone does not occur in its track's list");
     }
     // armed by orcvio_msckf_io_choose_clones: remove_clones is the caller's PREDICTION, checked on the device between the two updates
-    const bool cc = h->cc_armed;
-    if (cc) {
+    f.cc = h->cc_armed;
+    if (f.cc) {
         auto bad = [&](const char* what) { g_last_error = std::string(who) + ": armed by orcvio_msckf_io_choose_clones: " + what; return ORCVIO_ERR_INVALID; };
         if (st->n_remove != 2) return bad("n_remove must be 2");
         if (!clone_choice_possible(N, st->remove_clones[0], st->remove_clones[1])) return bad("remove_clones is not one of {N-3, N-2}, {0, N-3}, {0, N-5}, {0, 1}");
         if (!st->prune_tracks) return bad("the frame has no prune_tracks (the check rides in front of the prune update: pass a track set)");
     }
     HIPCHK(hipSetDevice(h->device));
-    StepEvents evs;
-    { const int rv = step_validate_events(h, st, ev, h->F > 0 || (st->slam_features && st->slam_features->n_features > 0), evs, who); if (rv != ORCVIO_OK) return rv; }
-    const int d_lost = evs.idp * evs.lost.count;   // states that leave in front of the first update
-    if (st->augment && h->n_extra + d_lost > h->res_n - 15) { g_last_error = std::string(who) + ": more extra states than the resident covariance has"; return ORCVIO_ERR_INVALID; }
-    static const bool timing = dbg_getenv("ORCVIO_TIMING") != nullptr;   // diagnostics: host wall time of the parts of this call
-    const auto tt0 = std::chrono::steady_clock::now();
-    static double tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    static int tcalls = 0;
-    auto tmark = [&](int i) { if (timing) tacc[i] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tt0).count(); };
+    { const int rv = step_validate_events(h, st, f.ev, h->F > 0 || (st->slam_features && st->slam_features->n_features > 0), f.evs, who); if (rv != ORCVIO_OK) return rv; }
+    f.d_lost = f.evs.idp * f.evs.lost.count;
+    if (st->augment && h->n_extra + f.d_lost > h->res_n - 15) { g_last_error = std::string(who) + ": more extra states than the resident covariance has"; return ORCVIO_ERR_INVALID; }
+    return ORCVIO_OK;
+}
+
+// The covariance's bookkeeping ahead of the first update and the plan of its launches; the first update's tracks validated (a refusal
+// there leaves nothing done); behind that the armings are taken, k_frame_head and the planned edits go out.
+static int frame_head(orcvio_msckf_handle* h, FrameRun& f) {
+    const orcvio_msckf_frame_step* st = f.st;
+    const int leg = f.leg;
     if (h->arena_swapped) step_arena_swap(h);   // (an earlier call left through an error path)
     { const int rw = step_words(h); if (rw != ORCVIO_OK) return rw; }   // (the kept status words and the two words that join the side stream)
     if (st->prune_tracks) { const int ra = step_arena2(h); if (ra != ORCVIO_OK) return ra; }
     hipStream_t s = h->stream;
-    std::memset(res, 0, sizeof(*res));
-    res->n_after = h->res_n;
+    std::memset(f.res, 0, sizeof(*f.res));
+    f.res->n_after = h->res_n;
     if (h->dl_pending) { HIPCHK(hipStreamSynchronize(h->dl_stream)); h->dl_pending = false; }
 
-    // ---- the covariance's bookkeeping ahead of the first update: propagation and augmentation.  The handle's fields are set first and
-    // the launches recorded; they go out once the first update's tracks have passed their checks (a validation failure leaves nothing done)
-    const CovState cov0 = cov_state(h);
-    enum { PLAN_HEAD_FAC, PLAN_PROPAGATE, PLAN_AUGMENT, PLAN_GATHER };
-    struct { int kind; CovEdit e; } plan[3];   // (fused: the factor's launch behind the head; unfused: propagation, augmentation, lost features)
-    int n_plan = 0;
-    std::vector<int> lost_map;   // (the unfused removal's index map, staged when its launch goes out)
+    // ---- propagation and augmentation.  The handle's fields are set first and the launches recorded; they go out once the first
+    // update's tracks have passed their checks (a validation failure leaves nothing done)
+    f.cov0 = cov_state(h);
     double* dPhi = h->d_covT + (size_t)46 * h->n_max; double* dQ = dPhi + 46 * 46;   // (the unfused propagation's Phi and Q, as orcvio_msckf_cov_propagate stages them)
-    const int aug_pose = h->res_n - (h->n_extra + d_lost);   // the new clone: in front of the feature states as they are BEFORE the removal
+    f.aug_pose = h->res_n - (h->n_extra + f.d_lost);
     // the fused form: ONE launch (k_frame_head) propagates and augments, pulls the whole arena and the in-state features' records out of
     // pinned memory and clears their dense rows; Phi, Q and the records are staged behind the tracks in the pinned arena
     const size_t slam_bytes = st->slam_features ? (size_t)st->slam_features->n_features * 160 + 9 * 64 : 0;
     const size_t off_aux = al256(upload_bytes(h));
-    const bool fused = h->step_fused && off_aux + 2 * al256(sizeof(double) * leg * leg) + slam_bytes <= h->in_cap;
-    FrameHeadArgs fa{};
+    f.fused = h->step_fused && off_aux + 2 * al256(sizeof(double) * leg * leg) + slam_bytes <= h->in_cap;
+    FrameHeadArgs& fa = f.fa;
     fa.pose_block = -1;
-    if (fused && (prop || st->augment || d_lost > 0)) {
-        const CovEdit e = h->head(prop, st->augment != 0, d_lost);   // (e.m: the state the first update sees)
-        fa.P = e.P; fa.n = e.n; fa.out = e.Pout; fa.m = e.m; fa.leg = leg; fa.pose = st->augment ? aug_pose : -1;
-        fa.lost = evs.lost;
+    if (f.fused && (f.prop || st->augment || f.d_lost > 0)) {
+        const CovEdit e = h->head(f.prop, st->augment != 0, f.d_lost);   // (e.m: the state the first update sees)
+        fa.P = e.P; fa.n = e.n; fa.out = e.Pout; fa.m = e.m; fa.leg = leg; fa.pose = st->augment ? f.aug_pose : -1;
+        fa.lost = f.evs.lost;
         fa.nb_cov = (e.m * e.m + 255) / 256;   // (the three regions enumerate every output element once)
         if (st->Phi) {
             char* hp = h->h_stage + off_aux;
@@ -393,32 +480,32 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
             fa.Phi = reinterpret_cast<const double*>(h->h_stage_dev + off_aux);
             fa.Q = reinterpret_cast<const double*>(h->h_stage_dev + off_aux + al256(sizeof(double) * leg * leg));
         }
-        if (armed) { fa.Phi = dPhi; fa.Q = dQ; fa.refuse = imu_status(h); }   // (device memory: where k_imu_phi_q leaves them)
-        if (e.fac) plan[n_plan++] = {PLAN_HEAD_FAC, e};   // no propagation: the factor's rows copied and deleted in a launch of their own
+        if (f.imu) { fa.Phi = dPhi; fa.Q = dQ; fa.refuse = imu_status(h); }   // (device memory: where k_imu_phi_q leaves them)
+        if (e.fac) f.plan[f.n_plan++] = {PLAN_HEAD_FAC, e};   // no propagation: the factor's rows copied and deleted in a launch of their own
     }
-    if (!fused && prop) plan[n_plan++] = {PLAN_PROPAGATE, h->propagate()};
-    if (!fused && st->augment) plan[n_plan++] = {PLAN_AUGMENT, h->augment()};
-    if (!fused && d_lost > 0) {   // the separate call's kernels (k_cov_remove / k_fac_remove) with its map
-        lost_map = lost_features_map(h->res_n, evs.lost.fbase, evs.idp, evs.lost_slots.data(), evs.lost.count);
-        plan[n_plan++] = {PLAN_GATHER, h->gather((int)lost_map.size())};
+    if (!f.fused && f.prop) f.plan[f.n_plan++] = {PLAN_PROPAGATE, h->propagate()};
+    if (!f.fused && st->augment) f.plan[f.n_plan++] = {PLAN_AUGMENT, h->augment()};
+    if (!f.fused && f.d_lost > 0) {   // the separate call's kernels (k_cov_remove / k_fac_remove) with its map
+        f.lost_map = lost_features_map(h->res_n, f.evs.lost.fbase, f.evs.idp, f.evs.lost_slots.data(), f.evs.lost.count);
+        f.plan[f.n_plan++] = {PLAN_GATHER, h->gather((int)f.lost_map.size())};
     }
     // ---- the first update's tracks: validated, the derived index arrays written (upload_finalize needs the prior's bookkeeping above)
     int rc = ORCVIO_OK;
-    if (st->slam_features) rc = fused ? slam_prepare(h, st->slam_features) : orcvio_msckf_upload_slam_features(h, st->slam_features);   // (validation; the copies touch the records' own buffers only)
-    if (rc == ORCVIO_OK) rc = upload_finalize(h, who);
-    if (rc != ORCVIO_OK) { cov_restore(h, cov0); (void)arena_mark_read(h, s); return rc; }
+    if (st->slam_features) rc = f.fused ? slam_prepare(h, st->slam_features) : orcvio_msckf_upload_slam_features(h, st->slam_features);   // (validation; the copies touch the records' own buffers only)
+    if (rc == ORCVIO_OK) rc = upload_finalize(h, f.who);
+    if (rc != ORCVIO_OK) { cov_restore(h, f.cov0); (void)arena_mark_read(h, s); return rc; }
     h->pw_missing = false;
-    tmark(0);
-    if (armed) { rc = imu_consume(h, s); if (rc != ORCVIO_OK) return rc; }   // nothing can refuse the frame any more: the arming is taken
-    h->tri2_armed = false;   // (... and so is the prune update's)
-    h->cc_armed = false;     // (... and the check of the clones that leave)
-    StepChoice choice{};
-    if (cc) {
-        choice.pred[0] = st->remove_clones[0]; choice.pred[1] = st->remove_clones[1];
+    f.tm.mark(0);
+    // ---- nothing can refuse the frame any more: the armings are taken, here and nowhere else
+    f.begun = true;
+    if (f.imu) { rc = imu_consume(h, s); if (rc != ORCVIO_OK) return rc; }
+    drop_one_shot_armings(h, false);   // (the prune update's, the check of the clones that leave; the first update's own: tri_consume, frame_first)
+    if (f.cc) {
+        f.choice.pred[0] = st->remove_clones[0]; f.choice.pred[1] = st->remove_clones[1];
         std::memset(cc_block(h), 0, sizeof(orcvio_msckf_clone_choice));   // (evaluated = 0 until this frame's launch has stored its block)
     }
-    const int* imu_also = armed ? imu_status(h) : nullptr;
-    if (fused) {
+    f.imu_also = f.imu ? imu_status(h) : nullptr;
+    if (f.fused) {
         fa.nseg = 1;
         fa.src[0] = h->h_stage_dev; fa.dst[0] = h->d_in; fa.bytes[0] = (unsigned)upload_bytes(h);
         if (st->slam_features && st->slam_features->n_features > 0) {   // the nine arrays of the records, staged packed behind Phi / Q
@@ -436,245 +523,277 @@ static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step
         rc = launch_frame_head(h, s, fa);
         if (rc != ORCVIO_OK) return rc;
     }
-    for (int i = 0; i < n_plan && rc == ORCVIO_OK; ++i) {   // the launches of the edits planned above
-        const CovEdit& e = plan[i].e;
-        if (plan[i].kind == PLAN_HEAD_FAC) {   // the factor's rows as orcvio_msckf_cov_augment copies them and as orcvio_msckf_cov_remove_features deletes them, in one gather
+    for (int i = 0; i < f.n_plan && rc == ORCVIO_OK; ++i) {   // the launches of the edits planned above
+        const CovEdit& e = f.plan[i].e;
+        if (f.plan[i].kind == PLAN_HEAD_FAC) {   // the factor's rows as orcvio_msckf_cov_augment copies them and as orcvio_msckf_cov_remove_features deletes them, in one gather
             const dim3 grid((e.fac_k * e.m + 255) / 256);
-            if (evs.lost.count > 0) hipLaunchKernelGGL(k_fac_head, grid, dim3(256), 0, s, e.S, e.ld_in, e.fac_k, fa.pose, evs.lost, e.m, e.Sout, e.ld_out);
+            if (f.evs.lost.count > 0) hipLaunchKernelGGL(k_fac_head, grid, dim3(256), 0, s, e.S, e.ld_in, e.fac_k, fa.pose, f.evs.lost, e.m, e.Sout, e.ld_out);
             else hipLaunchKernelGGL(k_fac_augment, grid, dim3(256), 0, s, e.S, e.ld_in, e.fac_k, e.n, fa.pose, e.Sout, e.ld_out);
             HIPCHK(hipGetLastError());
-        } else if (plan[i].kind == PLAN_PROPAGATE) {
-            if (!armed) {
+        } else if (f.plan[i].kind == PLAN_PROPAGATE) {
+            if (!f.imu) {
                 const AuxCopy cp[] = {{dPhi, st->Phi, sizeof(double) * (size_t)leg * leg}, {dQ, st->Q, sizeof(double) * (size_t)leg * leg}};
                 rc = aux_copies(h, s, cp, 2);
             }
-            if (rc == ORCVIO_OK) rc = launch_cov_propagate(h, s, e, leg, dPhi, dQ, imu_also);
-        } else if (plan[i].kind == PLAN_AUGMENT) rc = launch_cov_augment(h, s, e, aug_pose);
-        else rc = launch_cov_gather(h, s, e, lost_map);
+            if (rc == ORCVIO_OK) rc = launch_cov_propagate(h, s, e, leg, dPhi, dQ, f.imu_also);
+        } else if (f.plan[i].kind == PLAN_AUGMENT) rc = launch_cov_augment(h, s, e, f.aug_pose);
+        else rc = launch_cov_gather(h, s, e, f.lost_map);
     }
     if (rc != ORCVIO_OK) return rc;
-    res->n_after = h->res_n;
-    if (!fused) { rc = ingest_raw(h, s); if (rc != ORCVIO_OK) return rc; }
-    tmark(1);
-    // what the first update's outcome needs on the host once the handle's fields belong to the second
-    std::vector<int>& keep_rows = h->frame_row_ptr;
-    keep_rows = h->h_row_ptr;
-    FeatureView vA = feature_view(h);
-    vA.row_ptr = keep_rows.data();
-    const char* soA = h->h_stage + h->in_cap;
-    const double* posesA = h->d_poses; const double* dxA = h->d_dx; const int* infoA = h->d_info;
-    const int FA = h->F, nobsA = h->nobs;
+    f.res->n_after = h->res_n;
+    if (!f.fused) rc = ingest_raw(h, s);
+    return rc;
+}
+
+// The first update on what the head leaves.
+// (a frame without lost features and without in-state features has no first update: the covariance bookkeeping and, if there is one,
+//  the prune update are the whole frame -- the reference's removeLostFeatures returns before any arithmetic, src/orcvio.cpp:2440-2446)
+static int frame_first(orcvio_msckf_handle* h, FrameRun& f) {
+    hipStream_t s = h->stream;
+    h->frame_row_ptr = h->h_row_ptr;
+    f.vA = feature_view(h);
+    f.vA.row_ptr = h->frame_row_ptr.data();
+    f.soA = h->h_stage + h->in_cap;
+    f.posesA = h->d_poses; f.dxA = h->d_dx; f.infoA = h->d_info;
+    f.FA = h->F; f.nobsA = h->nobs;
     h->last_stream = s;
-    // (a frame without lost features and without in-state features has no first update: the covariance bookkeeping and, if there is one,
-    //  the prune update are the whole frame -- the reference's removeLostFeatures returns before any arithmetic, src/orcvio.cpp:2440-2446)
-    const bool first = FA > 0 || h->ekf_F > 0;
-    bool tri_frame_empty = false;
-    bool tri_frame = false;   // the first update triangulates its own tracks (orcvio_msckf_io_triangulate)
-    unsigned long long pubA = 0;
+    f.first = f.FA > 0 || h->ekf_F > 0;
     h->ekf_side_used = false;
-    if (first) {
-        UpdateCall c;
-        c.ekf_side = fused;           // (the in-state rows beside k_front: enqueue_update)
-        c.already_ingested = fused;   // (k_frame_head has pulled the whole arena)
-        c.info_also = imu_also;       // (a refused Phi refuses this update's commit)
-        tri_consume(h, c);            // (armed: k_triangulate behind the head, in front of the tracks' launch)
-        tri_frame = c.tri; tri_frame_empty = h->tri_refuse_empty;
-        rc = io_enqueue(h, s, false, true, c, true);
-        h->A_deferred = h->last_update_thin ? false : front_defers_assembly(h, false);
-        if (rc != ORCVIO_OK) {
-            if (h->ekf_side_used) {   // (a launch failed with the side stream's wait already out: let it through and drain it)
-                hipLaunchKernelGGL(k_obj_done, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned*>(h->d_step_words) + 32, h->ekf_side_seq);
-                (void)hipStreamSynchronize(h->side);
-            }
-            return rc;
-        }
-        h->cnt_plain_runs++;
-        h->pub_enqueued++;
-        pubA = h->pub_enqueued;
-        h->ran = true; h->last_update_objects = false; h->last_run_kind = 0; h->last_sharded = false;
-        commit_bookkeeping(h);
-    } else {
+    if (!f.first) {
         std::memset(h->h_stage + h->in_cap, 0, h->outs_small);   // (dx = 0, no status words)
-        infoA = nullptr;
+        f.infoA = nullptr;
+        return ORCVIO_OK;
     }
-    tmark(2);
-    // ---- the second update, on what the first commits
-    const bool second = st->prune_tracks != nullptr;
-    FeatureView vB{};
-    const char* soB = nullptr;
-    unsigned long long pubB = 0;
+    UpdateCall c;
+    c.ekf_side = f.fused;           // (the in-state rows beside k_front: enqueue_update)
+    c.already_ingested = f.fused;   // (k_frame_head has pulled the whole arena)
+    c.info_also = f.imu_also;       // (a refused Phi refuses this update's commit)
+    tri_consume(h, c);              // (armed: k_triangulate behind the head, in front of the tracks' launch)
+    f.tri_frame = c.tri; f.tri_frame_empty = h->tri_refuse_empty;
+    const int rc = io_enqueue(h, s, false, true, c, true);
+    f.pubA = frame_update_enqueued(h, rc);
+    if (rc != ORCVIO_OK && h->ekf_side_used) {   // (a launch failed with the side stream's wait already out: let it through and drain it)
+        hipLaunchKernelGGL(k_obj_done, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned*>(h->d_step_words) + 32, h->ekf_side_seq);
+        (void)hipStreamSynchronize(h->side);
+    }
+    return rc;
+}
+
+// The second half, on what the first update commits: the anchor changes alone, or the second update through the swapped-in second
+// arena; the marginalisation behind them.
+static int frame_second_half(orcvio_msckf_handle* h, FrameRun& f) {
+    const orcvio_msckf_frame_step* st = f.st;
+    hipStream_t s = h->stream;
+    StepEvents& evs = f.evs;
+    f.second = st->prune_tracks != nullptr;
     if (evs.k > 0) { evs.fs.slam = h->d_slam; evs.fs.cap = h->ekf_cap; }   // (the records' buffers stand: slam_prepare above)
-    StepSecond sb{st->prune_tracks, posesA, dxA, infoA, first ? st->prune_apply_dx : 0, evs.k > 0 ? &evs : nullptr, imu_also, tri2};
-    if (cc) {
-        if (evs.k > 0) choice.raise_evt = evs.fs.status;   // (a disagreement refuses the anchor change through the feature step's word)
-        sb.cc = &choice;
+    f.sb = StepSecond{st->prune_tracks, f.posesA, f.dxA, f.infoA, f.first ? st->prune_apply_dx : 0, evs.k > 0 ? &evs : nullptr, f.imu_also, f.tri2};
+    if (f.cc) {
+        if (evs.k > 0) f.choice.raise_evt = evs.fs.status;   // (a disagreement refuses the anchor change through the feature step's word)
+        f.sb.cc = &f.choice;
     }
-    int rcB = ORCVIO_OK;
-    unsigned long long pubE = 0;
-    if (!second && evs.k > 0) {   // no update behind the changes: the anchor change is what the call waits for
-        rcB = step_events_alone(h, s, fl, N, sb, false, true);
-        if (rcB == ORCVIO_OK) pubE = ++h->pub_enqueued;
+    if (!f.second && evs.k > 0) {   // no update behind the changes: the anchor change is what the call waits for
+        f.rcB = step_events_alone(h, s, f.fl, f.N, f.sb, false, true);
+        if (f.rcB == ORCVIO_OK) f.pubE = ++h->pub_enqueued;
     }
-    const CovState cov_before_second = cov_state(h);
-    if (second) {
+    f.cov_before_second = cov_state(h);
+    if (f.second) {
         step_arena_swap(h);
-        rcB = step_second_update(h, fl, N, sb, false, nullptr, who);
-        if (rcB == ORCVIO_OK) {
-            pubB = h->pub_enqueued;
+        f.rcB = step_second_enqueue(h, f.fl, f.N, f.sb, &f.pubB, f.who);
+        if (f.rcB == ORCVIO_OK) {
             h->step_row_ptr = h->h_row_ptr;
-            vB = feature_view(h);
-            vB.row_ptr = h->step_row_ptr.data();
-            soB = h->h_stage + h->in_cap;
+            f.vB = feature_view(h);
+            f.vB.row_ptr = h->step_row_ptr.data();
+            f.soB = h->h_stage + h->in_cap;
         }
     }
     // ---- marginalisation, enqueued behind the updates
-    const CovState cov_before_remove = cov_state(h);
-    int rcR = ORCVIO_OK;
+    f.cov_before_remove = cov_state(h);
     // (an armed choice: the marginalisation goes out behind the wait, once the device's verdict is known, and is not waited for)
-    if (rcB == ORCVIO_OK && st->n_remove > 0 && !cc) rcR = step_remove(h, leg, st->remove_clones, st->n_remove);
-    tmark(3);
-    // ---- ONE wait: the flag word behind the last update
-    rc = (pubB || pubE || pubA) ? io_wait(h, s, pubB ? pubB : (pubE ? pubE : pubA)) : ORCVIO_OK;
-    if (rc == ORCVIO_OK && armed && !(pubB || pubE || pubA)) HIPCHK(hipStreamSynchronize(s));   // (a frame without an update: the armed launch's status word is the one thing to wait for)
-    tmark(4);
-    if (timing && (++tcalls % 128) == 0) {
-        fprintf(stderr, "io_step_frame (mean of 128, us after entry): checks + finalize %.1f | head launched %.1f | first update enqueued %.1f | second + removal enqueued %.1f | results %.1f\n",
-                tacc[0] / 128, tacc[1] / 128, tacc[2] / 128, tacc[3] / 128, tacc[4] / 128);
-        for (double& v : tacc) v = 0.0;
-    }
-    auto leave = [&](int code) {
-        if (h->arena_swapped) step_arena_swap(h);
-        h->io_open = false;
-        res->n_after = h->res_n;
-        return code;
-    };
-    if (rc != ORCVIO_OK) { h->ran = false; return leave(rc); }
-    // the choice's verdict: held = the second half was (or is to be) held back -- no anchor change, no prune update, no marginalisation
-    bool held = cc && rcB != ORCVIO_OK;
-    if (cc && rcB == ORCVIO_OK) {
-        rc = clone_choice_collect(h, s);
-        if (rc != ORCVIO_OK) { h->ran = false; return leave(rc); }
-        held = cc_block(h)->evaluated != 0 && cc_block(h)->agree == 0;
+    if (f.rcB == ORCVIO_OK && st->n_remove > 0 && !f.cc) f.rcR = step_remove(h, f.leg, st->remove_clones, st->n_remove);
+    return ORCVIO_OK;
+}
+
+// ONE wait: the flag word behind the last update
+static int frame_wait(orcvio_msckf_handle* h, FrameRun& f) {
+    const unsigned long long pub = f.pubB ? f.pubB : (f.pubE ? f.pubE : f.pubA);
+    const int rc = pub ? io_wait(h, h->stream, pub) : ORCVIO_OK;
+    if (rc != ORCVIO_OK) { h->ran = false; return rc; }
+    if (f.imu && !pub) HIPCHK(hipStreamSynchronize(h->stream));   // (a frame without an update: the armed launch's status word is the one thing to wait for)
+    return ORCVIO_OK;
+}
+static void frame_timing(orcvio_msckf_handle* h) {
+    PhaseTimer* t = step_timer_of(h);
+    if (!t || !t->due(128)) return;
+    fprintf(stderr, "io_step_frame (mean of 128, us after entry): checks + finalize %.1f | head launched %.1f | first update enqueued %.1f | second + removal enqueued %.1f | results %.1f\n",
+            t->mean(0, 128), t->mean(1, 128), t->mean(2, 128), t->mean(3, 128), t->mean(4, 128));
+    t->reset();
+}
+
+// the word the anchor change left: a changed feature's position was not finite
+static int frame_changes_status(const orcvio_msckf_handle* h, FrameRun& f) {
+    const int sc = f.evs.k > 0 && *evt_status_host(h) != 0 && !f.held ? ORCVIO_ERR_NOT_SPD : ORCVIO_OK;   // (held: the word was raised by the choice)
+    if (f.rex) f.rex->status_changes = sc;
+    if (sc != ORCVIO_OK) g_last_error = std::string(f.who) + ": a changed feature's position is not finite (an incremented inverse depth of zero): no anchor change, no prune update";
+    return sc;
+}
+static void frame_prune_results(orcvio_msckf_frame_result* res, const char* so, const FeatureView& v) {
+    res->prune_dx = reinterpret_cast<const double*>(so + v.oo_dx);
+    res->prune_gamma = reinterpret_cast<const double*>(so + v.oo_gamma);
+    res->prune_accept = reinterpret_cast<const int32_t*>(so + v.oo_accept);
+}
+static FrameFacts frame_facts(const FrameRun& f, bool repaired) {
+    FrameFacts k;
+    k.repaired = repaired; k.first = f.first; k.second = f.second; k.held = f.held; k.imu_bad = f.imu_bad; k.rcB = f.rcB; k.rcR = f.rcR;
+    return k;
+}
+
+// What the results on the host say before any outcome is evaluated: the choice's verdict, the result pointers, a lost hand-off.
+static int frame_results(orcvio_msckf_handle* h, FrameRun& f) {
+    orcvio_msckf_frame_result* res = f.res;
+    f.held = f.cc && f.rcB != ORCVIO_OK;
+    if (f.cc && f.rcB == ORCVIO_OK) {
+        const int rc = clone_choice_collect(h, h->stream);
+        if (rc != ORCVIO_OK) { h->ran = false; return rc; }
+        f.held = cc_block(h)->evaluated != 0 && cc_block(h)->agree == 0;
         // held back, and the prune update took the direct form of a thin stack: that form writes no factor and its commit's bookkeeping
         // drops the resident one -- but the commit refused itself, the first update's factor stands untouched where it was
-        if (held && h->last_update_thin && cov_before_second.fac_follows()) {
-            h->d_Sres = cov_before_second.d_Sres; h->d_Stmp = cov_before_second.d_Stmp;
-            h->fac_n = cov_before_second.fac_n; h->fac_k = cov_before_second.fac_k; h->fac_ld = cov_before_second.fac_ld;
-            h->fac_tail = cov_before_second.fac_tail; h->fac_valid = true;
-        }
+        if (f.held && h->last_update_thin) h->keep_factor_of(f.cov_before_second);
     }
-    if (rex && evs.k > 0) {
-        rex->new_param = reinterpret_cast<const double*>(h->h_evt + EVT_H_PAR);
-        rex->new_inv_depth = rex->new_param + 3 * ANCHOR_MAX_K;
+    if (f.rex && f.evs.k > 0) {
+        f.rex->new_param = reinterpret_cast<const double*>(h->h_evt + EVT_H_PAR);
+        f.rex->new_inv_depth = f.rex->new_param + 3 * ANCHOR_MAX_K;
     }
-    auto changes_status = [&]() {   // the word the anchor change left: a changed feature's position was not finite
-        const int sc = evs.k > 0 && *evt_status_host(h) != 0 && !held ? ORCVIO_ERR_NOT_SPD : ORCVIO_OK;   // (held: the word was raised by the choice)
-        if (rex) rex->status_changes = sc;
-        if (sc != ORCVIO_OK) g_last_error = std::string(who) + ": a changed feature's position is not finite (an incremented inverse depth of zero): no anchor change, no prune update";
-        return sc;
-    };
-    res->dx = reinterpret_cast<const double*>(soA + vA.oo_dx);
-    res->gamma = reinterpret_cast<const double*>(soA + vA.oo_gamma);
-    res->accept = reinterpret_cast<const int32_t*>(soA + vA.oo_accept);
-    if (second && rcB == ORCVIO_OK) {
-        res->prune_dx = reinterpret_cast<const double*>(soB + vB.oo_dx);
-        res->prune_gamma = reinterpret_cast<const double*>(soB + vB.oo_gamma);
-        res->prune_accept = reinterpret_cast<const int32_t*>(soB + vB.oo_accept);
-    }
-    const int* infA = reinterpret_cast<const int*>(soA);
-    const int* infB = soB ? reinterpret_cast<const int*>(soB) : nullptr;
-    const bool lostA = first && infA[8] != 0, lostB = infB && infB[8] != 0 && !lostA;
+    res->dx = reinterpret_cast<const double*>(f.soA + f.vA.oo_dx);
+    res->gamma = reinterpret_cast<const double*>(f.soA + f.vA.oo_gamma);
+    res->accept = reinterpret_cast<const int32_t*>(f.soA + f.vA.oo_accept);
+    if (f.second && f.rcB == ORCVIO_OK) frame_prune_results(res, f.soB, f.vB);
+    f.lostA = f.first && reinterpret_cast<const int*>(f.soA)[8] != 0;
+    f.lostB = f.soB && reinterpret_cast<const int*>(f.soB)[8] != 0 && !f.lostA;
     // the armed launch found Phi or Q not finite: the head ran without propagation, both updates refused their commits
-    const bool imu_bad = armed && imu_refused(h);
-    const char* imu_msg = ": Phi or Q of the armed IMU propagation not finite: no propagation, no update";
-    if (lostA || lostB) {
-        // An in-launch hand-off was lost (another tenant of the device held compute units): that update's commit refused itself on the
-        // device, and so did the second update's if the first was hit.  Drain, take the marginalisation back (it read the covariance, its
-        // result is simply dropped), and run what was lost again the safe way -- separate launches, the outcome checked by the host.
+    f.imu_bad = f.imu && imu_refused(h);
+    return ORCVIO_OK;
+}
+
+// An in-launch hand-off was lost (another tenant of the device held compute units): that update's commit refused itself on the
+// device, and so did the second update's if the first was hit.  Drain, take the marginalisation back (it read the covariance, its
+// result is simply dropped), and run what was lost again the safe way -- separate launches, the outcome checked by the host.
+// A failure that is not a refusal of the device ends the call with its code.
+static int frame_repair(orcvio_msckf_handle* h, FrameRun& f) {
+    const orcvio_msckf_frame_step* st = f.st;
+    orcvio_msckf_frame_result* res = f.res;
+    hipStream_t s = h->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    if (h->ekf_side_used) {
+        HIPCHK(hipStreamSynchronize(h->side));
+        h->ekf_side_skip_until = h->cnt_step_frames + 4096;
+    }
+    { const int rh = handoff_reset(h); if (rh != ORCVIO_OK) return rh; }
+    cov_restore(h, f.cov_before_remove);
+    h->fac_valid = false;   // (the factor a lost update left in the spare buffer is garbage or the prior's: the repeat factors P itself)
+    FrameFacts k = frame_facts(f, true);
+    int rc = ORCVIO_OK;
+    if (f.lostA) {
+        if (h->arena_swapped) step_arena_swap(h);
+        rc = upload_begin(h, &f.fl, f.N, f.FA, f.nobsA, false, true, f.who);
+        if (rc == ORCVIO_OK && st->slam_features) { h->io_open = true; rc = orcvio_msckf_upload_slam_features(h, st->slam_features); }
+        if (rc == ORCVIO_OK) { h->io_open = true; rc = upload_finalize(h, f.who); }
+        if (rc == ORCVIO_OK) {
+            h->pw_missing = false;
+            if (f.tri_frame) { h->skip_active = true; h->tri_live = true; h->tri_refuse_empty = f.tri_frame_empty; }   // (the positions and d_skip of the lost attempt stand in HBM)
+            rc = f.imu_bad ? (int)ORCVIO_ERR_NOT_SPD : io_run_forked(h, res->stats);   // (a refused Phi: nothing to run again)
+        }
+        res->repaired++; h->cnt_step_repairs++;
+        res->status_first = rc;
+        if (rc != ORCVIO_OK && rc != ORCVIO_ERR_NOT_SPD) return rc;
+        if (f.second) step_arena_swap(h);
+        k.first_code = rc;
+    } else {
+        k.first_code = f.first ? feature_outcome_view(h, f.vA, f.soA, res->stats) : (int)ORCVIO_OK;
+        // the anchor changes went through behind the first update's commit and stand: the repeat of the second update does not
+        // apply them again.  Its pose step reads the first update's dx, which the lost update has overwritten on the device: put back
+        f.sb.ev = nullptr;
+        if (f.first) HIPCHK(hipMemcpyAsync(const_cast<double*>(f.dxA), f.soA + f.vA.oo_dx, sizeof(double) * (size_t)f.n, hipMemcpyHostToDevice, s));
+    }
+    FrameOutcome o = frame_outcome(k, ORCVIO_OK, ORCVIO_ERR_NOT_SPD);
+    res->status_first = o.status_first;
+    if (f.cc && o.status_first != ORCVIO_OK) {   // no second update will carry the choice: on the caller's records as they are (dx not applied)
+        rc = launch_clone_choice(h, s, f.fl, f.N, f.choice, nullptr, f.dxA, 0, nullptr, false);
+        if (rc == ORCVIO_OK) rc = clone_choice_collect(h, s);
+        if (rc != ORCVIO_OK) return rc;
+        f.held = cc_block(h)->agree == 0;
+    }
+    // (lostA: the anchor change refused itself on the first update's kept status word; it runs behind the repeat, once)
+    if (f.sb.ev && !f.held && (!f.second || o.status_first != ORCVIO_OK)) {   // no second update to carry them: the changes are bookkeeping and stand
+        rc = step_events_alone(h, s, f.fl, f.N, f.sb, true, false);
+        if (rc != ORCVIO_OK) return rc;
         HIPCHK(hipStreamSynchronize(s));
-        if (h->ekf_side_used) {
-            HIPCHK(hipStreamSynchronize(h->side));
-            h->ekf_side_skip_until = h->cnt_step_frames + 4096;
-        }
-        { const int rh = handoff_reset(h); if (rh != ORCVIO_OK) return rh; }
-        cov_restore(h, cov_before_remove);
-        h->fac_valid = false;   // (the factor a lost update left in the spare buffer is garbage or the prior's: the repeat factors P itself)
-        if (lostA) {
-            if (h->arena_swapped) step_arena_swap(h);
-            rc = upload_begin(h, &fl, N, FA, nobsA, false, true, who);
-            if (rc == ORCVIO_OK && st->slam_features) { h->io_open = true; rc = orcvio_msckf_upload_slam_features(h, st->slam_features); }
-            if (rc == ORCVIO_OK) { h->io_open = true; rc = upload_finalize(h, who); }
-            if (rc == ORCVIO_OK) {
-                h->pw_missing = false;
-                if (tri_frame) { h->skip_active = true; h->tri_live = true; h->tri_refuse_empty = tri_frame_empty; }   // (the positions and d_skip of the lost attempt stand in HBM)
-                rc = imu_bad ? (int)ORCVIO_ERR_NOT_SPD : io_run_forked(h, res->stats);   // (a refused Phi: nothing to run again)
-            }
+    }
+    if (f.second) {
+        HIPCHK(hipStreamSynchronize(s));
+        if (o.eval_second) {   // (a refused first update refuses the second, as in the one-pass form: it is not run again)
+            f.rcB = step_second_safe(h, f.fl, f.N, f.sb, res->prune_stats, f.who);
             res->repaired++; h->cnt_step_repairs++;
-            res->status_first = rc;
-            if (rc != ORCVIO_OK && rc != ORCVIO_ERR_NOT_SPD) return leave(rc);
-            if (second) step_arena_swap(h);
-        } else {
-            res->status_first = first ? feature_outcome_view(h, vA, soA, res->stats) : ORCVIO_OK;
-            if (imu_bad) res->status_first = ORCVIO_ERR_NOT_SPD;
-            // the anchor changes went through behind the first update's commit and stand: the repeat of the second update does not
-            // apply them again.  Its pose step reads the first update's dx, which the lost update has overwritten on the device: put back
-            sb.ev = nullptr;
-            if (first) HIPCHK(hipMemcpyAsync(const_cast<double*>(dxA), soA + vA.oo_dx, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+            frame_outcome_second(k, o, f.rcB, ORCVIO_OK);
         }
-        if (cc && res->status_first != ORCVIO_OK) {   // no second update will carry the choice: on the caller's records as they are (dx not applied)
-            rc = launch_clone_choice(h, s, fl, N, choice, nullptr, dxA, 0, nullptr, false);
-            if (rc == ORCVIO_OK) rc = clone_choice_collect(h, s);
-            if (rc != ORCVIO_OK) return leave(rc);
-            held = cc_block(h)->agree == 0;
-        }
-        // (lostA: the anchor change refused itself on the first update's kept status word; it runs behind the repeat, once)
-        if (sb.ev && !held && (!second || res->status_first != ORCVIO_OK)) {   // no second update to carry them: the changes are bookkeeping and stand
-            rc = step_events_alone(h, s, fl, N, sb, true, false);
-            if (rc != ORCVIO_OK) return leave(rc);
-            HIPCHK(hipStreamSynchronize(s));
-        }
-        if (second) {
-            HIPCHK(hipStreamSynchronize(s));
-            if (res->status_first != ORCVIO_OK) {   // (a refused first update refuses the second, as in the one-pass form)
-                res->status_prune = res->status_first;
-            } else {
-                rcB = step_second_update(h, fl, N, sb, true, res->prune_stats, who);
-                res->repaired++; h->cnt_step_repairs++;
-                res->status_prune = rcB;
-                if (rcB != ORCVIO_OK && rcB != ORCVIO_ERR_NOT_SPD) return leave(rcB);
-                if (cc) held = cc_block(h)->agree == 0;   // (held: step_second_update ran nothing behind the choice)
-                soB = h->h_stage + h->in_cap;
-                res->prune_dx = reinterpret_cast<const double*>(soB + h->oo_dx);
-                res->prune_gamma = reinterpret_cast<const double*>(soB + h->oo_gamma);
-                res->prune_accept = reinterpret_cast<const int32_t*>(soB + h->oo_accept);
-            }
-        }
-        if (st->n_remove > 0 && !held) { rcR = step_remove(h, leg, st->remove_clones, st->n_remove); if (rcR != ORCVIO_OK) return leave(rcR); }
-        h->cnt_step_frames++;
-        const int sc = changes_status();
-        return leave(res->status_first != ORCVIO_OK ? res->status_first : (res->status_prune != ORCVIO_OK ? res->status_prune : sc));
-    }
-    // ---- outcomes (the refusals of the device: M not positive definite, a non-finite result)
-    res->status_first = first ? feature_outcome_view(h, vA, soA, res->stats) : ORCVIO_OK;
-    if (imu_bad) { res->status_first = ORCVIO_ERR_NOT_SPD; g_last_error = std::string(who) + imu_msg; }
-    if (res->status_first != ORCVIO_OK) res->stats[3] = 0;
-    const int sc_changes = changes_status();
-    if (second) {
-        if (rcB != ORCVIO_OK) res->status_prune = rcB;
-        else if (res->status_first != ORCVIO_OK) { res->status_prune = res->status_first; res->prune_stats[3] = 0; }   // (refused with the first: info_also)
-        else if (sc_changes != ORCVIO_OK) { res->status_prune = sc_changes; res->prune_stats[3] = 0; }   // (refused with the changes: the kept status word)
-        else if (held) { (void)feature_outcome_view(h, vB, soB, res->prune_stats); res->status_prune = ORCVIO_OK; res->prune_stats[3] = 0; }   // (held back: not an error)
-        else {
-            res->status_prune = feature_outcome_view(h, vB, soB, res->prune_stats);
-            if (res->status_prune != ORCVIO_OK) res->prune_stats[3] = 0;
+        res->status_prune = o.status_prune;
+        if (o.eval_second) {
+            if (f.rcB != ORCVIO_OK && f.rcB != ORCVIO_ERR_NOT_SPD) return f.rcB;
+            if (f.cc) f.held = cc_block(h)->agree == 0;   // (held: step_second_safe ran nothing behind the choice)
+            frame_prune_results(res, h->h_stage + h->in_cap, feature_view(h));
         }
     }
+    if (st->n_remove > 0 && !f.held) { f.rcR = step_remove(h, f.leg, st->remove_clones, st->n_remove); if (f.rcR != ORCVIO_OK) return f.rcR; }
+    h->cnt_step_frames++;
+    k.changes = frame_changes_status(h, f);
+    return frame_outcome_return(k, o, ORCVIO_OK);
+}
+
+// The one-pass outcomes (the refusals of the device: M not positive definite, a non-finite result), by the table of
+// host/frame_outcome.hpp, and the marginalisation behind an agreed choice.
+static int frame_outcomes(orcvio_msckf_handle* h, FrameRun& f) {
+    const orcvio_msckf_frame_step* st = f.st;
+    orcvio_msckf_frame_result* res = f.res;
+    FrameFacts k = frame_facts(f, false);
+    k.first_code = f.first ? feature_outcome_view(h, f.vA, f.soA, res->stats) : (int)ORCVIO_OK;
+    if (f.imu_bad) g_last_error = std::string(f.who) + ": Phi or Q of the armed IMU propagation not finite: no propagation, no update";
+    k.changes = frame_changes_status(h, f);
+    FrameOutcome o = frame_outcome(k, ORCVIO_OK, ORCVIO_ERR_NOT_SPD);
+    if (o.eval_second) frame_outcome_second(k, o, feature_outcome_view(h, f.vB, f.soB, res->prune_stats), ORCVIO_OK);
+    res->status_first = o.status_first;
+    if (f.second) res->status_prune = o.status_prune;
+    if (o.clear_stats3) res->stats[3] = 0;
+    if (o.clear_prune_stats3) res->prune_stats[3] = 0;
     h->ran = false;   // (both commits are part of the call: nothing is left for orcvio_msckf_cov_commit)
     h->cnt_step_frames++;
-    if (cc && !held && rcB == ORCVIO_OK && st->n_remove > 0) rcR = step_remove(h, leg, st->remove_clones, st->n_remove);   // (enqueued behind the wait, not waited for)
-    if (rcR != ORCVIO_OK) return leave(rcR);
-    if (!second && rcB != ORCVIO_OK) return leave(rcB);
-    return leave(res->status_first != ORCVIO_OK ? res->status_first : (res->status_prune != ORCVIO_OK ? res->status_prune : sc_changes));
+    if (f.cc && !f.held && f.rcB == ORCVIO_OK && st->n_remove > 0) f.rcR = step_remove(h, f.leg, st->remove_clones, st->n_remove);   // (enqueued behind the wait, not waited for)
+    k.rcR = f.rcR;
+    return frame_outcome_return(k, o, ORCVIO_OK);
+}
+
+// One implementation behind both calls: ev == nullptr (or empty) is orcvio_msckf_io_step_frame.
+static int step_frame_impl(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* st, const orcvio_msckf_frame_events* ev, orcvio_msckf_frame_result* res,
+                           orcvio_msckf_frame_result_ex* rex, const char* who) {
+    FrameRun f;
+    f.st = st; f.ev = ev; f.res = res; f.rex = rex; f.who = who;
+    int rc = frame_check(h, f);
+    if (rc != ORCVIO_OK) return rc;   // nothing done
+    f.tm = PhaseTimer::begin(step_timer_of(h));
+    rc = frame_head(h, f);
+    if (rc != ORCVIO_OK) return frame_leave(h, f, rc);
+    f.tm.mark(1);
+    rc = frame_first(h, f);
+    if (rc != ORCVIO_OK) return frame_leave(h, f, rc);
+    f.tm.mark(2);
+    rc = frame_second_half(h, f);
+    if (rc != ORCVIO_OK) return frame_leave(h, f, rc);
+    f.tm.mark(3);
+    rc = frame_wait(h, f);
+    f.tm.mark(4);
+    frame_timing(h);
+    if (rc == ORCVIO_OK) rc = frame_results(h, f);
+    if (rc != ORCVIO_OK) return frame_leave(h, f, rc);
+    return frame_leave(h, f, f.lostA || f.lostB ? frame_repair(h, f) : frame_outcomes(h, f));
 }
 
 int32_t orcvio_msckf_io_step_frame(orcvio_msckf_handle* h, const orcvio_msckf_frame_step* st, orcvio_msckf_frame_result* res) {

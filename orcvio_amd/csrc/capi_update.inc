@@ -25,9 +25,7 @@ static int upload_begin(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags,
     //  smaller than that by the in-state features orcvio_msckf_io_step_frame_ex removes first: the frame call checks the exact dimension)
     if (!with_P && h->res_n != n && !(pending_aug && n <= h->res_n + 6)) { g_last_error = std::string(who) + ": P == NULL but the resident covariance does not match the window"; return ORCVIO_ERR_INVALID; }
     h->uploaded = false; h->ran = false; h->io_open = false;
-    h->tri_armed = false;          // (an arming of orcvio_msckf_io_triangulate belongs to the arena it was made on)
-    h->tri2_armed = false;         // (... and so does one of orcvio_msckf_io_triangulate_prune: the frame call has taken it by now)
-    h->cc_armed = false;           // (... and one of orcvio_msckf_io_choose_clones)
+    drop_one_shot_armings(h);      // (orcvio_msckf_io_triangulate's, _io_triangulate_prune's, _io_choose_clones' belong to the arena they were made on; the frame call has taken the last two by now)
     h->last_update_thin = false;   // (set again by the update itself if it takes the direct form of a thin stack)
     h->flags = *flags;
     h->N = N; h->F = F; h->nobs = nobs;
@@ -927,7 +925,7 @@ static int run_finish_impl(orcvio_msckf_handle* h, const double* d_blocks, int n
         for (int st = ST_FORM_U; st < ST_COUNT && r == ORCVIO_OK; ++st) r = launch_solve_stage(h, s, st, c);
         return r;
     });
-    if (rc == ORCVIO_OK) { h->ran = true; h->last_update_objects = false; h->last_run_kind = 1; h->last_sharded = false; }
+    if (rc == ORCVIO_OK) mark_update_enqueued(h, 1);
     return rc;
 }
 

@@ -81,6 +81,14 @@ struct CovBook {
         else if (f == FacAfter::drop) fac_valid = false;
         res_n = n;
     }
+    // ... whose commit dropped the factor (FacAfter::drop, the direct form of a thin stack writes none) but refused itself on the device
+    // (the step call's held-back prune update): the factor `before` that commit stands untouched where it was -- buffers, shape and
+    // validity are `before`'s again if its factor followed; the covariance's buffers and dimension stay as the commit left them
+    void keep_factor_of(const CovBook& before) {
+        if (!before.fac_follows()) return;
+        d_Sres = before.d_Sres; d_Stmp = before.d_Stmp;
+        fac_n = before.fac_n; fac_k = before.fac_k; fac_ld = before.fac_ld; fac_tail = before.fac_tail; fac_valid = true;
+    }
 
 private:
     CovEdit edit(int m, int ld_out) const { return CovEdit{d_Pres, d_Ptmp, d_Sres, d_Stmp, res_n, m, fac_k, fac_ld, ld_out, fac_follows()}; }

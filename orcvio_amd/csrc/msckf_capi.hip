@@ -34,6 +34,7 @@
 #include "frame_ops.hpp"
 #include "clone_choice_ops.hpp"
 #include "host/cov_book.hpp"
+#include "host/frame_outcome.hpp"
 #include <immintrin.h>
 #include <condition_variable>
 #include <memory>
@@ -53,6 +54,25 @@ static inline const char* dbg_getenv(const char* name) { return getenv(name); }
 #else
 static inline const char* dbg_getenv(const char*) { return nullptr; }
 #endif
+
+// Host wall time of the parts of a call (ORCVIO_TIMING; diagnostics build only: the product build's dbg_getenv says "unset" and every
+// mark is a test of a null pointer).  Marks are microseconds after the call's entry, summed over k calls and printed as means by the
+// caller.  The sums live in the OBJECT: a static of the function where the process has one timeline of that call, a member of the
+// handle where two handles must not share them (the frame call).
+struct PhaseTimer {
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int calls = 0;
+    static bool on() { static const bool t = dbg_getenv("ORCVIO_TIMING") != nullptr; return t; }
+    struct Run {   // the marks of ONE call
+        PhaseTimer* t = nullptr;
+        std::chrono::steady_clock::time_point t0{};
+        void mark(int i) { if (t) t->acc[i] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+    };
+    static Run begin(PhaseTimer* t) { return on() && t ? Run{t, std::chrono::steady_clock::now()} : Run{}; }
+    bool due(int k) { return on() && (++calls % k) == 0; }   // every k-th call: acc holds the sums of the last k
+    double mean(int i, int k) const { return acc[i] / k; }
+    void reset() { for (double& v : acc) v = 0.0; }
+};
 
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
@@ -347,6 +367,9 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     int* d_step_words = nullptr;        // [0..15] status words of the frame's first update, kept for the second update's commit (info_also)
     std::vector<int> step_row_ptr;      // the second update's row offsets
     long long cnt_step_frames = 0, cnt_step_repairs = 0;   // frames through orcvio_msckf_io_step_frame; updates of such frames run again after a lost hand-off
+#ifdef ORCVIO_DEBUG_HOOKS
+    PhaseTimer step_timer;              // ORCVIO_TIMING of the frame call, per handle (step_timer_of)
+#endif
     bool ekf_one_launch = true;         // the in-state features' evaluation, fill and gate in ONE launch (k_ekf_evalgate) instead of three (ORCVIO_EKF_ONE_LAUNCH=0, diagnostics)
     bool finpub_opt = true;             // a feature update's k_finish_sqrt + k_epilogue as ONE launch (k_finish_pub) on the in-place paths (ORCVIO_FINISH_PUB=0, diagnostics)
     bool last_finpub_commit = false;    // the update enqueued last committed by writing P+ into the spare covariance buffer: the host swaps d_Pres / d_Ptmp
@@ -409,6 +432,27 @@ static inline void fac_adopt_update(orcvio_msckf_handle* h) { h->commit_update(h
 static inline void commit_bookkeeping(orcvio_msckf_handle* h) {
     h->commit_update(h->n, h->kf, h->ldz, h->tail, h->last_finpub_commit, update_fac_after(h));   // (k_finish_pub wrote P+ into the spare buffer)
     h->last_finpub_commit = false;
+}
+
+// an update has been enqueued: what the host remembers of the launch (orcvio_msckf_cov_commit, the repeat of a lost hand-off and the
+// counters read these four).  kind: last_run_kind -- 0 run_update, 1 run_local / run_finish, 2 objects
+static inline void mark_update_enqueued(orcvio_msckf_handle* h, int kind, bool sharded = false) {
+    h->ran = true; h->last_update_objects = kind == 2; h->last_run_kind = kind; h->last_sharded = sharded;
+}
+// the one-shot armings that belong to the open arena are dropped: a new upload (upload_begin), a call that takes the track buffers
+// (orcvio_msckf_triangulate), the frame call once nothing can refuse the frame any more.  first_update_too = false: the frame call --
+// its first update's arming (orcvio_msckf_io_triangulate) is taken by tri_consume when that update is enqueued.
+static inline void drop_one_shot_armings(orcvio_msckf_handle* h, bool first_update_too = true) {
+    if (first_update_too) h->tri_armed = false;
+    h->tri2_armed = false;
+    h->cc_armed = false;
+}
+static inline PhaseTimer* step_timer_of(orcvio_msckf_handle* h) {
+#ifdef ORCVIO_DEBUG_HOOKS
+    return &h->step_timer;
+#else
+    (void)h; return nullptr;
+#endif
 }
 
 template <typename T>

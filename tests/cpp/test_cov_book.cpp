@@ -144,6 +144,16 @@ static int rows_of_the_table() {
                     b.commit_update(n, n, d.ld, 0, spare, FacAfter::leave);
                     CHECK(spare ? cov_is(b, B, A, n) : cov_is(b, A, B, n));
                     CHECK(f == NONE ? fac_gone(b) : fac_is(b, C, D, f == OTHER ? n + 6 : n, k, d.ld, tail));
+                    // a dropping commit that refused itself on the device (the held-back prune update): the factor of the snapshot in
+                    // front of it is kept -- buffers, shape, validity -- if it followed; the covariance stays as the commit left it
+                    const CovBook before = start(n, f, k, d.ld, tail);
+                    b = before;
+                    b.commit_update(n, n - 15, d.ld_m, 15, spare, FacAfter::drop);
+                    b.d_Sres = D; b.d_Stmp = C; b.fac_n = 1; b.fac_k = 2; b.fac_ld = 3; b.fac_tail = 4;   // (whatever stood there: none of it may survive)
+                    b.keep_factor_of(before);
+                    CHECK(spare ? cov_is(b, B, A, n) : cov_is(b, A, B, n));
+                    if (fac) CHECK(fac_is(b, C, D, n, k, d.ld, tail));
+                    else CHECK(!b.fac_valid && b.d_Sres == D && b.d_Stmp == C && b.fac_n == 1 && b.fac_k == 2 && b.fac_ld == 3 && b.fac_tail == 4);   // nothing done
                 }
                 // save -> any edit -> restore gives back all ten fields
                 const CovBook saved = start(n, f, k, d.ld, tail);
