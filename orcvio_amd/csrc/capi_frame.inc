@@ -160,27 +160,22 @@ int32_t orcvio_msckf_io_stage_object_tracks(orcvio_msckf_handle* h, const orcvio
     if (!h || !oflags || !efl || !tracks || n_tracks < 1) { g_last_error = std::string(who) + ": null argument / no tracks"; return ORCVIO_ERR_INVALID; }
     if (!h->io_open || h->io_with_P) { g_last_error = std::string(who) + ": call orcvio_msckf_io_begin with with_P = 0 first"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
-    ObjPrestage* ps = prestage_of(h);
-    h->prestage_valid = false;
+    ObjPrestage& ps = h->prestage;
+    ps.valid = false;
     const int oN = h->N;
     const int on = oflags->leg_dim + 6 * oN + h->n_extra;
     const int oNA = h->ekf_mode ? on - 15 : oflags->leg_dim + 6 * oN - 15, oNAP = round_up(oNA + 1, 16);
     if (!(oflags->leg_dim == 22 || oflags->leg_dim == 46) || oNAP > h->NAP_max) return ORCVIO_OK;   // (not a frame the one-launch compression takes: nothing staged)
-    ObjPlan pl;
-    int dof = 0, Fmax = 1;
-    size_t nd = 0, ni = 0;
-    int rc = objects_tracks_scan(h, oN, tracks, n_tracks, h->obj_use, pl, &dof, &Fmax, &nd, &ni);
+    int rc = objects_scan(h, oN, tracks, n_tracks, ps.scan);
     if (rc != ORCVIO_OK) return rc;
-    if (!obj_fused_eligible(h, tracks, h->obj_use, oN, pl.no_max)) return ORCVIO_OK;
+    if (!obj_fused_eligible(h, tracks, oN, ps.scan.no_max)) return ORCVIO_OK;
     // (the compression of an earlier call may still be reading the staging arena: its stream is drained first -- it is, in a filter loop,
     //  long done)
     if (h->obj_stream) HIPCHK(hipStreamSynchronize(h->obj_stream));
-    ObjFusedStage st;
-    rc = objects_fused_pack(h, efl, tracks, h->obj_use, pl, nd, ni, oN, oNAP, st);
+    rc = objects_fused_pack(h, efl, tracks, ps.scan, ps.pl, oN, oNAP, ps.st);
     if (rc != ORCVIO_OK) return rc;
-    ps->tracks = tracks; ps->n_tracks = n_tracks; ps->N = oN; ps->leg_dim = oflags->leg_dim; ps->efl = *efl;
-    ps->pl = pl; ps->dof = dof; ps->Fmax = Fmax; ps->nd = nd; ps->ni = ni; ps->st = st;
-    h->prestage_valid = true;
+    ps.tracks = tracks; ps.n_tracks = n_tracks; ps.N = oN; ps.leg_dim = oflags->leg_dim; ps.efl = *efl;
+    ps.valid = true;
     return ORCVIO_OK;
 }
 
@@ -236,9 +231,7 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     // ahead of the feature update's remaining five launches, which the host has 40 us to put out.  The compression then starts ~20 us
     // earlier and is done well before the feature half; possible when every object takes the one-launch compression (k_obj_fused), whose
     // staging and launches touch none of the handle's feature-problem fields.
-    ObjPlan early_pl;
-    int early_dof = 0, early_Fmax = 1;
-    size_t early_nd = 0, early_ni = 0;
+    ObjScan early_scan;   // what the scan of the tracks found, here or ahead of the call
     bool early = false;
     int early_rc = ORCVIO_OK;
     const int oN = N;
@@ -246,17 +239,16 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     const int oNA = h->ekf_mode ? on - 15 : oflags->leg_dim + 6 * oN - 15, oNAP = round_up(oNA + 1, 16);
     // (orcvio_msckf_io_stage_object_tracks ahead of this call: the scan and the staging of these very tracks are done -- ~14 us of host time
     //  that stood between the tracks' launch and the compression's)
-    ObjPrestage* ps = h->prestage ? static_cast<ObjPrestage*>(h->prestage.get()) : nullptr;
-    const bool pre = ps && h->prestage_valid && ps->tracks == tracks && ps->n_tracks == n_tracks && ps->N == oN && ps->leg_dim == oflags->leg_dim &&
-                     std::memcmp(&ps->efl, efl, sizeof(*efl)) == 0 && oNAP <= h->NAP_max;
-    h->prestage_valid = false;   // (one use)
+    const ObjPrestage& ps = h->prestage;
+    const bool pre = ps.valid && ps.tracks == tracks && ps.n_tracks == n_tracks && ps.N == oN && ps.leg_dim == oflags->leg_dim &&
+                     std::memcmp(&ps.efl, efl, sizeof(*efl)) == 0 && oNAP <= h->NAP_max;
+    h->prestage.valid = false;   // (one use)
     if (pre) {
-        early_pl = ps->pl; early_dof = ps->dof; early_Fmax = ps->Fmax; early_nd = ps->nd; early_ni = ps->ni;
+        early_scan = ps.scan;
         early = true;
         h->cnt_prestaged++;
     } else if (n_tracks > 0 && (oflags->leg_dim == 22 || oflags->leg_dim == 46) && oNAP <= h->NAP_max) {
-        if (objects_tracks_scan(h, oN, tracks, n_tracks, h->obj_use, early_pl, &early_dof, &early_Fmax, &early_nd, &early_ni) == ORCVIO_OK &&
-            obj_fused_eligible(h, tracks, h->obj_use, oN, early_pl.no_max)) early = true;
+        if (objects_scan(h, oN, tracks, n_tracks, early_scan) == ORCVIO_OK && obj_fused_eligible(h, tracks, oN, early_scan.no_max)) early = true;
     }
     // the chained object solve (above): opt-in, for frames whose objects all take the one-launch compression and commit in the call
     bool chain = h->frame_chain && early && commit_objects != 0 && !h->ekf_mode && h->n_extra == 0 && oflags->leg_dim == fflags.leg_dim &&
@@ -274,12 +266,12 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     const ChainGeom cgeom{prior_factor(h), h->n, h->NA, h->NAP, h->NP, h->ldz, h->kf, h->tail, h->flags.noise_feature};   // (the FEATURE update's solve, before the book-keeping below)
     std::function<int()> mid = [&]() -> int {
         prof_begin(h, h->obj_stream);
-        early_rc = pre ? objects_fused_launch(h, h->obj_stream, h->d_A, early_pl, ps->st, (int)h->obj_use.size(), oN, oNA, oNAP, oflags->leg_dim - 15, signal_done)
-                       : objects_tracks_fused(h, h->obj_stream, h->d_A, efl, tracks, h->obj_use, early_pl, early_nd, early_ni, oN, oNA, oNAP, oflags->leg_dim - 15, signal_done);
+        early_rc = pre ? objects_fused_launch(h, h->obj_stream, h->d_A, ps.pl, ps.st, early_scan.nobj, oN, oNA, oNAP, oflags->leg_dim - 15, signal_done)
+                       : objects_tracks_fused(h, h->obj_stream, h->d_A, efl, tracks, early_scan, oN, oNA, oNAP, oflags->leg_dim - 15, signal_done);
         // (the event the main stream joins on: not in the chained form, whose solve runs on this stream -- a record costs ~5 us of stream
         //  time between k_gemm_objA and the solve's first product; if the chain is dropped after all, it is recorded then)
         if (!chain && early_rc == ORCVIO_OK && hipEventRecord(h->ev_obj, h->obj_stream) != hipSuccess) { (void)hipGetLastError(); early_rc = ORCVIO_ERR_HIP; }
-        if (chain && early_rc == ORCVIO_OK) { chain_rc = frame_chain_solve(h, cgeom, w1, w2, early_dof, oflags->chi2_prob); chain_part1 = true; }
+        if (chain && early_rc == ORCVIO_OK) { chain_rc = frame_chain_solve(h, cgeom, w1, w2, early_scan.dof, oflags->chi2_prob); chain_part1 = true; }
         return ORCVIO_OK;   // (a refusal of the object half must not stop the feature half: it is reported below)
     };
     { const int rw = step_words(h); if (rw != ORCVIO_OK) return rw; }
@@ -332,12 +324,10 @@ int32_t orcvio_msckf_io_update_frame(orcvio_msckf_handle* h, orcvio_msckf_result
     int32_t dof = 0;
     bool commit_in_launch = false;
     h->frame_mode = true;
-    h->obj_early_done = early && early_rc == ORCVIO_OK;   // (the compression is out already: the call below does the bookkeeping only)
-    h->early_rows_tot = early_pl.rows_tot; h->early_no_max = early_pl.no_max; h->early_dof = early_dof; h->early_Fmax = early_Fmax;
-    h->early_nd = early_nd; h->early_ni = early_ni;
+    h->obj_early = early && early_rc == ORCVIO_OK ? &early_scan : nullptr;   // (the compression is out already: the call below does the bookkeeping only)
     int rco = early && early_rc != ORCVIO_OK ? early_rc
                                               : orcvio_msckf_objects_local_tracks(h, oflags, efl, N, tracks, n_tracks, nullptr, h->d_A, &dof, (void*)h->obj_stream);
-    h->obj_early_done = false;
+    h->obj_early = nullptr;
     h->frame_mode = false;
     h->last_stream = s;
     tmark(2);

@@ -16,29 +16,7 @@ static void prof_mark(orcvio_msckf_handle* h, hipStream_t s, const char* name) {
     h->prof_names.push_back(name);
 }
 
-// ---- object update: device scratch and host staging ------------------------------------------------------------------
-// ONE input arena per object update, mirrored in pinned host memory (grown on demand) and copied with one asynchronous
-// copy: [doubles ... | ints ...].  Device-side scratch (row arrays written by k_object_rows_batch, Cd, Sg, Gff, factors)
-// is separate and never crosses PCIe.
-struct ObjPlan {
-    int nobj = 0, rows_tot = 0, no_max = 0, ngroups = 0;
-    int NOP = 0, ldf = 0;
-    // device pointers
-    int *d_ridx = nullptr, *d_rowptr = nullptr, *d_clone = nullptr, *d_cols = nullptr;
-    ObjGroup* d_groups = nullptr;
-    double *d_hx = nullptr, *d_hf = nullptr, *d_res = nullptr;
-    double *d_Cd = nullptr, *d_Sg = nullptr, *d_Gff = nullptr;
-    // arrow structure of Hf (structured Householder QR instead of chol(Hf^T Hf)); arrow = false: the Gram route
-    bool arrow = false;
-    int Kmax = 0, rows_max = 0;
-    ObjArrow* d_arrow = nullptr;
-    int2* d_kp_range = nullptr;
-    int* d_kp_rows = nullptr;
-    double* d_Rarrow = nullptr;
-    double *d_Hr = nullptr, *d_Hfr = nullptr;   // [nobj][N][NOP] per-clone parts of Hf^T r; [nobj][NOP + 1] their sums and |r|^2
-    double* d_Bred = nullptr;   // [rows][9] the border of every row after the keypoint blocks have been eliminated
-    double* d_Qt = nullptr;     // [rows][OBJ_REFINE_ROW_DOUBLES] obj_refine_body: staging of objects too long for the LDS staging
-};
+// ---- object update: device scratch and host staging (the plan records: msckf_capi.hip; the staging itself: host/object_stage.hpp) ----
 static int obj_stage_reserve(orcvio_msckf_handle* h, size_t bytes) {
     if (bytes <= h->obj_stage_cap) return ORCVIO_OK;
     HIPCHK(hipDeviceSynchronize());
@@ -244,56 +222,6 @@ static int objects_prior(orcvio_msckf_handle* h, hipStream_t s, const double* P,
     }
     return ORCVIO_OK;
 }
-
-// ORCVIO_OPT_REF_STACK_HF: System::processObjects stacks Hx, Hf and r of all objects VERTICALLY, Hf with its 45 columns
-// shared (ros_wrapper/src/orcvio/src/System.cpp:684-702), and removeLostObjects projects the whole stack against that one Hf
-// (src/orcvio.cpp:2154-2193): the objects become ONE block of rows.  Host arrays of the staged update are rewritten in
-// place: one object, its rows regrouped by clone through the index list.
-static void merge_objects_ref_stack(int N, int nobj, int rows_tot, int* ridx, int* rowptr, ObjGroup* groups, int* ng) {
-    std::vector<int> old_ridx(ridx, ridx + rows_tot);
-    std::vector<ObjGroup> old(groups, groups + *ng);
-    int pos = 0, g = 0;
-    for (int c = 0; c < N; ++c) {
-        const int g0 = pos;
-        for (const ObjGroup& q : old)
-            if (q.clone == c)
-                for (int k = q.r0; k < q.r1; ++k) ridx[pos++] = old_ridx[k];
-        if (pos > g0) groups[g++] = ObjGroup{g0, pos, c, 0};
-    }
-    *ng = g;
-    rowptr[0] = 0; rowptr[1] = rows_tot;
-    (void)nobj;
-}
-
-// Arrow structure of the objects' Hf for the structured QR (k_obj_arrow_qr): rowkp[row] = keypoint block of the row (-1: a
-// border-only row), Ks[o] = keypoint blocks of object o.  Fills arrows / ranges / kp_rows (host mirrors of the device arrays);
-// returns false if some object does not fit the kernel's limits (<= 128 rows per keypoint, <= 2048 rows per object).
-static bool build_arrow(const int* rowkp, const int* rowptr, const int* Ks, int nobj, ObjArrow* arrows, int2* ranges, int* kp_rows,
-                        int* Kmax, int* rows_max) {
-    // per object K + 1 ranges into kp_rows: the rows of keypoint block 0 .. K-1, then the border-only rows
-    int off = 0, pos = 0;
-    *Kmax = 0; *rows_max = 0;
-    for (int o = 0; o < nobj; ++o) {
-        const int r0 = rowptr[o], r1 = rowptr[o + 1], K = Ks[o];
-        if (r1 - r0 > 2048 || K > 34) return false;
-        int cnt[36] = {0};
-        for (int r = r0; r < r1; ++r) cnt[rowkp[r] >= 0 ? rowkp[r] : K]++;
-        int start[36];
-        for (int k = 0; k <= K; ++k) {
-            if (k < K && cnt[k] > 128) return false;
-            start[k] = pos;
-            ranges[off + k] = int2{pos, pos + cnt[k]};
-            pos += cnt[k];
-        }
-        for (int r = r0; r < r1; ++r) kp_rows[start[rowkp[r] >= 0 ? rowkp[r] : K]++] = r;
-        arrows[o] = ObjArrow{r0, r1 - r0, K, off};
-        off += K + 1;
-        if (K > *Kmax) *Kmax = K;
-        if (r1 - r0 > *rows_max) *rows_max = r1 - r0;
-    }
-    return true;
-}
-
 // window-dependent sizes of an object update (no tracks)
 static int objects_problem(orcvio_msckf_handle* h, const orcvio_msckf_flags* flags, int N, const double* P, const char* who) {
     if (flags->leg_dim != 22 && flags->leg_dim != 46) { g_last_error = std::string(who) + ": leg_dim must be 22 or 46"; return ORCVIO_ERR_INVALID; }
@@ -317,6 +245,36 @@ static int objects_problem(orcvio_msckf_handle* h, const orcvio_msckf_flags* fla
     h->h_row_ptr.assign(1, 0);
     return ORCVIO_OK;
 }
+// Scan of an update's object tracks into the handle's lists (objects_tracks_scan, host/object_stage.hpp); voids what was staged ahead.
+static int objects_scan(orcvio_msckf_handle* h, int N, const orcvio_object_track* tracks, int n_tracks, ObjScan& sc) {
+    h->prestage.valid = false;   // (the lists and the staging arena of a pre-staged frame are about to be overwritten)
+    const char* why = "";
+    const int rc = objects_tracks_scan(N, h->ref_stack_hf, tracks, n_tracks, h->obj_use, h->obj_nv, sc, &why);
+    if (rc != ORCVIO_OK) g_last_error = why;
+    return rc;
+}
+static ObjPlan plan_of(const ObjScan& sc) { ObjPlan pl; pl.nobj = sc.nobj; pl.rows_tot = sc.rows_tot; pl.no_max = sc.no_max; return pl; }
+// device views of the integer arena
+static void plan_views(ObjPlan& pl, const ObjIntViews& v) {
+    pl.d_ridx = v.ridx; pl.d_rowptr = v.rowptr; pl.d_groups = v.groups;
+    pl.d_arrow = v.arrows; pl.d_kp_range = reinterpret_cast<int2*>(v.kp_range); pl.d_kp_rows = v.kp_rows;
+}
+
+// The shared head of the two objects_local* entry points, behind the scan: the prior, the handle's record of the update and -- nothing
+// usable on this rank (sc.nobj == 0) -- the zero block, behind which the caller returns.
+static int objects_begin(orcvio_msckf_handle* h, hipStream_t s, const double* P, const char* who, const ObjScan& sc, double* dst) {
+    h->last_stream = s;
+    prof_begin(h, s);
+    { const int rp = objects_prior(h, s, P, who); if (rp != ORCVIO_OK) return rp; }
+    h->uploaded = true;
+    h->objects_mode = true;
+    h->last_update_thin = false;
+    h->obj_dof = sc.dof; h->obj_rows = sc.rows_tot; h->obj_count = sc.nobj;
+    if (!h->d_obj_accept) { HIPCHK(hipMalloc(&h->d_obj_accept, sizeof(int) * 4)); HIPCHK(hipMalloc(&h->d_obj_gamma, sizeof(double) * 4)); }
+    if (sc.nobj > 0) return ORCVIO_OK;
+    HIPCHK(hipMemsetAsync(dst, 0, sizeof(double) * (size_t)h->NAP * h->NAP, s));   // a zero block
+    return launch_prior_fork(h, s);
+}
 
 // Local part of an object update: this rank's objects -> its compressed block [A' b'; b'^T c'] (NAP x NAP) in d_dst
 // (the handle's own block if NULL), Cholesky of P forked on the side stream.
@@ -326,177 +284,57 @@ int32_t orcvio_msckf_objects_local(orcvio_msckf_handle* h, const orcvio_msckf_fl
     if (!h || !flags || n_objects < 0 || (n_objects > 0 && !objs)) { g_last_error = "objects_local: null argument"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     { const int rp = objects_problem(h, flags, n_clones, P, "objects_local"); if (rp != ORCVIO_OK) return rp; }
-    const int N = n_clones, NAP = h->NAP;
-    // usable objects, row offsets, widest object state
-    std::vector<int> use;
-    ObjPlan pl;
-    int dof = 0;
-    for (int o = 0; o < n_objects; ++o) {
-        const orcvio_msckf_object_rows& ob = objs[o];
-        if (ob.n_rows < 0 || ob.n_obj_cols < 1 || ob.n_obj_cols > 112) { g_last_error = "objects_local: bad block shape (object state columns must be 1..112)"; return ORCVIO_ERR_INVALID; }
-        if (ob.n_rows > 0 && (!ob.row_clone || !ob.Hx6 || !ob.Hf || !ob.res)) { g_last_error = "objects_local: null block arrays"; return ORCVIO_ERR_INVALID; }
-        if (h->ref_stack_hf ? ob.n_rows == 0 : ob.n_rows <= ob.n_obj_cols) continue;   // nullspace_project_inplace_svd returns false
-        for (int r = 0; r < ob.n_rows; ++r)
-            if (ob.row_clone[r] < 0 || ob.row_clone[r] >= N) { g_last_error = "objects_local: row_clone out of range"; return ORCVIO_ERR_INVALID; }
-        if (h->ref_stack_hf && pl.no_max > 0 && ob.n_obj_cols != pl.no_max) { g_last_error = "objects_local: ORCVIO_OPT_REF_STACK_HF needs equal object state sizes"; return ORCVIO_ERR_INVALID; }
-        use.push_back(o);
-        pl.rows_tot += ob.n_rows;
-        dof += ob.n_rows - ob.n_obj_cols;
-        if (ob.n_obj_cols > pl.no_max) pl.no_max = ob.n_obj_cols;
-    }
-    if (h->ref_stack_hf) {   // one stacked block: projectable only if it has more rows than columns; dof = its rows - columns
-        if (pl.rows_tot <= pl.no_max) { use.clear(); pl.rows_tot = 0; }
-        dof = use.empty() ? 0 : pl.rows_tot - pl.no_max;
-    }
-    pl.nobj = (int)use.size();
+    const int N = n_clones;
+    std::vector<int> use;   // usable objects
+    ObjScan sc;
+    { const char* why = ""; const int rs = objects_rows_scan(N, h->ref_stack_hf, objs, n_objects, use, sc, &why); if (rs != ORCVIO_OK) { g_last_error = why; return rs; } }
     hipStream_t s = pick_stream(h, stream);
-    h->last_stream = s;
     double* dst = d_dst ? d_dst : h->d_Ab;
-    if (dof_out) *dof_out = dof;
-    prof_begin(h, s);
-    { const int rp = objects_prior(h, s, P, "objects_local"); if (rp != ORCVIO_OK) return rp; }
-    h->uploaded = true;
-    h->objects_mode = true;
-    h->last_update_thin = false;
-    h->obj_dof = dof; h->obj_rows = pl.rows_tot; h->obj_count = pl.nobj;
-    if (!h->d_obj_accept) { HIPCHK(hipMalloc(&h->d_obj_accept, sizeof(int) * 4)); HIPCHK(hipMalloc(&h->d_obj_gamma, sizeof(double) * 4)); }
-    if (pl.nobj == 0) {   // nothing usable on this rank: a zero block
-        HIPCHK(hipMemsetAsync(dst, 0, sizeof(double) * (size_t)NAP * NAP, s));
-        return launch_prior_fork(h, s);
-    }
-    int rc = objects_scratch(h, &pl);
-    if (rc != ORCVIO_OK) return rc;
-    // staging arena: [Hx6 rows x 6 | HfR rows x ldf] doubles, then ints [ridx rows | rowptr nobj+1 | arrows 4 nobj | kp ranges
-    // 2 x sum K | kp_rows rows | groups 4 x <= nobj N]
+    if (dof_out) *dof_out = sc.dof;
+    int rc = objects_begin(h, s, P, "objects_local", sc, dst);
+    if (rc != ORCVIO_OK || sc.nobj == 0) return rc;
+    ObjPlan pl = plan_of(sc);
+    if ((rc = objects_scratch(h, &pl)) != ORCVIO_OK) return rc;
+    // staging arena: [Hx6 rows x 6 | HfR rows x ldf] doubles, then the ints (ObjIntLayout)
     const size_t rows = (size_t)pl.rows_tot, ldf = (size_t)pl.ldf;
     size_t sumK = 0;
     for (int o : use) sumK += (size_t)((objs[o].n_obj_cols - 9) / 3 > 0 ? (objs[o].n_obj_cols - 9) / 3 : 0);
     const size_t nd = rows * 6 + rows * ldf;
-    const size_t o_ridx = 0, o_rowptr = o_ridx + rows, o_arrow = o_rowptr + pl.nobj + 1, o_range = o_arrow + (size_t)4 * pl.nobj,
-                 o_kprows = o_range + 2 * (sumK + (size_t)pl.nobj), o_groups = o_kprows + rows, ni = o_groups + (size_t)4 * pl.nobj * N;
-    if ((rc = obj_stage_reserve(h, nd * 8 + ni * 4)) != ORCVIO_OK) return rc;
-    double* hd = reinterpret_cast<double*>(h->h_obj_stage);
-    int* hi = reinterpret_cast<int*>(h->h_obj_stage + nd * 8);
-    double* hx = hd;
-    double* hf = hd + rows * 6;
-    int* ridx = hi + o_ridx;
-    int* rowptr = hi + o_rowptr;
-    ObjGroup* groups = reinterpret_cast<ObjGroup*>(hi + o_groups);
+    const ObjIntLayout lay = obj_int_layout(rows, pl.nobj, sumK, N, 0);
+    if ((rc = obj_stage_reserve(h, nd * 8 + lay.ni * 4)) != ORCVIO_OK) return rc;
+    double* hx = reinterpret_cast<double*>(h->h_obj_stage);
+    double* hf = hx + rows * 6;
+    const ObjIntViews hv = lay.views(reinterpret_cast<int*>(h->h_obj_stage + nd * 8));
     std::memset(hf, 0, sizeof(double) * rows * ldf);
-    std::vector<int>& rowkp = h->obj_fnr;   // (scratch) keypoint block of every row, -1: border only, -2: no arrow structure
+    std::vector<int>& rowkp = h->obj_fnr;   // (scratch) keypoint block of every row, -1: border only
     rowkp.assign(rows, -1);
     std::vector<int> Ks(pl.nobj, 0);
     bool structured = true;
     int r0 = 0, ng = 0;
-    rowptr[0] = 0;
+    hv.rowptr[0] = 0;
     for (size_t ui = 0; ui < use.size(); ++ui) {
         const orcvio_msckf_object_rows& ob = objs[use[ui]];
-        const int nc = ob.n_obj_cols;
-        const bool shape_ok = nc >= 9 && (nc - 9) % 3 == 0;   // [pose 6 | shape 3 | 3 per keypoint], ObjectLM.h:117-123
-        Ks[ui] = shape_ok ? (nc - 9) / 3 : 0;
-        structured = structured && shape_ok;
-        int cnt[ORCVIO_MAX_CLONES + 1] = {0};
-        for (int r = 0; r < ob.n_rows; ++r) {
-            std::memcpy(hx + (size_t)(r0 + r) * 6, ob.Hx6 + (size_t)r * 6, 6 * sizeof(double));
-            double* row = hf + (size_t)(r0 + r) * ldf;
-            const double* src = ob.Hf + (size_t)r * nc;
-            std::memcpy(row, src, nc * sizeof(double));
-            row[pl.no_max] = ob.res[r];
-            cnt[ob.row_clone[r] + 1]++;
-            if (structured) {   // the row's non-zeros behind the border must lie in ONE keypoint block
-                int blk = -1;
-                for (int c = 9; c < nc; ++c)
-                    if (src[c] != 0.0) {
-                        const int b = (c - 9) / 3;
-                        if (blk >= 0 && b != blk) { structured = false; break; }
-                        blk = b;
-                    }
-                rowkp[r0 + r] = blk;
-            }
-        }
-        for (int c = 0; c < N; ++c) cnt[c + 1] += cnt[c];
-        for (int c = 0; c < N; ++c)
-            if (cnt[c + 1] > cnt[c]) groups[ng++] = ObjGroup{r0 + cnt[c], r0 + cnt[c + 1], c, (int)ui};
-        int fill[ORCVIO_MAX_CLONES + 1];
-        std::memcpy(fill, cnt, sizeof(int) * (N + 1));
-        for (int r = 0; r < ob.n_rows; ++r) ridx[r0 + fill[ob.row_clone[r]]++] = r0 + r;   // rows grouped by clone (stable)
+        Ks[ui] = obj_pack_rows(ob, r0, ldf, pl.no_max, hx, hf, rowkp.data(), structured);
+        obj_group_rows(ob.row_clone, ob.n_rows, N, r0, (int)ui, hv.ridx, hv.groups, &ng);
         r0 += ob.n_rows;
-        rowptr[ui + 1] = r0;
+        hv.rowptr[ui + 1] = r0;
     }
     if (h->ref_stack_hf && pl.nobj > 1) {
-        merge_objects_ref_stack(N, pl.nobj, pl.rows_tot, ridx, rowptr, groups, &ng);
+        merge_objects_ref_stack(N, pl.rows_tot, hv.ridx, hv.rowptr, hv.groups, &ng);
         pl.nobj = 1; h->obj_count = 1; structured = false;
         rc = objects_scratch(h, &pl);   // the scratch of ONE block: Cd | Sg | Hr adjacent again (the row arrays depend on the row count only)
         if (rc != ORCVIO_OK) return rc;
     }
     pl.ngroups = ng;
     pl.arrow = structured && h->arrow_opt &&
-               build_arrow(rowkp.data(), rowptr, Ks.data(), pl.nobj, reinterpret_cast<ObjArrow*>(hi + o_arrow),
-                           reinterpret_cast<int2*>(hi + o_range), hi + o_kprows, &pl.Kmax, &pl.rows_max);
+               build_arrow(rowkp.data(), hv.rowptr, Ks.data(), pl.nobj, hv.arrows, hv.kp_range, hv.kp_rows, &pl.Kmax, &pl.rows_max);
     if (pl.arrow) { rc = objects_scratch(h, &pl); if (rc != ORCVIO_OK) return rc; }   // (room for the arrow factors)
     // device views of the arena
     double* dd = reinterpret_cast<double*>(h->d_obj_in);
-    int* di = reinterpret_cast<int*>(h->d_obj_in + nd * 8);
     pl.d_hx = dd; pl.d_hf = dd + rows * 6;
-    pl.d_ridx = di + o_ridx; pl.d_rowptr = di + o_rowptr; pl.d_groups = reinterpret_cast<ObjGroup*>(di + o_groups);
-    pl.d_arrow = reinterpret_cast<ObjArrow*>(di + o_arrow); pl.d_kp_range = reinterpret_cast<int2*>(di + o_range); pl.d_kp_rows = di + o_kprows;
-    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, nd * 8 + (o_groups + (size_t)4 * ng) * 4); if (ri != ORCVIO_OK) return ri; }
+    plan_views(pl, lay.views(reinterpret_cast<int*>(h->d_obj_in + nd * 8)));
+    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, lay.ingest_bytes(nd, ng)); if (ri != ORCVIO_OK) return ri; }
     return objects_pipeline(h, s, dst, pl);
-}
-
-// Pass 1 over the object tracks of an update: which are usable (more in-window rows than state columns, math_utils.hpp:292), their
-// row offsets, the staged sizes, the gate's degrees of freedom.  Touches nothing of the handle but the list itself.
-static int objects_tracks_scan(orcvio_msckf_handle* h, int N, const orcvio_object_track* tracks, int n_tracks, std::vector<ObjUse>& use, ObjPlan& pl,
-                               int* dof_out, int* Fmax_out, size_t* nd_out, size_t* ni_out) {
-    typedef ObjUse Use;
-    h->prestage_valid = false;   // (the lists and the staging arena of a pre-staged frame are about to be overwritten)
-    use.clear();
-    std::vector<signed char>& nvs = h->obj_nv;
-    nvs.clear();
-    int dof = 0, Fmax = 1;
-    size_t nd = 0, ni = 0;
-    for (int t = 0; t < n_tracks; ++t) {
-        const orcvio_object_track& ob = tracks[t];
-        const int K = ob.n_keypoints, F = ob.n_frames, ncol = 9 + 3 * K;
-        if (K < 0 || K > 34 || F < 1) { g_last_error = "objects_local_tracks: 0..34 keypoints (object state <= 112 columns), >= 1 frame"; return ORCVIO_ERR_INVALID; }
-        // (K = 0: a bbox-only track -- object state [pose 6 | shape 3], four rows per frame; kps / frame_zs are not read)
-        if (!ob.wTo || !ob.shape || (K > 0 && (!ob.kps || !ob.frame_zs)) || !ob.frame_wTc || !ob.frame_bbox || !ob.frame_clone) { g_last_error = "objects_local_tracks: null track arrays"; return ORCVIO_ERR_INVALID; }
-        int rows = 0, fin = 0, distinct = 1;
-        unsigned long long seen = 0ull;   // (N <= ORCVIO_MAX_CLONES = 60)
-        const size_t off_nv = nvs.size();
-        nvs.resize(off_nv + (size_t)F);
-        signed char* nvp = nvs.data() + off_nv;
-        for (int f = 0; f < F; ++f) {
-            const int c = ob.frame_clone[f];
-            if (c >= N) { g_last_error = "objects_local_tracks: frame_clone out of the window"; return ORCVIO_ERR_INVALID; }
-            if (c < 0) { nvp[f] = -1; continue; }
-            if (seen >> c & 1ull) distinct = 0;
-            seen |= 1ull << c;
-            ++fin;
-            int nv = 0;
-            const double* zs = ob.frame_zs + (size_t)f * K * 2;
-            for (int k = 0; k < K; ++k)
-                if (std::isfinite(zs[2 * k]) && std::isfinite(zs[2 * k + 1])) ++nv;   // row finite test, ObjectLM.cpp:171-198
-            nvp[f] = (signed char)nv;
-            rows += 2 * nv + 4;
-        }
-        if (h->ref_stack_hf ? rows == 0 : rows <= ncol) continue;   // nullspace_project_inplace_svd returns false
-        if (h->ref_stack_hf && pl.no_max > 0 && ncol != pl.no_max) { g_last_error = "objects_local_tracks: ORCVIO_OPT_REF_STACK_HF needs equal object state sizes"; return ORCVIO_ERR_INVALID; }
-        use.push_back(Use{t, pl.rows_tot, rows, ncol, nd, ni, fin, distinct, off_nv});
-        nd += 16 + 3 + (size_t)3 * K + (size_t)F * (16 + 2 * K + 4);
-        ni += (size_t)2 * F;
-        pl.rows_tot += rows;
-        dof += rows - ncol;
-        if (ncol > pl.no_max) pl.no_max = ncol;
-        if (F > Fmax) Fmax = F;
-    }
-    if (h->ref_stack_hf) {
-        if (pl.rows_tot <= pl.no_max) { use.clear(); pl.rows_tot = 0; }
-        dof = use.empty() ? 0 : pl.rows_tot - pl.no_max;
-    }
-    pl.nobj = (int)use.size();
-    *dof_out = dof; *Fmax_out = Fmax; *nd_out = nd; *ni_out = ni;
-    return ORCVIO_OK;
 }
 
 // ---- object tracks, one-launch compression (object_fused.hpp) ------------------------------------------------------------------
@@ -517,10 +355,10 @@ static int obj_fused_lds_rows(orcvio_msckf_handle* h, int Kmax, int NOP, int N) 
     if (h->obj_fused_budget <= base) return 0;
     return (int)((h->obj_fused_budget - base) / (sizeof(double) * OBJ_REFINE_ROW_DOUBLES));
 }
-
 // Can every usable track of this update take the one-launch compression?  (In-window frames on distinct clones, at most
 // OBJ_FUSED_MAXF of them, at most 8 * OBJ_FUSED_KPW keypoints, rows within the LDS staging.)
-static bool obj_fused_eligible(orcvio_msckf_handle* h, const orcvio_object_track* tracks, const std::vector<ObjUse>& use, int N, int no_max) {
+static bool obj_fused_eligible(orcvio_msckf_handle* h, const orcvio_object_track* tracks, int N, int no_max) {
+    const std::vector<ObjUse>& use = h->obj_use;
     if (!h->obj_fused_opt || !h->arrow_opt || h->ref_stack_hf || h->obj_refine_mode == 0 || use.empty()) return false;
     int Kmax = 0;
     for (const ObjUse& u : use) Kmax = std::max(Kmax, tracks[u.t].n_keypoints);
@@ -537,16 +375,14 @@ static bool obj_fused_eligible(orcvio_msckf_handle* h, const orcvio_object_track
 //  problem still stands in the handle's fields)
 // In two parts: the host's staging (objects_fused_pack: the pinned arena, the device scratch, the plan) and the launches
 // (objects_fused_launch) -- orcvio_msckf_io_stage_object_tracks runs the first ahead of the frame call.
-struct ObjFusedStage { size_t nd_tot = 0, ni_tot = 0, args_off = 0, o_arrow = 0; int Kmax = 0, rows_max = 0; };
-static int objects_fused_pack(orcvio_msckf_handle* h, const orcvio_object_eval_flags* fl, const orcvio_object_track* tracks,
-                              const std::vector<ObjUse>& use, ObjPlan& pl, size_t nd, size_t ni, const int N, const int NAP, ObjFusedStage& st) {
-    static_assert(sizeof(ObjEvalArgs) % sizeof(double) == 0, "ObjEvalArgs is copied as doubles");
-    const size_t arg_dbl = sizeof(ObjEvalArgs) / sizeof(double);
-    const size_t args_off = nd;
-    nd += arg_dbl * use.size();
-    const size_t o_arrow = ni, ni_tot = o_arrow + (size_t)4 * use.size();
+static int objects_fused_pack(orcvio_msckf_handle* h, const orcvio_object_eval_flags* fl, const orcvio_object_track* tracks, const ObjScan& sc,
+                              ObjPlan& pl, const int N, const int NAP, ObjFusedStage& st) {
+    const std::vector<ObjUse>& use = h->obj_use;
+    const size_t arg_dbl = OBJ_ARG_DOUBLES, args_off = sc.nd, nd = sc.nd + arg_dbl * use.size();
+    const size_t o_arrow = sc.ni, ni_tot = o_arrow + (size_t)4 * use.size();
     int rc = obj_stage_reserve(h, nd * 8 + ni_tot * 4);
     if (rc != ORCVIO_OK) return rc;
+    pl = plan_of(sc);
     pl.NOP = round_up(pl.no_max, 16);
     pl.ldf = round_up(pl.no_max + 1, 16);
     {   // device scratch: Y, the clone tiles, |r|^2
@@ -565,41 +401,11 @@ static int objects_fused_pack(orcvio_msckf_handle* h, const orcvio_object_eval_f
     for (size_t ui = 0; ui < use.size(); ++ui) {
         const ObjUse& u = use[ui];
         const orcvio_object_track& ob = tracks[u.t];
-        const int K = ob.n_keypoints, F = ob.n_frames;
-        double* q = hd + u.off_d;
-        std::memcpy(q, ob.wTo, 16 * 8); q += 16;
-        std::memcpy(q, ob.shape, 3 * 8); q += 3;
-        if (K > 0) std::memcpy(q, ob.kps, (size_t)3 * K * 8);
-        q += 3 * K;
-        std::memcpy(q, ob.frame_wTc, (size_t)16 * F * 8); q += (size_t)16 * F;
-        if (K > 0) std::memcpy(q, ob.frame_zs, (size_t)2 * K * F * 8);
-        q += (size_t)2 * K * F;
-        std::memcpy(q, ob.frame_bbox, (size_t)4 * F * 8);
-        int* fc = hi + u.off_i;
-        int* fr0 = fc + F;
-        int rr = u.row0;
-        const signed char* nvp = h->obj_nv.data() + u.off_nv;
-        for (int f = 0; f < F; ++f) {
-            fc[f] = ob.frame_clone[f];
-            fr0[f] = 0;
-            if (fc[f] < 0) continue;
-            fr0[f] = rr;
-            rr += 2 * (int)nvp[f] + 4;   // (the keypoint counts of objects_tracks_scan: one pass over the observations per update)
-        }
-        arrows[ui] = ObjArrow{u.row0, rr - u.row0, K, 0};
-        if (K > Kmax) Kmax = K;
-        if (rr - u.row0 > rows_max) rows_max = rr - u.row0;
-        ObjEvalArgs a;
-        a.wTo = dd + u.off_d; a.shape = a.wTo + 16; a.kps = a.shape + 3; a.frame_wTc = a.kps + 3 * K;
-        a.frame_zs = a.frame_wTc + (size_t)16 * F; a.frame_bbox = a.frame_zs + (size_t)2 * K * F;
-        a.frame_clone = di + u.off_i; a.frame_row0 = a.frame_clone + F;
-        a.K = K; a.F = F; a.ncol = u.ncol; a.ldhf = pl.ldf; a.rcol = pl.no_max; a.row_cols = nullptr;
-        a.obj_left = fl->use_left_perturbation; a.new_bbox = fl->use_new_bbox_residual; a.vio_left = fl->vio_use_left_perturbation;
-        a.fix_D = fl->fix_dcampose_dimupose_to_identity;
-        std::memcpy(a.R_b2c, fl->R_b2c, sizeof(a.R_b2c));
-        std::memcpy(a.t_c_b, fl->t_c_b, sizeof(a.t_c_b));
-        a.Hx6 = nullptr; a.Hf = nullptr; a.res = nullptr; a.row_clone = nullptr;
-        std::memcpy(hd + args_off + arg_dbl * ui, &a, sizeof(a));
+        const int rows = obj_pack_track(ob, u, h->obj_nv.data() + u.off_nv, fl, pl.ldf, pl.no_max, ObjRowArrays{}, hd, hi, dd, di,
+                                        reinterpret_cast<ObjEvalArgs*>(hd + args_off + arg_dbl * ui));
+        arrows[ui] = ObjArrow{u.row0, rows, ob.n_keypoints, 0};
+        if (ob.n_keypoints > Kmax) Kmax = ob.n_keypoints;
+        if (rows > rows_max) rows_max = rows;
     }
     pl.arrow = true; pl.Kmax = Kmax; pl.rows_max = rows_max; pl.ngroups = 0;
     st.nd_tot = nd; st.ni_tot = ni_tot; st.args_off = args_off; st.o_arrow = o_arrow; st.Kmax = Kmax; st.rows_max = rows_max;
@@ -670,28 +476,85 @@ static int objects_fused_launch(orcvio_msckf_handle* h, hipStream_t s, double* d
     return ORCVIO_OK;
 }
 static int objects_tracks_fused(orcvio_msckf_handle* h, hipStream_t s, double* dst, const orcvio_object_eval_flags* fl,
-                                const orcvio_object_track* tracks, const std::vector<ObjUse>& use, ObjPlan& pl, size_t nd, size_t ni,
-                                const int N, const int NA, const int NAP, const int cb0, const bool signal_done) {
+                                const orcvio_object_track* tracks, const ObjScan& sc, const int N, const int NA, const int NAP, const int cb0,
+                                const bool signal_done) {
+    ObjPlan pl;
     ObjFusedStage st;
-    int rc = objects_fused_pack(h, fl, tracks, use, pl, nd, ni, N, NAP, st);
-    if (rc == ORCVIO_OK) rc = objects_fused_launch(h, s, dst, pl, st, (int)use.size(), N, NA, NAP, cb0, signal_done);
+    int rc = objects_fused_pack(h, fl, tracks, sc, pl, N, NAP, st);
+    if (rc == ORCVIO_OK) rc = objects_fused_launch(h, s, dst, pl, st, sc.nobj, N, NA, NAP, cb0, signal_done);
     return rc;
 }
 
-// What orcvio_msckf_io_stage_object_tracks leaves for the frame call that follows it (one use; any other scan of object tracks voids it)
-struct ObjPrestage {
-    bool valid = false;
-    const orcvio_object_track* tracks = nullptr;
-    int n_tracks = 0, N = 0, leg_dim = 0;
-    orcvio_object_eval_flags efl;
-    ObjPlan pl;
-    int dof = 0, Fmax = 1;
-    size_t nd = 0, ni = 0;
-    ObjFusedStage st;
-};
-static ObjPrestage* prestage_of(orcvio_msckf_handle* h) {
-    if (!h->prestage) h->prestage = std::shared_ptr<void>(new ObjPrestage, [](void* p) { delete static_cast<ObjPrestage*>(p); });
-    return static_cast<ObjPrestage*>(h->prestage.get());
+// ---- object tracks, the general pipeline: rows materialised (k_object_rows_batch), then objects_pipeline ----------------------------------
+// The host's staging: [track data (doubles) | kernel arguments (doubles)], then ints [frame_clone, frame_row0 per track | ObjIntLayout].
+struct ObjGeneralStage { size_t nd_tot = 0, args_off = 0; ObjIntLayout lay; bool stacked = false; };
+static int objects_general_pack(orcvio_msckf_handle* h, const orcvio_object_eval_flags* fl, const orcvio_object_track* tracks, const ObjScan& sc,
+                                ObjPlan& pl, ObjGeneralStage& st) {
+    const int N = h->N;
+    const std::vector<ObjUse>& use = h->obj_use;
+    pl = plan_of(sc);
+    int rc = objects_scratch(h, &pl);
+    if (rc != ORCVIO_OK) return rc;
+    const size_t arg_dbl = OBJ_ARG_DOUBLES, args_off = sc.nd, nd = sc.nd + arg_dbl * use.size();
+    size_t sumK = 0;
+    for (const ObjUse& u : use) sumK += (size_t)tracks[u.t].n_keypoints;
+    const ObjIntLayout lay = obj_int_layout((size_t)pl.rows_tot, pl.nobj, sumK, N, sc.ni);
+    if ((rc = obj_stage_reserve(h, nd * 8 + lay.ni * 4)) != ORCVIO_OK) return rc;
+    double* hd = reinterpret_cast<double*>(h->h_obj_stage);
+    int* hi = reinterpret_cast<int*>(h->h_obj_stage + nd * 8);
+    double* dd = reinterpret_cast<double*>(h->d_obj_in);
+    int* di = reinterpret_cast<int*>(h->d_obj_in + nd * 8);
+    const ObjIntViews hv = lay.views(hi);
+    const ObjRowArrays ra{pl.d_hx, pl.d_hf, pl.d_res, pl.d_clone, pl.d_cols};
+    ObjArrowBuild ab;
+    ab.ok = h->arrow_opt && !(h->ref_stack_hf && pl.nobj > 1);
+    int ng = 0;
+    hv.rowptr[0] = 0;
+    for (size_t ui = 0; ui < use.size(); ++ui) {
+        const ObjUse& u = use[ui];
+        const orcvio_object_track& ob = tracks[u.t];
+        const signed char* nvp = h->obj_nv.data() + u.off_nv;
+        const int *fc = hi + u.off_i, *fr0 = fc + ob.n_frames;
+        const int rows = obj_pack_track(ob, u, nvp, fl, pl.ldf, pl.no_max, ra, hd, hi, dd, di, reinterpret_cast<ObjEvalArgs*>(hd + args_off + arg_dbl * ui));
+        obj_group_rows(fc, fr0, nvp, ob.n_frames, N, u.row0, (int)ui, hv.ridx, hv.groups, &ng);
+        hv.rowptr[ui + 1] = u.row0 + rows;
+        obj_arrow_from_masks(ob, fc, fr0, u.row0, rows, h->obj_vmask, ab, hv.arrows + ui, hv.kp_range, hv.kp_rows);
+    }
+    st.stacked = h->ref_stack_hf && pl.nobj > 1;
+    if (st.stacked) {
+        merge_objects_ref_stack(N, pl.rows_tot, hv.ridx, hv.rowptr, hv.groups, &ng);
+        pl.nobj = 1; h->obj_count = 1;
+        rc = objects_scratch(h, &pl);   // the scratch of ONE block: Cd | Sg | Hr adjacent again (the row arrays depend on the row count only)
+        if (rc != ORCVIO_OK) return rc;
+    }
+    pl.ngroups = ng;
+    pl.arrow = ab.ok;   // (never after a merge)
+    if (pl.arrow) {   // room for the arrow factors (the row arrays the kernel arguments point at do not move: same sizes)
+        pl.Kmax = ab.Kmax; pl.rows_max = ab.rows_max;
+        double* keep_objH = h->d_objH; int* keep_obj_i = h->d_obj_i;
+        rc = objects_scratch(h, &pl);
+        if (rc != ORCVIO_OK) return rc;
+        if (h->d_objH != keep_objH || h->d_obj_i != keep_obj_i) { g_last_error = "objects_local_tracks: scratch moved"; return ORCVIO_ERR_HIP; }
+    }
+    plan_views(pl, lay.views(di));
+    st.nd_tot = nd; st.args_off = args_off; st.lay = lay;
+    return ORCVIO_OK;
+}
+// The launches: the ingest, the rows of n_eval tracks of at most Fmax frames, the compression (no synchronisation: the staging is pinned).
+static int objects_general_launch(orcvio_msckf_handle* h, hipStream_t s, double* dst, const ObjPlan& pl, const ObjGeneralStage& st, const int n_eval,
+                                  const int Fmax) {
+    const int N = h->N, NAP = h->NAP;
+    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, st.lay.ingest_bytes(st.nd_tot, pl.ngroups)); if (ri != ORCVIO_OK) return ri; }
+    // the rows, and in the same launch the zeroing of what the compression accumulates into (Cd, Sg, Hr: adjacent) and of the
+    // two pivot counters.  After a merge for ORCVIO_OPT_REF_STACK_HF the scratch layout is another one: plain fills there.
+    const bool fold_zero = !st.stacked;
+    const size_t nzero = (size_t)pl.nobj * pl.NOP * NAP + (size_t)pl.nobj * N * 64 + (size_t)pl.nobj * N * pl.NOP;
+    const unsigned zero_rows = fold_zero ? (unsigned)((nzero / 2 + (size_t)Fmax * 64 * 8 - 1) / ((size_t)Fmax * 64 * 8)) : 0u;   // ~8 double2 per thread
+    hipLaunchKernelGGL(k_object_rows_batch, dim3(Fmax, (unsigned)n_eval + zero_rows), dim3(64), 0, s,
+                       reinterpret_cast<const ObjEvalArgs*>(reinterpret_cast<double*>(h->d_obj_in) + st.args_off), n_eval, pl.d_Cd, nzero, h->d_info + 4);
+    HIPCHK(hipGetLastError());
+    h->obj_status_cleared = fold_zero;   // (info[9..12] zeroed by that launch: objects_finish_impl need not)
+    return objects_pipeline(h, s, dst, pl, fold_zero, true);
 }
 
 // The same from object TRACKS (state at the LM optimum + observations): the residual rows and Jacobians of SURVEY 8a rows
@@ -706,201 +569,26 @@ int32_t orcvio_msckf_objects_local_tracks(orcvio_msckf_handle* h, const orcvio_m
     const auto tt0 = std::chrono::steady_clock::now();
     { const int rp = objects_problem(h, flags, n_clones, P, "objects_local_tracks"); if (rp != ORCVIO_OK) return rp; }
     const int N = n_clones, NAP = h->NAP;
-    typedef ObjUse Use;
-    std::vector<Use>& use = h->obj_use;
-    ObjPlan pl;
-    int dof = 0, Fmax = 1;
-    size_t nd = 0, ni = 0;   // staged doubles / ints
-    if (h->obj_early_done) {   // (the frame call has scanned the tracks already, for the compression it launched ahead)
-        pl.rows_tot = h->early_rows_tot; pl.no_max = h->early_no_max; pl.nobj = (int)use.size();
-        dof = h->early_dof; Fmax = h->early_Fmax; nd = h->early_nd; ni = h->early_ni;
-    } else {
-        const int rs = objects_tracks_scan(h, N, tracks, n_tracks, use, pl, &dof, &Fmax, &nd, &ni);
-        if (rs != ORCVIO_OK) return rs;
-    }
+    ObjScan sc;
+    if (h->obj_early) sc = *h->obj_early;   // (the frame call has scanned the tracks already, for the compression it launched ahead)
+    else { const int rs = objects_scan(h, N, tracks, n_tracks, sc); if (rs != ORCVIO_OK) return rs; }
     hipStream_t s = pick_stream(h, stream);
-    h->last_stream = s;
     double* dst = d_dst ? d_dst : h->d_Ab;
-    if (dof_out) *dof_out = dof;
-    prof_begin(h, s);
+    if (dof_out) *dof_out = sc.dof;
     const auto tt1 = std::chrono::steady_clock::now();
-    { const int rp = objects_prior(h, s, P, "objects_local_tracks"); if (rp != ORCVIO_OK) return rp; }
+    int rc = objects_begin(h, s, P, "objects_local_tracks", sc, dst);
+    if (rc != ORCVIO_OK || sc.nobj == 0) return rc;
     const auto tt2 = std::chrono::steady_clock::now();
-    h->uploaded = true;
-    h->objects_mode = true;
-    h->last_update_thin = false;
-    h->obj_dof = dof; h->obj_rows = pl.rows_tot; h->obj_count = pl.nobj;
-    if (!h->d_obj_accept) { HIPCHK(hipMalloc(&h->d_obj_accept, sizeof(int) * 4)); HIPCHK(hipMalloc(&h->d_obj_gamma, sizeof(double) * 4)); }
-    if (pl.nobj == 0) {
-        HIPCHK(hipMemsetAsync(dst, 0, sizeof(double) * (size_t)NAP * NAP, s));
-        return launch_prior_fork(h, s);
-    }
-    int rc = launch_prior_fork(h, s);   // the Cholesky of P runs on the side stream while the tracks are staged and their rows evaluated
+    rc = launch_prior_fork(h, s);   // the Cholesky of P runs on the side stream while the tracks are staged and their rows evaluated
     if (rc != ORCVIO_OK) return rc;
     h->obj_last_fused = false;
-    if (h->obj_early_done) { h->obj_early_done = false; h->obj_last_fused = true; return ORCVIO_OK; }   // (the frame call launched the compression ahead: objects_tracks_fused on its stream)
-    if (obj_fused_eligible(h, tracks, use, N, pl.no_max)) return objects_tracks_fused(h, s, dst, fl, tracks, use, pl, nd, ni, N, h->NA, NAP, h->flags.leg_dim - 15, h->frame_mode);
-    rc = objects_scratch(h, &pl);
-    if (rc != ORCVIO_OK) return rc;
-    // staging arena: [track data (doubles) | kernel arguments (doubles)], then ints [frame_clone, frame_row0 per track | ridx |
-    // rowptr | arrows | kp ranges | kp_rows | groups]
-    static_assert(sizeof(ObjEvalArgs) % sizeof(double) == 0, "ObjEvalArgs is copied as doubles");
-    const size_t arg_dbl = sizeof(ObjEvalArgs) / sizeof(double);
-    const size_t args_off = nd;
-    nd += arg_dbl * use.size();
-    const size_t rows = (size_t)pl.rows_tot;
-    size_t sumK = 0;
-    for (const Use& u : use) sumK += (size_t)tracks[u.t].n_keypoints;
-    const size_t o_ridx = ni, o_rowptr = o_ridx + rows, o_arrow = o_rowptr + pl.nobj + 1, o_range = o_arrow + (size_t)4 * pl.nobj,
-                 o_kprows = o_range + 2 * (sumK + (size_t)pl.nobj), o_groups = o_kprows + rows, ni_tot = o_groups + (size_t)4 * pl.nobj * N;
-    if ((rc = obj_stage_reserve(h, nd * 8 + ni_tot * 4)) != ORCVIO_OK) return rc;
-    double* hd = reinterpret_cast<double*>(h->h_obj_stage);
-    int* hi = reinterpret_cast<int*>(h->h_obj_stage + nd * 8);
-    double* dd = reinterpret_cast<double*>(h->d_obj_in);
-    int* di = reinterpret_cast<int*>(h->d_obj_in + nd * 8);
-    int* ridx = hi + o_ridx;
-    int* rowptr = hi + o_rowptr;
-    ObjGroup* groups = reinterpret_cast<ObjGroup*>(hi + o_groups);
-    // The arrow structure of the structured QR of Hf (per object K + 1 row lists: the rows of every keypoint block, then the
-    // border-only rows) is written here, frame by frame, straight from the observation masks -- the order of build_arrow (rows
-    // ascending within a list), without a pass over the 15 000 rows of a config-3 update per array.
-    ObjArrow* arrows = reinterpret_cast<ObjArrow*>(hi + o_arrow);
-    int2* kp_ranges = reinterpret_cast<int2*>(hi + o_range);
-    int* kp_rows = hi + o_kprows;
-    const bool want_arrow = h->arrow_opt && !(h->ref_stack_hf && pl.nobj > 1);
-    bool arrow_ok = want_arrow;
-    int arrow_off = 0, arrow_pos = 0, arrow_Kmax = 0, arrow_rows_max = 0;
-    int ng = 0;
-    rowptr[0] = 0;
-    for (size_t ui = 0; ui < use.size(); ++ui) {
-        const Use& u = use[ui];
-        const orcvio_object_track& ob = tracks[u.t];
-        const int K = ob.n_keypoints, F = ob.n_frames;
-        double* q = hd + u.off_d;
-        std::memcpy(q, ob.wTo, 16 * 8); q += 16;
-        std::memcpy(q, ob.shape, 3 * 8); q += 3;
-        if (K > 0) std::memcpy(q, ob.kps, (size_t)3 * K * 8);
-        q += 3 * K;
-        std::memcpy(q, ob.frame_wTc, (size_t)16 * F * 8); q += (size_t)16 * F;
-        if (K > 0) std::memcpy(q, ob.frame_zs, (size_t)2 * K * F * 8);
-        q += (size_t)2 * K * F;
-        std::memcpy(q, ob.frame_bbox, (size_t)4 * F * 8);
-        int* fc = hi + u.off_i;
-        int* fr0 = fc + F;
-        // rows of the frames in frame order (the reference's interleaved layout); groups by clone for the compression
-        int first[ORCVIO_MAX_CLONES], count[ORCVIO_MAX_CLONES];
-        for (int c = 0; c < N; ++c) { first[c] = -1; count[c] = 0; }
-        int rr = u.row0;
-        bool contiguous = true;   // every clone's rows are one contiguous run (frames map to distinct clones)
-        std::vector<int>& fnr = h->obj_fnr;
-        fnr.assign(F, 0);
-        int kcnt[36] = {0};   // rows of every keypoint block, [K]: border-only rows
-        std::vector<unsigned long long>& vmask = h->obj_vmask;   // observed keypoints of every frame of this track
-        vmask.assign(F, 0ull);
-        for (int f = 0; f < F; ++f) {
-            fc[f] = ob.frame_clone[f];
-            fr0[f] = 0;
-            if (fc[f] < 0) continue;
-            int nv = 0;
-            unsigned long long mk = 0ull;
-            const double* zs = ob.frame_zs + (size_t)f * K * 2;
-            for (int k = 0; k < K; ++k)
-                if (std::isfinite(zs[2 * k]) && std::isfinite(zs[2 * k + 1])) { mk |= 1ull << k; kcnt[k] += 2; ++nv; }
-            vmask[f] = mk;
-            kcnt[K] += 4;
-            fr0[f] = rr;
-            const int c = fc[f], nr = 2 * nv + 4;
-            fnr[f] = nr;
-            if (first[c] < 0) first[c] = rr; else if (first[c] + count[c] != rr) contiguous = false;
-            count[c] += nr;
-            rr += nr;
-        }
-        if (contiguous) {
-            for (int r = u.row0; r < rr; ++r) ridx[r] = r;
-            for (int c = 0; c < N; ++c)
-                if (count[c] > 0) groups[ng++] = ObjGroup{first[c], first[c] + count[c], c, (int)ui};
-        } else {   // two frames of the object share a clone: group the rows through the index list
-            int pos = u.row0;
-            for (int c = 0; c < N; ++c) {
-                if (count[c] == 0) continue;
-                const int g0 = pos;
-                for (int f = 0; f < F; ++f)
-                    if (fc[f] == c)
-                        for (int r = 0; r < fnr[f]; ++r) ridx[pos++] = fr0[f] + r;
-                groups[ng++] = ObjGroup{g0, pos, c, (int)ui};
-            }
-        }
-        rowptr[ui + 1] = rr;
-        if (arrow_ok) {
-            if (rr - u.row0 > 2048) arrow_ok = false;
-            int start[36];
-            for (int k = 0; k <= K && arrow_ok; ++k) {
-                if (k < K && kcnt[k] > 128) { arrow_ok = false; break; }
-                start[k] = arrow_pos;
-                kp_ranges[arrow_off + k] = int2{arrow_pos, arrow_pos + kcnt[k]};
-                arrow_pos += kcnt[k];
-            }
-            if (arrow_ok) {
-                for (int f = 0; f < F; ++f) {
-                    if (fc[f] < 0) continue;
-                    const unsigned long long mk = vmask[f];
-                    int rj = fr0[f];
-                    for (int k = 0; k < K; ++k)
-                        if (mk >> k & 1ull) { int& st = start[k]; kp_rows[st] = rj; kp_rows[st + 1] = rj + 1; st += 2; rj += 2; }
-                    int& sb = start[K];
-                    kp_rows[sb] = rj; kp_rows[sb + 1] = rj + 1; kp_rows[sb + 2] = rj + 2; kp_rows[sb + 3] = rj + 3;
-                    sb += 4;
-                }
-                arrows[ui] = ObjArrow{u.row0, rr - u.row0, K, arrow_off};
-                arrow_off += K + 1;
-                if (K > arrow_Kmax) arrow_Kmax = K;
-                if (rr - u.row0 > arrow_rows_max) arrow_rows_max = rr - u.row0;
-            }
-        }
-        ObjEvalArgs a;
-        a.wTo = dd + u.off_d; a.shape = a.wTo + 16; a.kps = a.shape + 3; a.frame_wTc = a.kps + 3 * K;
-        a.frame_zs = a.frame_wTc + (size_t)16 * F; a.frame_bbox = a.frame_zs + (size_t)2 * K * F;
-        a.frame_clone = di + u.off_i; a.frame_row0 = a.frame_clone + F;
-        a.K = K; a.F = F; a.ncol = u.ncol; a.ldhf = pl.ldf; a.rcol = pl.no_max; a.row_cols = pl.d_cols;
-        a.obj_left = fl->use_left_perturbation; a.new_bbox = fl->use_new_bbox_residual; a.vio_left = fl->vio_use_left_perturbation;
-        a.fix_D = fl->fix_dcampose_dimupose_to_identity;
-        std::memcpy(a.R_b2c, fl->R_b2c, sizeof(a.R_b2c));
-        std::memcpy(a.t_c_b, fl->t_c_b, sizeof(a.t_c_b));
-        a.Hx6 = pl.d_hx; a.Hf = pl.d_hf; a.res = pl.d_res; a.row_clone = pl.d_clone;
-        std::memcpy(hd + args_off + arg_dbl * ui, &a, sizeof(a));
-    }
-    const int n_eval = pl.nobj;   // (the row kernel is launched per evaluated track whatever happens to the blocks afterwards)
-    bool stacked = false;
-    if (h->ref_stack_hf && pl.nobj > 1) {
-        merge_objects_ref_stack(N, pl.nobj, pl.rows_tot, ridx, rowptr, groups, &ng);
-        pl.nobj = 1; h->obj_count = 1; stacked = true;
-        rc = objects_scratch(h, &pl);   // the scratch of ONE block: Cd | Sg | Hr adjacent again (the row arrays depend on the row count only)
-        if (rc != ORCVIO_OK) return rc;
-    }
-    pl.ngroups = ng;
-    pl.arrow = !stacked && want_arrow && arrow_ok;
-    if (pl.arrow) { pl.Kmax = arrow_Kmax; pl.rows_max = arrow_rows_max; }
-    if (pl.arrow) {   // room for the arrow factors (the row arrays the kernel arguments point at do not move: same sizes)
-        double* keep_objH = h->d_objH; int* keep_obj_i = h->d_obj_i;
-        rc = objects_scratch(h, &pl);
-        if (rc != ORCVIO_OK) return rc;
-        if (h->d_objH != keep_objH || h->d_obj_i != keep_obj_i) { g_last_error = "objects_local_tracks: scratch moved"; return ORCVIO_ERR_HIP; }
-    }
-    pl.d_ridx = di + o_ridx; pl.d_rowptr = di + o_rowptr; pl.d_groups = reinterpret_cast<ObjGroup*>(di + o_groups);
-    pl.d_arrow = reinterpret_cast<ObjArrow*>(di + o_arrow); pl.d_kp_range = reinterpret_cast<int2*>(di + o_range); pl.d_kp_rows = di + o_kprows;
+    if (h->obj_early) { h->obj_early = nullptr; h->obj_last_fused = true; return ORCVIO_OK; }   // (the frame call launched the compression ahead: objects_tracks_fused on its stream)
+    if (obj_fused_eligible(h, tracks, N, sc.no_max)) return objects_tracks_fused(h, s, dst, fl, tracks, sc, N, h->NA, NAP, h->flags.leg_dim - 15, h->frame_mode);
+    ObjPlan pl;
+    ObjGeneralStage st;
+    if ((rc = objects_general_pack(h, fl, tracks, sc, pl, st)) != ORCVIO_OK) return rc;
     const auto tt3 = std::chrono::steady_clock::now();
-    { const int ri = launch_ingest(h, s, h->h_obj_stage_dev, h->d_obj_in, nd * 8 + (o_groups + (size_t)4 * ng) * 4); if (ri != ORCVIO_OK) return ri; }
-    (void)n_eval;
-    // the rows, and in the same launch the zeroing of what the compression accumulates into (Cd, Sg, Hr: adjacent) and of the
-    // two pivot counters.  After a merge for ORCVIO_OPT_REF_STACK_HF the scratch layout is another one: plain fills there.
-    const bool fold_zero = !stacked;
-    const size_t nzero = (size_t)pl.nobj * pl.NOP * NAP + (size_t)pl.nobj * N * 64 + (size_t)pl.nobj * N * pl.NOP;
-    const unsigned zero_rows = fold_zero ? (unsigned)((nzero / 2 + (size_t)Fmax * 64 * 8 - 1) / ((size_t)Fmax * 64 * 8)) : 0u;   // ~8 double2 per thread
-    hipLaunchKernelGGL(k_object_rows_batch, dim3(Fmax, (unsigned)use.size() + zero_rows), dim3(64), 0, s,
-                       reinterpret_cast<const ObjEvalArgs*>(dd + args_off), (int)use.size(), pl.d_Cd, nzero, h->d_info + 4);
-    HIPCHK(hipGetLastError());
-    h->obj_status_cleared = fold_zero;   // (info[9..12] zeroed by that launch: objects_finish_impl need not)
-    rc = objects_pipeline(h, s, dst, pl, fold_zero, true);   // (no synchronisation: everything staged lives in the handle's pinned arena)
+    rc = objects_general_launch(h, s, dst, pl, st, sc.nobj, sc.Fmax);
     if (timing) {
         const auto tt4 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };

@@ -35,6 +35,7 @@
 #include "clone_choice_ops.hpp"
 #include "host/cov_book.hpp"
 #include "host/frame_outcome.hpp"
+#include "host/object_stage.hpp"
 #include <immintrin.h>
 #include <condition_variable>
 #include <memory>
@@ -86,12 +87,39 @@ struct PhaseTimer {
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static void so3_exp_decl(const double w[3], double R[9]);   // Sophus SO3d::exp (defined with incrementState_IMUCam below)
 
-struct ObjUse {   // a usable object track of the current object update
-    int t, row0, rows, ncol;
-    size_t off_d, off_i;
-    int fin;        // in-window frames
-    int distinct;   // 1: every in-window frame on a clone of its own (the one-launch compression's condition)
-    size_t off_nv;  // first entry of the track's per-frame keypoint counts in the handle's obj_nv (-1 entries: frame not in the window)
+// ---- object update: what a call, or orcvio_msckf_io_stage_object_tracks ahead of one, plans and stages ----------------------------------
+// ONE input arena per object update, mirrored in pinned host memory (grown on demand) and pulled by one launch: [doubles ... | ints ...].
+// Device-side scratch (row arrays written by k_object_rows_batch, Cd, Sg, Gff, factors) is separate and never crosses PCIe.
+struct ObjPlan {
+    int nobj = 0, rows_tot = 0, no_max = 0, ngroups = 0;
+    int NOP = 0, ldf = 0;
+    // device pointers
+    int *d_ridx = nullptr, *d_rowptr = nullptr, *d_clone = nullptr, *d_cols = nullptr;
+    ObjGroup* d_groups = nullptr;
+    double *d_hx = nullptr, *d_hf = nullptr, *d_res = nullptr;
+    double *d_Cd = nullptr, *d_Sg = nullptr, *d_Gff = nullptr;
+    // arrow structure of Hf (structured Householder QR instead of chol(Hf^T Hf)); arrow = false: the Gram route
+    bool arrow = false;
+    int Kmax = 0, rows_max = 0;
+    ObjArrow* d_arrow = nullptr;
+    int2* d_kp_range = nullptr;
+    int* d_kp_rows = nullptr;
+    double* d_Rarrow = nullptr;
+    double *d_Hr = nullptr, *d_Hfr = nullptr;   // [nobj][N][NOP] per-clone parts of Hf^T r; [nobj][NOP + 1] their sums and |r|^2
+    double* d_Bred = nullptr;   // [rows][9] the border of every row after the keypoint blocks have been eliminated
+    double* d_Qt = nullptr;     // [rows][OBJ_REFINE_ROW_DOUBLES] obj_refine_body: staging of objects too long for the LDS staging
+};
+// the staged arena of the one-launch compression: sizes, and where the kernel arguments and the arrows lie
+struct ObjFusedStage { size_t nd_tot = 0, ni_tot = 0, args_off = 0, o_arrow = 0; int Kmax = 0, rows_max = 0; };
+// What orcvio_msckf_io_stage_object_tracks leaves for the frame call that follows it (one use; any other scan of object tracks voids it)
+struct ObjPrestage {
+    bool valid = false;
+    const orcvio_object_track* tracks = nullptr;
+    int n_tracks = 0, N = 0, leg_dim = 0;
+    orcvio_object_eval_flags efl;
+    ObjScan scan;
+    ObjPlan pl;
+    ObjFusedStage st;
 };
 
 struct IpcComm;
@@ -171,8 +199,7 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     int obj_fused_opt = 1;              // ORCVIO_OBJ_FUSED=0: object tracks always through the three-launch pipeline (rows materialised)
     unsigned* d_obj_done = nullptr;     // completion counter of k_gemm_objA (cumulative; never reset)
     unsigned obj_done_total = 0u;       // what that counter reads once every compression enqueued so far has finished
-    int early_rows_tot = 0, early_no_max = 0, early_dof = 0, early_Fmax = 1; size_t early_nd = 0, early_ni = 0;   // ... and what its scan of the tracks found
-    bool obj_early_done = false;        // orcvio_msckf_io_update_frame has enqueued this update's compression already (objects_local_tracks skips it)
+    const ObjScan* obj_early = nullptr; // orcvio_msckf_io_update_frame has enqueued this update's compression already (objects_local_tracks skips it): what its scan of the tracks found
     bool obj_last_fused = false;        // the last object update from tracks took the one-launch compression
     size_t obj_lds_budget = 0;          // dynamic LDS the border launch of the object update may take on THIS handle's device (0: not asked yet)
     bool arrow_opt = true;              // ORCVIO_OPT_OBJECT_QR: structured Householder QR of Hf (0: chol(Hf^T Hf), round 1's route)
@@ -279,9 +306,8 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     int la_solve = 3;                   // look-ahead depth of the fused solve (0: k_potrf_solve, one workgroup holds the whole trailing matrix; 2 / 3: k_potrf_solve_la)
     size_t chain_fin_oo = 0;            // ... and where in the second outputs arena it put P++ (checked against the object half's layout)
     double chain_fin_thr = 0.0;         // ... and the threshold it used
-    std::shared_ptr<void> prestage;     // ObjPrestage (capi_objects.inc): what orcvio_msckf_io_stage_object_tracks left for the next frame call
+    ObjPrestage prestage;               // what orcvio_msckf_io_stage_object_tracks left for the next frame call (valid: it still stands, no other scan of object tracks since)
     unsigned long long cnt_prestaged = 0;   // frame calls that found their object tracks staged ahead
-    bool prestage_valid = false;        // ... still stands (no other scan of object tracks since)
     int chain_fin_dof = -1;             // degrees of freedom the chained object solve's in-launch finish gated with (-1: it did not)
     int fuse_finish = 1;                // P+ / dx (and an object update's gate) by finish workgroups of k_potrf_solve_la (LaFin) instead of a k_finish_sqrt
                                         // launch behind it: 1 = in the chained frame call (both halves: 8-9 us off the frame), 2 = every update whose solve
@@ -328,7 +354,7 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     char *h_lm = nullptr, *d_lm = nullptr;             // staging of orcvio_msckf_object_lm, its own (an open io_begin's arena and the object update's staging stay as they are): pinned [inputs | outputs] + device copy
     size_t lm_cap = 0;
     std::vector<ObjUse> obj_use;        // (objects_local_tracks: per-track records, kept across calls: no allocation per frame)
-    std::vector<int> obj_fnr;           // rows of every frame of the track being staged
+    std::vector<int> obj_fnr;           // (objects_local) keypoint block of every row
     std::vector<signed char> obj_nv;    // (objects_tracks_scan) detected keypoints of every frame of every usable track: the ONE pass over the observations
     std::vector<int> obj_rowkp, obj_Ks; // keypoint block of every row / keypoint count of every object (structured QR of Hf)
     std::vector<unsigned long long> obj_vmask;   // (objects_local_tracks) observed keypoints of every frame of the track being staged

@@ -3,6 +3,7 @@
 // structured Householder QR of Hf, Y = Q1^T X by substitution or through an explicit basis, the sum of the clone tiles.
 // Included by msckf_kernels.hpp (it uses that file's MFMA / DPP helpers and Gram bodies); not a translation unit of its own.
 #pragma once
+#include "host/object_types.hpp"
 
 namespace orcvio_amd {
 
@@ -24,8 +25,8 @@ namespace orcvio_amd {
 // Compact row storage: Hx6 [rows][6];  HfR [rows][ldf], ldf = 16 ceil((no_max + 1)/16): columns [0, no) Hf of the
 // object (zero up to no_max), column no_max = the residual, zero behind it.
 // k_obj_cross: one wavefront per (object, clone) group {first, last+1 into ridx, clone, object}; ridx lists the rows of
-// the update grouped by (object, clone).  MFMA with A = hx^T (6 of 16 rows live), B = [Hf | r] tile by tile and hx.
-struct ObjGroup { int r0, r1, clone, obj; };
+// the update grouped by (object, clone) (ObjGroup: host/object_types.hpp).  MFMA with A = hx^T (6 of 16 rows live), B = [Hf | r] tile
+// by tile and hx.
 __device__ __forceinline__ void obj_cross_body(const ObjGroup* __restrict__ groups, int g, int l, const int* __restrict__ ridx,
                                                const double* __restrict__ Hx6, const double* __restrict__ HfR, int ldf,
                                                int no_max, int cb0, int NAP, int NOP, int N,
@@ -136,8 +137,6 @@ __device__ __forceinline__ void obj_assemble_B_body(int idx, const double* __res
 // R = [[blockdiag R_kk, R_kb], [0, R_b]] up to the column order.  k_obj_arrow_solve then forms Y = R^-T C by forward
 // substitution, one thread per column of C.  A pivot that is zero to rounding (a keypoint seen in one frame only, an exactly
 // dependent column) is dropped (its row of Y is zero) and counted.
-struct ObjArrow { int row0, rows, K, kp_off; };   // rows [row0, row0 + rows) of the update; K keypoint blocks; kp_off: first
-                                                  // entry of this object in kp_range
 // Rout per object (stride arrow_stride(Kmax)): [K][3 x 3 R_kk | 3 x 9 R_kb] , then 9 x 9 R_b, then the pivot tolerance
 __host__ __device__ inline int arrow_stride(int Kmax) { return 36 * Kmax + 81 + 3; }
 // Two launches (a first version did both phases in one 1024-thread workgroup per object: 755 spilled VGPRs, 209 us):

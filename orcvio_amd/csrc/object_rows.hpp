@@ -10,30 +10,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include "host/object_types.hpp"   // ObjEvalArgs
 
 namespace orcvio_amd {
-
-struct ObjEvalArgs {
-    const double* wTo;        // [16]
-    const double* shape;      // [3]
-    const double* kps;        // [K][3]
-    const double* frame_wTc;  // [F][16]
-    const double* frame_zs;   // [F][K][2]
-    const double* frame_bbox; // [F][4]
-    const int* frame_clone;   // [F] (-1: not in the window)
-    const int* frame_row0;    // [F] first output row of the frame (only for in-window frames)
-    int K, F, ncol;           // ncol = 9 + 3K
-    int ldhf;                 // leading dimension of Hf (>= ncol; the columns beyond ncol are written as 0)
-    int rcol;                 // >= ncol: the residual is ALSO written to column rcol of the Hf row (compact [Hf | r] rows of the
-                              // object compression, msckf_kernels.hpp k_obj_cross); -1: not
-    int* row_cols;            // optional: ncol of the object is written per row
-    int obj_left, new_bbox, vio_left, fix_D;
-    double R_b2c[9], t_c_b[3];
-    int* row_clone;
-    double* Hx6;
-    double* Hf;
-    double* res;
-};
 
 __device__ __forceinline__ void skew3d(const double* w, double* S) {
     S[0] = 0; S[1] = -w[2]; S[2] = w[1]; S[3] = w[2]; S[4] = 0; S[5] = -w[0]; S[6] = -w[1]; S[7] = w[0]; S[8] = 0;
