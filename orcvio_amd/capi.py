@@ -2052,6 +2052,24 @@ def debug_read(upd: MsckfUpdater, which: str):
             if rc != 0:
                 raise MsckfError(rc, 'debug_read dense')
         return out
+    if which in ('front', 'T3', 'Xobs', 'obs_pos', 'S', 'Gpart'):   # the front end of the last feature update as its launches left it
+        st = np.zeros(8, dtype=np.int32)
+        rc = lib.orcvio_msckf_debug_read(upd.h, 22, st.ctypes.data_as(C.c_void_p), st.nbytes)
+        if rc != 0:
+            raise MsckfError(rc, 'debug_read front')
+        F, N, nobs, chunks = (int(x) for x in st[:4])
+        if which == 'front':   # (fused: this upload takes k_front; deferred: k_front left the Grams only and A is assembled on demand)
+            return dict(F=F, N=N, nobs=nobs, chunks=chunks, rows_per_chunk=int(st[4]), fused=int(st[5]), deferred=int(st[6]),
+                        prior_forked=int(st[7]))
+        code, shape, dt = {'T3': (17, (3 * F, NAP), np.float64), 'Xobs': (18, (2 * nobs, 16), np.float64),
+                           'obs_pos': (19, (nobs,), np.int32), 'S': (20, (N, 16, 16), np.float64),
+                           'Gpart': (21, (chunks, NAP, NAP), np.float64)}[which]
+        out = np.zeros(shape, dtype=dt)
+        if out.size:
+            rc = lib.orcvio_msckf_debug_read(upd.h, code, out.ctypes.data_as(C.c_void_p), out.nbytes)
+            if rc != 0:
+                raise MsckfError(rc, f'debug_read {which}')
+        return out
     shapes = {'Hs': (0, (m_tot, NAP)), 'Ab': (1, (NAP, NAP)), 'A': (2, (NAP, NAP)), 'RP': (3, (NP, NP)),
               'M': (4, (NP, NP)), 'RM': (5, (NP, NP)), 'Z': (6, (n, ldz)), 'U': (8, (NP, NP)),
               'P': (16, (n, n))}   # (the prior as its pull left it in device memory)

@@ -10,7 +10,9 @@
 //        13 the dense rows [dense_rows][NAP] (caller-projected rows, then the rows of the entering features: zero U part, V part),
 //        14 {dense_rows, NAP} -> int32[2],
 //        15 did the last object update take the one-launch compression (k_obj_fused)? -> int32,
-//        16 the n x n prior of the last update as it stands in device memory (h->d_P: a host P as its pull left it)
+//        16 the n x n prior of the last update as it stands in device memory (h->d_P: a host P as its pull left it),
+//        17 T3 [3F][NAP], 18 Xobs [2 nobs][16], 19 obs_pos -> int32[nobs], 20 S [N][256], 21 Gpart [chunks][NAP^2],
+//        22 {F, N, nobs, chunks, rows per chunk, k_front?, A deferred?, prior forked?} -> int32[8]
 int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst, int64_t max_bytes) {
     if (!h || !dst) return ORCVIO_ERR_INVALID;
     HIPCHK(hipSetDevice(h->device));
@@ -67,6 +69,33 @@ int32_t orcvio_msckf_debug_read(orcvio_msckf_handle* h, int32_t which, void* dst
             return ORCVIO_OK;
         }
         case 16: src = h->d_P; bytes = (size_t)h->n * h->n * sizeof(double); break;   // the prior as the pull left it in device memory
+        // ---- the front end of the last feature update, as its launches left it (tests/test_gpu_front_blocks.py) ----
+        case 17: src = h->d_T3; bytes = (size_t)3 * h->F * h->NAP * sizeof(double); break;      // T3 [3F][NAP]
+        case 18: src = h->d_Xobs; bytes = (size_t)32 * h->nobs * sizeof(double); break;         // Xobs [2 nobs][16]
+        case 19: {   // obs_pos [nobs]: the position of every observation in the clone-sorted order (rows 2 pos, 2 pos + 1 of Xobs), as
+                     // upload_finalize left it in the arena -- the list every route reads, there or through its pull
+            const size_t b = sizeof(int32_t) * (size_t)h->nobs;
+            if (!h->uploaded || h->objects_mode) { g_last_error = "debug_read: no feature upload"; return ORCVIO_ERR_INVALID; }
+            if ((size_t)max_bytes < b) { g_last_error = "debug_read: buffer too small"; return ORCVIO_ERR_INVALID; }
+            if (b) std::memcpy(dst, h->h_stage + h->io_cobs, b);
+            return ORCVIO_OK;
+        }
+        case 20: src = h->d_S; bytes = (size_t)256 * h->N * sizeof(double); break;              // S [N][256], one tile per clone
+        case 21: {   // Gpart [chunks][NAP^2]: the partial Grams of T3 the last front end wrote (lower tiles; both triangles behind k_front)
+            const int ch = front_fused_active(h, false) ? h->front_chunks : h->chunks;
+            src = h->d_Gpart; bytes = (size_t)ch * pp; break;
+        }
+        case 22: {   // {F, N, nobs, row chunks of the last front end, rows per chunk, would this upload take k_front?, is A still to be
+                     //  assembled (k_front left the Grams only)?, was the prior's factorisation forked?}
+            const bool fused = front_fused_active(h, false);
+            const int ch = fused ? h->front_chunks : h->chunks;
+            const int t3 = 3 * h->F;
+            const int rpc = fused ? round_up((t3 + ch - 1) / ch, 4) : h->rows_per_chunk;
+            int32_t st[8] = {h->F, h->N, h->nobs, ch, rpc, fused ? 1 : 0, h->A_deferred ? 1 : 0, h->prior_forked ? 1 : 0};
+            if ((size_t)max_bytes < sizeof(st)) return ORCVIO_ERR_INVALID;
+            std::memcpy(dst, st, sizeof(st));
+            return ORCVIO_OK;
+        }
         case 7: {
             int32_t dims[8] = {h->n, h->NA, h->NAP, h->NP, h->m_tot, h->Mmax, h->ldz, h->reg_path ? 1 : 0};
             if ((size_t)max_bytes < sizeof(dims)) return ORCVIO_ERR_INVALID;
