@@ -1156,8 +1156,26 @@ int32_t orcvio_msckf_cov_prefactor(orcvio_msckf_handle* h);
  * after an update that carried entering features (orcvio_msckf_upload_new_features) the resident covariance becomes the augmented
  * one -- P+ with the d k new feature states behind it (in front of the nuisance block) -- computed from H_1, H_2, r_1 still on the
  * device; dx_new [d k] is returned.  Instead of orcvio_msckf_cov_commit for such an update.  The caller raises
- * ORCVIO_OPT_EXTRA_STATES by d k before its next upload. */
+ * ORCVIO_OPT_EXTRA_STATES by d k before its next upload.  This call DROPS the resident square-root factor (the frame's next update
+ * factors the augmented prior again); see orcvio_msckf_cov_commit_new_features_fac. */
 int32_t orcvio_msckf_cov_commit_new_features(orcvio_msckf_handle* h, double* dx_new);
+/* The same tail with the resident square-root factor carried along.  With P+ = S+ S+^T, HH = H_2^-1 H_1 and sigma = noise_feature,
+ *     P_aug = S_aug S_aug^T,   S_aug = [  S+       0              ]   (d k more columns, block-diagonal sigma H_2^-1 in the new rows)
+ *                                      [ -HH S+    sigma H_2^-1    ]
+ * so the frame's second update (pruneImuStateBuffer's) starts from the factor instead of a Cholesky chain of the augmented prior.
+ * Preconditions, refusals and dx_new are those of orcvio_msckf_cov_commit_new_features: no finished update with entering features
+ * ORCVIO_ERR_INVALID, n + d k beyond the handle's capacity ORCVIO_ERR_CAPACITY, a zero on diag(H_2) ORCVIO_ERR_NOT_SPD; a refusal
+ * leaves the resident covariance, its factor and the bookkeeping untouched.  The old block and the moved nuisance block of P are
+ * 0.5 (P+ + P+^T) bit for bit, P21 = -HH P+ and P22 = HH P+ HH^T + sigma^2 W symmetrised as the call above forms them (the order of
+ * summation differs: the new blocks agree to rounding, not bit for bit), P_aug is symmetric exactly.
+ * The factor follows exactly when orcvio_msckf_cov_commit would have kept S+ for this update -- ORCVIO_OPT_RESIDENT_FACTOR on, no
+ * ORCVIO_OPT_SCHMIDT_STATES, not the direct form of a thin stack -- and its columns, those of S+ plus d k, fit the handle's factor
+ * buffers (round_up(n_max + 1, 16) columns).  In every other case it is dropped as above; that is not an error.  Device work: two
+ * launches (k_aug_rows, k_aug_finish), one fetch, one wait.  The caller raises ORCVIO_OPT_EXTRA_STATES by d k, as above.
+ * Measured on MI355X (leg 22, 20 clones, 12 in-state features, 1 and 3 entering features, profiles/r32a_entering_commit_ab.json): the
+ * call 32-40 us against 62-79 us for the call above, the call plus the frame's next update 137-146 us against 175-183 us; the next
+ * update itself gains 0-7 us of that (the Cholesky chain of its prior was mostly hidden beside the tracks already). */
+int32_t orcvio_msckf_cov_commit_new_features_fac(orcvio_msckf_handle* h, double* dx_new);
 /* Schmidt branch of pruneImuStateBuffer (src/orcvio.cpp:2881-2920): the listed clones (window ranks before the call, ascending)
  * leave the window but stay in the resident covariance as nuisance states -- their blocks move to the end, in the listed order. */
 int32_t orcvio_msckf_cov_clones_to_nuisance(orcvio_msckf_handle* h, int32_t leg_dim, const int32_t* clone_indices, int32_t count);

@@ -38,6 +38,7 @@ EXPORTS = [
     'orcvio_msckf_objects_download', 'orcvio_msckf_cov_set', 'orcvio_msckf_cov_get', 'orcvio_msckf_cov_propagate',
     'orcvio_msckf_cov_augment', 'orcvio_msckf_cov_remove_clones', 'orcvio_msckf_cov_commit', 'orcvio_msckf_cov_prefactor', 'orcvio_msckf_upload_new_features', 'orcvio_msckf_download_new_feature_blocks', 'orcvio_msckf_upload_nuisance_poses',
     'orcvio_msckf_augment_state_nuisance', 'orcvio_msckf_cov_clones_to_nuisance', 'orcvio_msckf_cov_commit_new_features',
+    'orcvio_msckf_cov_commit_new_features_fac',
     'orcvio_msckf_update_object_tracks', 'orcvio_msckf_objects_local_tracks',
     'orcvio_msckf_upload_ekf_rows', 'orcvio_msckf_download_ekf', 'orcvio_msckf_upload_slam_features', 'orcvio_msckf_upload_dense_rows', 'orcvio_msckf_augment_new_features', 'orcvio_msckf_gate_tracks', 'orcvio_msckf_new_feature_rows', 'orcvio_msckf_augment_state',
     'orcvio_msckf_profile_stages', 'orcvio_msckf_update_object_lm_msgs',
@@ -1774,6 +1775,15 @@ class MsckfUpdater:
         dx_new = np.zeros(d * k)
         self.lib.orcvio_msckf_cov_commit_new_features.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         self._chk(self.lib.orcvio_msckf_cov_commit_new_features(self.h, _d(dx_new)), 'orcvio_msckf_cov_commit_new_features')
+        return dx_new
+
+    def cov_commit_new_features_fac(self):
+        """As cov_commit_new_features, with the resident square-root factor carried along (S_aug = [[S+, 0], [-HH S+, sigma H_2^-1]])
+        where the update's own commit would have kept S+ and the widened factor fits; returns dx_new."""
+        k, d, _ = self._new
+        dx_new = np.zeros(d * k)
+        self.lib.orcvio_msckf_cov_commit_new_features_fac.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._chk(self.lib.orcvio_msckf_cov_commit_new_features_fac(self.h, _d(dx_new)), 'orcvio_msckf_cov_commit_new_features_fac')
         return dx_new
 
     def cov_prefactor(self):

@@ -395,6 +395,68 @@ int32_t orcvio_msckf_cov_commit_new_features(orcvio_msckf_handle* h, double* dx_
     return ORCVIO_OK;
 }
 
+// The same tail with the resident square-root factor CARRIED ALONG (cov_ops.hpp, k_aug_rows / k_aug_finish): two launches, no
+// memset, dx_new and the singular word in one fetch behind one wait.  The factor follows exactly when the update's own commit
+// would adopt S+ = sigma Z^T (update_fac_after) and the widened factor fits the factor buffers; otherwise it is dropped, as the
+// call above drops it.  Preconditions, refusals and dx_new are that call's.
+int32_t orcvio_msckf_cov_commit_new_features_fac(orcvio_msckf_handle* h, double* dx_new) {
+    if (!h || !h->ran || h->new_F <= 0 || !dx_new) { g_last_error = "cov_commit_new_features_fac: no finished update with entering features"; return ORCVIO_ERR_INVALID; }
+    HIPCHK(hipSetDevice(h->device));
+    const int n = h->n, k = h->new_F, d = h->new_idp, sz = d * k, nt = n + sz, tail = 6 * h->n_nui, kf = h->kf;
+    if (nt > h->n_max) { g_last_error = "cov_commit_new_features_fac: the augmented state exceeds the handle's capacity"; return ORCVIO_ERR_CAPACITY; }
+    if (d != 1 && d != 3) { g_last_error = "cov_commit_new_features_fac: feature states are 1 or 3 wide"; return ORCVIO_ERR_INVALID; }
+    const size_t lds = aug_rows_lds_bytes(n, d);
+    if (lds > (size_t)64 * 1024) { g_last_error = "cov_commit_new_features_fac: state too wide for a workgroup's LDS"; return ORCVIO_ERR_CAPACITY; }
+    hipStream_t s = h->last_stream ? h->last_stream : h->stream;
+    const bool follows = CovBook::new_features_fac_follows(update_fac_after(h), kf, sz, h->NP_max);
+    // scratch: HH [sz][n + 1] | nHHP [sz][n] | dx_new [sz] | singular word (the last two contiguous: ONE fetch)
+    const size_t need = ((size_t)sz * (n + 1) + (size_t)sz * n + sz + 1) * sizeof(double);
+    if (need > h->aug_cap) {
+        HIPCHK(hipDeviceSynchronize());
+        if (h->d_aug) (void)hipFree(h->d_aug);
+        h->d_aug = nullptr; h->aug_cap = 0;
+        HIPCHK(hipMalloc(&h->d_aug, need * 2));
+        h->aug_cap = need * 2;
+    }
+    double* HH = reinterpret_cast<double*>(h->d_aug);
+    double* nHHP = HH + (size_t)sz * (n + 1);
+    double* dxn = nHHP + (size_t)sz * n;
+    int* flag = reinterpret_cast<int*>(dxn + sz);
+    const double* dout = reinterpret_cast<const double*>(h->d_new + h->new_out_off);
+    const double* H1 = dout; const double* H2 = dout + (size_t)sz * n; const double* r1 = H2 + (size_t)k * d * d;
+    const double sigma = h->flags.noise_feature;
+    AugFacArgs f{};
+    if (follows) {   // S+ as k_fac_commit writes it (orcvio_msckf_cov_commit), into the spare factor buffer with the augmented state's leading dimension
+        const PriorFactor pf = prior_factor(h);
+        f.on = 1; f.Z = h->d_Z; f.ldz = h->ldz; f.kf = kf; f.sigma = sigma;
+        f.apply = h->last_update_objects ? h->d_obj_accept : (const int*)nullptr; f.fail = h->d_info + 2;
+        f.prior = pf.base; f.sLi = pf.sLi; f.sLj = pf.sLj;
+        f.Sout = h->d_Stmp; f.ldo = CovBook::ld_for(nt);
+    }
+    const int nb_P = (nt * nt + 255) / 256, nb_S = follows ? ((kf + sz) * f.ldo + 255) / 256 : 0, nb_Q = (sz * (sz + 1) / 2 + 3) / 4;
+#define LAUNCH_AUG(D)                                                                                                                   \
+    do {                                                                                                                                \
+        hipLaunchKernelGGL(k_aug_rows<D>, dim3(sz, aug_rows_split(n, follows ? kf : 0)), dim3(AUG_ROWS_THREADS), lds, s, H1, H2, r1, n, k, h->ref_h2_ldlt ? 1 : 0, \
+                           (const double*)h->d_Pout, (const double*)h->d_dx, HH, nHHP, dxn, flag, f);                                   \
+        hipLaunchKernelGGL(k_aug_finish<D>, dim3(nb_P + nb_S + nb_Q), dim3(256), 0, s, (const double*)h->d_Pout, n, sz, tail, H2,       \
+                           (const double*)HH, (const double*)nHHP, sigma * sigma, h->d_Ptmp, nb_P, nb_S, f);                            \
+    } while (0)
+    if (d == 3) LAUNCH_AUG(3); else LAUNCH_AUG(1);
+#undef LAUNCH_AUG
+    HIPCHK(hipGetLastError());
+    std::vector<double> back((size_t)sz + 1, 0.0);
+    const FetchCopy fc[] = {{back.data(), dxn, sizeof(double) * ((size_t)sz + 1)}};
+    const int rc = fetch_copies(h, s, fc, 1);   // (the one wait; `s` may be another stream than the handle's own: nothing is left on it)
+    if (rc != ORCVIO_OK) return rc;
+    int bad = 0;
+    std::memcpy(&bad, &back[sz], sizeof(int));
+    if (bad) { g_last_error = "cov_commit_new_features_fac: singular H_2"; return ORCVIO_ERR_NOT_SPD; }
+    std::memcpy(dx_new, back.data(), sizeof(double) * sz);
+    h->commit_new_features_fac(nt, kf, sz, follows);
+    h->new_F = 0;
+    return ORCVIO_OK;
+}
+
 // Factor the resident covariance NOW (asynchronously, on the handle's stream): P = L L^T, L kept as the resident square-root
 // factor.  processModel adds Q to the IMU block, after which no factor of P is known; a caller that propagates and augments when
 // the image arrives and updates when the front end has finished tracking it (milliseconds later) takes the Cholesky of the

@@ -185,6 +185,213 @@ __global__ __launch_bounds__(256) void k_aug_assemble(const double* __restrict__
     out[idx] = v;
 }
 
+// ---- ... with the resident square-root factor carried along (orcvio_msckf_cov_commit_new_features_fac): two launches, no memset.
+// With P+ = S+ S+^T, HH = H_2^-1 H_1 and W = R^-1 R^-T (R = H_2 upper triangular),
+//     P_aug = S_aug S_aug^T,   S_aug = [  S+       0             ]   n rows,   kf columns | sz columns
+//                                      [ -HH S+    sigma R^-1 (bd) ]   sz rows
+// (block-diagonal second block, one d x d block per feature; under ORCVIO_OPT_REF_H2_LDLT too: there only HH and x divide by
+// diag(H_2), W does not).  The factor is carried only without nuisance states, so its new rows stand behind ALL old ones.
+//   k_aug_rows    grid (new row r, 64-column share y): every workgroup does the back-substitution of its feature's rows i >= r % d
+//                 of [HH | x] in LDS (k_aug_hh's arithmetic; the rows below its own and the other shares' copies are recomputed,
+//                 d <= 3: no workgroup waits for another), then its 64 columns of row r of -HH P+ into scratch and its 64
+//                 columns of row r of -HH S+ straight into the spare factor buffer; one share stores row r of HH, one dx_new[r]
+//                 (k_aug_dx's arithmetic), workgroup (0, 0) the singular word (stored, not raised: nothing to clear in front)
+//   k_aug_finish  behind the launch boundary: P_aug but its new-new block element by element (k_aug_assemble's cases), S_aug but
+//                 the rows k_aug_rows wrote (old rows as k_fac_commit writes them, exact zeros, sigma R^-1, zeros in the padding up to
+//                 the leading dimension), and one wavefront per pair (r <= c) of the new-new block: Q(r, c) and Q(c, r) = rows of
+//                 -HH P+ times rows of HH, P22 = -(Q + Q^T) / 2 + s2 (W + W^T) / 2 stored at (r, c) and (c, r) -- symmetric exactly
+// S+ of the old rows: sigma Z^T, or the prior's own factor behind a refused or rejected update, by k_fac_commit's status words.
+// Measured on MI355X (scripts/gpu_entering_commit_ab.py, profiles/r32a_entering_commit_ab.json: leg 22, 20 clones, 12 in-state
+// features, n = 154 / 178, 1 and 3 entering features, both calls alternating in one process): the call 32-40 us against 62-79 us for
+// orcvio_msckf_cov_commit_new_features; the call plus the frame's next update 137-146 us against 175-183 us (35-39 us less, the old
+// route's own spread over the repeats at most 5 us).  Nearly all of it is the call: k_aug_rows 10-12 us + k_aug_finish 5-6 us against
+// a memset and five launches of 21 us together, one fetch and one wait fewer; the next update itself gains 0-7 us, because the
+// Cholesky chain of its prior runs inside k_front beside the tracks' workgroups and was mostly hidden already.
+struct AugFacArgs {
+    int on;                         // 0: the factor is dropped -- nothing below is read or written
+    const double* Z; int ldz, kf;   // Z = L_M^-1 S^T of the update: S+(c, i) = sigma Z[i ldz + c]
+    double sigma;
+    const int* apply; const int* fail;
+    const double* prior; long sLi, sLj;
+    double* Sout; int ldo;          // S_aug(j, i) = Sout[i ldo + j]
+};
+__device__ __forceinline__ bool aug_fac_applied(const AugFacArgs& f) { return (f.apply ? (*f.apply != 0) : true) && f.fail[0] == 0 && f.fail[1] == 0; }
+__device__ __forceinline__ double aug_fac_old(const AugFacArgs& f, bool app, int c, int i) {
+    return app ? f.sigma * f.Z[(size_t)i * f.ldz + c] : f.prior[(long)c * f.sLi + (long)i * f.sLj];
+}
+// R^-1 of one feature's upper-triangular D x D block, column by column (k_aug_hh's arithmetic; D a constant: registers, no scratch)
+template <int D>
+__device__ __forceinline__ void aug_rinv(const double* __restrict__ R, double (&Ri)[D * D]) {
+#pragma unroll
+    for (int q = 0; q < D * D; ++q) Ri[q] = 0.0;
+#pragma unroll
+    for (int cc = 0; cc < D; ++cc)
+#pragma unroll
+        for (int i = D - 1; i >= 0; --i) {
+            double m = i == cc ? 1.0 : 0.0;
+#pragma unroll
+            for (int k = i + 1; k < D; ++k) m -= R[i * D + k] * Ri[k * D + cc];
+            Ri[i * D + cc] = m / R[i * D + i];
+        }
+}
+// entry (a, b) of a D x D array in registers, a and b not known at compile time
+template <int D>
+__device__ __forceinline__ double aug_pick(const double (&M)[D * D], int a, int b) {
+    double v = 0.0;
+#pragma unroll
+    for (int q = 0; q < D * D; ++q) v = (q == a * D + b) ? M[q] : v;
+    return v;
+}
+enum { AUG_ROWS_THREADS = 1024, AUG_ROWS_WAVES = AUG_ROWS_THREADS / 64 };
+// dynamic LDS of k_aug_rows: [d][n + 1] rows of [HH | x], then the partial sums of -HH P+ [waves][64]
+static inline size_t aug_rows_lds_bytes(int n, int d) { return sizeof(double) * ((size_t)d * (n + 1) + (size_t)AUG_ROWS_WAVES * 64); }
+// grid.y of k_aug_rows: the workgroups of one row -- workgroup y takes the 64 columns y of -HH P+ and the 64 columns Y-1-y of -HH S+
+static inline int aug_rows_split(int n, int kf_or_0) { const int a = (n + 63) / 64, b = (kf_or_0 + 63) / 64; return a > b ? a : b; }
+template <int D>
+__global__ __launch_bounds__(AUG_ROWS_THREADS) void k_aug_rows(const double* __restrict__ H1, const double* __restrict__ H2,
+                                                               const double* __restrict__ r1, int n, int n_new, int diag_only,
+                                                               const double* __restrict__ Pp, const double* __restrict__ dx,
+                                                               double* __restrict__ HH /* [d n_new][n + 1] */, double* __restrict__ nHHP /* [d n_new][n] */,
+                                                               double* __restrict__ dx_new, int* __restrict__ singular, AugFacArgs f) {
+    extern __shared__ double aug_lds[];
+    constexpr int d = D;
+    const int r = blockIdx.x, j = r / d, i0 = r - j * d;
+    const int y = blockIdx.y, Y = gridDim.y;           // this row's workgroups: each recomputes the row, each has columns of its own
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    double* sH = aug_lds;                              // [d][n + 1]
+    double* sPart = aug_lds + (size_t)d * (n + 1);     // [waves][64]
+    const double* R = H2 + (size_t)j * d * d;
+    for (int c = tid; c <= n; c += AUG_ROWS_THREADS) {
+        double v[D], mine = 0.0;
+#pragma unroll
+        for (int i = d - 1; i >= 0; --i) {
+            v[i] = 0.0;
+            if (i < i0) continue;   // (uniform over the workgroup)
+            double m = c < n ? H1[(size_t)(d * j + i) * n + c] : r1[d * j + i];
+            if (!diag_only) {
+#pragma unroll
+                for (int k = i + 1; k < d; ++k) m -= R[i * d + k] * v[k];
+            }
+            v[i] = m / R[i * d + i];
+            sH[i * (n + 1) + c] = v[i];
+            if (i == i0) mine = v[i];
+        }
+        if (y == 0) HH[(size_t)r * (n + 1) + c] = mine;
+    }
+    if (r == 0 && y == 0 && tid == 0) {
+        bool bad = false;
+        for (int q = 0; q < n_new; ++q)
+            for (int i = 0; i < d; ++i) bad = bad || H2[(size_t)q * d * d + i * d + i] == 0.0;
+        *singular = bad ? 1 : 0;
+    }
+    __syncthreads();
+    const double* hrow = sH + i0 * (n + 1);
+    if (y == Y - 1 && wave == AUG_ROWS_WAVES - 1) {   // dx_new[r] = x[r] - HH[r][:] dx
+        double s = 0.0;
+        for (int c = lane; c < n; c += 64) s += hrow[c] * dx[c];
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) dx_new[r] = hrow[n] - s;
+    }
+    // -HH P+, the 64 columns y: every wavefront a slice of the sum, the slices added in their order afterwards
+    const int cl = (n + AUG_ROWS_WAVES - 1) / AUG_ROWS_WAVES;
+    const bool has_P = y * 64 < n;
+    if (has_P) {
+        const int b = y * 64 + lane, c0 = wave * cl, c1 = c0 + cl < n ? c0 + cl : n;
+        const double* col = Pp + (b < n ? b : n - 1);
+        double acc = 0.0;
+#pragma unroll 8
+        for (int c = c0; c < c1; ++c) acc += hrow[c] * col[(size_t)c * n];
+        sPart[wave * 64 + lane] = acc;
+    }
+    if (f.on) {   // -HH S+, the 64 columns Y-1-y: one wavefront per column of S+, four columns in flight
+        const bool app = aug_fac_applied(f);
+        for (int ib = (Y - 1 - y) * 64 + wave * 4; ib < f.kf; ib += Y * 64) {
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int c = lane; c < n; c += 64) {
+                const double hv = hrow[c];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int i = ib + u < f.kf ? ib + u : f.kf - 1;
+                    acc[u] += hv * aug_fac_old(f, app, c, i);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                double s = acc[u];
+                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+                if (lane == 0 && ib + u < f.kf) f.Sout[(size_t)(ib + u) * f.ldo + n + r] = -s;
+            }
+        }
+    }
+    __syncthreads();
+    if (has_P && tid < 64 && y * 64 + tid < n) {
+        double s = 0.0;
+        for (int sl = 0; sl < AUG_ROWS_WAVES; ++sl) s += sPart[sl * 64 + tid];
+        nHHP[(size_t)r * n + y * 64 + tid] = -s;
+    }
+}
+// grid: nb_P blocks over P_aug, nb_S over S_aug (0 without the factor), then four pairs of the new-new block per block
+template <int D>
+__global__ __launch_bounds__(256) void k_aug_finish(const double* __restrict__ Pp, int n, int sz, int tail, const double* __restrict__ H2,
+                                                    const double* __restrict__ HH, const double* __restrict__ nHHP, double s2,
+                                                    double* __restrict__ out, int nb_P, int nb_S, AugFacArgs f) {
+    constexpr int d = D;
+    const int nt = n + sz, n0 = n - tail;
+    const int blk = blockIdx.x, tid = threadIdx.x;
+    if (blk < nb_P) {
+        const int idx = blk * 256 + tid;
+        if (idx >= nt * nt) return;
+        const int i = idx / nt, j = idx - i * nt;
+        auto src = [&](int q) { return q < n0 ? q : (q < n0 + sz ? n + (q - n0) : q - sz); };   // index in the [old + tail | new] order
+        const int a = src(i), b = src(j);
+        if (a < n && b < n) out[idx] = 0.5 * (Pp[(size_t)a * n + b] + Pp[(size_t)b * n + a]);
+        else if (a >= n && b < n) out[idx] = nHHP[(size_t)(a - n) * n + b];
+        else if (a < n && b >= n) out[idx] = nHHP[(size_t)(b - n) * n + a];
+        return;   // (new-new: the pair blocks)
+    }
+    if (blk < nb_P + nb_S) {   // (f.on; the factor's new rows stand at n .. nt-1: no nuisance states)
+        const int idx = (blk - nb_P) * 256 + tid;
+        if (idx >= (f.kf + sz) * f.ldo) return;
+        const int i = idx / f.ldo, j = idx - i * f.ldo;
+        double v = 0.0;
+        if (i < f.kf) {
+            if (j >= n && j < nt) return;   // k_aug_rows wrote -HH S+
+            if (j < n) v = aug_fac_old(f, aug_fac_applied(f), j, i);
+        } else if (j >= n && j < nt && (j - n) / d == (i - f.kf) / d) {
+            const int q = (j - n) / d;
+            double Ri[D * D];
+            aug_rinv<D>(H2 + (size_t)q * d * d, Ri);
+            v = f.sigma * aug_pick<D>(Ri, j - n - q * d, i - f.kf - q * d);
+        }
+        f.Sout[idx] = v;
+        return;
+    }
+    const int p = (blk - nb_P - nb_S) * 4 + (tid >> 6), lane = tid & 63;
+    if (p >= sz * (sz + 1) / 2) return;
+    int r = 0, c = p;
+    while (c >= sz - r) { c -= sz - r; ++r; }   // pair p -> (r, c), r <= c  (wave-uniform)
+    c += r;
+    double q1 = 0.0, q2 = 0.0;
+    for (int b = lane; b < n; b += 64) {
+        q1 += nHHP[(size_t)r * n + b] * HH[(size_t)c * (n + 1) + b];
+        q2 += nHHP[(size_t)c * n + b] * HH[(size_t)r * (n + 1) + b];
+    }
+    for (int o = 32; o > 0; o >>= 1) { q1 += __shfl_xor(q1, o); q2 += __shfl_xor(q2, o); }
+    if (lane != 0) return;
+    double v = -0.5 * (q1 + q2);
+    if (r / d == c / d) {
+        const int q = r / d, ri = r - q * d, ci = c - q * d;
+        double Ri[D * D];
+        aug_rinv<D>(H2 + (size_t)q * d * d, Ri);
+        double w1 = 0.0, w2 = 0.0;   // W(ri, ci) and W(ci, ri), W = R^-1 R^-T summed in k_aug_hh's order
+#pragma unroll
+        for (int k = 0; k < d; ++k) { w1 += aug_pick<D>(Ri, ri, k) * aug_pick<D>(Ri, ci, k); w2 += aug_pick<D>(Ri, ci, k) * aug_pick<D>(Ri, ri, k); }
+        v += 0.5 * s2 * (w1 + w2);
+    }
+    out[(size_t)(n0 + r) * nt + n0 + c] = v;
+    out[(size_t)(n0 + c) * nt + n0 + r] = v;
+}
+
 
 
 // ---- in-state SLAM features on the resident covariance (src/orcvio.cpp:2664-2720, updateFeatureCov_1didp :3611-3774,

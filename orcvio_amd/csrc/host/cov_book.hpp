@@ -51,6 +51,17 @@ struct CovBook {
     CovEdit change_anchors() { const CovEdit e = edit(res_n, fac_ld); if (!e.fac) fac_valid = false; return e; }
     // an update's commit with entering features wrote the augmented covariance [nt][nt] into the spare buffer
     void commit_new_features(int nt) { swap_P(nt); fac_valid = false; }
+    // ... with the factor carried along: S_aug = [[S+, 0], [-HH S+, sigma R^-1]] has the k columns of the update's S+ = sigma Z^T and
+    // k_new more, one per new state.  It follows exactly when the update's own commit would adopt S+ (f) and the widened factor
+    // fits the factor buffers (cols_max^2 doubles: k + k_new <= cols_max columns of ld_for(nt) <= cols_max) -- asked BEFORE the
+    // launches, which write the spare factor buffer only then
+    static bool new_features_fac_follows(FacAfter f, int k, int k_new, int cols_max) { return f == FacAfter::adopt && k + k_new <= cols_max; }
+    // P roles change to nt; the factor is adopted with k + k_new columns, ld_for(nt), tail 0 (the new columns are not zero in the
+    // rows >= 15), or dropped.  A refused call (singular H_2) does not come here: nothing changes
+    void commit_new_features_fac(int nt, int k, int k_new, bool follows) {
+        swap_P(nt);
+        if (follows) fac_adopt(nt, k + k_new, ld_for(nt), 0); else fac_valid = false;
+    }
     // P = L L^T has been factored into the spare factor buffer (the caller asks fac_follows() first) with leading dimension
     // ld_for(res_n); reversed: the rows >= 15 are zero in the last 15 columns
     void prefactor(bool reversed) { fac_adopt(res_n, res_n, ld_for(res_n), reversed ? 15 : 0); }

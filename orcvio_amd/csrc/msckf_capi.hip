@@ -297,7 +297,7 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     double* d_dense = nullptr;          // [dense_cap][NAP_max]
     bool ekf_eval = false;              // the four blocks are evaluated on the device from the SLAM features (k_ekf_eval)
     double* d_slam = nullptr;           // [12 cap] param 3 | inv_depth 1 | p_w 3 | p_fej 3 | z 2
-    char* d_aug = nullptr; size_t aug_cap = 0;   // scratch of orcvio_msckf_cov_commit_new_features
+    char* d_aug = nullptr; size_t aug_cap = 0;   // scratch of orcvio_msckf_cov_commit_new_features and of _fac (each lays it out for itself)
     char* d_new = nullptr; size_t new_cap = 0, new_out_off = 0;   // entering features (orcvio_msckf_upload_new_features): inputs, then H_1 | H_2 | r_1
     int new_F = 0, new_idp = 3;
     double* d_Rf = nullptr;             // [maxF][6] R factor of every track's H_f (k_feature), for orcvio_msckf_augment_new_features
