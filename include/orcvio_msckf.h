@@ -1491,6 +1491,53 @@ int32_t orcvio_msckf_cov_propagate_imu_checked(orcvio_msckf_handle* h, const orc
 int32_t orcvio_msckf_cov_zupt_frame_checked(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame* frame, const orcvio_msckf_zupt_check* chk,
                                             double* dx, int32_t* applied, int32_t* n_after, orcvio_msckf_zupt_verdict* verdict);
 
+/* ---- Zero-velocity frames of a HYBRID filter: the in-state features leave in front of the update ----------------------------------------
+ * When either zero-velocity check accepts a frame, the reference deletes ALL in-state (EKF-SLAM) features before
+ * measurementUpdate_ZUPT_vpq runs (checkZUPTFeat, src/orcvio.cpp:3102-3119; checkZUPTIMU, :3302-3319: a conservativeResize that cuts the
+ * trailing feature_idp_dim x feature_states.size() rows and columns, feature_states.clear()); the update then runs on b = leg + 6 N
+ * states and pruneImuStateBuffer marginalises the previous clone (:2641-2645).  cov_zupt / cov_zupt_frame / _checked above keep the
+ * extra states through the update: another filter.  The calls below are the reference's frame, and the drop, the update and the
+ * marginalisation are ONE launch (k_zupt_cov_keep; k_zupt_fac_keep for the factor): the update writes only what stays, the P buffers
+ * change roles once.
+ *   cov_zupt_frame_hybrid          frame as cov_zupt_frame reads it, idp_dim (1 or 3) and n_feature_states F >= 0, ALL of which leave when
+ *                                  the update is applied.  The launches of cov_propagate (Phi, Q given, or armed by
+ *                                  orcvio_msckf_io_propagate_imu exactly as cov_zupt_frame), cov_augment, the fused update; one wait.
+ *                                  Applied: P, dx [leg + 6 n_clones] (as the reference's K r has after the resize), the factor's validity,
+ *                                  shape and contents and *n_after = b - 6 (remove_previous != 0) are bit for bit those of cov_propagate,
+ *                                  cov_augment, cov_remove_features (all F slots), cov_zupt, cov_remove_clones.  The gate reads the 15 rows
+ *                                  at the columns < b only, as those calls do: a NaN behind b leaves with the features.
+ *                                  Refused on the device (ORCVIO_ERR_NOT_SPD, *applied = 0, dx = 0): propagation and augmentation stand, NO
+ *                                  feature leaves and NOTHING is marginalised, *n_after is the dimension behind the augmentation -- this
+ *                                  DIFFERS from cov_zupt_frame, whose marginalisation stands behind a refusal.  P and the factor are the
+ *                                  prior's own, bit for bit.  A HIP error at the wait (ORCVIO_ERR_HIP / _TIMEOUT): the launches wrote the
+ *                                  spare buffers only, the propagated and augmented prior and its factor stand, as in cov_zupt -- not
+ *                                  cov_zupt_frame's "nothing resident".  F = 0 is allowed: applied results are cov_zupt_frame's, bit for bit.
+ *   cov_zupt_frame_checked_hybrid  everything cov_zupt_frame_checked documents (an armed handle only, leg_dim 22, Phi = Q = NULL, the
+ *                                  one-sample case, the verdict), the fused update reading the check's status block.  Accepted and
+ *                                  applied: as above, and nothing is enqueued behind the wait.  Rejected by the check: ORCVIO_OK,
+ *                                  *applied = 0, P bit for bit what io_propagate_imu + cov_augment leave, every feature in place; the
+ *                                  caller goes on with orcvio_msckf_io_step_frame_ex.
+ *   zupt_check_feat                checkZUPTFeat's decision (:3081-3100) on the n pixel distances the front end computed; host
+ *                                  arithmetic, no handle.  n < 20: *accept = 0, *kth = NaN.  Otherwise *kth is the ninth largest distance
+ *                                  and *accept = *kth < max_dis.  A null pointer, n < 0, a non-finite distance or threshold:
+ *                                  ORCVIO_ERR_INVALID.
+ * Refused before anything is enqueued (ORCVIO_ERR_INVALID, nothing done, an arming stands): everything cov_zupt_frame (_checked)
+ * refuses; idp_dim not 1 or 3; F < 0; a resident dimension behind the augmentation that is not leg + 6 N + idp_dim F, or
+ * idp_dim F != ORCVIO_OPT_EXTRA_STATES; nuisance states declared (ORCVIO_OPT_SCHMIDT_STATES > 0): the reference's resize cuts the
+ * TRAILING rows, which are then nuisance rows and not feature rows -- not reproduced here, and use_schmidt is 0 in every shipped
+ * configuration.  The calls do not change ORCVIO_OPT_EXTRA_STATES: the caller sets it to 0 when *applied = 1, by the convention of
+ * cov_remove_features. */
+typedef struct orcvio_msckf_zupt_frame_hybrid {
+    orcvio_msckf_zupt_frame frame;      /* as orcvio_msckf_cov_zupt_frame reads it */
+    int32_t idp_dim;                    /* 1 or 3 */
+    int32_t n_feature_states;           /* F >= 0: ALL of them leave when the update is applied */
+} orcvio_msckf_zupt_frame_hybrid;
+int32_t orcvio_msckf_cov_zupt_frame_hybrid(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame_hybrid* frame, double* dx /* [leg + 6 n_clones] */,
+                                           int32_t* applied, int32_t* n_after);
+int32_t orcvio_msckf_cov_zupt_frame_checked_hybrid(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame_hybrid* frame, const orcvio_msckf_zupt_check* chk,
+                                                   double* dx, int32_t* applied, int32_t* n_after, orcvio_msckf_zupt_verdict* verdict);
+int32_t orcvio_msckf_zupt_check_feat(const double* dis, int32_t n, double max_dis, int32_t* accept, double* kth);
+
 /* ---- Environment switches (read once per process; diagnostics and A/B measurements -- every one of them leaves the results unchanged) ----
  *   ORCVIO_COMM_TIMEOUT_S   bound of every wait another rank can strand, seconds (default 180)
  *   ORCVIO_IPC_WAIT_S       ipc transport: bound of the device-side wait for a peer's block, seconds (default 20, at most the above)

@@ -51,6 +51,7 @@ EXPORTS = [
     'orcvio_msckf_cov_zupt', 'orcvio_msckf_cov_zupt_frame', 'orcvio_msckf_cov_propagate_imu', 'orcvio_msckf_io_propagate_imu',
     'orcvio_msckf_zupt_check_default', 'orcvio_msckf_cov_zupt_check_imu', 'orcvio_msckf_cov_propagate_imu_checked',
     'orcvio_msckf_cov_zupt_frame_checked', 'orcvio_msckf_cov_propagate_imu_calib',
+    'orcvio_msckf_cov_zupt_frame_hybrid', 'orcvio_msckf_cov_zupt_frame_checked_hybrid', 'orcvio_msckf_zupt_check_feat',
 ]
 
 
@@ -189,6 +190,11 @@ class ZuptFrame(C.Structure):
     _fields_ = [('zupt', Zupt), ('Phi', _dp), ('Q', _dp), ('augment', C.c_int32), ('remove_previous', C.c_int32)]
 
 
+class ZuptFrameHybrid(C.Structure):
+    """orcvio_msckf_zupt_frame_hybrid: one stationary frame of a hybrid filter (include/orcvio_msckf.h)."""
+    _fields_ = [('frame', ZuptFrame), ('idp_dim', C.c_int32), ('n_feature_states', C.c_int32)]
+
+
 class ImuConfig(C.Structure):
     """orcvio_msckf_imu_config (include/orcvio_msckf.h)."""
     _fields_ = [('leg_dim', C.c_int32), ('use_larvio', C.c_int32), ('use_left_perturbation', C.c_int32), ('use_closed_form', C.c_int32),
@@ -318,6 +324,9 @@ def _bind(lib):
     lib.orcvio_msckf_cov_propagate_imu_checked.argtypes = [C.c_void_p, C.POINTER(ImuConfig), C.POINTER(ImuState), _dp, _dp, C.c_int32, C.c_double,
                                                            C.POINTER(ImuInfo), _dp, _dp, C.POINTER(ZuptCheck), C.POINTER(ZuptVerdict)]
     lib.orcvio_msckf_cov_zupt_frame_checked.argtypes = [C.c_void_p, C.POINTER(ZuptFrame), C.POINTER(ZuptCheck), _dp, _ip, _ip, C.POINTER(ZuptVerdict)]
+    lib.orcvio_msckf_cov_zupt_frame_hybrid.argtypes = [C.c_void_p, C.POINTER(ZuptFrameHybrid), _dp, _ip, _ip]
+    lib.orcvio_msckf_cov_zupt_frame_checked_hybrid.argtypes = [C.c_void_p, C.POINTER(ZuptFrameHybrid), C.POINTER(ZuptCheck), _dp, _ip, _ip, C.POINTER(ZuptVerdict)]
+    lib.orcvio_msckf_zupt_check_feat.argtypes = [_dp, C.c_int32, C.c_double, _ip, _dp]
     lib.orcvio_msckf_upload_nuisance_poses.argtypes = [C.c_void_p, C.c_void_p]
     lib.orcvio_msckf_update_object_tracks.argtypes = [C.c_void_p, C.POINTER(MsckfFlags), C.POINTER(ObjectEvalFlags), C.c_int32,
                                                       C.POINTER(ObjectTrackC), C.c_int32, _dp, C.POINTER(MsckfResult)]
@@ -1740,6 +1749,44 @@ class MsckfUpdater:
             raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame_checked')
         return dict(dx=dx[:nu], applied=int(applied.value), n_after=int(n_after.value), rc=rc), self._verdict(out, rc)
 
+    def _zupt_hybrid_struct(self, leg_dim, n_clones, r, noises, idp_dim, n_feature_states, Phi, Q, augment, remove_previous, keep):
+        f = ZuptFrameHybrid()
+        f.frame.zupt = self._zupt_struct(leg_dim, n_clones, r, noises)
+        if Phi is not None:
+            keep.append(np.ascontiguousarray(Phi, dtype=np.float64)); f.frame.Phi = _d(keep[-1])
+        if Q is not None:
+            keep.append(np.ascontiguousarray(Q, dtype=np.float64)); f.frame.Q = _d(keep[-1])
+        f.frame.augment, f.frame.remove_previous = int(bool(augment)), int(bool(remove_previous))
+        f.idp_dim, f.n_feature_states = int(idp_dim), int(n_feature_states)
+        return f
+
+    def cov_zupt_frame_hybrid(self, leg_dim, n_clones, r, noises, idp_dim, n_feature_states, Phi=None, Q=None, augment=True,
+                              remove_previous=True, raise_on_refusal=True):
+        """orcvio_msckf_cov_zupt_frame_hybrid: one stationary frame of a hybrid filter in one call -- every in-state feature leaves in
+        front of the update, the previous clone behind it, one fused launch.  Returns dict(dx [leg + 6 n_clones], applied, n_after, rc)."""
+        keep = []
+        f = self._zupt_hybrid_struct(leg_dim, n_clones, r, noises, idp_dim, n_feature_states, Phi, Q, augment, remove_previous, keep)
+        b = max(int(leg_dim) + 6 * int(n_clones), 1)
+        dx = np.zeros(b)
+        applied, n_after = C.c_int32(-1), C.c_int32(-1)
+        rc = self.lib.orcvio_msckf_cov_zupt_frame_hybrid(self.h, C.byref(f), _d(dx), C.byref(applied), C.byref(n_after))
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame_hybrid')
+        return dict(dx=dx, applied=int(applied.value), n_after=int(n_after.value), rc=rc)
+
+    def cov_zupt_frame_checked_hybrid(self, chk, leg_dim, n_clones, r, noises, idp_dim, n_feature_states, augment=True, remove_previous=True,
+                                      raise_on_refusal=True):
+        """orcvio_msckf_cov_zupt_frame_checked_hybrid: the hybrid stationary frame on a handle armed by io_propagate_imu, the
+        zero-velocity check in front of its fused update, one wait.  Returns (dict(dx, applied, n_after, rc), the verdict's dict)."""
+        f = self._zupt_hybrid_struct(leg_dim, n_clones, r, noises, idp_dim, n_feature_states, None, None, augment, remove_previous, [])
+        dx = np.zeros(max(int(leg_dim) + 6 * int(n_clones), 1))
+        applied, n_after = C.c_int32(-1), C.c_int32(-1)
+        out = ZuptVerdict()
+        rc = self.lib.orcvio_msckf_cov_zupt_frame_checked_hybrid(self.h, C.byref(f), C.byref(chk), _d(dx), C.byref(applied), C.byref(n_after), C.byref(out))
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame_checked_hybrid')
+        return dict(dx=dx, applied=int(applied.value), n_after=int(n_after.value), rc=rc), self._verdict(out, rc)
+
     def set_object_dof_rank(self, on: bool):
         """ORCVIO_OPT_OBJECT_DOF: 1 = the object gate counts rows - rank(H_f) degrees of freedom (default rows - columns)."""
         self._chk(self.lib.orcvio_msckf_set_option(self.h, 11, int(bool(on))), 'orcvio_msckf_set_option')
@@ -2014,6 +2061,17 @@ def _rotation_to_quaternion(R):
     if q[3] < 0:
         q = -q
     return q / np.linalg.norm(q)
+
+
+def zupt_check_feat(dis, max_dis):
+    """orcvio_msckf_zupt_check_feat: checkZUPTFeat's decision on the pixel distances of the tracked features.  Returns
+    dict(accept, kth); raises MsckfError on a refusal."""
+    d = np.ascontiguousarray(dis, dtype=np.float64).reshape(-1)
+    accept, kth = C.c_int32(-1), np.zeros(1)
+    rc = load().orcvio_msckf_zupt_check_feat(_d(d) if d.size else None, int(d.size), float(max_dis), C.byref(accept), _d(kth))
+    if rc != 0:
+        raise MsckfError(rc, 'orcvio_msckf_zupt_check_feat')
+    return dict(accept=int(accept.value), kth=float(kth[0]))
 
 
 def zupt_residual(v, R_prev, p_prev, R_cur, p_cur):

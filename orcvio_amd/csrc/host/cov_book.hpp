@@ -75,6 +75,22 @@ struct CovBook {
     }
     // ... refused on the device: the spare buffers took bit copies of the prior and of its factor, whose trailing columns are still zero
     void zupt_refused(int tail_before) { if (fac_valid) fac_tail = tail_before; }
+    // the zero-velocity update that writes only the m states that stay (the in-state features and the previous clone leave in the
+    // same launch).  Whether it is applied is decided on the device and nothing is enqueued behind it before the wait, so this
+    // changes NOTHING yet: the record goes to the launches and, with the outcome, to zupt_keep_done.  The factor follows by zupt's rule
+    CovEdit zupt_keep(int m, bool no_nuisance, int kmax) const {
+        CovEdit e = edit(m, ld_for(m));
+        e.fac = e.fac && no_nuisance && fac_k <= kmax;
+        return e;
+    }
+    // ... its outcome.  Applied: the P buffers change roles at m, the factor is adopted at (m, fac_k, ld_for(m), tail 0) or dropped.
+    // Not applied (refused on the device, rejected by the check in front, or an outcome nobody could fetch): the spare buffers took
+    // bit copies or nothing certain, the resident ones were only read -- no buffer changes roles, the factor's shape, validity and
+    // fac_tail are the prior's, as cov_zupt leaves them
+    void zupt_keep_done(const CovEdit& e, bool applied) {
+        if (!applied) return;
+        swap_P(e.m); follow(e, 0);
+    }
     // the step call's fused frame head: propagation, augmentation and the removal of d_lost feature states in ONE launch, so the P
     // buffers change roles once (the separate edits: three times)
     CovEdit head(bool propagated, bool augmented, int d_lost) {

@@ -1343,7 +1343,7 @@ class MsckfBackend {
     }
 
     // checkZUPTIMU (src/orcvio.cpp:3129-3323) without its side effects (the reference deletes the in-state features and runs the
-    // update when it accepts: the caller's, zuptUpdate below).  imu_recent_zupt: the messages the IMU step selected (:676-690).  With
+    // update when it accepts: zuptFrame / zuptFrameChecked below do both in one call; zuptUpdate keeps the features).  imu_recent_zupt: the messages the IMU step selected (:676-690).  With
     // the covariance resident: orcvio_msckf_cov_zupt_check_imu, one launch on the marginal in HBM.  Without: the SAME arithmetic on
     // ss.state_cov (zupt_check_model.hpp, the header the kernel is built from), the 56 sums in row order -- equal to the device's to
     // rounding, not bit for bit.  Neither forms the 6 (S - 1) x 6 (S - 1) matrix.  Validation and refusals as the library call's.
@@ -1412,6 +1412,28 @@ class MsckfBackend {
         out.state_incremented = applyZuptIncrement(flags, ss, map_server, out.delta_x, idp_dim, use_schmidt);
         return out;
     }
+
+    // The stationary frame of a HYBRID filter as the reference runs it: when a zero-velocity check accepts, every in-state feature is
+    // deleted in FRONT of the update (checkZUPTFeat :3102-3119, checkZUPTIMU :3302-3319), the update runs on leg + 6 N states and
+    // the previous clone is marginalised (:2641-2645).  One call, one wait: orcvio_msckf_cov_zupt_frame_hybrid -- propagation (Phi, Q;
+    // nullptr: none, or armed by orcvio_msckf_io_propagate_imu), augmentation, the fused update.  ss holds the window WITH this
+    // frame's clone (stateAugmentation's host half is the caller's, as is erasing the previous clone from imu_states_augment when
+    // the outcome is updated).  Applied: the reference's bookkeeping (:3108-3114) -- is_initialized = ekf_feature = in_state = false for
+    // every id in feature_states (in_state is this layer's ekf_feature), feature_states.clear() -- then the increments on dx [leg + 6 N].
+    // ORCVIO_OPT_EXTRA_STATES is declared for the call from feature_states and is 0 behind it, as in this layer's other calls.
+    // Refused on the device: nothing of that; every feature stays, in ss as in the covariance.
+    UpdateOutcome zuptFrame(StateServer& ss, MapServer& map_server, double noise_v, double noise_p, double noise_q, const double* Phi,
+                            const double* Q, bool augment, bool remove_previous, int idp_dim = 1) {
+        return zuptFrameCall(ss, map_server, noise_v, noise_p, noise_q, Phi, Q, augment, remove_previous, idp_dim, nullptr, nullptr);
+    }
+    // ... with checkZUPTIMU inside (orcvio_msckf_cov_zupt_frame_checked_hybrid, a handle armed by orcvio_msckf_io_propagate_imu): the
+    // device takes the decision, `verdict` reports it.  Rejected: status ORCVIO_OK, nothing updated, every feature in place -- the
+    // caller goes on with the moving frame.
+    UpdateOutcome zuptFrameChecked(StateServer& ss, MapServer& map_server, const orcvio_msckf_zupt_check& chk, double noise_v, double noise_p,
+                                   double noise_q, bool augment, bool remove_previous, ZuptCheckOutcome& verdict, int idp_dim = 1) {
+        return zuptFrameCall(ss, map_server, noise_v, noise_p, noise_q, nullptr, nullptr, augment, remove_previous, idp_dim, &chk, &verdict);
+    }
+
 
     // System::processObjects -> removeLostObjects straight from object TRACKS (state at the LM optimum + observations: what
     // ObjectInitNode returns per object), rows evaluated on the device; sharded over the ranks when a communicator exists
@@ -1792,6 +1814,43 @@ class MsckfBackend {
     orcvio_msckf_handle* handle() { return h_; }
 
   private:
+    // the two forms of the hybrid stationary frame (zuptFrame, zuptFrameChecked): chk == nullptr is the unchecked call
+    UpdateOutcome zuptFrameCall(StateServer& ss, MapServer& map_server, double noise_v, double noise_p, double noise_q, const double* Phi,
+                                const double* Q, bool augment, bool remove_previous, int idp_dim, const orcvio_msckf_zupt_check* chk,
+                                ZuptCheckOutcome* verdict) {
+        UpdateOutcome out;
+        orcvio_msckf_zupt_frame_hybrid f{};
+        orcvio_msckf_zupt& z = f.frame.zupt;
+        z.leg_dim = flags.leg_dim; z.n_clones = (int32_t)ss.imu_states_augment.size();
+        z.noise_v = noise_v; z.noise_p = noise_p; z.noise_q = noise_q;
+        if (z.n_clones < 2) { out.status = ORCVIO_ERR_INVALID; return out; }
+        const std::vector<double> r = zuptResidual(ss);
+        std::memcpy(z.r, r.data(), sizeof(z.r));
+        f.frame.Phi = Phi; f.frame.Q = Q; f.frame.augment = augment ? 1 : 0; f.frame.remove_previous = remove_previous ? 1 : 0;
+        f.idp_dim = idp_dim; f.n_feature_states = (int32_t)ss.feature_states.size();
+        out.delta_x.assign((size_t)(z.leg_dim + 6 * z.n_clones), 0.0);
+        int32_t applied = 0, n_after = 0;
+        OptionScope extra(h_, ORCVIO_OPT_EXTRA_STATES, idp_dim * f.n_feature_states);   // (declared for this call, 0 behind it)
+        if (extra.status != ORCVIO_OK) { out.status = extra.status; return out; }
+        if (chk) {
+            orcvio_msckf_zupt_verdict v{};
+            out.status = orcvio_msckf_cov_zupt_frame_checked_hybrid(h_, &f, chk, out.delta_x.data(), &applied, &n_after, &v);
+            verdict->status = v.status; verdict->evaluated = v.evaluated != 0; verdict->do_zupt = v.accept != 0;
+            verdict->dof = v.dof; verdict->chi2 = v.chi2; verdict->chi2_check = v.chi2_check; verdict->speed = v.speed;
+        } else {
+            out.status = orcvio_msckf_cov_zupt_frame_hybrid(h_, &f, out.delta_x.data(), &applied, &n_after);
+        }
+        out.updated = applied != 0;
+        if (out.status != ORCVIO_OK || !applied) return out;
+        for (const FeatureIDType id : ss.feature_states) {   // (:3108-3114; in_state is this layer's ekf_feature / in_state)
+            Feature& ft = map_server.at(id);
+            ft.is_initialized = false; ft.in_state = false;
+        }
+        ss.feature_states.clear();
+        out.state_incremented = applyZuptIncrement(flags, ss, map_server, out.delta_x, idp_dim, false);
+        return out;
+    }
+
     orcvio_msckf_handle* h_ = nullptr;
     int rank_ = 0, world_ = 0;
 

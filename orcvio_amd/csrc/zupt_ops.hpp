@@ -14,6 +14,12 @@
 // for another, and the results go to the spare buffers (the host swaps), so no workgroup reads what another has written.
 // The update is REFUSED when one of the 15 rows of P is not finite or M is not positive definite: every workgroup sees the same 15
 // rows and takes the same decision; P+ is then a bit copy of P, dx = 0, the status word is raised and k_zupt_fac copies S.
+//   k_zupt_cov_keep / k_zupt_fac_keep   the same update for the stationary frame of a HYBRID filter, where every in-state feature
+//                leaves in FRONT of the update (checkZUPTFeat :3102-3119, checkZUPTIMU :3302-3319) and the previous clone behind it
+//                (:2641-2645): both are gathers of P+ / S+, which these kernels write anyway, so they write them COMPACTED -- the
+//                states 0 .. b-1 without the previous clone's six.  One body per pair (zupt_cov_body, zupt_fac_body): the gate, M, C,
+//                V, dx and the tile arithmetic are k_zupt_cov's on the leading b x b block, bit for bit gather -> update -> gather.
+//                Refused (or rejected by the check in front: a.also): the bit copy at the input's dimension, nothing leaves.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,8 +46,40 @@ __device__ __forceinline__ void zupt_combine(const double* p, double* y) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_zupt_cov(const double* __restrict__ P, ZuptArgs a, double* __restrict__ out, double* __restrict__ dx,
-                                                  int* __restrict__ status) {
+// column `col` of V = C^-1 Y from the 15 rows of P (leading dimension ld), C in the lower triangle of sM
+__device__ __forceinline__ void zupt_v_col(const double* __restrict__ P, int ld, int b, int col, const double (*sM)[9], double* v) {
+    double p[15];
+    for (int l = 0; l < 15; ++l) p[l] = P[(size_t)zupt_row(l, b) * ld + col];
+    zupt_combine(p, v);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        double x = v[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) x -= sM[i][k] * v[k];
+        v[i] = x / sM[i][i];
+    }
+}
+__device__ __forceinline__ double zupt_dx_entry(const double* v, const double* sz) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s += v[i] * sz[i];
+    return s;
+}
+
+// What stays behind a fused update (k_zupt_cov_keep, k_zupt_fac_keep): the states 0 .. b-1 without the six rows that begin at `hole`
+// (hole >= m: none), so kept state i is state zupt_src(i, hole) of the prior -- a prefix and at most one hole, no index map.
+struct ZuptKeep {
+    int m, hole;   // the kept dimension, the first row of the dropped clone
+};
+__device__ __forceinline__ int zupt_src(int i, int hole) { return i < hole ? i : i + 6; }
+
+// ONE body for both covariance kernels.  KEEP = false: k_zupt_cov, P and out are [n][n].  KEEP = true: P is [n][n], the gate and the
+// update see its leading b x b block only (the states behind b have left BEFORE the update: they are neither scanned nor written),
+// applied: out is [m][m], one tile of the OUTPUT index space per workgroup (the workgroups behind ceil(m / 32) have nothing to
+// do); not applied: out is the bit copy [n][n], the tile loop running over the input's index space.
+template <bool KEEP>
+__device__ __forceinline__ void zupt_cov_body(const double* __restrict__ P, const ZuptArgs& a, const ZuptKeep kp, double* __restrict__ out,
+                                              double* __restrict__ dx, int* __restrict__ status) {
     __shared__ double s15[15][16];   // P at the 15 x 15 rows / columns of H
     __shared__ double sYs[9][16];    // Y at those 15 columns
     __shared__ double sM[9][9];      // M, then its Cholesky factor C in the lower triangle
@@ -50,13 +88,14 @@ __global__ __launch_bounds__(256) void k_zupt_cov(const double* __restrict__ P, 
     __shared__ double sT[ZUPT_TILE][ZUPT_TILE + 1];   // the transposed tile of P
     __shared__ int sBad;
     const int tid = threadIdx.x, n = a.n, b = a.b;
+    const int ns = KEEP ? b : n;   // the columns the gate scans and dx covers
     const int J0 = blockIdx.x * ZUPT_TILE, I0 = blockIdx.y * ZUPT_TILE;
     if (tid == 0) sBad = 0;
     __syncthreads();
     {   // the gate's scan: every entry of the 15 rows
         bool bad = false;
-        for (int idx = tid; idx < 15 * n; idx += 256) {
-            const int l = idx / n, j = idx - l * n;
+        for (int idx = tid; idx < 15 * ns; idx += 256) {
+            const int l = idx / ns, j = idx - l * ns;
             bad = bad || !isfinite(P[(size_t)zupt_row(l, b) * n + j]);
         }
         if (tid < 225) s15[tid / 15][tid % 15] = P[(size_t)zupt_row(tid / 15, b) * n + zupt_row(tid % 15, b)];
@@ -104,64 +143,72 @@ __global__ __launch_bounds__(256) void k_zupt_cov(const double* __restrict__ P, 
     __syncthreads();
     const bool refused = sBad != 0 || (a.also && a.also[2] != 0);
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *status = refused ? 1 : 0;
+    const int no = KEEP && !refused ? kp.m : n;        // the dimension of what this launch writes
+    const int hole = KEEP && !refused ? kp.hole : no;  // (a copy has no hole)
+    if (KEEP && (J0 >= no || I0 >= no)) return;        // (uniform: a tile of the input's grid the smaller output does not have)
     if (!refused && tid < 2 * ZUPT_TILE) {   // V = C^-1 Y at the tile's columns (tid < 32) and rows (tid >= 32): ONE code path for both
         const int w = tid / ZUPT_TILE, t = tid - w * ZUPT_TILE;
-        const int col = (w == 0 ? J0 : I0) + t;
+        const int oc = (w == 0 ? J0 : I0) + t;
+        const int col = KEEP ? zupt_src(oc, hole) : oc;
         double v[9];
-        if (col < n) {
-            double p[15];
-            for (int l = 0; l < 15; ++l) p[l] = P[(size_t)zupt_row(l, b) * n + col];
-            zupt_combine(p, v);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-                double x = v[i];
-#pragma unroll
-                for (int k = 0; k < i; ++k) x -= sM[i][k] * v[k];
-                v[i] = x / sM[i][i];
-            }
+        if (oc < no) {
+            zupt_v_col(P, n, b, col, sM, v);
         } else {
 #pragma unroll
             for (int i = 0; i < 9; ++i) v[i] = 0.0;
         }
 #pragma unroll
         for (int i = 0; i < 9; ++i) sV[w][i][t] = v[i];
-        if (w == 0 && blockIdx.y == 0 && col < n) {
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < 9; ++i) s += v[i] * sz[i];
-            dx[col] = s;
-        }
+        if (w == 0 && blockIdx.y == 0 && oc < no) dx[col] = zupt_dx_entry(v, sz);
     }
-    if (refused && blockIdx.y == 0 && tid < ZUPT_TILE && J0 + tid < n) dx[J0 + tid] = 0.0;
+    if (KEEP && !refused && blockIdx.x == 0 && blockIdx.y == 0 && tid >= 2 * ZUPT_TILE && tid < 2 * ZUPT_TILE + 6 && hole < no) {
+        double v[9];   // dx at the dropped clone's six states, which no tile of the output has
+        zupt_v_col(P, n, b, hole + (tid - 2 * ZUPT_TILE), sM, v);
+        dx[hole + (tid - 2 * ZUPT_TILE)] = zupt_dx_entry(v, sz);
+    }
+    if (refused && blockIdx.y == 0 && tid < ZUPT_TILE && J0 + tid < ns) dx[J0 + tid] = 0.0;
     const int tx = tid & (ZUPT_TILE - 1), ty = tid / ZUPT_TILE;   // 32 x 8 lanes over the tile
     for (int rr = ty; rr < ZUPT_TILE; rr += 256 / ZUPT_TILE) {   // sT[rr][tx] = P[J0 + rr][I0 + tx]
         const int i = J0 + rr, j = I0 + tx;
-        sT[rr][tx] = (i < n && j < n) ? P[(size_t)i * n + j] : 0.0;
+        sT[rr][tx] = (i < no && j < no) ? P[(size_t)(KEEP ? zupt_src(i, hole) : i) * n + (KEEP ? zupt_src(j, hole) : j)] : 0.0;
     }
     __syncthreads();
     const int keep = n - a.nui6;
     for (int rr = ty; rr < ZUPT_TILE; rr += 256 / ZUPT_TILE) {
         const int i = I0 + rr, j = J0 + tx;
-        if (i >= n || j >= n) continue;
-        const double pij = P[(size_t)i * n + j], pji = sT[tx][rr];
+        if (i >= no || j >= no) continue;
+        const double pij = P[(size_t)(KEEP ? zupt_src(i, hole) : i) * n + (KEEP ? zupt_src(j, hole) : j)], pji = sT[tx][rr];
         double v;
         if (refused) v = pij;
         else {
             v = 0.5 * (pij + pji);
-            if (!(i >= keep && j >= keep)) {
+            if (KEEP || !(i >= keep && j >= keep)) {   // (KEEP: no nuisance states, the calls refuse them)
                 double s = 0.0;
 #pragma unroll
                 for (int k = 0; k < 9; ++k) s = fma(sV[1][k][rr], sV[0][k][tx], s);
                 v -= s;
             }
         }
-        out[(size_t)i * n + j] = v;
+        out[(size_t)i * no + j] = v;
     }
 }
 
-// S(state i, column c) = F[c * ld + i], c < k.  out has the same shape and leading dimension.
-__global__ __launch_bounds__(256) void k_zupt_fac(const double* __restrict__ F, int ld, int k, ZuptArgs a, const int* __restrict__ status,
-                                                  double* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_zupt_cov(const double* __restrict__ P, ZuptArgs a, double* __restrict__ out, double* __restrict__ dx,
+                                                  int* __restrict__ status) {
+    zupt_cov_body<false>(P, a, ZuptKeep{a.n, a.n}, out, dx, status);
+}
+// the update that writes what stays: grid ceil(n / 32)^2 (the refused form copies [n][n])
+__global__ __launch_bounds__(256) void k_zupt_cov_keep(const double* __restrict__ P, ZuptArgs a, ZuptKeep kp, double* __restrict__ out,
+                                                       double* __restrict__ dx, int* __restrict__ status) {
+    zupt_cov_body<true>(P, a, kp, out, dx, status);
+}
+
+// S(state i, column c) = F[c * ld + i], c < k.  KEEP = false (k_zupt_fac): out has the same shape and leading dimension.  KEEP = true:
+// applied, row i of S+ goes to its kept position with leading dimension ld_out, the rows >= b and the dropped clone's are not written;
+// refused, the bit copy at ld.  ONE body for both.
+template <bool KEEP>
+__device__ __forceinline__ void zupt_fac_body(const double* __restrict__ F, int ld, int k, const ZuptArgs& a, const ZuptKeep kp, int ld_out,
+                                              const int* __restrict__ status, double* __restrict__ out) {
     __shared__ double sW[9][ZUPT_KMAX];   // W = H S, row j becoming reflector j's part over the columns of S
     __shared__ double sRed[2][4][9];
     __shared__ double sG[9][9];           // sG[j][i] = w~_j . w~_i (i < j)
@@ -219,10 +266,12 @@ __global__ __launch_bounds__(256) void k_zupt_fac(const double* __restrict__ F, 
     }
     __syncthreads();
     // the reflectors on row [0_9 | S_i]: z = W~ s;  t_j = beta_j (z_j - sum_{m<j} G_jm t_m);  s+ = s - sum_j t_j w~_j
+    const bool mine = KEEP ? (i < b && !(i >= kp.hole && i < kp.hole + 6)) : i < n;   // this lane's row is written
+    const int io = KEEP && i >= kp.hole ? i - 6 : i;
     double z[9];
 #pragma unroll
     for (int m = 0; m < 9; ++m) z[m] = 0.0;
-    if (i < n)
+    if (mine)
         for (int c = wv; c < k; c += 4) {
             const double s = F[(size_t)c * ld + i];
 #pragma unroll
@@ -239,13 +288,23 @@ __global__ __launch_bounds__(256) void k_zupt_fac(const double* __restrict__ F, 
         for (int m = 0; m < j; ++m) v -= sG[j][m] * t[m];
         t[j] = sBeta[j] * v;
     }
-    if (i < n)
+    if (mine)
         for (int c = wv; c < k; c += 4) {
             double s = F[(size_t)c * ld + i];
 #pragma unroll
             for (int j = 0; j < 9; ++j) s -= t[j] * sW[j][c];
-            out[(size_t)c * ld + i] = s;
+            out[(size_t)c * ld_out + io] = s;
         }
+}
+
+__global__ __launch_bounds__(256) void k_zupt_fac(const double* __restrict__ F, int ld, int k, ZuptArgs a, const int* __restrict__ status,
+                                                  double* __restrict__ out) {
+    zupt_fac_body<false>(F, ld, k, a, ZuptKeep{a.n, a.n}, ld, status, out);
+}
+// grid ceil(n / 64) (the refused form copies every row)
+__global__ __launch_bounds__(256) void k_zupt_fac_keep(const double* __restrict__ F, int ld, int k, ZuptArgs a, ZuptKeep kp, int ld_out,
+                                                       const int* __restrict__ status, double* __restrict__ out) {
+    zupt_fac_body<true>(F, ld, k, a, kp, ld_out, status, out);
 }
 
 }  // namespace orcvio_amd
