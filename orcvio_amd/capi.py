@@ -1653,39 +1653,52 @@ class MsckfUpdater:
         z.noise_v, z.noise_p, z.noise_q = (float(x) for x in noises)
         return z
 
+    def _zupt_hybrid_struct(self, leg_dim, n_clones, r, noises, idp_dim, n_feature_states, Phi, Q, augment, remove_previous, keep):
+        f = ZuptFrameHybrid()
+        f.frame.zupt = self._zupt_struct(leg_dim, n_clones, r, noises)
+        if Phi is not None:
+            keep.append(np.ascontiguousarray(Phi, dtype=np.float64)); f.frame.Phi = _d(keep[-1])
+        if Q is not None:
+            keep.append(np.ascontiguousarray(Q, dtype=np.float64)); f.frame.Q = _d(keep[-1])
+        f.frame.augment, f.frame.remove_previous = int(bool(augment)), int(bool(remove_previous))
+        f.idp_dim, f.n_feature_states = int(idp_dim), int(n_feature_states)
+        return f
+
+    def _zupt_call(self, name, leg_dim, n_clones, r, noises, raise_on_refusal, frame=None, hybrid=None, chk=None):
+        """The marshalling of the five zero-velocity calls.  frame: (Phi, Q, augment, remove_previous), None for cov_zupt; hybrid:
+        (idp_dim, n_feature_states); chk: the check's constants.  Returns the result dict, with the verdict's dict where there is a check."""
+        keep = []   # Phi / Q stay alive across the call
+        f = self._zupt_hybrid_struct(leg_dim, n_clones, r, noises, *(hybrid or (0, 0)), *(frame or (None, None, False, False)), keep)
+        if hybrid is None:   # the struct nests the frame's, which nests the update's
+            f = f.frame if frame is not None else f.frame.zupt
+        if hybrid is not None:   # the features have left in front of K r
+            nu = int(leg_dim) + 6 * int(n_clones)
+        else:
+            n = C.c_int32(0)
+            self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), None), 'orcvio_msckf_cov_get')
+            nu = n.value + (6 if frame is not None and frame[2] else 0)
+        dx = np.zeros(max(nu, 1))
+        applied, n_after, out = C.c_int32(-1), C.c_int32(-1), ZuptVerdict()
+        args = [self.h, C.byref(f)] + ([C.byref(chk)] if chk is not None else []) + [_d(dx), C.byref(applied)] + \
+            ([C.byref(n_after)] if frame is not None else []) + ([C.byref(out)] if chk is not None else [])
+        rc = getattr(self.lib, name)(*args)
+        if rc != 0 and (raise_on_refusal or rc != 6):
+            raise MsckfError(rc, name)
+        res = dict(dx=dx[:nu], applied=int(applied.value))
+        if frame is not None:
+            res['n_after'] = int(n_after.value)
+        res['rc'] = rc
+        return (res, self._verdict(out, rc)) if chk is not None else res
+
     def cov_zupt(self, leg_dim, n_clones, r, noises, raise_on_refusal=True):
         """orcvio_msckf_cov_zupt: measurementUpdate_ZUPT_vpq on the resident covariance (its factor kept).  r [9]; noises: the three
         VARIANCES (v, p, q).  Returns dict(dx [n], applied, rc)."""
-        z = self._zupt_struct(leg_dim, n_clones, r, noises)
-        n = C.c_int32(0)
-        self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), None), 'orcvio_msckf_cov_get')
-        dx = np.zeros(max(n.value, 1))
-        applied = C.c_int32(-1)
-        rc = self.lib.orcvio_msckf_cov_zupt(self.h, C.byref(z), _d(dx), C.byref(applied))
-        if rc != 0 and (raise_on_refusal or rc != 6):
-            raise MsckfError(rc, 'orcvio_msckf_cov_zupt')
-        return dict(dx=dx[:n.value], applied=int(applied.value), rc=rc)
+        return self._zupt_call('orcvio_msckf_cov_zupt', leg_dim, n_clones, r, noises, raise_on_refusal)
 
     def cov_zupt_frame(self, leg_dim, n_clones, r, noises, Phi=None, Q=None, augment=True, remove_previous=True, raise_on_refusal=True):
         """orcvio_msckf_cov_zupt_frame: one stationary frame in one call (propagate, augment, the zero-velocity update, the previous
         clone marginalised).  n_clones: the window AFTER the augmentation.  Returns dict(dx, applied, n_after, rc)."""
-        f = ZuptFrame()
-        f.zupt = self._zupt_struct(leg_dim, n_clones, r, noises)
-        keep = []
-        if Phi is not None:
-            keep.append(np.ascontiguousarray(Phi, dtype=np.float64)); f.Phi = _d(keep[-1])
-        if Q is not None:
-            keep.append(np.ascontiguousarray(Q, dtype=np.float64)); f.Q = _d(keep[-1])
-        f.augment, f.remove_previous = int(bool(augment)), int(bool(remove_previous))
-        n = C.c_int32(0)
-        self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), None), 'orcvio_msckf_cov_get')
-        nu = n.value + (6 if augment else 0)
-        dx = np.zeros(max(nu, 1))
-        applied, n_after = C.c_int32(-1), C.c_int32(-1)
-        rc = self.lib.orcvio_msckf_cov_zupt_frame(self.h, C.byref(f), _d(dx), C.byref(applied), C.byref(n_after))
-        if rc != 0 and (raise_on_refusal or rc != 6):
-            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame')
-        return dict(dx=dx[:nu], applied=int(applied.value), n_after=int(n_after.value), rc=rc)
+        return self._zupt_call('orcvio_msckf_cov_zupt_frame', leg_dim, n_clones, r, noises, raise_on_refusal, (Phi, Q, augment, remove_previous))
 
     @staticmethod
     def zupt_check(use_left=0, **over):
@@ -1735,57 +1748,22 @@ class MsckfUpdater:
     def cov_zupt_frame_checked(self, chk, leg_dim, n_clones, r, noises, augment=True, remove_previous=True, raise_on_refusal=True):
         """orcvio_msckf_cov_zupt_frame_checked: the stationary frame on a handle armed by io_propagate_imu, the zero-velocity check in
         front of its update, one wait.  Returns (dict(dx, applied, n_after, rc), the dict of cov_zupt_check_imu)."""
-        f = ZuptFrame()
-        f.zupt = self._zupt_struct(leg_dim, n_clones, r, noises)
-        f.augment, f.remove_previous = int(bool(augment)), int(bool(remove_previous))
-        n = C.c_int32(0)
-        self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), None), 'orcvio_msckf_cov_get')
-        nu = n.value + (6 if augment else 0)
-        dx = np.zeros(max(nu, 1))
-        applied, n_after = C.c_int32(-1), C.c_int32(-1)
-        out = ZuptVerdict()
-        rc = self.lib.orcvio_msckf_cov_zupt_frame_checked(self.h, C.byref(f), C.byref(chk), _d(dx), C.byref(applied), C.byref(n_after), C.byref(out))
-        if rc != 0 and (raise_on_refusal or rc != 6):
-            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame_checked')
-        return dict(dx=dx[:nu], applied=int(applied.value), n_after=int(n_after.value), rc=rc), self._verdict(out, rc)
-
-    def _zupt_hybrid_struct(self, leg_dim, n_clones, r, noises, idp_dim, n_feature_states, Phi, Q, augment, remove_previous, keep):
-        f = ZuptFrameHybrid()
-        f.frame.zupt = self._zupt_struct(leg_dim, n_clones, r, noises)
-        if Phi is not None:
-            keep.append(np.ascontiguousarray(Phi, dtype=np.float64)); f.frame.Phi = _d(keep[-1])
-        if Q is not None:
-            keep.append(np.ascontiguousarray(Q, dtype=np.float64)); f.frame.Q = _d(keep[-1])
-        f.frame.augment, f.frame.remove_previous = int(bool(augment)), int(bool(remove_previous))
-        f.idp_dim, f.n_feature_states = int(idp_dim), int(n_feature_states)
-        return f
+        return self._zupt_call('orcvio_msckf_cov_zupt_frame_checked', leg_dim, n_clones, r, noises, raise_on_refusal,
+                               (None, None, augment, remove_previous), chk=chk)
 
     def cov_zupt_frame_hybrid(self, leg_dim, n_clones, r, noises, idp_dim, n_feature_states, Phi=None, Q=None, augment=True,
                               remove_previous=True, raise_on_refusal=True):
         """orcvio_msckf_cov_zupt_frame_hybrid: one stationary frame of a hybrid filter in one call -- every in-state feature leaves in
         front of the update, the previous clone behind it, one fused launch.  Returns dict(dx [leg + 6 n_clones], applied, n_after, rc)."""
-        keep = []
-        f = self._zupt_hybrid_struct(leg_dim, n_clones, r, noises, idp_dim, n_feature_states, Phi, Q, augment, remove_previous, keep)
-        b = max(int(leg_dim) + 6 * int(n_clones), 1)
-        dx = np.zeros(b)
-        applied, n_after = C.c_int32(-1), C.c_int32(-1)
-        rc = self.lib.orcvio_msckf_cov_zupt_frame_hybrid(self.h, C.byref(f), _d(dx), C.byref(applied), C.byref(n_after))
-        if rc != 0 and (raise_on_refusal or rc != 6):
-            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame_hybrid')
-        return dict(dx=dx, applied=int(applied.value), n_after=int(n_after.value), rc=rc)
+        return self._zupt_call('orcvio_msckf_cov_zupt_frame_hybrid', leg_dim, n_clones, r, noises, raise_on_refusal,
+                               (Phi, Q, augment, remove_previous), (idp_dim, n_feature_states))
 
     def cov_zupt_frame_checked_hybrid(self, chk, leg_dim, n_clones, r, noises, idp_dim, n_feature_states, augment=True, remove_previous=True,
                                       raise_on_refusal=True):
         """orcvio_msckf_cov_zupt_frame_checked_hybrid: the hybrid stationary frame on a handle armed by io_propagate_imu, the
         zero-velocity check in front of its fused update, one wait.  Returns (dict(dx, applied, n_after, rc), the verdict's dict)."""
-        f = self._zupt_hybrid_struct(leg_dim, n_clones, r, noises, idp_dim, n_feature_states, None, None, augment, remove_previous, [])
-        dx = np.zeros(max(int(leg_dim) + 6 * int(n_clones), 1))
-        applied, n_after = C.c_int32(-1), C.c_int32(-1)
-        out = ZuptVerdict()
-        rc = self.lib.orcvio_msckf_cov_zupt_frame_checked_hybrid(self.h, C.byref(f), C.byref(chk), _d(dx), C.byref(applied), C.byref(n_after), C.byref(out))
-        if rc != 0 and (raise_on_refusal or rc != 6):
-            raise MsckfError(rc, 'orcvio_msckf_cov_zupt_frame_checked_hybrid')
-        return dict(dx=dx, applied=int(applied.value), n_after=int(n_after.value), rc=rc), self._verdict(out, rc)
+        return self._zupt_call('orcvio_msckf_cov_zupt_frame_checked_hybrid', leg_dim, n_clones, r, noises, raise_on_refusal,
+                               (None, None, augment, remove_previous), (idp_dim, n_feature_states), chk)
 
     def set_object_dof_rank(self, on: bool):
         """ORCVIO_OPT_OBJECT_DOF: 1 = the object gate counts rows - rank(H_f) degrees of freedom (default rows - columns)."""

@@ -1,7 +1,8 @@
 // capi_zupt_check.inc -- part of msckf_capi.hip (ONE translation unit: included there, in this order; not compiled on its own).
 // Zero-velocity DETECTION from IMU samples on the resident covariance (checkZUPTIMU, src/orcvio.cpp:3129-3323): the packing and the
-// validation of host/zupt_check_model.hpp, k_zupt_check (zupt_check_ops.hpp), and its three call sites -- stand-alone, behind the
-// propagation from raw samples, and inside the stationary frame in front of the update it decides on.
+// validation of host/zupt_check_model.hpp, k_zupt_check (zupt_check_ops.hpp), its verdict, and two of its three call sites -- stand-alone
+// and behind the propagation from raw samples.  The third, inside the stationary frame in front of the update it decides on, is
+// capi_zupt.inc's (zupt_frame_run), which follows in the translation unit and uses the zchk_* helpers here.
 
 void orcvio_msckf_zupt_check_default(orcvio_msckf_zupt_check* c) {
     if (!c) return;
@@ -114,91 +115,4 @@ int32_t orcvio_msckf_cov_propagate_imu_checked(orcvio_msckf_handle* h, const orc
     if (h && (h->comm || h->ipc)) { g_last_error = "cov_propagate_imu_checked: not with a communicator on the handle"; return ORCVIO_ERR_INVALID; }
     { const int rc = zchk_constants(chk, "cov_propagate_imu_checked"); if (rc != ORCVIO_OK) return rc; }
     return imu_propagate_call(h, cfg, state, prev_meas, samples, n_samples, time_bound, info, Phi_out, Q_out, chk, verdict, "cov_propagate_imu_checked");
-}
-
-// The checked stationary frame, both forms.  hy == nullptr: cov_zupt_frame_checked (the update on every state, the marginalisation
-// enqueued behind the wait).  hy != nullptr: cov_zupt_frame_checked_hybrid (the fused update writes what stays: nothing behind the wait).
-static int zupt_frame_checked(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame* f, const orcvio_msckf_zupt_frame_hybrid* hy,
-                              const orcvio_msckf_zupt_check* chk, double* dx, int32_t* applied, int32_t* n_after,
-                              orcvio_msckf_zupt_verdict* verdict, const std::string& who) {
-    if (!h || !f || !chk || !dx || !applied || !n_after || !verdict) { g_last_error = who + ": null argument"; return ORCVIO_ERR_INVALID; }
-    zchk_verdict_clear(verdict);
-    const orcvio_msckf_zupt* z = &f->zupt;
-    if (!h->imu_armed) { g_last_error = who + ": the handle is not armed by orcvio_msckf_io_propagate_imu (whose samples the check reads)"; return ORCVIO_ERR_INVALID; }
-    if (f->Phi || f->Q) { g_last_error = who + ": Phi and Q must be NULL (they come from the armed IMU propagation)"; return ORCVIO_ERR_INVALID; }
-    if (z->leg_dim != 22) { g_last_error = who + ": leg_dim must be 22"; return ORCVIO_ERR_INVALID; }
-    const int n = h->res_n + (f->augment ? 6 : 0);   // what the update sees
-    { const int rv = hy ? zupt_hybrid_validate(h, hy, n, who.c_str()) : zupt_validate(h, z, n, who.c_str()); if (rv != ORCVIO_OK) return rv; }
-    const int n_dx = hy ? z->leg_dim + 6 * z->n_clones : n;   // (the hybrid form: the features have left in front of K r)
-    if (f->augment && h->n_extra > h->res_n - 15) { g_last_error = who + ": more extra states than the resident covariance has"; return ORCVIO_ERR_INVALID; }
-    const int S = h->imu_S;
-    ZchkJob j;
-    const bool check = S >= 2;   // (one selected sample: :3134, nothing to test with -- the frame is not a zero-velocity one)
-    if (check) {
-        const int rc = zchk_prepare(chk, h->imu_after.R, h->imu_after.v, h->imu_after.ba, h->imu_cfg.gravity, h->imu_sel.data(), S, who.c_str(), &j);
-        if (rc != ORCVIO_OK) return rc;
-    } else {
-        const int rc = zchk_constants(chk, who.c_str());
-        if (rc != ORCVIO_OK) return rc;
-    }
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    // nothing can refuse the frame any more: the arming is taken
-    int rc = imu_consume(h, s);
-    if (rc == ORCVIO_OK) rc = launch_cov_propagate(h, s, h->propagate(), 22, imu_dphi(h), imu_dq(h), imu_status(h));
-    if (rc == ORCVIO_OK && f->augment) rc = orcvio_msckf_cov_augment(h);
-    if (rc != ORCVIO_OK) return rc;
-    *n_after = h->res_n;
-    *applied = 0;
-    if (!check) {   // no verdict, no update: propagation and augmentation stand, one wait for the propagation's own refusal
-        for (int i = 0; i < n_dx; ++i) dx[i] = 0.0;
-        int refused = 0;
-        const FetchCopy fc[] = {{&refused, imu_status(h), sizeof(int)}};
-        rc = fetch_copies(h, s, fc, 1);
-        if (rc != ORCVIO_OK) return rc;
-        if (refused) { g_last_error = who + ": Phi or Q of the armed IMU propagation not finite: no propagation"; return ORCVIO_ERR_NOT_SPD; }
-        return ORCVIO_OK;
-    }
-    rc = zchk_enqueue(h, s, j, imu_status(h));   // (the check's status block carries the propagation's refusal on: the update reads one block)
-    if (rc != ORCVIO_OK) return rc;
-    const CovState before = cov_state(h);
-    CovEdit kept;
-    rc = hy ? zupt_keep_enqueue(h, z, f->remove_previous != 0, zchk_status(h), &kept) : zupt_enqueue(h, z, zchk_status(h));
-    if (rc != ORCVIO_OK) { cov_restore(h, before); return rc; }
-    double out[4] = {0, 0, 0, 0};
-    int st[4] = {0, 0, 0, 0}, upd = 0;
-    const FetchCopy fc[] = {{dx, zupt_dx(h), sizeof(double) * (size_t)n_dx}, {&upd, zupt_status(h), sizeof(int)}, {out, zchk_out(h), sizeof(out)}, {st, zchk_status(h), sizeof(st)}};
-    rc = fetch_copies(h, s, fc, 4);
-    if (rc != ORCVIO_OK) {   // the outcome is unknown, but the update's launches wrote the spare buffers only: the propagated, augmented prior stands
-        cov_restore(h, before);
-        if (!hy) h->fac_valid = false;   // (the hybrid form, as cov_zupt: the prior's factor stands with it)
-        return rc;
-    }
-    const int rv = zchk_verdict(j, out, st[2], who.c_str(), verdict);
-    if (upd != 0) {   // rejected by the check, or refused: the spare buffers took bit copies of the prior and of its factor
-        if (!hy) h->zupt_refused(before.fac_tail);   // (the hybrid form has changed no role: every feature is in place)
-        if (rv != ORCVIO_OK) return rv;
-        if (!verdict->accept) return ORCVIO_OK;   // the check's decision: not an error, the caller goes on with the moving frame
-        g_last_error = who + ": H P H^T + R not positive definite, or a non-finite covariance: the update was not applied";
-        return ORCVIO_ERR_NOT_SPD;
-    }
-    *applied = 1;
-    if (hy) h->zupt_keep_done(kept, true);
-    if (!hy && f->remove_previous) {   // behind the wait, and only now that the update is known to be applied: enqueued, not waited for
-        const int32_t prev = z->n_clones - 2;
-        rc = orcvio_msckf_cov_remove_clones(h, z->leg_dim, &prev, 1);
-        if (rc != ORCVIO_OK) return rc;
-    }
-    *n_after = h->res_n;
-    return ORCVIO_OK;
-}
-
-int32_t orcvio_msckf_cov_zupt_frame_checked(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame* f, const orcvio_msckf_zupt_check* chk,
-                                            double* dx, int32_t* applied, int32_t* n_after, orcvio_msckf_zupt_verdict* verdict) {
-    return zupt_frame_checked(h, f, nullptr, chk, dx, applied, n_after, verdict, "cov_zupt_frame_checked");
-}
-
-int32_t orcvio_msckf_cov_zupt_frame_checked_hybrid(orcvio_msckf_handle* h, const orcvio_msckf_zupt_frame_hybrid* hy, const orcvio_msckf_zupt_check* chk,
-                                                   double* dx, int32_t* applied, int32_t* n_after, orcvio_msckf_zupt_verdict* verdict) {
-    return zupt_frame_checked(h, hy ? &hy->frame : nullptr, hy, chk, dx, applied, n_after, verdict, "cov_zupt_frame_checked_hybrid");
 }

@@ -1396,11 +1396,7 @@ class MsckfBackend {
                              bool use_schmidt = false) {
         UpdateOutcome out;
         orcvio_msckf_zupt z{};
-        z.leg_dim = flags.leg_dim; z.n_clones = (int32_t)ss.imu_states_augment.size();
-        z.noise_v = noise_v; z.noise_p = noise_p; z.noise_q = noise_q;
-        if (z.n_clones < 2) { out.status = ORCVIO_ERR_INVALID; return out; }
-        const std::vector<double> r = zuptResidual(ss);
-        std::memcpy(z.r, r.data(), sizeof(z.r));
+        if (!fillZupt(ss, noise_v, noise_p, noise_q, z)) { out.status = ORCVIO_ERR_INVALID; return out; }
         int32_t n = 0;
         out.status = orcvio_msckf_cov_get(h_, &n, nullptr);
         if (out.status != ORCVIO_OK) return out;
@@ -1814,6 +1810,16 @@ class MsckfBackend {
     orcvio_msckf_handle* handle() { return h_; }
 
   private:
+    // orcvio_msckf_zupt from the state server: the window, the VARIANCES, the residual.  false: the update needs the two newest clones
+    bool fillZupt(const StateServer& ss, double noise_v, double noise_p, double noise_q, orcvio_msckf_zupt& z) const {
+        z.leg_dim = flags.leg_dim; z.n_clones = (int32_t)ss.imu_states_augment.size();
+        z.noise_v = noise_v; z.noise_p = noise_p; z.noise_q = noise_q;
+        if (z.n_clones < 2) return false;
+        const std::vector<double> r = zuptResidual(ss);
+        std::memcpy(z.r, r.data(), sizeof(z.r));
+        return true;
+    }
+
     // the two forms of the hybrid stationary frame (zuptFrame, zuptFrameChecked): chk == nullptr is the unchecked call
     UpdateOutcome zuptFrameCall(StateServer& ss, MapServer& map_server, double noise_v, double noise_p, double noise_q, const double* Phi,
                                 const double* Q, bool augment, bool remove_previous, int idp_dim, const orcvio_msckf_zupt_check* chk,
@@ -1821,11 +1827,7 @@ class MsckfBackend {
         UpdateOutcome out;
         orcvio_msckf_zupt_frame_hybrid f{};
         orcvio_msckf_zupt& z = f.frame.zupt;
-        z.leg_dim = flags.leg_dim; z.n_clones = (int32_t)ss.imu_states_augment.size();
-        z.noise_v = noise_v; z.noise_p = noise_p; z.noise_q = noise_q;
-        if (z.n_clones < 2) { out.status = ORCVIO_ERR_INVALID; return out; }
-        const std::vector<double> r = zuptResidual(ss);
-        std::memcpy(z.r, r.data(), sizeof(z.r));
+        if (!fillZupt(ss, noise_v, noise_p, noise_q, z)) { out.status = ORCVIO_ERR_INVALID; return out; }
         f.frame.Phi = Phi; f.frame.Q = Q; f.frame.augment = augment ? 1 : 0; f.frame.remove_previous = remove_previous ? 1 : 0;
         f.idp_dim = idp_dim; f.n_feature_states = (int32_t)ss.feature_states.size();
         out.delta_x.assign((size_t)(z.leg_dim + 6 * z.n_clones), 0.0);

@@ -36,6 +36,7 @@
 #include "host/cov_book.hpp"
 #include "host/frame_outcome.hpp"
 #include "host/object_stage.hpp"
+#include "host/zupt_frame_outcome.hpp"
 #include <immintrin.h>
 #include <condition_variable>
 #include <memory>
@@ -508,8 +509,8 @@ const char* orcvio_msckf_last_error(void) { return g_last_error.c_str(); }
 #include "capi_object_mapper.inc"   // the object mapper: the start and the Levenberg-Marquardt refinement of object tracks, with keypoints and bbox-only
 #include "capi_imu.inc"   // IMU propagation from raw samples: the host half (host/imu_model.hpp), k_imu_phi_q, the propagation behind it
 #include "capi_imu_calib.inc"   // ... at leg_dim 46 (IMU intrinsics in the state): the imu_*46 host half, k_imu_phi_q46
-#include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: the 9-row update, the factor kept, the one-call stationary frame
-#include "capi_zupt_check.inc"   // zero-velocity detection from IMU samples: k_zupt_check stand-alone, behind the IMU propagation, inside the stationary frame
+#include "capi_zupt_check.inc"   // zero-velocity detection from IMU samples: k_zupt_check's packing, launch and verdict; stand-alone and behind the IMU propagation
+#include "capi_zupt.inc"   // zero-velocity frames on the resident covariance: ONE driver for the update and the four stationary frames (unchecked / checked, hybrid)
 #include "capi_frame.inc"   // one frame in one call: feature update + object update, the objects' compression beside the features' solve
 #include "capi_clone_choice.inc"   // the check of the clones that leave inside the one-call frame: arming, k_clone_choice's launch, its result
 #include "capi_step.inc"   // one FILTER frame in one call: propagate, augment, update, prune update, marginalise on the resident covariance
