@@ -1152,6 +1152,36 @@ int32_t orcvio_msckf_cov_augment(orcvio_msckf_handle* h);
 int32_t orcvio_msckf_cov_remove_clones(orcvio_msckf_handle* h, int32_t leg_dim, const int32_t* clone_indices, int32_t count);
 int32_t orcvio_msckf_cov_commit(orcvio_msckf_handle* h);
 int32_t orcvio_msckf_cov_prefactor(orcvio_msckf_handle* h);
+/* Marginals of the resident covariance without fetching all of P: the per-image readers of state_cov (getPpose / getPvel behind the
+ * odometry message, src/orcvio.cpp:2999-3026) want a few dozen numbers, cov_get moves n^2 doubles behind a drained stream.
+ *   out = P[idx, idx]                 (m == 0)   [n_idx][n_idx], bit copies
+ *   out = T P[idx, idx] T^T           (m >= 1)   [m][m]
+ * with P indexed as cov_get returns it (row-major, P_m[i][j] = P[idx[i]][idx[j]]).  Nothing is symmetrised and no entry of P is
+ * examined: a NaN at a gathered entry passes through, one elsewhere has no effect.  ONE launch of one workgroup (k_cov_marginal, FP64)
+ * on the handle's stream, where cov_get's copy would go: it sees whatever the last cov_* call, commit or frame call left -- a frame
+ * call's marginalisation that is enqueued and not waited for included -- and changes nothing resident (P, the factor, their
+ * bookkeeping, the armings and the open arena stay as they are).  Every sum runs over l = 0 .. n_idx-1 in ascending order as one FMA
+ * chain: the same input twice gives the same bits, and |out - exact| <= (2 n_idx + 4) 2^-53 (|T| |P_m| |T|^T) componentwise.
+ *   cov_marginal_submit    validates, stages T (no synchronisation) and enqueues the launch, which stores its result into a pinned
+ *                          block of the handle and a sequence word behind it.  At most ONE submit is outstanding per handle; other
+ *                          calls on the handle are legal before the collect (the kernel reads P at its own place in stream order).
+ *   cov_marginal_collect   waits for that word as the io_* calls wait for theirs -- a bounded spin (ORCVIO_IO_SPIN_SECONDS), then a
+ *                          stream synchronisation, then ORCVIO_ERR_TIMEOUT -- and copies the block to out; *rows = m, or n_idx for a
+ *                          gather.  No copy by the runtime, no pageable memory on the device's side.
+ *   cov_get_marginal       submit followed by collect.
+ * Refused with ORCVIO_ERR_INVALID before anything is enqueued (nothing changed, a later good call succeeds): a NULL argument, no
+ * resident covariance, n_idx outside 1..64, an index outside [0, n), m outside 0..64, T NULL with m > 0 or given with m == 0, a
+ * non-finite entry of T, a second submit before the collect, a collect without a submit, a communicator on the handle. */
+#define ORCVIO_MARGINAL_MAX 64
+typedef struct orcvio_msckf_marginal {
+    int32_t n_idx;        /* 1..64 */
+    const int32_t* idx;   /* [n_idx] state indices of the resident covariance; any order, repeats allowed */
+    int32_t m;            /* 0: out = P[idx, idx], [n_idx][n_idx];  1..64: out = T P[idx, idx] T^T, [m][m] */
+    const double* T;      /* [m][n_idx] row-major; NULL exactly when m == 0 */
+} orcvio_msckf_marginal;
+int32_t orcvio_msckf_cov_get_marginal(orcvio_msckf_handle* h, const orcvio_msckf_marginal* marginal, double* out);
+int32_t orcvio_msckf_cov_marginal_submit(orcvio_msckf_handle* h, const orcvio_msckf_marginal* marginal);
+int32_t orcvio_msckf_cov_marginal_collect(orcvio_msckf_handle* h, double* out, int32_t* rows /* may be NULL */);
 /* The tail of measurementUpdate_hybrid on the device (src/orcvio.cpp:1818-1821, :1904-1947; with ORCVIO_OPT_SCHMIDT_STATES :1920-1935):
  * after an update that carried entering features (orcvio_msckf_upload_new_features) the resident covariance becomes the augmented
  * one -- P+ with the d k new feature states behind it (in front of the nuisance block) -- computed from H_1, H_2, r_1 still on the

@@ -13,7 +13,7 @@ SOURCES = ['msckf_capi.hip']
 # every file the one translation unit is made of: the C-ABI sections (capi_*.inc), the kernel headers, the HIP-free headers under
 # host/ that it includes (not host/orcvio_msckf_host.hpp: the C++ shim over the C-ABI is no part of the library), the public header
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.hpp', '.inc'))) + \
-    [os.path.join('host', 'clone_choice_model.hpp'), os.path.join('host', 'cov_book.hpp'), os.path.join('host', 'frame_outcome.hpp'), os.path.join('host', 'imu_model.hpp'), os.path.join('host', 'ingest_sym_map.hpp'), os.path.join('host', 'ipc_protocol.hpp'), os.path.join('host', 'object_stage.hpp'), os.path.join('host', 'object_types.hpp'), os.path.join('host', 'zupt_check_model.hpp'), os.path.join('host', 'zupt_frame_outcome.hpp'), os.path.join('..', '..', 'include', 'orcvio_msckf.h')]
+    [os.path.join('host', 'clone_choice_model.hpp'), os.path.join('host', 'cov_book.hpp'), os.path.join('host', 'cov_marginal_spec.hpp'), os.path.join('host', 'frame_outcome.hpp'), os.path.join('host', 'imu_model.hpp'), os.path.join('host', 'ingest_sym_map.hpp'), os.path.join('host', 'ipc_protocol.hpp'), os.path.join('host', 'object_stage.hpp'), os.path.join('host', 'object_types.hpp'), os.path.join('host', 'zupt_check_model.hpp'), os.path.join('host', 'zupt_frame_outcome.hpp'), os.path.join('..', '..', 'include', 'orcvio_msckf.h')]
 
 
 def _stale(lib) -> bool:

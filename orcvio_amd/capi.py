@@ -52,6 +52,7 @@ EXPORTS = [
     'orcvio_msckf_zupt_check_default', 'orcvio_msckf_cov_zupt_check_imu', 'orcvio_msckf_cov_propagate_imu_checked',
     'orcvio_msckf_cov_zupt_frame_checked', 'orcvio_msckf_cov_propagate_imu_calib',
     'orcvio_msckf_cov_zupt_frame_hybrid', 'orcvio_msckf_cov_zupt_frame_checked_hybrid', 'orcvio_msckf_zupt_check_feat',
+    'orcvio_msckf_cov_get_marginal', 'orcvio_msckf_cov_marginal_submit', 'orcvio_msckf_cov_marginal_collect',
 ]
 
 
@@ -229,6 +230,14 @@ class ZuptVerdict(C.Structure):
                 ('chi2_check', C.c_double), ('speed', C.c_double)]
 
 
+class Marginal(C.Structure):
+    """orcvio_msckf_marginal (include/orcvio_msckf.h): out = P[idx, idx] (m == 0) or T P[idx, idx] T^T."""
+    _fields_ = [('n_idx', C.c_int32), ('idx', _ip), ('m', C.c_int32), ('T', _dp)]
+
+
+MARGINAL_MAX = 64
+
+
 class MsckfState(C.Structure):
     _fields_ = [('R_b2w_imu', C.c_double * 9), ('v', C.c_double * 3), ('p', C.c_double * 3), ('bg', C.c_double * 3),
                 ('ba', C.c_double * 3), ('R_b2c', C.c_double * 9), ('t_c_b', C.c_double * 3), ('td', C.c_double),
@@ -301,6 +310,9 @@ def _bind(lib):
     lib.orcvio_msckf_objects_download.argtypes = [C.c_void_p, C.POINTER(MsckfResult)]
     lib.orcvio_msckf_cov_set.argtypes = [C.c_void_p, C.c_int32, _dp]
     lib.orcvio_msckf_cov_get.argtypes = [C.c_void_p, _ip, _dp]
+    lib.orcvio_msckf_cov_get_marginal.argtypes = [C.c_void_p, C.POINTER(Marginal), _dp]
+    lib.orcvio_msckf_cov_marginal_submit.argtypes = [C.c_void_p, C.POINTER(Marginal)]
+    lib.orcvio_msckf_cov_marginal_collect.argtypes = [C.c_void_p, _dp, _ip]
     lib.orcvio_msckf_cov_propagate.argtypes = [C.c_void_p, C.c_int32, _dp, _dp]
     lib.orcvio_msckf_cov_augment.argtypes = [C.c_void_p]
     lib.orcvio_msckf_cov_remove_clones.argtypes = [C.c_void_p, C.c_int32, _ip, C.c_int32]
@@ -1425,6 +1437,44 @@ class MsckfUpdater:
         P = np.zeros((n.value, n.value))
         self._chk(self.lib.orcvio_msckf_cov_get(self.h, C.byref(n), _d(P)), 'orcvio_msckf_cov_get')
         return P
+
+    @staticmethod
+    def _marginal(idx, T):
+        """The orcvio_msckf_marginal of (idx, T) and the arrays it points into (kept alive by the caller)."""
+        ix = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        q = Marginal()
+        q.n_idx = int(ix.size)
+        q.idx = ix.ctypes.data_as(_ip)
+        Tc = None
+        if T is not None:
+            Tc = np.ascontiguousarray(T, dtype=np.float64)
+            if Tc.ndim != 2 or Tc.shape[1] != ix.size:
+                raise ValueError('T must be [m][len(idx)]')
+            q.m = int(Tc.shape[0])
+            q.T = _d(Tc)
+        return q, (ix, Tc)
+
+    def cov_get_marginal(self, idx, T=None):
+        """orcvio_msckf_cov_get_marginal: P[idx, idx] of the resident covariance (T None: bit copies), or T P[idx, idx] T^T, by one
+        one-workgroup launch that stores into pinned memory -- without fetching P."""
+        q, keep = self._marginal(idx, T)
+        r = q.m if q.m > 0 else q.n_idx
+        out = np.zeros((r, r))
+        self._chk(self.lib.orcvio_msckf_cov_get_marginal(self.h, C.byref(q), _d(out)), 'orcvio_msckf_cov_get_marginal')
+        return out
+
+    def cov_marginal_submit(self, idx, T=None):
+        """orcvio_msckf_cov_marginal_submit: validates, stages and enqueues; cov_marginal_collect() brings the result."""
+        q, keep = self._marginal(idx, T)
+        self._chk(self.lib.orcvio_msckf_cov_marginal_submit(self.h, C.byref(q)), 'orcvio_msckf_cov_marginal_submit')
+
+    def cov_marginal_collect(self):
+        """orcvio_msckf_cov_marginal_collect: the result of the outstanding submit, [rows][rows]."""
+        out = np.zeros((MARGINAL_MAX, MARGINAL_MAX))
+        rows = C.c_int32(0)
+        self._chk(self.lib.orcvio_msckf_cov_marginal_collect(self.h, _d(out), C.byref(rows)), 'orcvio_msckf_cov_marginal_collect')
+        r = rows.value
+        return out.ravel()[:r * r].reshape(r, r).copy()
 
     def io_step_frame_ex(self, win, Phi=None, Q=None, augment=True, slam=None, idp_dim=1, prune=None, prune_apply_dx=False, remove=(),
                          n_feature_states=0, lost=(), changes=(), R_b2c=None, t_c_b=None, literal_3d=0, raise_on_refusal=True, triangulate=None,

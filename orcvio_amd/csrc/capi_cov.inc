@@ -159,6 +159,70 @@ int32_t orcvio_msckf_cov_get(orcvio_msckf_handle* h, int32_t* n_out, double* P_o
     return ORCVIO_OK;
 }
 
+// ---- marginals of the resident covariance without fetching all of P (k_cov_marginal, cov_marginal_ops.hpp) ------------------------
+// The launch goes onto the handle's stream where cov_get's copy would go: it sees what the last cov_* call, commit or frame call left
+// (a frame call's marginalisation that is enqueued and not waited for included) and changes nothing resident -- not P, not the
+// factor, not the bookkeeping, no arming, not the open arena.  Everything is validated before anything is enqueued
+// (host/cov_marginal_spec.hpp).
+int32_t orcvio_msckf_cov_marginal_submit(orcvio_msckf_handle* h, const orcvio_msckf_marginal* q) {
+    const char* who = "cov_marginal_submit: ";
+    if (!h || !q) { g_last_error = std::string(who) + "null argument"; return ORCVIO_ERR_INVALID; }
+    if (h->comm || h->ipc) { g_last_error = std::string(who) + "not with a communicator on the handle"; return ORCVIO_ERR_INVALID; }
+    if (h->marg_submitted) { g_last_error = std::string(who) + "the previous submit has not been collected"; return ORCVIO_ERR_INVALID; }
+    if (const char* why = marginal_refusal(q->n_idx, q->idx, q->m, q->T, h->res_n)) { g_last_error = std::string(who) + why; return ORCVIO_ERR_INVALID; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const int k = q->n_idx, m = q->m;
+    if (m > 0) {   // T is caller memory: through the pinned bounce buffer, nothing to wait for
+        const AuxCopy cp[] = {{h->d_margT, q->T, sizeof(double) * (size_t)m * k}};
+        const int rc = aux_copies(h, s, cp, 1);
+        if (rc != ORCVIO_OK) return rc;
+    }
+    CovMarginalArgs a{};
+    a.P = h->d_Pres; a.n = h->res_n; a.k = k; a.m = m; a.T = h->d_margT;
+    a.out = reinterpret_cast<double*>(h->h_marg_dev);
+    a.out_seq = reinterpret_cast<unsigned long long*>(h->h_marg_dev + MARG_SEQ_OFFSET); a.seq = h->marg_seq + 1;
+    for (int i = 0; i < k; ++i) a.idx.v[i] = q->idx[i];
+    hipLaunchKernelGGL(k_cov_marginal, dim3(1), dim3(COV_MARGINAL_THREADS), m > 0 ? cov_marginal_lds_bytes(k, m) : 0, s, a);
+    HIPCHK(hipGetLastError());
+    h->marg_seq = a.seq;
+    h->marg_submitted = true;
+    h->marg_rows = m > 0 ? m : k;
+    return ORCVIO_OK;
+}
+
+// The wait of io_wait on the block's own word: a bounded spin, then a stream synchronisation, then ORCVIO_ERR_TIMEOUT.  No copy by the
+// runtime and no pageable memory on the way: the kernel stored into the pinned block, the host copies out of it.
+int32_t orcvio_msckf_cov_marginal_collect(orcvio_msckf_handle* h, double* out, int32_t* rows) {
+    const char* who = "cov_marginal_collect: ";
+    if (!h || !out) { g_last_error = std::string(who) + "null argument"; return ORCVIO_ERR_INVALID; }
+    if (!h->marg_submitted) { g_last_error = std::string(who) + "nothing has been submitted"; return ORCVIO_ERR_INVALID; }
+    const unsigned long long* seq = reinterpret_cast<const unsigned long long*>(h->h_marg + MARG_SEQ_OFFSET);
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (__atomic_load_n(seq, __ATOMIC_ACQUIRE) < h->marg_seq) {
+        _mm_pause();
+        if ((++spins & 4095u) == 0 &&
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > h->io_spin_seconds) break;
+    }
+    h->marg_submitted = false;   // (whatever comes of it: the request is spent)
+    if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) < h->marg_seq) {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) < h->marg_seq) { g_last_error = std::string(who) + "the result was not published"; return ORCVIO_ERR_TIMEOUT; }
+    }
+    const int r = h->marg_rows;
+    std::memcpy(out, h->h_marg, sizeof(double) * (size_t)r * r);
+    if (rows) *rows = r;
+    return ORCVIO_OK;
+}
+
+int32_t orcvio_msckf_cov_get_marginal(orcvio_msckf_handle* h, const orcvio_msckf_marginal* q, double* out) {
+    if (!h || !q || !out) { g_last_error = "cov_get_marginal: null argument"; return ORCVIO_ERR_INVALID; }
+    const int rc = orcvio_msckf_cov_marginal_submit(h, q);
+    return rc != ORCVIO_OK ? rc : orcvio_msckf_cov_marginal_collect(h, out, nullptr);
+}
+
 int32_t orcvio_msckf_cov_propagate(orcvio_msckf_handle* h, int32_t leg, const double* Phi, const double* Q) {
     if (!h || !Phi || !Q || (leg != 22 && leg != 46) || h->res_n < leg) { g_last_error = "cov_propagate: invalid"; return ORCVIO_ERR_INVALID; }
     HIPCHK(hipSetDevice(h->device));

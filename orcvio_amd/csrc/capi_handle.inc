@@ -236,6 +236,9 @@ static void stage_prior(orcvio_msckf_handle* h, const double* P, int n, bool upp
     }
 }
 // ---- create / destroy ---------------------------------------------------------------------
+// the pinned block of orcvio_msckf_cov_marginal_*: [result doubles [64][64] | sequence word on a line of its own]
+enum { MARG_SEQ_OFFSET = sizeof(double) * MARGINAL_MAX * MARGINAL_MAX, MARG_BLOCK_BYTES = MARG_SEQ_OFFSET + 128 };
+static_assert(MARGINAL_MAX == ORCVIO_MARGINAL_MAX, "the header's bound is the kernel's");
 static void free_all(orcvio_msckf_handle* h) {
     (void)hipDeviceSynchronize();   // (asynchronous copies out of the pinned buffers, a commit's tail: nothing of this handle is in flight any more)
     void* ptrs[] = {h->d_in, h->d_outs,
@@ -257,6 +260,8 @@ static void free_all(orcvio_msckf_handle* h) {
     if (h->d_tri_words) (void)hipFree(h->d_tri_words);
     if (h->h_tri2) (void)hipHostFree(h->h_tri2);
     if (h->h_cc) (void)hipHostFree(h->h_cc);
+    if (h->h_marg) (void)hipHostFree(h->h_marg);
+    if (h->d_margT) (void)hipFree(h->d_margT);
     for (void* q : {(void*)h->d_tri2_list, (void*)h->d_tri2_words, (void*)h->d_skip2}) if (q) (void)hipFree(q);
     if (h->d_in2) (void)hipFree(h->d_in2);
     if (h->d_step_words) (void)hipFree(h->d_step_words);
@@ -384,6 +389,13 @@ int32_t orcvio_msckf_create(int32_t device, int32_t max_clones, int32_t max_feat
         h->imu_recs46.resize((size_t)IMU_MAX_SAMPLES * IMU_REC46);
         HIPCHK(hipMalloc(&h->d_zchk, sizeof(double) * ((size_t)ZCHK_MAX_SAMPLES * ZCHK_ROW + 16)));   // k_zupt_check: rows, results, status words
         HIPCHK(hipMemset(h->d_zchk, 0, sizeof(double) * ((size_t)ZCHK_MAX_SAMPLES * ZCHK_ROW + 16)));
+        // orcvio_msckf_cov_marginal_submit: the pinned result block with its sequence word, the staging of T, and k_cov_marginal's dynamic
+        // LDS at 64 x 64 (97.5 KB).  Here, so that neither the submit nor the collect ever allocates
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_marg), MARG_BLOCK_BYTES, hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->h_marg_dev), h->h_marg, 0));
+        std::memset(h->h_marg, 0, MARG_BLOCK_BYTES);
+        HIPCHK(hipMalloc(&h->d_margT, sizeof(double) * MARGINAL_MAX * MARGINAL_MAX));
+        HIPCHK(hipFuncSetAttribute((const void*)k_cov_marginal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cov_marginal_lds_bytes(MARGINAL_MAX, MARGINAL_MAX)));
         HIPCHK(hipMalloc(&h->d_tri_valid, sizeof(int) * max_features));
         HIPCHK(hipMalloc(&h->d_tri_flags, sizeof(int) * max_features));
         HIPCHK(hipMalloc(&h->d_tri_init, sizeof(int) * max_features));

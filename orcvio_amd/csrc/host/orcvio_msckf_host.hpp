@@ -23,6 +23,7 @@
 #include "../../../include/orcvio_msckf.h"
 #include "zupt_check_model.hpp"
 #include "clone_choice_model.hpp"
+#include "cov_marginal_spec.hpp"
 
 namespace orcvio_amd {
 
@@ -346,6 +347,33 @@ class MsckfBackend {
         if (rc != ORCVIO_OK) return rc;
         ss.state_cov.assign((size_t)n * n, 0.0);
         return orcvio_msckf_cov_get(h_, &n, ss.state_cov.data());
+    }
+    // getPpose() / getPvel() (src/orcvio.cpp:2999-3026) on the resident covariance, without bringing state_cov back: ONE congruence of
+    // the nine leading IMU states (odometry_marginal_spec, host/cov_marginal_spec.hpp) by one small launch that stores into pinned
+    // memory.  R_imu_body = IMUState::T_imu_body.linear(), row-major.  P_body_pose [6][6] is getPpose()'s matrix in its own order
+    // (position first), P_body_vel [3][3] getPvel()'s.
+    // The pair overlaps the caller's host work: the frame call, then odometryCovarianceSubmit, then the state increment, then Collect
+    // (the leading IMU rows are untouched by the frame's marginalisation, so a submit directly behind the frame call reads the
+    // values the publisher wants).
+    int odometryCovarianceSubmit(const double R_imu_body[9]) {
+        int32_t idx[ODOMETRY_MARGINAL_DIM];
+        double T[ODOMETRY_MARGINAL_DIM * ODOMETRY_MARGINAL_DIM];
+        odometry_marginal_spec(R_imu_body, idx, T);
+        const orcvio_msckf_marginal q{ODOMETRY_MARGINAL_DIM, idx, ODOMETRY_MARGINAL_DIM, T};
+        return orcvio_msckf_cov_marginal_submit(h_, &q);   // (idx and T are staged when it returns)
+    }
+    int odometryCovarianceCollect(double P_body_pose[36], double P_body_vel[9]) {
+        double out[ORCVIO_MARGINAL_MAX * ORCVIO_MARGINAL_MAX];   // (collect copies what was submitted: room for any request)
+        int32_t rows = 0;
+        const int rc = orcvio_msckf_cov_marginal_collect(h_, out, &rows);
+        if (rc != ORCVIO_OK) return rc;
+        if (rows != ODOMETRY_MARGINAL_DIM) return ORCVIO_ERR_INVALID;   // (the outstanding submit was not odometryCovarianceSubmit's)
+        odometry_marginal_split(out, P_body_pose, P_body_vel);
+        return ORCVIO_OK;
+    }
+    int odometryCovariance(const double R_imu_body[9], double P_body_pose[36], double P_body_vel[9]) {
+        const int rc = odometryCovarianceSubmit(R_imu_body);
+        return rc != ORCVIO_OK ? rc : odometryCovarianceCollect(P_body_pose, P_body_vel);
     }
     int propagateCovariance(const std::vector<double>& Phi, const std::vector<double>& Q) {
         return orcvio_msckf_cov_propagate(h_, flags.leg_dim, Phi.data(), Q.data());

@@ -21,6 +21,7 @@
 #include "triangulate.hpp"
 #include "triangulate_arm.hpp"
 #include "cov_ops.hpp"
+#include "cov_marginal_ops.hpp"
 #include "zupt_ops.hpp"
 #include "imu_ops.hpp"
 #include "zupt_check_ops.hpp"
@@ -278,6 +279,12 @@ struct orcvio_msckf_handle : CovBook {   // (the resident covariance, its factor
     bool cc_armed = false;
     int cc_tracking_ok = 0;
     unsigned long long cc_seq = 0;      // launches of k_clone_choice so far: the value the next one stores behind its block
+    // orcvio_msckf_cov_marginal_submit / _collect (k_cov_marginal): all of it allocated at create
+    char *h_marg = nullptr, *h_marg_dev = nullptr;   // pinned, host-coherent: the result block [64][64] | its sequence word (MARG_SEQ_OFFSET)
+    double* d_margT = nullptr;          // device staging of T [64][64]
+    unsigned long long marg_seq = 0;    // launches of k_cov_marginal so far: the value the next one stores behind its block
+    bool marg_submitted = false;        // a submit has not been collected
+    int marg_rows = 0;                  // rows (= columns) of the outstanding result
     int* d_flag = nullptr;              // step counter of that launch (inside the d_info allocation, own 128-byte line)
     // device buffers
     double *d_poses = nullptr, *d_pw = nullptr, *d_obs_z = nullptr, *d_obs_zvel = nullptr, *d_P = nullptr;
